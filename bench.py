@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: collocation-point NS-residual evals/sec (full training step).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..5] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Started either by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the environment) or plainly as above - then this process starts the N ranks itself as CHILD
@@ -27,6 +27,10 @@ scripts/pmc_summarize.py from separate rocprofv3 --pmc passes) and are null unle
 exactly this csrc/ (content hash) and this shape.  `sustained` = >= 2 s of back-to-back steps after the timed
 region (clock-settled figure).  `cpu_baseline` = the oracle's torch-autograd restatement of the reference step
 on this host's cores, bounded sample.
+
+--dump-outputs DIR: rank 0 writes what the last timed step handed its caller - the loss terms, the gradient and the
+Adam-updated parameters (and the entropy net's, ev flavour) - as DIR/<name>.npy (float32; loss terms float64), right
+after the timed region.  Inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -227,7 +231,11 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=None)
     ap.add_argument("--sustain-seconds", type=float, default=2.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
     args.flavour = args.flavour or cfg["flavour"]
     args.layers = args.layers or cfg["layers"]
@@ -249,6 +257,30 @@ def parse_args():
         args.cpu_sample = max(1024, int(16384 * weight_count(6, 256) / weight_count(args.layers, args.hidden)))
         args.cpu_sample = min(args.cpu_sample, 65536)
     return args
+
+
+LOSS_KEYS = ("loss", "loss_e", "loss_b", "loss_s", "loss_eq1", "loss_eq2", "loss_eq3", "loss_eq4")
+# per array (8 MB of float32; at most four arrays): a larger one is written as the entries at
+# np.sort(np.random.RandomState(0).choice(size, DUMP_MAX_ELEMS, replace=False)) - the same sample on every run
+DUMP_MAX_ELEMS = 1 << 21
+
+
+def dump_outputs(E, out_dir):
+    """The last step's outputs as out_dir/<name>.npy: loss terms (float64, in LOSS_KEYS order), gradient and updated
+    parameters of the main net (and of the entropy net, ev flavour)."""
+    os.makedirs(out_dir, exist_ok=True)
+    terms = E.loss_terms()
+    arrays = dict(loss_terms=np.array([float(terms[k]) for k in LOSS_KEYS], dtype=np.float64),
+                  grads=E.grads, params=E.net.params)
+    if E.net_e is not None:
+        arrays.update(grads_e=E.grads_e, params_e=E.net_e.params)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step written to %s" % out_dir)
 
 
 def build_engine(eng, dev, args, precision, pg, world, rank):
@@ -372,6 +404,8 @@ def main():
         dt = float(t.item())
     loss = float(E.loss_terms()["loss"])
     log("timed region done: %.3f ms/step, loss %.6f" % (1e3 * dt / args.steps, loss))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(E, args.dump_outputs)
 
     # ---- sustained: >= sustain-seconds of back-to-back steps (every rank takes part: the step all-reduces) ----
     sustained = None

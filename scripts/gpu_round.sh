@@ -7,7 +7,7 @@
 #   clock   GRBM_GUI_ACTIVE of the three kernels on seeded and on all-zero parameters -> gpurun_out/TAG_clock.txt
 set -e
 TAG=$1; shift
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $ROOT/gpurun_out
 for step in "$@"; do
   cd $ROOT

@@ -2,7 +2,7 @@
 # Board power and shader clock per MFMA operand type: tests/micro/mfma_dtype_power loops each type for SECONDS while this
 # script samples rocm-smi and tags every sample with the type running at that moment.
 #   bash scripts/mfma_power.sh [SECONDS] > gpurun_out/mfma_power.txt
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SECS=${1:-4}
 LOG=$(mktemp)
 "$ROOT/tests/micro/mfma_dtype_power" "$SECS" > "$LOG" 2>&1 &

@@ -5,7 +5,7 @@
 # gpurun_out/pmc_<tag>/summary.txt and gpurun_out/pmc_<tag>/pmc.json (copy the latter two into profiles/).
 set -u
 PREC=${1:-bf16x3}; TAG=${2:-r2}; shift 2 || true
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

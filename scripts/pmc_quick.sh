@@ -1,7 +1,7 @@
 #!/bin/bash
 # one SQ counter pass over the default bench with a given library:  scripts/pmc_quick.sh <tag> [lib.so]
 TAG=$1; LIB=${2:-}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/pmcq_$TAG
 mkdir -p $OUT
 [ -n "$LIB" ] && export NSFNET_PINN_LIB=$ROOT/$LIB

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Board power and shader clock (rocm-smi / amd-smi, once a second) while forward + reverse sweep + dW loop.
 #   bash scripts/power_probe.sh > gpurun_out/power_probe.txt        POWER_CASES="precision,layers,hidden,grid,zero ..." (zero=1: all-zero parameters)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 rocm-smi --showmaxpower 2>/dev/null | grep -i "power" || true
 sample() {
   for i in 1 2 3 4; do

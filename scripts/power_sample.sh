@@ -1,6 +1,6 @@
 #!/bin/bash
 # sample socket power / clocks while the default bench loops:  bash scripts/power_sample.sh [bench args]   (GPU box)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/power_sample.txt
 rocm-smi --showmaxpower --showpower --showclocks > $OUT 2>&1
 python3 $ROOT/bench.py --steps 1500 --warmup 20 --no-cpu-baseline --alt-precision "" --sustain-seconds 0 "$@" > $ROOT/gpurun_out/power_bench.log 2>&1 &

@@ -169,3 +169,70 @@ def test_strong_scaling_two_gloo_ranks(tmp_path):
                          capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "STRONG_OK 2880000 []" in out.stdout            # (no alt modes in the strong table)
+
+
+def test_dump_outputs_writes_the_last_step_as_npy(tmp_path):
+    """--dump-outputs: loss terms (float64, bench.LOSS_KEYS order), gradient and parameters (float32) as DIR/<name>.npy;
+    arrays over bench.DUMP_MAX_ELEMS are written as a fixed, seeded sample."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def engine(n_params, n_params_e=None):
+        terms = {k: torch.tensor(float(i) + 0.5) for i, k in enumerate(bench.LOSS_KEYS)}
+        net = types.SimpleNamespace(params=torch.arange(n_params, dtype=torch.float32))
+        net_e = None if n_params_e is None else types.SimpleNamespace(params=torch.ones(n_params_e))
+        return types.SimpleNamespace(loss_terms=lambda: terms, grads=-net.params, net=net, net_e=net_e,
+                                     grads_e=None if net_e is None else 2 * net_e.params)
+
+    bench.dump_outputs(engine(1000), str(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["grads.npy", "loss_terms.npy", "params.npy"]
+    lt = np.load(tmp_path / "a" / "loss_terms.npy")
+    assert lt.dtype == np.float64 and list(lt) == [i + 0.5 for i in range(len(bench.LOSS_KEYS))]
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, np.arange(1000)) and np.array_equal(np.load(tmp_path / "a" / "grads.npy"), -p)
+
+    big = bench.DUMP_MAX_ELEMS + 5
+    for d in ("b", "c"):
+        bench.dump_outputs(engine(big, 7), str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "b"))
+    assert names == ["grads.npy", "grads_e.npy", "loss_terms.npy", "params.npy", "params_e.npy"]
+    p = np.load(tmp_path / "b" / "params.npy")
+    idx = np.sort(np.random.RandomState(0).choice(big, bench.DUMP_MAX_ELEMS, replace=False))
+    assert p.size == bench.DUMP_MAX_ELEMS and np.array_equal(p, idx.astype(np.float32))
+    assert np.array_equal(p, np.load(tmp_path / "c" / "params.npy"))       # same sample every run
+    total = sum(os.path.getsize(tmp_path / "b" / n) for n in names)
+    assert total <= 64 << 20
+
+
+def test_bench_rejects_a_step_count_below_one(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0"])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_match_the_json_line(tmp_path):
+    """The dumped loss terms are the last timed step's: loss_terms[0] is the JSON line's final_loss, and the gradient
+    and parameters have the net's parameter count."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    out_dir = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "1", "--grid", "64", "--steps", "3",
+                          "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, env=env, timeout=600)
+    d = _one_json_line(out)
+    assert d["steps"] == 3
+    lt = np.load(out_dir / "loss_terms.npy")
+    assert lt.dtype == np.float64 and lt[0] == d["config"]["final_loss"]
+    p, g = np.load(out_dir / "params.npy"), np.load(out_dir / "grads.npy")
+    n = 2 * 50 + 3 * 50 * 50 + 3 * 50 + 4 * 50 + 3       # 4x50 net: weights and biases
+    assert p.dtype == g.dtype == np.float32 and p.shape == g.shape == (n,)
+    assert np.isfinite(p).all() and np.isfinite(g).all() and np.abs(g).max() > 0

@@ -29,10 +29,11 @@ def _case(sup_n=9):
     return dict(x=x, y=y, xb=xb, yb=yb, ub=ub, vb=vb, w=w, sup=(xs, ys, us, vs, ps_))
 
 
-def _build_solver(case):
+def _build_solver(case, monkeypatch=None):
+    """monkeypatch: undo the fakes after the test (in this pytest process); the spawned ranks exit instead."""
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     import fakes
-    fakes.install()
+    fakes.install(monkeypatch)
     from nsfnet_amd import ev_pinn_solver as es
     torch.manual_seed(3)
     P = es.PysicsInformedNeuralNetwork(Re=800, layers=2, layers_1=2, hidden_size=10, hidden_size_1=6, N_f=70,
@@ -80,7 +81,7 @@ def test_two_rank_sharded_training_matches_single_process(tmp_path, monkeypatch)
     # single process, full batch, same code path
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
-    P = _build_solver(_case())
+    P = _build_solver(_case(), monkeypatch)
     assert not P.is_distributed
     import io, contextlib
     with contextlib.redirect_stdout(io.StringIO()):
@@ -103,7 +104,7 @@ def test_rank_with_empty_supervised_share(tmp_path, monkeypatch):
     np.testing.assert_array_equal(r0["sums"], r1["sums"])
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
-    P = _build_solver(_case(1))
+    P = _build_solver(_case(1), monkeypatch)
     import io, contextlib
     with contextlib.redirect_stdout(io.StringIO()):
         P.train(num_epoch=3, lr=1e-3)
@@ -136,7 +137,7 @@ def test_single_process_fake_path_matches_autograd_oracle(monkeypatch):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
     case = _case()
-    P = _build_solver(case)
+    P = _build_solver(case, monkeypatch)
     P.set_supervised_data(None)
     torch.manual_seed(3)
     net = ar.RefFCNet(2, 3, 2, 10); net_e = ar.RefFCNet(2, 1, 2, 6)
