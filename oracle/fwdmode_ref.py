@@ -222,3 +222,36 @@ def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):
     denom = np.sqrt(v) / np.sqrt(bc2) + eps
     p = p - (lr / bc1) * m / denom
     return p, m, v
+
+
+def pde_loss_and_grad_chunked(params, x, y, Re, alpha_e=1.0, vis_t=None, e=None, w=None, scale=1.0,
+                              eq4_weight=0.1, params_e=None, chunk=8192):
+    """pde_loss_and_grad over N points in passes of <= chunk points (each pass normalised by the global N), so
+    that the fp64 oracle runs at the sizes the kernels are measured at without holding every saved activation.
+    Returns the summed sums and grad and the concatenated eqs / out.  params_e (ev flavour): the entropy net; e
+    then defaults to its output, and grad_e is its parameter gradient (backward1 of each pass's e_adj, summed)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    N = x.size
+    opt = lambda a, lo, hi: None if a is None else np.asarray(a, dtype=np.float64).reshape(-1)[lo:hi]
+    sums, grad, grad_e, eqs, outs = None, None, None, [], []
+    for lo in range(0, N, int(chunk)):
+        hi = min(N, lo + int(chunk))
+        ek, saved_e = opt(e, lo, hi), None
+        if params_e is not None:
+            ev, saved_e = forward1(params_e, x[lo:hi], y[lo:hi])
+            if ek is None:
+                ek = ev[:, 0]
+        r = pde_loss_and_grad(params, x[lo:hi], y[lo:hi], Re, alpha_e=alpha_e, vis_t=opt(vis_t, lo, hi), e=ek,
+                              w=opt(w, lo, hi), scale=scale, n_total=N, eq4_weight=eq4_weight)
+        sums = np.asarray(r["sums"]) if sums is None else sums + r["sums"]
+        grad = r["grad"] if grad is None else grad + r["grad"]
+        if params_e is not None:
+            ge = backward1(params_e, x[lo:hi], y[lo:hi], saved_e, r["e_adj"].reshape(-1, 1))
+            grad_e = ge if grad_e is None else grad_e + ge
+        eqs.append(r["eqs"]); outs.append(r["out"])
+    out = dict(sums=[float(s) for s in sums], grad=grad, out=np.concatenate(outs),
+               eqs=[np.concatenate([q[k] for q in eqs]) for k in range(len(eqs[0]))])
+    if params_e is not None:
+        out["grad_e"] = grad_e
+    return out

@@ -6,7 +6,9 @@ size-independent properties - the fp64 oracle cannot run the whole set in second
     count add up to the full-batch result (this is the multi-GPU contract);
   * permutation invariance of loss and gradient;
   * forward/backward consistency: a central finite difference of the forward loss along a
-    random direction equals grad . direction.
+    random direction equals grad . direction;
+  * and once, whole: every residual, the loss sums, the loss and the gradient against the fp64 oracle run over all
+    360 000 points in 8 192-point passes (fr.pde_loss_and_grad_chunked, computed once and shared by both modes).
 Both precision modes run all four: fp32 (f32-input MFMA, 64-column tiles at hidden 256) and bf16x3 (the
 128-column bf16 MFMA kernels that produce bench.py's headline number).  Tolerances per mode in TOL below
 (bf16x3: residuals <= 2e-4 of max, the north star's 1e-4 on the loss).
@@ -126,3 +128,45 @@ def test_directional_derivative(base):
     fd = (vals[0] - vals[1]) / (2 * eps)
     gd = float(base["grads"] @ d)
     assert abs(fd - gd) < 2e-2 * abs(gd), (fd, gd)
+
+
+# the small-N oracle bars (test_hip_kernels.py, test_pipelined_kernels.py): residual max-abs / max|ref|, sums relative,
+# loss relative, gradient relative L2
+ORACLE_BARS = {"fp32": dict(eq=2e-5, sums=1e-5, loss=1e-5, grad=1e-4), "bf16x3": dict(eq=5e-4, sums=2e-4, loss=1e-4, grad=1e-4)}
+
+
+@pytest.fixture(scope="module")
+def full_oracle():
+    """The fp64 oracle over all 360 000 points (in 8 192-point passes), shared by both precision modes."""
+    flat = ar.flat_params(ar.seeded_net(3, L, H, seed=1234)).numpy().astype(np.float64)
+    x, y = (a.reshape(-1).astype(np.float32).astype(np.float64) for a in ar.uniform_grid(GRID, GRID))
+    P = fr.unflatten(flat, 2, 3, L, H)
+    r = fr.pde_loss_and_grad_chunked(P, x, y, RE)
+    xb, yb, ub, vb = (a.reshape(-1).astype(np.float32) for a in ar.cavity_boundary())
+    b = fr.bc_loss_and_grad(P, xb.astype(np.float64), yb.astype(np.float64), ub, vb, alpha_b=10.0)
+    return dict(eqs=r["eqs"], sums=np.asarray(r["sums"]), grad=r["grad"] + b["grad"],
+                loss=10.0 * sum(b["sums"]) / xb.size + sum(r["sums"]) / x.size)
+
+
+def test_whole_batch_against_chunked_oracle(base, full_oracle):
+    """The headline workload whole: every residual, the loss sums, the loss and the gradient at all 360 000 points
+    against the fp64 oracle - the gradient behind bench.py's number, with every sweep and dW group iterating."""
+    E, ref, bar = base["E"], full_oracle, ORACLE_BARS[base["prec"]]
+    E.net.set_flat(torch.tensor(base["flat"]))     # (an earlier test may have left perturbed fields behind)
+    E.loss_and_grad()
+    torch.cuda.synchronize()
+    f = E.plan_f
+    errs = {}
+    for k, name in enumerate(("eq1", "eq2", "eq3")):
+        errs[name] = np.abs(f.field(name).cpu().numpy().astype(np.float64) - ref["eqs"][k]).max() / np.abs(ref["eqs"][k]).max()
+    sums = E.sums.cpu().numpy().astype(np.float64)
+    errs["sums"] = np.abs(sums[:3] - ref["sums"]).max() / np.abs(ref["sums"]).max()
+    errs["loss"] = abs(float(E.loss_terms()["loss"]) - ref["loss"]) / ref["loss"]
+    # (the bar on every layer's weight and bias block: the output layer's dominate the norm of the whole gradient)
+    g = fr.unflatten(E.grads.cpu().numpy().astype(np.float64), 2, 3, L, H)
+    errs["grad"] = max(_rel_l2(p, q) for pq, rq in zip(g, fr.unflatten(ref["grad"], 2, 3, L, H)) for p, q in zip(pq, rq))
+    print("[full size] %s: %s" % (base["prec"], " ".join("%s %.2e" % kv for kv in errs.items())))
+    for name in ("eq1", "eq2", "eq3"):
+        assert errs[name] <= bar["eq"], (name, errs[name])
+    for k in ("sums", "loss", "grad"):
+        assert errs[k] <= bar[k], (k, errs[k])
