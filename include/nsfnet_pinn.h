@@ -104,6 +104,20 @@ int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
                                   const float* vis_t, const float* fields, const float* coef_eq4,
                                   float Re, float coord_scale, float* ebar_out, int phases, void* stream);
 
+/* ---- residual forward + backward in one call ------------------------------
+ * pinn_residual_forward(save = 1) followed by pinn_residual_backward (MSE seeds coef_eq4,
+ * known before the forward), with the same arguments and the same results: fields,
+ * vis_t_out, vis_t_minus, loss_sums, ebar_out and the partial gradients for
+ * pinn_grad_reduce.  On the role-split hidden-256 plan the two sweeps of each tile run
+ * in one kernel (PINN_FUSE=0 at plan creation keeps the separate launches); on every
+ * other plan this is exactly the two calls.  Not for seeds that depend on the loss sums
+ * (the L2 loss mode). */
+int pinn_residual_forward_backward(pinn_plan_t plan, void* ws, const float* prep,
+                                   const float* x, const float* y, const float* e, const float* w,
+                                   float* vis_t_minus, float* vis_t_out, float* fields,
+                                   const float* coef_eq4, float Re, float vis_t0, float alpha_evm,
+                                   float coord_scale, float* loss_sums, float* ebar_out, void* stream);
+
 /* ---- value forward / backward -----------------------------------------------
  * Replaces neural_net_u and the boundary / supervised MSE terms
  * (NSFnet/pinn_solver.py:124-130,199-207; ev:280-288,374-379,399-411) and, with

@@ -55,6 +55,7 @@ struct pinn_plan_s {
   int stagger;           // $PINN_STAGGER, read once at plan creation
   int pipe_f, grid_fp;   // schedule of the forward with saved activations (0 8-wave, 1 pipelined, 2 role-split); grid of 1 / 2 (pairs of tiles)
   int pipe_b;            // schedule of the reverse sweep; for 1 / 2 grid_b is the pair grid
+  int fuse;              // role-split pair: pinn_residual_forward_backward runs both sweeps of a tile in one kernel (fwdbwd_bf16_split.hip)
   int wsplit;            // wide net (hidden > 256): role-split sweeps at 64-column tiles (fwd / bwd_bf16_wsplit.hip) instead of the 8-wave ones
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
@@ -206,6 +207,10 @@ int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t*
   p->wsplit = p->s24w && L >= 2 && env_int("PINN_WSPLIT", 1) != 0 && fwd_wsplit_lds_bytes(HP) <= PINN_LDS_MAX &&
               bwd_wsplit_lds_bytes(HP, L) <= PINN_LDS_MAX;
   p->grid_fp = cus < (p->ntiles + 1) / 2 ? cus : (p->ntiles + 1) / 2;
+  // The fused sweeps need the role-split pair on both sides, in one precision, and fit in LDS up to 7 hidden layers at hidden 256; deeper
+  // nets keep the two launches.  $PINN_FUSE=0 keeps them too (same-build A/B).
+  p->fuse = p->pipe_f == 2 && p->pipe_b == 2 && p->s0_skip && net->prec_fwd == net->prec_bwd && env_int("PINN_FUSE", 1) != 0 &&
+            fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
   p->stagger = env_int("PINN_STAGGER", 0);
   if (env_int("PINN_VERBOSE", 0))
     fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
@@ -251,6 +256,7 @@ int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t*
     int rc = dispatch_fwd(p, fa, nullptr);
     if (!rc && (p->pipe_f || p->wsplit)) rc = dispatch_fwd(p, fa, nullptr, true);
     if (!rc) rc = dispatch_bwd(p, ba, nullptr);
+    if (!rc && p->fuse) rc = launch_fwdbwd_split(HP, terms_of(net->prec_fwd), fa, ba, p->grid_fp, nullptr);
     if (!rc) rc = dispatch_dw(p, da, nullptr);
     if (rc) { delete p; return hipfail(rc, "pinn_plan_create(kernel attributes)"); }
   }
@@ -349,6 +355,51 @@ int pinn_residual_backward(pinn_plan_t plan, void* ws, const float* prep,
                            float Re, float coord_scale, float* ebar_out, void* stream) {
   return pinn_residual_backward_phases(plan, ws, prep, x, y, e, w, vis_t, fields, coef_eq4, Re, coord_scale,
                                        ebar_out, 3, stream);
+}
+
+int pinn_residual_forward_backward(pinn_plan_t plan, void* ws, const float* prep,
+                                   const float* x, const float* y, const float* e, const float* w,
+                                   float* vis_t_minus, float* vis_t_out, float* fields,
+                                   const float* coef_eq4, float Re, float vis_t0, float alpha_evm,
+                                   float coord_scale, float* loss_sums, float* ebar_out, void* stream) {
+  if (!plan || !ws || !prep || !x || !y || !fields || !coef_eq4) return fail(-22, "pinn_residual_forward_backward: null argument%s");
+  if (plan->streams != 4) return fail(-22, "pinn_residual_forward_backward: plan is not a residual (4-stream) plan%s");
+  if (!plan->fuse) {
+    int rc = pinn_residual_forward(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,
+                                   coord_scale, 1, loss_sums, stream);
+    return rc ? rc : pinn_residual_backward(plan, ws, prep, x, y, e, w, vis_t_out, fields, coef_eq4, Re, coord_scale,
+                                            ebar_out, stream);
+  }
+  if (!(Re > 0.f)) return fail(-22, "pinn_residual_forward_backward: Re must be > 0%s");
+  // the argument blocks of the two launches it replaces (pinn_residual_forward, save = 1 / pinn_residual_backward)
+  FwdArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.x = x; fa.y = y; fa.n = (int)plan->n; fa.ntiles = plan->ntiles; fa.L = plan->net.L; fa.n_out = plan->net.n_out;
+  fa.prep = prep; fa.S = WS(plan, off_S);
+  fa.fld = fields; fa.e = e; fa.w = w; fa.vtm = vis_t_minus; fa.vis_used = vis_t_out;
+  fa.inv_re = 1.0f / Re; fa.vis_t0 = vis_t0; fa.alpha_evm = alpha_evm; fa.scale = coord_scale;
+  fa.s24 = plan->s24w;
+  fa.partials = WS(plan, off_partials);
+  fa.sl0 = plan->sl0; fa.sblk = plan->sblk; fa.s0_skip = plan->s0_skip32;
+  BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
+  a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
+  a.fld = fields; a.e = e; a.w = w; a.vis_used = vis_t_out;
+  for (int k = 0; k < 4; ++k) a.coef_eq[k] = coef_eq4[k];
+  a.inv_re = 1.0f / Re; a.scale = coord_scale; a.ebar = ebar_out;
+  a.s24 = plan->s24w;
+  a.sl0 = plan->sl0; a.sblk = plan->sblk; a.s0_skip = plan->s0_skip32;
+  a.sg = WS(plan, off_sg);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launch_fwdbwd_split(plan->net.HP, terms_of(plan->net.prec_fwd), fa, a, plan->grid_fp, s);
+  if (rc) return hipfail(rc, "pinn_residual_forward_backward");
+  if (loss_sums) {
+    rc = launch_loss_sums(fa.partials, plan->grid_fp, loss_sums, s);
+    if (rc) return hipfail(rc, "pinn_residual_forward_backward(loss sums)");
+  }
+  rc = run_dw_and_stash(plan, ws, prep, x, y, s);
+  return rc ? hipfail(rc, "pinn_residual_forward_backward(dW)") : 0;
 }
 
 int pinn_value_forward(pinn_plan_t plan, void* ws, const float* prep,

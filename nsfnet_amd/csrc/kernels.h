@@ -139,6 +139,9 @@ int launch_fwd_split(int HP, int terms, const FwdArgs& a, int grid, hipStream_t 
 size_t fwd_split_lds_bytes(int HP, int L);
 int launch_bwd_split(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s);
 size_t bwd_split_lds_bytes(int HP, int L);
+// the two role-split sweeps of each tile in one kernel (fwdbwd_bf16_split.hip): residual mode, MSE seeds
+int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s);
+size_t fwdbwd_split_lds_bytes(int HP, int L);
 int launch_bwd_pipe(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s);
 size_t bwd_pipe_lds_bytes(int HP, int L);
 // wide nets (256 < HP <= 448), residual mode, 24-bit spill: the role-split schedule at 64-column tiles (fwd_bf16_wsplit.hip)

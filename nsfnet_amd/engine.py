@@ -203,6 +203,21 @@ class ResidualPlan(PointPlan):
             _ptr(self.vis_t), _ptr(self.fields), coef, float(Re), float(scale),
             _ptr(self.ebar if want_ebar else None), int(phases), _stream()), "pinn_residual_backward")
 
+    def forward_backward(self, Re, coef_eq, e=None, vis_t0=0.0, alpha_evm=0.0, scale=1.0, want_ebar=False,
+                         sums_out=None):
+        """forward(save=True) then backward(coef_eq) in one call, for seeds known before the forward (MSE loss):
+        on the role-split hidden-256 plan both sweeps of a tile run in one kernel."""
+        if not self.with_backward:
+            raise RuntimeError("plan was created without backward workspace")
+        if want_ebar and self.ebar is None:
+            self.ebar = torch.zeros(((self.n + 127) // 128) * 128, dtype=torch.float32, device=self.net.device)
+        coef = (ctypes.c_float * 4)(*[float(c) for c in coef_eq])
+        _lib.check(self.lib.pinn_residual_forward_backward(
+            self.handle, _ptr(self.ws), _ptr(self.net.prep), _ptr(self.x), _ptr(self.y), _ptr(e), _ptr(self.w),
+            _ptr(self.vis_t_minus), _ptr(self.vis_t), _ptr(self.fields), coef, float(Re), float(vis_t0),
+            float(alpha_evm), float(scale), _ptr(self.sums if sums_out is None else sums_out),
+            _ptr(self.ebar if want_ebar else None), _stream()), "pinn_residual_forward_backward")
+
     def field(self, name):
         return self.fields[FLD[name], :self.n]
 
@@ -474,14 +489,25 @@ class PinnEngine:
             sums[S_EQ:S_EQ + NLOSS].zero_()
             for k, ((lo, hi_), ck) in enumerate(zip(f.bounds, f.chunks)):
                 ek = None if e is None else e[lo:hi_]
-                ck.forward(self.Re, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
-                           sums_out=f.tmp_sums)
-                sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
-                ck.backward(self.Re, coef_eq, e=ek, scale=self.scale, want_ebar=self.e_trainable)
+                if hasattr(ck, "forward_backward"):      # (MSE seeds: known before the forward)
+                    ck.forward_backward(self.Re, coef_eq, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm,
+                                        scale=self.scale, want_ebar=self.e_trainable, sums_out=f.tmp_sums)
+                    sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
+                else:
+                    ck.forward(self.Re, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
+                               sums_out=f.tmp_sums)
+                    sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
+                    ck.backward(self.Re, coef_eq, e=ek, scale=self.scale, want_ebar=self.e_trainable)
                 grad_reduce(self.net, [ck], self.grads, accumulate=k > 0)
             if side is not None:
                 main.wait_stream(side)
             grad_reduce(self.net, value_plans, self.grads, accumulate=True)
+        elif not l2 and hasattr(f, "forward_backward"):      # MSE seeds: one call, the sweeps fused where the plan allows
+            f.forward_backward(self.Re, coef_eq, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale,
+                               want_ebar=self.e_trainable, sums_out=sums[S_EQ:S_EQ + NLOSS])
+            if side is not None:
+                main.wait_stream(side)
+            grad_reduce(self.net, [f] + value_plans, self.grads)
         else:
             f.forward(self.Re, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
                       sums_out=sums[S_EQ:S_EQ + NLOSS])
