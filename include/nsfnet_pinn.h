@@ -153,6 +153,36 @@ int pinn_adam_step(float* params, const float* grads, float* m, float* v, int64_
 int pinn_adam_step_dev(float* params, const float* grads, float* m, float* v, int64_t n,
                        float lr, float beta1, float beta2, float eps, int64_t* step_counter, void* stream);
 
+/* ---- residual-based resampling of the collocation points (RAD) -----------------
+ * No reference counterpart (its roadmap asks for finer control of the PDE points,
+ * ev-NSFnet/README.md).  A pool of n_pool candidate points evaluated by a forward-only
+ * residual plan (its fields, plane stride npad) is resampled to m points by systematic
+ * resampling, all sums in fp64 and in a fixed order (bit-reproducible):
+ *   e2_i = eq1^2 + eq2^2 + eq3^2 + w4 eq4^2,  a_i = e2_i^(k/2)  (k = 0: 1; k = 1: sqrt; k = 2: e2_i;
+ *          k = 0 with a non-finite e2_i: NaN, so that a non-finite residual always shows in S)
+ *   S = sum a_i (S == 0: a_i = 1),  b_i = a_i + c S / n_pool,  C_i = inclusive prefix sum of b,
+ *   T = C_{n_pool-1},  o_i = min(m, floor(C_i m / T + u)),  o_{-1} = 0,  o_{n_pool-1} = m,
+ *   pool point i is written to out[o_{i-1} .. o_i).
+ * out is ascending (the selection keeps the pool order) and a point may appear more than once.
+ *
+ * Limits: 1 <= n_pool <= 2^30 and 1 <= m <= 2^30 (as for a plan's points).
+ *
+ * Bytes of device scratch the two calls below need for a pool of n_pool points (-1 if n_pool is out of range). */
+int64_t pinn_resample_scratch_bytes(int64_t n_pool);
+/* out [m] int64 pool indices.  After the call the first 8 bytes of scratch hold S (fp64), for the
+ * caller to check (a non-finite S means a non-finite residual in the pool).  k, c, w4 >= 0 and
+ * finite, 0 <= u < 1; fields 16-byte aligned, npad >= n_pool and a multiple of 4. */
+int pinn_resample_select(int64_t n_pool, const float* fields, int64_t npad, double w4, double k, double c,
+                         double u, int64_t m, void* scratch, int64_t* out, void* stream);
+/* dst_*[j - lo] = src_*[idx[j]] for j in [lo, hi) (0 <= lo < hi; indices outside [0, n_pool) are skipped): x and y always, w and vis_t_minus when both
+ * their source and destination are non-NULL.  w_sum (device, one double, or NULL; needs w)
+ * receives the fp64 sum of the gathered w in a fixed order.  scratch as for the select call
+ * with the same n_pool (its first 8 bytes are left alone). */
+int pinn_resample_gather(const int64_t* idx, int64_t lo, int64_t hi, int64_t n_pool,
+                         const float* src_x, const float* src_y, const float* src_w, const float* src_vtm,
+                         float* dst_x, float* dst_y, float* dst_w, float* dst_vtm,
+                         void* scratch, double* w_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

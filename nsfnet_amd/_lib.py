@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # $NSFNET_PINN_LIB selects another build of the same ABI (kernel experiments: scripts/abl_build.py)
 LIB_PATH = os.environ.get("NSFNET_PINN_LIB") or os.path.join(_HERE, "lib", "libnsfnet_pinn.so")
 
-c_void_p, c_int, c_int64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/nsfnet_pinn.h one to one
 SIGNATURES = {
@@ -46,6 +46,11 @@ SIGNATURES = {
                                c_float, c_float, c_float, c_float, c_int64, c_void_p]),
     "pinn_adam_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "pinn_resample_scratch_bytes": (c_int64, [c_int64]),
+    "pinn_resample_select": (c_int, [c_int64, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_int64,
+                                     c_void_p, c_void_p, c_void_p]),
+    "pinn_resample_gather": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -486,4 +486,39 @@ int pinn_adam_step_dev(float* params, const float* grads, float* m, float* v, in
   return rc ? hipfail(rc, "pinn_adam_step_dev") : 0;
 }
 
+int64_t pinn_resample_scratch_bytes(int64_t n_pool) {
+  return n_pool < 1 || n_pool > (int64_t)1 << 30 ? -1 : (int64_t)resample_scratch_bytes((long)n_pool);
+}
+
+int pinn_resample_select(int64_t n_pool, const float* fields, int64_t npad, double w4, double k, double c,
+                         double u, int64_t m, void* scratch, int64_t* out, void* stream) {
+  if (!fields || !scratch || !out) return fail(-22, "pinn_resample_select: null argument%s");
+  if (n_pool < 1 || n_pool > (int64_t)1 << 30) return fail(-22, "pinn_resample_select: pool size must be 1..2^30 (got %s%ld)", "", (long)n_pool);
+  if (m < 1 || m > (int64_t)1 << 30) return fail(-22, "pinn_resample_select: m must be 1..2^30 (got %s%ld)", "", (long)m);
+  if (npad < n_pool || npad % 4 != 0) return fail(-22, "pinn_resample_select: npad must be >= n_pool and a multiple of 4%s");
+  if (reinterpret_cast<uintptr_t>(fields) % 16 != 0) return fail(-22, "pinn_resample_select: fields must be 16-byte aligned%s");
+  if (!std::isfinite(k) || k < 0.0) return fail(-22, "pinn_resample_select: k must be finite and >= 0%s");
+  if (!std::isfinite(c) || c < 0.0) return fail(-22, "pinn_resample_select: c must be finite and >= 0%s");
+  if (!std::isfinite(w4) || w4 < 0.0) return fail(-22, "pinn_resample_select: w4 must be finite and >= 0%s");
+  if (!(u >= 0.0 && u < 1.0)) return fail(-22, "pinn_resample_select: u must be in [0, 1)%s");
+  int rc = launch_resample_select((long)n_pool, fields, (long)npad, w4, k, c, u, (long)m, scratch,
+                                  reinterpret_cast<long long*>(out), (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_resample_select") : 0;
+}
+
+int pinn_resample_gather(const int64_t* idx, int64_t lo, int64_t hi, int64_t n_pool,
+                         const float* src_x, const float* src_y, const float* src_w, const float* src_vtm,
+                         float* dst_x, float* dst_y, float* dst_w, float* dst_vtm,
+                         void* scratch, double* w_sum, void* stream) {
+  if (!idx || !src_x || !src_y || !dst_x || !dst_y || !scratch) return fail(-22, "pinn_resample_gather: null argument%s");
+  if (n_pool < 1 || n_pool > (int64_t)1 << 30) return fail(-22, "pinn_resample_gather: pool size must be 1..2^30 (got %s%ld)", "", (long)n_pool);
+  if (lo < 0 || hi <= lo) return fail(-22, "pinn_resample_gather: need 0 <= lo < hi%s");
+  if (!src_w != !dst_w) return fail(-22, "pinn_resample_gather: src_w and dst_w must both be given or both be NULL%s");
+  if (!src_vtm != !dst_vtm) return fail(-22, "pinn_resample_gather: src_vtm and dst_vtm must both be given or both be NULL%s");
+  if (w_sum && !dst_w) return fail(-22, "pinn_resample_gather: w_sum needs the weights%s");
+  int rc = launch_resample_gather(reinterpret_cast<const long long*>(idx), (long)lo, (long)hi, (long)n_pool, src_x, src_y,
+                                  src_w, src_vtm, dst_x, dst_y, dst_w, dst_vtm, scratch, w_sum, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_resample_gather") : 0;
+}
+
 }  // extern "C"

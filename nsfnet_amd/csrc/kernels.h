@@ -155,3 +155,10 @@ int launch_adam_dev(float* p, const float* g, float* m, float* v, long n, float 
                     float eps, long long* step_counter, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, long n, float step_size, float b1, float b2,
                 float eps, float bc2_sqrt, hipStream_t s);
+// residual-based resampling of the collocation points (resample.hip)
+size_t resample_scratch_bytes(long n_pool);
+int launch_resample_select(long n, const float* fields, long npad, double w4, double k, double c, double u, long m,
+                           void* scratch, long long* out, hipStream_t s);
+int launch_resample_gather(const long long* idx, long lo, long hi, long n_pool, const float* sx, const float* sy,
+                           const float* sw, const float* sv, float* dx, float* dy, float* dw, float* dv, void* scratch,
+                           double* w_sum, hipStream_t s);

@@ -45,6 +45,17 @@ class SDFWeightConfig:
     decay: float = 5.0
 
 
+@dataclass
+class ResamplingConfig:
+    """Residual-based redraw of the collocation points from a larger pool (PinnEngine.resample), off by default."""
+    enabled: bool = False
+    every: int = 5000
+    pool_points: int = 1000000
+    k: float = 1.0
+    c: float = 1.0
+    seed: int = 0
+
+
 def _default_stages():
     table = [(0.05, 1e-3), (0.03, 2e-4), (0.01, 4e-5), (0.005, 1e-5), (0.002, 2e-6), (0.002, 2e-6)]
     return [TrainingStage(a, 500000, lr, "Stage %d" % (i + 1)) for i, (a, lr) in enumerate(table)]
@@ -59,6 +70,7 @@ class TrainingConfig:
     sort_training_points: bool = True
     sdf_weighting: SDFWeightConfig = field(default_factory=SDFWeightConfig)
     coordinate_transform: bool = False
+    resampling: ResamplingConfig = field(default_factory=ResamplingConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -112,6 +124,9 @@ class ConfigManager:
             problems.append("network sizes must be >= 1")
         if c.training.N_f < 1:
             problems.append("training.N_f must be >= 1")
+        rs = c.training.resampling
+        if rs.enabled and (rs.every < 1 or rs.pool_points < 1 or rs.k < 0 or rs.c < 0 or rs.seed < 0):
+            problems.append("training.resampling: every, pool_points >= 1 and k, c, seed >= 0 required")
         for st in c.training.training_stages:
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
@@ -130,5 +145,8 @@ class ConfigManager:
         print("training   : N_f=%d log_interval=%d sort=%s sdf=%s coord_transform=%s stages=%d"
               % (t.N_f, t.log_interval, t.sort_training_points, t.sdf_weighting.enabled, t.coordinate_transform,
                  len(t.training_stages)))
+        if t.resampling.enabled:
+            print("resampling : every=%d pool_points=%d k=%s c=%s seed=%d"
+                  % (t.resampling.every, t.resampling.pool_points, t.resampling.k, t.resampling.c, t.resampling.seed))
         print("supervision: enabled=%s samples=%d weight=%s"
               % (c.supervision.enabled, c.supervision.num_samples, c.supervision.loss_weight))

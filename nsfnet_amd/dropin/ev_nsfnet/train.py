@@ -68,6 +68,22 @@ def main():
             sdf = loader.get_sdf_weights()
         PINN.set_coordinate_transform(loader.get_coord_scale())
         PINN.set_eq_training_data(X=(xf, yf), weights=sdf)
+        rs = cfg.training.resampling
+        if rs.enabled:    # the candidate pool: the same pipeline (LHS, coordinate map, sort, SDF weights) at N_f = pool_points
+            pool_loader = cavity.DataLoader(path="./datasets/", N_f=rs.pool_points, N_b=1000,
+                                            sort_training_points=cfg.training.sort_training_points,
+                                            sdf_weighting=cfg.training.sdf_weighting,
+                                            coord_transform=cfg.training.coordinate_transform)
+            if rank == 0:
+                pool_loader.loading_boundary_data()
+                pool = [pool_loader.loading_training_data() + (pool_loader.get_sdf_weights(),)]
+            else:
+                pool = [None]
+            if distributed:
+                dist.broadcast_object_list(pool, src=0)
+            xp, yp, sdfp = pool[0]
+            PINN.set_resample_pool(X=(xp, yp), weights=sdfp)
+            PINN.set_resampling(every=rs.every, k=rs.k, c=rs.c, seed=rs.seed)
         ref = args.data or "./data/cavity_Re%s_256_Uniform.mat" % cfg.physics.Re
         star = loader.loading_evaluate_data(ref) if os.path.exists(ref) else None
         sup = cfg.supervision

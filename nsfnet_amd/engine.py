@@ -309,6 +309,34 @@ class ValuePlan(PointPlan):
             "pinn_value_backward")
 
 
+def resample_scratch(n_pool, device):
+    """Device scratch of the two resampling calls for a pool of n_pool points."""
+    nbytes = int(_lib.load().pinn_resample_scratch_bytes(int(n_pool)))
+    if nbytes < 0:
+        raise ValueError("bad pool size %d" % n_pool)
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def resample_select(pool, w4, k, c, u, m, scratch):
+    """Systematic-resampling selection of m points of the evaluated forward-only ResidualPlan `pool`
+    (pinn_resample_select).  Returns (ascending int64 pool indices [m], S = sum of a as a host float):
+    reading S is the one host synchronisation of a resample."""
+    out = torch.empty(int(m), dtype=torch.int64, device=pool.fields.device)
+    _lib.check(_lib.load().pinn_resample_select(pool.n, _ptr(pool.fields), pool.npad, float(w4), float(k), float(c),
+                                                float(u), int(m), _ptr(scratch), _ptr(out), _stream()),
+               "pinn_resample_select")
+    return out, float(scratch[:8].view(torch.float64).item())
+
+
+def resample_gather(idx, lo, hi, n_pool, src, dst, scratch, w_sum=None):
+    """dst[name][j - lo] = src[name][idx[j]] for j in [lo, hi), name in x, y, w, vtm (w / vtm where both are
+    given); w_sum: a one-element fp64 device tensor that receives the fixed-order sum of the gathered w."""
+    _lib.check(_lib.load().pinn_resample_gather(
+        _ptr(idx), int(lo), int(hi), int(n_pool), _ptr(src["x"]), _ptr(src["y"]), _ptr(src.get("w")), _ptr(src.get("vtm")),
+        _ptr(dst["x"]), _ptr(dst["y"]), _ptr(dst.get("w")), _ptr(dst.get("vtm")), _ptr(scratch), _ptr(w_sum), _stream()),
+        "pinn_resample_gather")
+
+
 def grad_reduce(net, plans, grads_out, accumulate=False):
     lib = net.lib
     n = len(plans)
@@ -353,6 +381,7 @@ class PinnEngine:
         self.plan_f = self.plan_b = self.plan_s = self.plan_e = None
         self._graphs = {}
         self._side = None
+        self._resample_calls = 0        # resample() calls so far: part of each call's seed, kept across pools
         import os
         self._overlap = os.environ.get("NSFNET_OVERLAP_BC", "1") not in ("0", "", "false")
         self.n_f_global = self.n_b_global = self.n_s_global = 0
@@ -430,6 +459,85 @@ class PinnEngine:
         else:
             self._graphs.clear()
             self.plan_f.vis_t_minus = fresh
+
+    # ---- residual-based resampling of the collocation points ----
+    def set_resample_pool(self, x, y, weights=None):
+        """Candidate points of THIS rank for resample(): a forward-only residual plan over them (and, for the ev
+        flavour, a forward-only plan of the entropy net).  `weights` (pool SDF weights) must be given exactly when
+        the live collocation set has weights.  A new pool does not restart the draws: the call counter that goes into
+        resample()'s seed keeps counting, so refreshing the pool every stage with one seed gives fresh U values."""
+        if self.plan_f is not None and (weights is None) != (self.plan_f.w is None):
+            raise ValueError("pool weights must be given exactly when the collocation set has weights")
+        pool = ResidualPlan(self.net, x, y, with_backward=False)
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(np.asarray(weights, dtype=np.float32).reshape(-1)).to(self.device).contiguous()
+            if w.numel() != pool.n:
+                raise ValueError("pool weights must have one entry per pool point")
+        self._pool, self._pool_w = pool, w
+        self._pool_e = ValuePlan(self.net_e, x, y, with_backward=False) if self.net_e is not None else None
+        self._pool_scratch = resample_scratch(pool.n, self.device)
+
+    def resample(self, k=1.0, c=1.0, seed=0):
+        """Replace the live collocation points by plan_f.n points of the pool, drawn with density
+        |r|^k / mean|r|^k + c (systematic resampling, pinn_resample_select) under the current parameters, Re, scale,
+        vis_t0 and alpha_evm.  The live buffers are rewritten IN PLACE, so a captured step replays on the new points;
+        parameters, Adam moments, the boundary / supervised plans and n_f_global are not touched.  Each rank draws from
+        its own pool shard (per-rank stratification).  The weights are renormalised to mean 1 over the global selected
+        set; the entropy-net state vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-
+        ordered after the last step; one 8-byte host read.  Returns the int64 pool indices (ascending, may repeat)."""
+        f, pool = self.plan_f, getattr(self, "_pool", None)
+        if pool is None or f is None:
+            raise RuntimeError("resample() needs set_collocation() and set_resample_pool() first")
+        if (self._pool_w is None) != (f.w is None):
+            raise ValueError("pool weights must be given exactly when the collocation set has weights")
+        e = vtm0 = None
+        if self.net_e is not None:
+            self._pool_e.forward(save=False)
+            e = self._pool_e.pred[0]
+            vtm0 = (self.alpha_evm * e.abs()).contiguous()       # init_vis_t at the pool points
+            pool.vis_t_minus = vtm0.clone()                        # (the forward overwrites its state argument)
+        pool.forward(self.Re, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=False)
+        rank = torch.distributed.get_rank(self.pg) if self.world_size > 1 else 0
+        u = np.random.default_rng([int(seed), self._resample_calls, rank]).random()     # (calls counted per engine)
+        self._resample_calls += 1
+        w4 = self.eq4_weight if self.net_e is not None else 0.0
+        idx, S = resample_select(pool, w4, k, c, u, f.n, self._pool_scratch)
+        if not math.isfinite(S):
+            raise FloatingPointError("resample: the pool's residual sum is %r (non-finite residual or coordinate in the "
+                                     "pool); the collocation set is unchanged" % S)
+        chunks = list(zip(f.bounds, f.chunks)) if isinstance(f, ChunkedResidual) else [((0, f.n), f)]
+        src = dict(x=pool.x, y=pool.y, w=self._pool_w, vtm=vtm0)
+        w_sums = torch.zeros(len(chunks), dtype=torch.float64, device=self.device) if f.w is not None else None
+        for j, ((lo, hi), ck) in enumerate(chunks):
+            dst = dict(x=ck.x, y=ck.y, w=ck.w, vtm=ck.vis_t_minus)
+            resample_gather(idx, lo, hi, pool.n, src, dst, self._pool_scratch,
+                            None if w_sums is None else w_sums[j:j + 1])
+            if self.plan_e is not None:
+                self.plan_e.x[lo:hi].copy_(ck.x)
+                self.plan_e.y[lo:hi].copy_(ck.y)
+        if w_sums is not None:
+            total = 0.0
+            for v in w_sums.cpu().tolist():          # chunk order
+                total += v
+            if self.world_size > 1:
+                t = torch.tensor([total], dtype=torch.float64, device=self.device)
+                torch.distributed.all_reduce(t, group=self.pg)
+                total = float(t.item())
+            mean = total / self.n_f_global
+            for _, ck in chunks:                     # mean 1 over the global set (cavity_data._compute_sdf_weights)
+                ck.w.copy_((ck.w.double() / mean).float())
+            if isinstance(f, ChunkedResidual):
+                f.w.copy_(torch.cat([ck.w for _, ck in chunks]))
+        return idx
+
+    def collocation_points(self):
+        """(x, y, w) of the live collocation set as fresh device tensors (w None without weights)."""
+        f = self.plan_f
+        if isinstance(f, ChunkedResidual):
+            return (torch.cat([c.x for c in f.chunks]), torch.cat([c.y for c in f.chunks]),
+                    None if f.w is None else f.w.clone())
+        return f.x.clone(), f.y.clone(), None if f.w is None else f.w.clone()
 
     # ---- one loss + gradient evaluation ----
     def loss_and_grad(self):

@@ -112,6 +112,7 @@ class PysicsInformedNeuralNetwork:
         self.opt = AdamHandle(learning_rate) if not opt else opt
         self.x_f = self.y_f = self.x_b = None
         self._stash_bc = None
+        self._resampling = dict(every=0, k=1.0, c=1.0, seed=0)
 
         if self.rank == 0:
             print(f"Distributed training setup:")
@@ -160,6 +161,32 @@ class PysicsInformedNeuralNetwork:
         self.engine.set_collocation(xf, yf, weights=w, n_global=total)     # includes init_vis_t (:184)
         if self.rank == 0:
             print(f"GPU {self.rank}: Processing {hi - lo} equation points out of {total} total")
+
+    # ---------------------------------------------------------------- residual-based resampling
+    def set_resample_pool(self, X, weights=None):
+        """X = (x, y) candidate points, sharded over the ranks like set_eq_training_data: every rank resamples its
+        collocation shard from its own pool shard.  weights (pool SDF weights) exactly when the collocation set has
+        weights."""
+        total = X[0].shape[0]
+        lo, hi = self._shard(total)
+        self.engine.set_resample_pool(_col(X[0])[lo:hi], _col(X[1])[lo:hi],
+                                      None if weights is None else _col(weights)[lo:hi])
+
+    def resample_collocation(self, k=1.0, c=1.0, seed=None):
+        """Redraw the collocation points from the pool with density |r|^k / mean|r|^k + c (PinnEngine.resample);
+        seed None: the one given to set_resampling.  Refreshes x_f, y_f and eq_weights; returns the local pool indices."""
+        self.engine.alpha_evm = float(self.alpha_evm)
+        idx = self.engine.resample(k, c, self._resampling["seed"] if seed is None else seed)
+        x, y, w = self.engine.collocation_points()
+        self.x_f, self.y_f = x.reshape(-1, 1), y.reshape(-1, 1)
+        self.eq_weights = w
+        return idx
+
+    def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
+        """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
 
     def init_vis_t(self):
         self.engine.alpha_evm = float(self.alpha_evm)
@@ -284,7 +311,10 @@ class PysicsInformedNeuralNetwork:
             self.log_interval = 100
         self.freeze_evm_net(0)
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
+        rs = self._resampling
         for epoch_id in range(num_epoch):
+            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
+                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
             self.global_step += 1
             self._apply_freeze_schedule(epoch_id)
             interval = self.log_interval if self.log_interval > 0 else 100

@@ -94,6 +94,7 @@ class PysicsInformedNeuralNetwork:
         self.x_f = self.y_f = self.x_b = self.y_b = self.u_b = self.v_b = None
         self._terms = None
         self.log_every, self.save_every = 1000, 10000
+        self._resampling = dict(every=0, k=1.0, c=1.0, seed=0)
 
     # ---------------------------------------------------------------- data
     def set_boundary_data(self, X=None, time=False):
@@ -107,6 +108,25 @@ class PysicsInformedNeuralNetwork:
         self.x_f = torch.as_tensor(_col(X[0])).reshape(-1, 1).to(self.device)
         self.y_f = torch.as_tensor(_col(X[1])).reshape(-1, 1).to(self.device)
         self.engine.set_collocation(_col(X[0]), _col(X[1]))
+
+    # ---------------------------------------------------------------- residual-based resampling
+    def set_resample_pool(self, X, weights=None):
+        """X = (x, y) candidate points for resample_collocation (e.g. a larger LHS draw than the collocation set)."""
+        self.engine.set_resample_pool(_col(X[0]), _col(X[1]), None if weights is None else _col(weights))
+
+    def resample_collocation(self, k=1.0, c=1.0, seed=None):
+        """Redraw the collocation points from the pool with density |r|^k / mean|r|^k + c (PinnEngine.resample);
+        seed None: the one given to set_resampling.  Returns the selected pool indices."""
+        idx = self.engine.resample(k, c, self._resampling["seed"] if seed is None else seed)
+        x, y, _ = self.engine.collocation_points()
+        self.x_f, self.y_f = x.reshape(-1, 1), y.reshape(-1, 1)
+        return idx
+
+    def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
+        """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
 
     def set_optimizers(self, opt):
         self.opt = opt
@@ -184,7 +204,10 @@ class PysicsInformedNeuralNetwork:
         print('--------')
         print(num_epoch)
         print('--------')
+        rs = self._resampling
         while epoch_id < num_epoch:
+            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
+                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
             lr = self.opt.param_groups[0]['lr']
             log_now = self.log_every and epoch_id % self.log_every == 0
             save_now = self.save_every and epoch_id % self.save_every == 0

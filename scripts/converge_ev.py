@@ -9,6 +9,7 @@ viscosity state restarts from alpha*|e| as at the start of a run).
 
     python scripts/converge_ev.py --re 3000 --dns tests/golden/dns/cavity_Re3000_256_Uniform.mat \
         --out gpurun_out/conv_ev --first 1 --last 2 [--resume DIR] [--epochs-scale 0.5]
+        [--resample-every 5000 --pool 1000000 --rs-k 1 --rs-c 1]   (residual-based resampling, off by default)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,6 +32,12 @@ def main():
     ap.add_argument("--nf", type=int, default=120000)
     ap.add_argument("--layers", type=int, default=6)
     ap.add_argument("--hidden", type=int, default=80)
+    ap.add_argument("--resample-every", type=int, default=0,
+                    help="> 0: redraw the collocation points from a pool every this many steps of each stage (DESIGN.md 7.1)")
+    ap.add_argument("--pool", type=int, default=1000000, help="pool points (same pipeline as the collocation set)")
+    ap.add_argument("--rs-k", type=float, default=1.0)
+    ap.add_argument("--rs-c", type=float, default=1.0)
+    ap.add_argument("--rs-seed", type=int, default=0)
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     os.makedirs(a.out, exist_ok=True)
@@ -52,6 +59,13 @@ def main():
     xf, yf = loader.loading_training_data()
     P.set_coordinate_transform(loader.get_coord_scale())
     P.set_eq_training_data(X=(xf, yf), weights=loader.get_sdf_weights())
+    if a.resample_every > 0:      # drawn after the collocation set: the set and the init are those of the run without
+        pool = cavity.EvDataLoader(path="./datasets/", N_f=a.pool, N_b=1000, sort_training_points=False,
+                                   sdf_weighting=SimpleNamespace(enabled=True, min_weight=0.2, decay=5.0),
+                                   coord_transform=False)
+        pool.loading_boundary_data()
+        P.set_resample_pool(X=pool.loading_training_data(), weights=pool.get_sdf_weights())
+        P.set_resampling(every=a.resample_every, k=a.rs_k, c=a.rs_c, seed=a.rs_seed)
     P.clear_supervised_data(); P.set_supervised_loss_weight(0.0)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
@@ -68,7 +82,9 @@ def main():
         rec = dict(stage=k, alpha_evm=alpha, lr=lr, steps=n, seconds=round(dt, 1), ms_per_step=round(1e3 * dt / n, 4),
                    loss=float(P.loss), loss_b=float(P.loss_b), loss_e=float(P.loss_e),
                    err_u=float(eu), err_v=float(ev), Re=a.re, net="%dx%d+4x40" % (a.layers, a.hidden), N_f=a.nf,
-                   precision=os.environ.get("NSFNET_PRECISION", "fp32"))
+                   precision=os.environ.get("NSFNET_PRECISION", "fp32"),
+                   resample=(dict(every=a.resample_every, pool=a.pool, k=a.rs_k, c=a.rs_c, seed=a.rs_seed)
+                             if a.resample_every > 0 else None))
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
