@@ -1,7 +1,8 @@
 // Role-split forward and reverse sweep of one tile in ONE kernel (residual mode, MSE seeds, hidden 256): the phases of
-// fwd_bf16_split.hip and bwd_bf16_split.hip (see there for the schedule, the shared K-region image and the reference
-// lines replaced), run back to back per tile, so the last hidden layer's saved activations S_{L-1} never leave the
-// registers.  S_{L-1} has one reader, the reverse sweep's first epilogue (dW_l needs a_{l-1}; the output-layer gradient
+// split_phases.h, which fwd_bf16_split.hip and bwd_bf16_split.hip run as two launches (fwd_bf16_split.hip describes the
+// schedule and the shared K-region image; the two kernels name the reference lines replaced), run back to back per
+// tile, so the last hidden layer's saved activations S_{L-1} never leave the registers (KEEP in split_phases.h).
+// S_{L-1} has one reader, the reverse sweep's first epilogue (dW_l needs a_{l-1}; the output-layer gradient
 // is summed inside the reverse sweep), and the MSE seed 2 alpha_e c_k / N is known before the forward runs, so nothing
 // global separates a tile's forward from its reverse sweep.
 //
@@ -22,8 +23,7 @@
 // the reverse sweep's output-adjoint block exists; the commit sink of the lanes that own no accumulator slot is the
 // unused fourth output row of the dW_out accumulator.
 #include "kernels.h"
-#include "bf16_util.h"
-#include "reduce_util.h"
+#include "split_phases.h"
 
 template <int HP>
 struct FusedLds {
@@ -35,14 +35,10 @@ struct FusedLds {
 
 template <int HP, int TERMS>
 __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, BwdArgs a) {
-  static_assert(HP == 256, "four waves x 64 features per group");
   using G = FusedLds<HP>;
-  using XI = typename G::XI;
-  constexpr int GT = HP, KS = HP / 16, PPL = 32, COLS = 128;
-  constexpr int RING = 2, WPRE = RING - 1, SQ = 2;        // weight ring, S quads requested ahead (the split pair's defaults)
-  constexpr size_t PLQ = (size_t)(HP / 4) * PPL;          // f32x4 per plane of S / Z-bar
+  using SW = SplitWave<HP, TERMS>;
+  constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-  unsigned char* const X = ldsb;
   float* const part = reinterpret_cast<float*>(ldsb + G::X_BYTES);
   float* const woutL = part + G::PART_F;                  // [3][HP]
   float* const w0L = woutL + 3 * HP;                      // [w0x | w0y | b0][HP]
@@ -62,210 +58,24 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
   float lsum[4] = {0.f, 0.f, 0.f, 0.f};
   float dbo[3] = {0.f, 0.f, 0.f};
 
-  auto qbase = [&](int fb, int g) { return 64 * (2 * fb + (g >> 1)) + 16 * w + 8 * (g & 1); };
-#define PHASE_LANE_F()                                 \
-  int lane = lane0;                                    \
-  asm volatile("" : "+v"(lane));                       \
-  const int col = lane & 31, h = lane >> 5;            \
-  (void)col; (void)h
-#define E_SB() __builtin_amdgcn_sched_barrier(0)
-
-  f32x16 acc[2][4];                       // [feature block][stream]
-  u32x2 st[2][4][2];                      // parked epilogue output of one region: [quad][stream][hi | lo]
-  u32x4 skeep[8][3];                      // S_{L-1} of the tile, 24-bit quads in the spill's plane order (XA -> XB)
-  u32x4 sq[SQ + 1][3];                    // saved-activation quads in flight (reverse sweep)
-  bool have_parked = false;
+  SW sw(ldsb, P, woutL, w0L, w, lane0);
 
   // ---- bias quad of layer l from the prepared buffer (uniform address: scalar loads, no wait on the spill stores) ----
-  auto bias4 = [&](int l, int fb, int g, int h) {
-    typedef __attribute__((address_space(4))) const f32x4 cf32x4;
-    const cf32x4* bp = (const cf32x4*)(uintptr_t)(P + prep_b(HP, l) + qbase(fb, g));
-    const f32x4 b0 = bp[0], b1 = bp[1];
-    return h ? b1 : b0;
-  };
-  auto dump_kp = [&](int fb, int g0, int k, int p, int col, int h) {
-    const int off = XI::chunk_off(col, qbase(fb, g0 + k) >> 3) + 8 * h;
-    *reinterpret_cast<u32x2*>(X + p * XI::PLANE * 2 + off) = st[k][p][0];
-    if (TERMS == 3) *reinterpret_cast<u32x2*>(X + XI::HALF * 2 + p * XI::PLANE * 2 + off) = st[k][p][1];
-  };
-  auto dump_k = [&](int fb, int g0, int k, int col, int h) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) dump_kp(fb, g0, k, p, col, h);
-  };
-  auto dump = [&](int fb, int g0, int col, int h) { dump_k(fb, g0, 0, col, h); dump_k(fb, g0, 1, col, h); };
-
-  u32x4 wh[2][RING], wl[2][RING];
-  typedef __attribute__((address_space(1))) u32x4 gu32x4;
-  auto w_lane = [&](int col, int h) { return ((2 * (col >> 4) + (w >> 1)) * KS) * 64 + 16 * (w & 1) + (col & 15) + 32 * h; };
-  auto wload = [&](size_t poff, int s, int wlane) {      // poff: prep_wf (forward) or prep_wtf (reverse) of the layer
-    const gu32x4* const wf = reinterpret_cast<const gu32x4*>(pin_base(reinterpret_cast<const u32x4*>(P + poff)));
-#pragma unroll
-    for (int fb = 0; fb < 2; ++fb) {
-      wh[fb][s % RING] = (wf + (size_t)fb * 4 * KS * 64 + s * 64)[wlane];
-      if (TERMS == 3) wl[fb][s % RING] = (wf + (size_t)(HP * HP / 8) + (size_t)fb * 4 * KS * 64 + s * 64)[wlane];
-    }
-  };
-  auto quad_o = [&](int qq, int h) { return qbase(qq >> 2, qq & 3) + 4 * h; };
-  auto sload = [&](const float* Sl, int qq, int col, int h) {
-    const int o = quad_o(qq, h);
-    const unsigned so = (unsigned)(((o - 4 * h) >> 2) + h) * PPL + col;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      sq[qq % (SQ + 1)][k] = __builtin_bit_cast(u32x4, __builtin_nontemporal_load(pin_base(reinterpret_cast<const f32x4*>(Sl) + k * PLQ) + so));
-  };
-  auto unpack_plane = [&](const u32x4 (&pk)[3], int p) {
-    return unpack24(u32x2{pk[p >> 1][2 * (p & 1)], pk[p >> 1][2 * (p & 1) + 1]}, pk[2][p]);
+  auto bias = [&](int l) {
+    return [&, l](int fb, int g, int, int h) {
+      typedef __attribute__((address_space(4))) const f32x4 cf32x4;
+      const cf32x4* bp = (const cf32x4*)(uintptr_t)(P + prep_b(HP, l) + sw.qbase(fb, g));
+      const f32x4 b0 = bp[0], b1 = bp[1];
+      return h ? b1 : b0;
+    };
   };
   // The dummy partner of an odd tile count reads its OWN S (the +1 scratch block its forward just wrote), not tile 0's as
   // bwd_bf16_split.hip does: here tile 0 may still be in its forward on another workgroup.  Its output adjoints are zero,
   // so its z-bars are zeros either way.
-  auto s_layer = [&](int tile, int l) { return a.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
-
-  // ---------------- M / G phase: acc <- W x image, region q in quarter q (both sweeps; fwd_bf16_split.hip) ----------------
-  // REV: reverse sweep (W_l^T; parked region 3 dumped only after an E' phase that parked; pre_s: the next E' phase's
-  // first S quads requested in the last k-steps)
-  auto mphase = [&](auto REV, int l, int tile, auto PRE_S) {
-    constexpr bool rev = decltype(REV)::value, pre_s = decltype(PRE_S)::value;
-    PHASE_LANE_F();
-    const int wlane = w_lane(col, h);
-    const size_t poff = rev ? prep_wtf(HP, l) : prep_wf(HP, l);
-    u32x4 bh[2], bo[2];
-    const float* const Snext = rev && pre_s ? s_layer(tile, l - 1) : nullptr;
-    auto bload = [&](int u) {
-      const int s = u >> 2, j = u & 3;
-      const int off = XI::chunk_off(col, 2 * s + h);
-      bh[u & 1] = *reinterpret_cast<const u32x4*>(X + j * XI::PLANE * 2 + off);
-      if (TERMS == 3) bo[u & 1] = *reinterpret_cast<const u32x4*>(X + XI::HALF * 2 + j * XI::PLANE * 2 + off);
-    };
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (rev && q == 0 && have_parked) dump(1, 2, col, h);
-      bload(16 * q);
-#pragma unroll
-      for (int u = 16 * q; u < 16 * q + 16; ++u) {
-        const int s = u >> 2, j = u & 3;
-        if (j == 0 && s + WPRE < KS) wload(poff, s + WPRE, wlane);
-        if (rev && pre_s && u >= 4 * (KS - WPRE) && u < 4 * (KS - WPRE) + SQ) sload(Snext, u - 4 * (KS - WPRE), col, h);
-        if ((u & 15) != 15) bload(u + 1);
-        if (!rev && q == 0 && (u & 1)) dump_kp(1, 2, u >> 3, (u >> 1) & 3, col, h);
-#pragma unroll
-        for (int fb = 0; fb < 2; ++fb) {
-          if (s == 0) {
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[fb][j] = TERMS == 3 ? MFMA_Q(0, wh[fb][0], bo[u & 1], zero) : MFMA_Q(0, wh[fb][0], bh[u & 1], zero);
-            if (TERMS == 3) {
-              acc[fb][j] = MFMA_Q(1, wl[fb][0], bh[u & 1], acc[fb][j]);
-              acc[fb][j] = MFMA_Q(0, wh[fb][0], bh[u & 1], acc[fb][j]);
-            }
-          } else {
-            if (TERMS == 3) {
-              acc[fb][j] = MFMA_Q(s, wh[fb][s % RING], bo[u & 1], acc[fb][j]);
-              acc[fb][j] = MFMA_Q(s + 1, wl[fb][s % RING], bh[u & 1], acc[fb][j]);
-            }
-            acc[fb][j] = MFMA_Q(s, wh[fb][s % RING], bh[u & 1], acc[fb][j]);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __syncthreads();
-    }
-    have_parked = false;
-  };
-
-  // ---------------- forward E phase of layer lE (fwd_bf16_split.hip) ----------------
-  // EK: 0 = layer 0, 1 = hidden layer 1..L-2 (S spilled), 2 = last hidden layer = XA (output layer, S kept in skeep)
-  auto fphase = [&](auto EKIND, int lE, int tileE) {
-    constexpr int EK = decltype(EKIND)::value;
-    constexpr bool last = EK == 2, first = EK == 0;
-    PHASE_LANE_F();
-    float* const Sl = fa.S + spill_off(tileE, lE, L, a.sl0, a.sblk, (size_t)HP * COLS);
-    float po[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) po[c][s] = 0.f;
-    float px = 0.f, py = 0.f;
-    if (first) {
-      const int pt = tileE * PPL + col;
-      px = pt < a.n ? a.x[pt] : 0.f; py = pt < a.n ? a.y[pt] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int fb = q >> 1;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int g = 2 * (q & 1) + k, o = qbase(fb, g) + 4 * h;
-        if (!last && q == 3 && k == 1) {      // first weight k-steps of M_{lE+1}
-#pragma unroll
-          for (int s = 0; s < WPRE; ++s) wload(prep_wf(HP, lE + 1), s, w_lane(col, h));
-        }
-        f32x4 av[4], sv[4];
-        f32x4 b4, wx4, wy4;
-        if (first) {
-          wx4 = *reinterpret_cast<const f32x4*>(w0L + o); wy4 = *reinterpret_cast<const f32x4*>(w0L + HP + o);
-          b4 = *reinterpret_cast<const f32x4*>(w0L + 2 * HP + o);
-        } else {
-          b4 = bias4(lE, fb, g, h);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          float z, zx, zy, zd;
-          if (first) {
-            z = fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e])); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
-          } else {
-            z = acc[fb][0][r] + b4[e]; zx = acc[fb][1][r]; zy = acc[fb][2][r]; zd = acc[fb][3][r];
-          }
-          const float t = fast_tanh(z);
-          const float d1 = 1.f - t * t;
-          const float d2 = -2.f * t * d1;
-          av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * (zx * zx + zy * zy) + d1 * zd;
-          sv[0][e] = t; sv[1][e] = zx; sv[2][e] = zy; sv[3][e] = zd;
-          E_SB();
-        }
-        const unsigned so = (unsigned)(((o - 4 * h) >> 2) + h) * PPL + col;
-        u32x4 pk[3];
-        if (q > 0 && !last) dump_k((q - 1) >> 1, 2 * ((q - 1) & 1), k, col, h);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          if (!last) {
-            split4(av[p][0], av[p][1], av[p][2], av[p][3], st[k][p][0], st[k][p][1]);
-          } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const f32x4 wo = *reinterpret_cast<const f32x4*>(woutL + c * HP + o);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) po[c][p] = fmaf(wo[e], av[p][e], po[c][p]);
-            }
-          }
-          if (!first) {      // 24-bit format (bf16_util.h pack24): spilled, or kept for XB
-            u32x2 hi24; unsigned lo24;
-            pack24(sv[p], hi24, lo24);
-            pk[p >> 1][2 * (p & 1)] = hi24[0]; pk[p >> 1][2 * (p & 1) + 1] = hi24[1]; pk[2][p] = lo24;
-            if (!last) {
-              if (p & 1) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[p >> 1]), pin_base(reinterpret_cast<const f32x4*>(Sl) + (p >> 1) * PLQ) + so);
-              if (p == 3) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[2]), pin_base(reinterpret_cast<const f32x4*>(Sl) + 2 * PLQ) + so);
-            }
-          }
-          if (last) asm volatile("" : "+v"(po[0][p]), "+v"(po[1][p]), "+v"(po[2][p]));
-          E_SB();
-        }
-        if (last) {
-#pragma unroll
-          for (int kk = 0; kk < 3; ++kk) skeep[2 * q + k][kk] = pk[kk];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (last && q == 3) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-            partG[(w * 12 + c * 4 + s) * 32 + col] = po[c][s] + __shfl_xor(po[c][s], 32, 64);
-      }
-      __syncthreads();
-    }
-  };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto Sw_of = [&](int tile, int l) { return fa.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto none = [](auto&&...) {};      // no kernel work in this hook
 
   // ---------------- point stage + output adjoints of column col (start of XB) ----------------
   // Every lane of the group computes its column's point (the output adjoints are needed by all of them); lanes 0-31 of
@@ -327,7 +137,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     oc[1][0] = av; oc[1][1] = (r2 * u) * bsc; oc[1][2] = (r2 * v + r3) * bsc; oc[1][3] = -nub * r2 * bsc2;
     oc[2][0] = 0.f; oc[2][1] = r1 * bsc; oc[2][2] = r2 * bsc; oc[2][3] = 0.f;
     // opaque from here on, as the LDS values of bwd_bf16_split.hip are: the compiler then contracts the epilogue's dot
-    // products of them exactly as there (with the zeros and expressions visible it picked other fma pairings: 1-ulp dW_out)
+    // products of them as there (with the zeros and expressions visible it picked other fma pairings: 1-ulp gradients)
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -338,136 +148,22 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     }
   };
 
-  // ---------------- reverse E phase of layer lE (bwd_bf16_split.hip) ----------------
-  // EK: 0 = last hidden layer = XB (point stage first; S from skeep), 1 = layer L-2..1, 2 = layer 0 (recomputed S)
-  auto bphase = [&](auto EKIND, int lE, int tileE, float pxE, float pyE, float vtm_old) {
-    constexpr int EK = decltype(EKIND)::value;
-    constexpr bool first = EK == 0, last = EK == 2;
-    PHASE_LANE_F();
-    const float* const Sl = s_layer(tileE, lE);
-    float* const Zl = a.Zb + spill_off(tileE, lE, L, a.sl0, a.sblk, (size_t)HP * COLS);
-    float oc[3][4];
-    if (first) {
-      if (tileE < a.ntiles) {
-        point_stage(tileE, col, w == 0 && h == 0, vtm_old, oc);
-      } else {      // the dummy partner tile: zero output adjoints
+  // the output adjoints of XB: the point stage of the tile, or zeros for the dummy partner
+  auto seed = [&](int tile, float vtm_old) {
+    return [&, tile, vtm_old](int col, int h, float (&oc)[3][4]) {
+      if (tile < a.ntiles) {
+        point_stage(tile, col, w == 0 && h == 0, vtm_old, oc);
+      } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
           for (int s = 0; s < 4; ++s) { oc[c][s] = 0.f; asm volatile("" : "+v"(oc[c][s])); }
       }
-    }
-    auto commit = [&](int base, int o4, float v) {        // lanes col < 4 of each half own feature o4 + col (reduce_util.h)
-      float* p = col < 4 ? &sgacc[base + o4 + (col & 3)] : &sink[lane];
-      lds_rmw_add(p, v);
     };
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (q > 0 && !last) dump((q - 1) >> 1, 2 * ((q - 1) & 1), col, h);
-      const int fb = q >> 1;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int g = 2 * (q & 1) + k, qq = 2 * q + k, o = quad_o(qq, h);
-        if (!first && !last && qq + SQ < 8) sload(Sl, qq + SQ, col, h);
-        if (!last && qq == 7) {
-#pragma unroll
-          for (int s = 0; s < WPRE; ++s) wload(prep_wtf(HP, lE), s, w_lane(col, h));
-        }
-        f32x4 sc[4];
-        if (last) {
-          const f32x4 wx4 = *reinterpret_cast<const f32x4*>(w0L + o), wy4 = *reinterpret_cast<const f32x4*>(w0L + HP + o);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(w0L + 2 * HP + o);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[0][e] = fast_tanh(fmaf(wx4[e], pxE, fmaf(wy4[e], pyE, b4[e])));
-          sc[1] = wx4; sc[2] = wy4; sc[3] = f32x4{0.f, 0.f, 0.f, 0.f};
-        } else if (first) {
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            sc[p] = unpack_plane(skeep[qq], p);
-            asm volatile("" : "+v"(sc[p]));      // opaque, as the values bwd_bf16_split.hip reads back
-          }
-        } else {
-#pragma unroll
-          for (int p = 0; p < 4; ++p) sc[p] = unpack_plane(sq[qq % (SQ + 1)], p);
-        }
-        f32x4 zq[4], wov[3], dwv[2], wo4[3];
-        if (first) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) wo4[c] = *reinterpret_cast<const f32x4*>(woutL + c * HP + o);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          float ga, gx, gy, gd;
-          if (first) {
-            ga = wo4[0][e] * oc[0][0] + wo4[1][e] * oc[1][0] + wo4[2][e] * oc[2][0];
-            gx = wo4[0][e] * oc[0][1] + wo4[1][e] * oc[1][1] + wo4[2][e] * oc[2][1];
-            gy = wo4[0][e] * oc[0][2] + wo4[1][e] * oc[1][2] + wo4[2][e] * oc[2][2];
-            gd = wo4[0][e] * oc[0][3] + wo4[1][e] * oc[1][3] + wo4[2][e] * oc[2][3];
-          } else {
-            ga = acc[fb][0][r]; gx = acc[fb][1][r]; gy = acc[fb][2][r]; gd = acc[fb][3][r];
-          }
-          const float t = sc[0][e], zx = sc[1][e], zy = sc[2][e], zd = sc[3][e];
-          const float d1 = 1.f - t * t;
-          const float d2 = -2.f * t * d1;
-          const float d3 = -2.f * d1 * (1.f - 3.f * t * t);
-          const float zz = zx * zx + zy * zy;
-          zq[1][e] = d1 * gx + 2.f * d2 * zx * gd;
-          zq[2][e] = d1 * gy + 2.f * d2 * zy * gd;
-          zq[3][e] = d1 * gd;
-          zq[0][e] = d1 * ga + d2 * (zx * gx + zy * gy) + (d3 * zz + d2 * zd) * gd;
-          if (first) {
-            const float ax = d1 * zx, ay = d1 * zy, ad = d2 * zz + d1 * zd;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) wov[c][e] = oc[c][0] * t + oc[c][1] * ax + oc[c][2] * ay + oc[c][3] * ad;
-          }
-          if (last) { dwv[0][e] = zq[0][e] * pxE + zq[1][e]; dwv[1][e] = zq[0][e] * pyE + zq[2][e]; }
-          E_SB();
-        }
-        const int o4 = o;
-        commit(sg_db(HP, lE), o4, sum_cols4<32>(zq[0][0], zq[0][1], zq[0][2], zq[0][3], lane));
-        if (first) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            commit(sg_wout(HP, L) + c * HP, o4, sum_cols4<32>(wov[c][0], wov[c][1], wov[c][2], wov[c][3], lane));
-        }
-        if (last) {
-          commit(sg_w0x(HP, L), o4, sum_cols4<32>(dwv[0][0], dwv[0][1], dwv[0][2], dwv[0][3], lane));
-          commit(sg_w0y(HP, L), o4, sum_cols4<32>(dwv[1][0], dwv[1][1], dwv[1][2], dwv[1][3], lane));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!last) {
-          const unsigned so = (unsigned)(((o - 4 * h) >> 2) + h) * PPL + col;
-          u32x4 pk[3];
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], st[k][p][0], st[k][p][1]);
-            u32x2 hi24; unsigned lo24;
-            pack24(zq[p], hi24, lo24);
-            pk[p >> 1][2 * (p & 1)] = hi24[0]; pk[p >> 1][2 * (p & 1) + 1] = hi24[1]; pk[2][p] = lo24;
-            if (p & 1) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[p >> 1]), pin_base(reinterpret_cast<const f32x4*>(Zl) + (p >> 1) * PLQ) + so);
-            if (p == 3) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[2]), pin_base(reinterpret_cast<const f32x4*>(Zl) + 2 * PLQ) + so);
-            E_SB();
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __syncthreads();
-    }
-    have_parked = !last;
-  };
-  auto idle = [&]() {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) __syncthreads();
   };
 
-  using K0 = std::integral_constant<int, 0>;
-  using K1 = std::integral_constant<int, 1>;
-  using K2 = std::integral_constant<int, 2>;
-  using FWD = std::false_type;
-  using REV = std::true_type;
   const int npairs = (a.ntiles + 1) / 2;
-  if (grp == 1) idle();
+  if (grp == 1) SW::idle();
   for (int pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
     const int tile = 2 * pair + grp;
     // the tile's point and its vis_t_minus entry (read before the owner thread rewrites it in XB)
@@ -477,22 +173,22 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
       px = pt < a.n ? a.x[pt] : 0.f; py = pt < a.n ? a.y[pt] : 0.f;
       vtm_old = (fa.vtm && pt < a.n) ? fa.vtm[pt] : 0.f;
     }
-    fphase(K0{}, 0, tile);
+    sw.template fphase<0, true>(0, tile, nullptr, a.x, a.y, a.n, partG, bias(0), none);
     for (int l = 1; l < L - 1; ++l) {
-      mphase(FWD{}, l, tile, std::false_type{});
-      fphase(K1{}, l, tile);
+      sw.template mphase<false, false>(l, nullptr);
+      sw.template fphase<1, true>(l, tile, Sw_of(tile, l), a.x, a.y, a.n, partG, bias(l), none);
     }
-    mphase(FWD{}, L - 1, tile, std::false_type{});
-    fphase(K2{}, L - 1, tile);                                  // XA
-    bphase(K0{}, L - 1, tile, px, py, vtm_old);                 // XB
+    sw.template mphase<false, false>(L - 1, nullptr);
+    sw.template fphase<2, true>(L - 1, tile, nullptr, a.x, a.y, a.n, partG, bias(L - 1), none);                 // XA
+    sw.template bphase<0, true>(L - 1, L, nullptr, Z_of(tile, L - 1), px, py, sgacc, sink, seed(tile, vtm_old), none);  // XB
     for (int l = L - 1; l >= 2; --l) {
-      mphase(REV{}, l, tile, std::true_type{});
-      bphase(K1{}, l - 1, tile, px, py, 0.f);
+      sw.template mphase<true, true>(l, S_of(tile, l - 1));
+      sw.template bphase<1, true>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, sink, none, none);
     }
-    mphase(REV{}, 1, tile, std::false_type{});
-    bphase(K2{}, 0, tile, px, py, 0.f);
+    sw.template mphase<true, false>(1, nullptr);
+    sw.template bphase<2, true>(0, L, nullptr, Z_of(tile, 0), px, py, sgacc, sink, none, none);
   }
-  if (grp == 0) idle();
+  if (grp == 0) SW::idle();
   // ---------------- flush: loss partials (fwd_split order), then dbo and the skinny gradients (bwd_split order) ----------------
   float* red = reinterpret_cast<float*>(ldsb);
   __syncthreads();
