@@ -6,6 +6,7 @@
 // on hardware by tests/micro/mfma_bf16_layout.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kernels.h"
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -72,6 +73,17 @@ __device__ __forceinline__ void pack24_quad(const f32x4& x0, const f32x4& x1, co
 }
 __device__ __forceinline__ f32x4 unpack24_plane(const u32x4 (&pk)[3], int p) {
   return unpack24(u32x2{pk[p >> 1][2 * (p & 1)], pk[p >> 1][2 * (p & 1) + 1]}, pk[2][p]);
+}
+// plane p alone, for epilogues that produce a quad one plane at a time ...
+__device__ __forceinline__ void pack24_plane(const f32x4& x, int p, u32x4 (&pk)[3]) {
+  u32x2 h; unsigned l;
+  pack24(x, h, l);
+  pk[p >> 1][2 * (p & 1)] = h[0]; pk[p >> 1][2 * (p & 1) + 1] = h[1]; pk[2][p] = l;
+}
+// ... and, after plane p, the 16-byte planes of pk it completed into the block at dst (planes plq f32x4 apart)
+__device__ __forceinline__ void store24_planes(float* dst, size_t plq, unsigned so, int p, const u32x4 (&pk)[3]) {
+  if (p & 1) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[p >> 1]), pin_base(reinterpret_cast<const f32x4*>(dst) + (p >> 1) * plq) + so);
+  if (p == 3) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[2]), pin_base(reinterpret_cast<const f32x4*>(dst) + 2 * plq) + so);
 }
 
 // tanh for the bf16 modes: 1 - 2/(exp(2z)+1) on v_exp_f32 / v_rcp_f32 (both 1 ulp: abs. error

@@ -104,14 +104,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
     prev_tile = tile;
   }
   for (int q = 0; q < 4; ++q) {                       // drain: point stage of the last tile
-    if (q == 0 && prev_tile >= 0)
-      for (int i2 = gtid; i2 < 3 * COLS; i2 += GT) {
-        const int c3 = i2 / COLS, cc = i2 % COLS;
-        float s = cc < PPL ? P[prep_bout(HP, L) + c3] : 0.f;
-        for (int ww = 0; ww < 4; ++ww) s += partG[(ww * 12 + c3 * 4 + cc / PPL) * 32 + (cc % PPL)];
-        outvG[c3 * COLS + cc] = s;
-      }
-    if (q == 1 && prev_tile >= 0 && prev_tile < a.ntiles) residual_point_stage<PPL, COLS>(a, outvG, prev_tile, gtid, npad, lsum);
+    pstage(q, prev_tile);
     __syncthreads();
   }
   if (grp == 0) SW::idle();

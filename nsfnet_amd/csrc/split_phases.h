@@ -84,17 +84,6 @@ struct SplitWave {
     for (int k = 0; k < 3; ++k)
       sq[qq % (SQ + 1)][k] = __builtin_bit_cast(u32x4, __builtin_nontemporal_load(pin_base(reinterpret_cast<const f32x4*>(Sl) + k * PLQ) + so));
   }
-  // plane p of a quad into the 24-bit spill format (bf16_util.h pack24): hi16 of streams 0-1, of streams 2-3, lo8 of all four
-  __device__ __forceinline__ void pack_plane(const f32x4& v, int p, u32x4 (&pk)[3]) {
-    u32x2 hi24; unsigned lo24;
-    pack24(v, hi24, lo24);
-    pk[p >> 1][2 * (p & 1)] = hi24[0]; pk[p >> 1][2 * (p & 1) + 1] = hi24[1]; pk[2][p] = lo24;
-  }
-  // ... and each 16-byte plane of it into the block at Sl once complete
-  __device__ __forceinline__ void store_planes(float* Sl, unsigned so, int p, const u32x4 (&pk)[3]) {
-    if (p & 1) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[p >> 1]), pin_base(reinterpret_cast<const f32x4*>(Sl) + (p >> 1) * PLQ) + so);
-    if (p == 3) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[2]), pin_base(reinterpret_cast<const f32x4*>(Sl) + 2 * PLQ) + so);
-  }
   __device__ __forceinline__ static void idle() {
 #pragma unroll
     for (int q = 0; q < 4; ++q) __syncthreads();
@@ -227,8 +216,8 @@ struct SplitWave {
           // (layer 0 is not spilled: t = tanh(w0x x + w0y y + b0), z_x = w0x, z_y = w0y, z_D = 0 cost the reverse sweep
           // and the dW kernel one FMA pair and one tanh to recompute - a sixth of the spill at 6 layers)
           if (!first) {
-            pack_plane(sv[p], p, pk);
-            if (!(KEEP && last)) store_planes(Sl, so, p, pk);
+            pack24_plane(sv[p], p, pk);
+            if (!(KEEP && last)) store24_planes(Sl, PLQ, so, p, pk);
           }
           if (last) asm volatile("" : "+v"(po[0][p]), "+v"(po[1][p]), "+v"(po[2][p]));   // (no sinking behind the loop)
           __builtin_amdgcn_sched_barrier(0);
@@ -357,8 +346,8 @@ struct SplitWave {
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
             split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], st[k][p][0], st[k][p][1]);
-            pack_plane(zq[p], p, pk);
-            store_planes(Zl, so, p, pk);
+            pack24_plane(zq[p], p, pk);
+            store24_planes(Zl, PLQ, so, p, pk);
             __builtin_amdgcn_sched_barrier(0);
           }
         }

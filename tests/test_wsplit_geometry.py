@@ -1,8 +1,9 @@
-"""CPU model of the index arithmetic of the wide role-split sweeps (nsfnet_amd/csrc/fwd_bf16_wsplit.hip, bwd_bf16_wsplit.hip):
-which (wave, block, quad, lane row, element) owns which feature, where a feature's 8-element chunk sits in the shared image
-for each group (the last K region has one copy per group), and the order in which the reverse sweep walks a phase's
-register quads.  The formulas are restated here and the source is checked to still contain them, so a changed constant
-fails on the CPU before it reaches a GPU (the end-to-end statement is tests/test_wide_split_kernels.py)."""
+"""CPU model of the index arithmetic of the wide role-split sweeps (nsfnet_amd/csrc/wsplit_phases.h, the phase bodies of
+fwd_bf16_wsplit.hip and bwd_bf16_wsplit.hip): which (wave, block, quad, lane row, element) owns which feature, where a
+feature's 8-element chunk sits in the shared image for each group (the last K region has one copy per group), and the
+order in which the reverse sweep walks a phase's register quads.  The formulas are restated here and the source is checked
+to still contain them, so a changed constant fails on the CPU before it reaches a GPU (the end-to-end statement is
+tests/test_wide_split_kernels.py)."""
 import os
 
 import pytest
@@ -18,17 +19,18 @@ def geo(HP):
     return dict(NB=NB, MQ=MQ, KS=HP // 16, LASTK=LASTK, LASTN=HP - LASTK, RSE=512)
 
 
-def test_source_still_states_the_modelled_formulas():
-    f = open(os.path.join(CSRC, "fwd_bf16_wsplit.hip")).read()
-    b = open(os.path.join(CSRC, "bwd_bf16_wsplit.hip")).read()
-    for src in (f, b):
-        assert "NB = HP / 32, MQ = (NB + 3) / 4, KS = HP / 16" in src
-        assert "(NB - w + 3) / 4" in src
-        assert "(o >> 3) + ((o >= G::LASTK && g) ? G::LASTN / 8 : 0)" in src
-        assert "XI::RSE - HP >= LASTN" in src
-    assert "32 * (4 * bq + w) + 8 * (k + 2 * hi) + 4 * h" in f and "32 * (4 * bq + w) + 8 * (k + 2 * hi) + 4 * h" in b
-    assert "i < 6 ? ((i % 3) == 2 ? MQ - 1 : i / 3) : 2 + (i - 6) / 2" in b
-    assert "i < 6 ? ((i % 3) == 2 ? i / 3 : i % 3) : (i - 6) % 2" in b
+def test_shared_header_states_the_modelled_formulas():
+    hdr = open(os.path.join(CSRC, "wsplit_phases.h")).read()
+    for name in ("fwd_bf16_wsplit.hip", "bwd_bf16_wsplit.hip"):
+        assert '#include "wsplit_phases.h"' in open(os.path.join(CSRC, name)).read()
+    assert "NB = HP / 32, MQ = (NB + 3) / 4, KS = HP / 16" in hdr
+    assert "(NB - w + 3) / 4" in hdr
+    assert "(o >> 3) + ((o >= LASTK && grp) ? LASTN / 8 : 0)" in hdr
+    assert "img_chunk(16 * s) + h" in hdr
+    assert "XI::RSE - HP >= LASTN" in hdr
+    assert "32 * (4 * bq + w) + 8 * (k + 2 * hi) + 4 * h" in hdr
+    assert "i < 6 ? ((i % 3) == 2 ? MQ - 1 : i / 3) : 2 + (i - 6) / 2" in hdr
+    assert "i < 6 ? ((i % 3) == 2 ? i / 3 : i % 3) : (i - 6) % 2" in hdr
 
 
 @pytest.mark.parametrize("HP", SUPPORTED)
