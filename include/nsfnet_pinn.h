@@ -183,6 +183,39 @@ int pinn_resample_gather(const int64_t* idx, int64_t lo, int64_t hi, int64_t n_p
                          float* dst_x, float* dst_y, float* dst_w, float* dst_vtm,
                          void* scratch, double* w_sum, void* stream);
 
+/* ---- L-BFGS direction (compact representation) --------------------------------------
+ * No reference counterpart (its authors' next step: "L-BFGS integration in Stage 3",
+ * ev-NSFnet/AGENTS.md:73).  The device half of torch.optim.LBFGS.step: the history of pairs
+ * s = t_prev d_prev, y = g - g_prev, the inverse-Hessian direction d = -H g and the scalars the
+ * host-side line search needs.  A pair enters only if y's > 1e-10; once `history` pairs are held
+ * the oldest is dropped; gamma (H0 = gamma I) is y's / y'y of the newest accepted pair.  With
+ * S = [s_0 .. s_k-1], Y likewise (oldest first), R_ij = s_i'y_j (i <= j), D = diag(s_i'y_i),
+ * a = S'g, b = Y'g (Byrd, Nocedal & Schnabel 1994):
+ *   u = R^-1 a ,  p = R^-T ((D + gamma Y'Y) u - gamma b) ,  d = -(gamma g + S p - gamma Y u)
+ * which equals the two-loop recursion.  All sums are fp64 in a fixed order (no atomics): the result
+ * is bit-reproducible, and ranks that hold the same g compute the same d and scalars.
+ *
+ * Vectors: n fp32 entries, g and d 16-byte aligned.  history: 1..PINN_LBFGS_MAX_HISTORY.  The
+ * workspace (256-byte aligned, pinn_lbfgs_workspace_bytes; -1 for bad sizes) holds history + 1
+ * slots of s and y (a rejected pair never overwrites a live one), g_prev, R and Y'Y in fp64 and
+ * the reduction partials.  result: 8 doubles (device). */
+#define PINN_LBFGS_MAX_HISTORY 1024
+int64_t pinn_lbfgs_workspace_bytes(int64_t n, int history);
+/* Empty history.  The next pinn_lbfgs_direction must pass t_prev = 0. */
+int pinn_lbfgs_reset(void* ws, int64_t n, int history, void* stream);
+/* One iteration's direction at gradient g.  t_prev = 0: no pair (first iteration, or after a
+ * reset): the history is emptied, gamma = 1 and d = -g.  Otherwise d holds the previous direction
+ * on entry and the pair (t_prev d, g - g_prev) is offered to the history first; t_prev < 0 offers
+ * the pair of a zero step (s = 0: rejected, history and gamma kept, as torch does after a line
+ * search that accepted t = 0).  On return d is
+ * the new direction, g_prev = g, and
+ *   result[0] = g'd   [1] = max|d|   [2] = sum|g|   [3] = max|g|   (max: NaN-propagating)
+ *   result[4] = 1 accepted / 0 rejected / -1 first   [5] = pairs held   [6] = gamma   [7] = y's */
+int pinn_lbfgs_direction(void* ws, int64_t n, int history, const float* g, float t_prev, float* d, double* result,
+                         void* stream);
+/* Line-search probe at a trial gradient g against direction d: result[0..3] as above. */
+int pinn_lbfgs_probe(void* ws, int64_t n, int history, const float* g, const float* d, double* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

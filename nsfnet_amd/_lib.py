@@ -51,6 +51,10 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
     "pinn_resample_gather": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_lbfgs_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "pinn_lbfgs_reset": (c_int, [c_void_p, c_int64, c_int, c_void_p]),
+    "pinn_lbfgs_direction": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "pinn_lbfgs_probe": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -521,4 +521,43 @@ int pinn_resample_gather(const int64_t* idx, int64_t lo, int64_t hi, int64_t n_p
   return rc ? hipfail(rc, "pinn_resample_gather") : 0;
 }
 
+int64_t pinn_lbfgs_workspace_bytes(int64_t n, int history) {
+  if (n < 1 || n > (int64_t)1 << 30 || history < 1 || history > PINN_LBFGS_MAX_HISTORY) return -1;
+  return (int64_t)lbfgs_workspace_bytes((long)n, (long)history);
+}
+
+static int lbfgs_args(const char* what, void* ws, int64_t n, int history) {
+  if (!ws) return fail(-22, "%s: null workspace", what);
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "%s: n must be 1..2^30", what);
+  if (history < 1 || history > PINN_LBFGS_MAX_HISTORY) return fail(-22, "%s: history must be 1..1024", what);
+  if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(-22, "%s: workspace must be 256-byte aligned", what);
+  return 0;
+}
+
+int pinn_lbfgs_reset(void* ws, int64_t n, int history, void* stream) {
+  if (int rc = lbfgs_args("pinn_lbfgs_reset", ws, n, history)) return rc;
+  int rc = launch_lbfgs_reset(ws, (long)n, history, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_lbfgs_reset") : 0;
+}
+
+int pinn_lbfgs_direction(void* ws, int64_t n, int history, const float* g, float t_prev, float* d, double* result,
+                         void* stream) {
+  if (int rc = lbfgs_args("pinn_lbfgs_direction", ws, n, history)) return rc;
+  if (!g || !d || !result) return fail(-22, "pinn_lbfgs_direction: null argument%s");
+  if (reinterpret_cast<uintptr_t>(g) % 16 != 0 || reinterpret_cast<uintptr_t>(d) % 16 != 0)
+    return fail(-22, "pinn_lbfgs_direction: g and d must be 16-byte aligned%s");
+  if (!std::isfinite(t_prev)) return fail(-22, "pinn_lbfgs_direction: t_prev must be finite%s");
+  int rc = launch_lbfgs_direction(ws, (long)n, history, g, t_prev, d, result, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_lbfgs_direction") : 0;
+}
+
+int pinn_lbfgs_probe(void* ws, int64_t n, int history, const float* g, const float* d, double* result, void* stream) {
+  if (int rc = lbfgs_args("pinn_lbfgs_probe", ws, n, history)) return rc;
+  if (!g || !d || !result) return fail(-22, "pinn_lbfgs_probe: null argument%s");
+  if (reinterpret_cast<uintptr_t>(g) % 16 != 0 || reinterpret_cast<uintptr_t>(d) % 16 != 0)
+    return fail(-22, "pinn_lbfgs_probe: g and d must be 16-byte aligned%s");
+  int rc = launch_lbfgs_probe(ws, (long)n, history, g, d, result, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_lbfgs_probe") : 0;
+}
+
 }  // extern "C"

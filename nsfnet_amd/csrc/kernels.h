@@ -162,3 +162,9 @@ int launch_resample_select(long n, const float* fields, long npad, double w4, do
 int launch_resample_gather(const long long* idx, long lo, long hi, long n_pool, const float* sx, const float* sy,
                            const float* sw, const float* sv, float* dx, float* dy, float* dw, float* dv, void* scratch,
                            double* w_sum, hipStream_t s);
+// L-BFGS direction by the compact representation (lbfgs.hip)
+size_t lbfgs_workspace_bytes(long n, long m);
+int launch_lbfgs_reset(void* ws, long n, long m, hipStream_t s);
+int launch_lbfgs_direction(void* ws, long n, long m, const float* g, float t_prev, float* d, double* result,
+                           hipStream_t s);
+int launch_lbfgs_probe(void* ws, long n, long m, const float* g, const float* d, double* result, hipStream_t s);

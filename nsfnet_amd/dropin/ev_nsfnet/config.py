@@ -29,6 +29,9 @@ class TrainingStage:
     epochs: int
     lr: float
     name: str
+    optimizer: str = "adam"             # adam | lbfgs (lbfgs: epochs = L-BFGS iterations, lr = step scale)
+    history_size: int = 100             # lbfgs only
+    line_search: str = "strong_wolfe"   # lbfgs only: strong_wolfe | none
 
 
 @dataclass
@@ -94,7 +97,9 @@ def _fill(obj, data):
             continue
         cur = getattr(obj, key)
         if key == "training_stages":
-            setattr(obj, key, [TrainingStage(float(s["alpha"]), int(s["epochs"]), float(s["lr"]), str(s["name"]))
+            setattr(obj, key, [TrainingStage(float(s["alpha"]), int(s["epochs"]), float(s["lr"]), str(s["name"]),
+                                             str(s.get("optimizer", "adam")), int(s.get("history_size", 100)),
+                                             str(s.get("line_search", "strong_wolfe")))
                                for s in (val or [])])
         elif is_dataclass(cur):
             _fill(cur, val)
@@ -130,6 +135,12 @@ class ConfigManager:
         for st in c.training.training_stages:
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
+            if st.optimizer not in ("adam", "lbfgs"):
+                problems.append("stage %s: optimizer must be adam or lbfgs (got %r)" % (st.name, st.optimizer))
+            if st.line_search not in ("strong_wolfe", "none"):
+                problems.append("stage %s: line_search must be strong_wolfe or none (got %r)" % (st.name, st.line_search))
+            if not 1 <= st.history_size <= 1024:
+                problems.append("stage %s: history_size must be 1..1024" % st.name)
         if problems:
             raise ValueError("invalid configuration: " + "; ".join(problems))
         return True

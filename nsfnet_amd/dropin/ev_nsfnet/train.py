@@ -14,6 +14,7 @@ import torch.distributed as dist
 
 import cavity_data as cavity
 import pinn_solver as psolver
+from nsfnet_amd.pinn_solver import AdamHandle
 from config import ConfigManager
 from logger import get_logger
 
@@ -100,7 +101,16 @@ def main():
                 log.stage(st.name, st.alpha, st.epochs, st.lr)
             PINN.current_stage = st.name
             PINN.set_alpha_evm(st.alpha)
-            PINN.train(num_epoch=max(1, int(st.epochs * args.epochs_scale)), lr=st.lr)
+            epochs = max(1, int(st.epochs * args.epochs_scale))
+            if st.optimizer == "lbfgs":     # one epoch = one L-BFGS iteration of the main net, lr = step scale
+                # max_eval: room for the line search (torch's default for max_iter = 1 is one evaluation)
+                opt = torch.optim.LBFGS(PINN.net.parameters(), lr=st.lr, max_iter=1, max_eval=25,
+                                        history_size=st.history_size,
+                                        line_search_fn=None if st.line_search == "none" else st.line_search)
+                PINN.train(num_epoch=epochs, lr=st.lr, optimizer=opt)
+                PINN.set_optimizers(AdamHandle(st.lr))      # a later adam stage runs Adam again
+            else:
+                PINN.train(num_epoch=epochs, lr=st.lr)
             if rank == 0 and star is not None:
                 PINN.evaluate(*star)
         if rank == 0:

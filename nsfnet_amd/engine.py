@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import lbfgs as _lbfgs
 
 NLOSS = 8
 FLD = dict(u=0, v=1, u_x=2, u_y=3, v_x=4, v_y=5, eq1=6, eq2=7, eq3=8, eq4=9, p=10)
@@ -346,6 +347,75 @@ def grad_reduce(net, plans, grads_out, accumulate=False):
                "pinn_grad_reduce")
 
 
+class LbfgsHistory:
+    """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
+    g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
+
+    def __init__(self, n, history_size, device):
+        self.lib = _lib.load()
+        self.n, self.history_size, self.device = int(n), int(history_size), torch.device(device)
+        nbytes = int(self.lib.pinn_lbfgs_workspace_bytes(self.n, self.history_size))
+        if nbytes < 0:
+            raise ValueError("L-BFGS: bad size (n=%d, history_size=%d; history_size must be 1..1024)"
+                             % (self.n, self.history_size))
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.d = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.x0 = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.result = torch.zeros(8, dtype=torch.float64, device=self.device)
+        self.probe_result = torch.zeros(8, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        _lib.check(self.lib.pinn_lbfgs_reset(_ptr(self.ws), self.n, self.history_size, _stream()), "pinn_lbfgs_reset")
+
+    def direction(self, g, t_prev):
+        """New d at gradient g (t_prev = 0: first iteration).  Device result block [g'd, max|d|, sum|g|, max|g|,
+        accepted, pairs, gamma, y's] (no sync)."""
+        _lib.check(self.lib.pinn_lbfgs_direction(_ptr(self.ws), self.n, self.history_size, _ptr(g), float(t_prev),
+                                                 _ptr(self.d), _ptr(self.result), _stream()), "pinn_lbfgs_direction")
+        return self.result
+
+    def probe(self, g):
+        """[g'd, max|d|, sum|g|, max|g|] of a trial gradient against d (device, no sync)."""
+        _lib.check(self.lib.pinn_lbfgs_probe(_ptr(self.ws), self.n, self.history_size, _ptr(g), _ptr(self.d),
+                                             _ptr(self.probe_result), _stream()), "pinn_lbfgs_probe")
+        return self.probe_result
+
+
+class _EngineSpace:
+    """The vector space of lbfgs.step over a PinnEngine: x = the main net's parameters, g = grads (the kept copies
+    are the whole exchange buffer, so the loss sums of an accepted point come back with its gradient)."""
+
+    def __init__(self, engine, hist):
+        self.e, self.h = engine, hist
+
+    def evaluate(self):
+        e = self.e
+        e.loss_and_grad()
+        loss = e.loss_terms()["loss"]
+        r = self.h.probe(e.grads)
+        v = torch.cat([loss.reshape(1).to(torch.float64), r[:4]]).cpu().tolist()      # the one readback
+        return v[0], v[1], v[4]
+
+    def direction(self, t_prev):
+        if t_prev > 0 and float(np.float32(t_prev)) == 0.0:
+            t_prev = -1.0            # below fp32 range: a zero step (torch's s = t d rounds to 0, the pair is rejected)
+        r = self.h.direction(self.e.grads, t_prev).cpu().tolist()
+        return r[0], r[1], r[2], r[3]
+
+    def save_x(self):
+        self.h.x0.copy_(self.e.net.params)
+
+    def set_x(self, t):
+        torch.add(self.h.x0, self.h.d, alpha=float(t), out=self.e.net.params)     # in place: captured steps stay valid
+        self.e.net.prepare()
+
+    def keep(self):
+        return self.e.flat.clone()
+
+    def restore(self, h):
+        self.e.flat.copy_(h)
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -392,6 +462,9 @@ class PinnEngine:
         # coefficients change, from 2 alpha / N to alpha / ||r_k||, and the norms have to be known first - one
         # host read of the forward sums per evaluation (no hipGraph in this mode).
         self.loss_mode = "MSE"
+        self._lbfgs = None                  # LbfgsHistory (created by the first lbfgs_step)
+        self._lbfgs_state = _lbfgs.LbfgsState()
+        self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
 
     # ---- views into the exchange buffer ----
     @property
@@ -412,6 +485,7 @@ class PinnEngine:
         one activation workspace (ChunkedResidual); default: one pass, everything resident."""
         import os
         self._graphs.clear()      # captured steps hold the old plan's pointers
+        self.lbfgs_reset()
         if chunk_points is None and os.environ.get("NSFNET_CHUNK_POINTS"):
             chunk_points = int(os.environ["NSFNET_CHUNK_POINTS"])
         n = int(np.asarray(x).size)
@@ -426,6 +500,7 @@ class PinnEngine:
 
     def set_boundary(self, x, y, u, v, n_global=None):
         self._graphs.clear()      # captured steps hold the old plan's pointers
+        self.lbfgs_reset()
         self.plan_b = ValuePlan(self.net, x, y, targets=[u, v, None])
         self.n_b_global = int(n_global if n_global is not None else self.plan_b.n)
 
@@ -435,6 +510,7 @@ class PinnEngine:
         branch on that rank, :400): it contributes zero sums and no gradient but still takes part in
         the step's all-reduce and divides by the global counts."""
         self._graphs.clear()      # captured steps hold the old plan's pointers
+        self.lbfgs_reset()
         self._n_p_valid = None
         self.sums[S_SUP:S_SUP + NLOSS].zero_()
         self._sup_stale = False
@@ -503,6 +579,7 @@ class PinnEngine:
         self._resample_calls += 1
         w4 = self.eq4_weight if self.net_e is not None else 0.0
         idx, S = resample_select(pool, w4, k, c, u, f.n, self._pool_scratch)
+        self.lbfgs_reset()                       # the objective changes: the history no longer describes it
         if not math.isfinite(S):
             raise FloatingPointError("resample: the pool's residual sum is %r (non-finite residual or coordinate in the "
                                      "pool); the collocation set is unchanged" % S)
@@ -677,6 +754,44 @@ class PinnEngine:
         self.net.adam_step(self.grads, lr)
         if self.net_e is not None and self.e_trainable:
             self.net_e.adam_step(self.grads_e, lr)
+
+    # ---- L-BFGS ----
+    def lbfgs_reset(self):
+        """Forget the L-BFGS history: the next lbfgs_step starts like a fresh torch.optim.LBFGS."""
+        self._lbfgs_state = _lbfgs.LbfgsState()
+
+    def lbfgs_step(self, lr=1.0, max_iter=20, max_eval=None, tolerance_grad=1e-7, tolerance_change=1e-9,
+                   history_size=100, line_search_fn=None, owner=None):
+        """torch.optim.LBFGS.step(closure) on the full-batch MSE loss of the main net (every rank computes the same
+        direction from the all-reduced gradient).  The state persists across calls.  Ev flavour: the entropy net is
+        frozen for the whole call and vis_t_minus is refreshed from it first (init_vis_t), so every evaluation sees
+        the same viscosity.  Adam's moments and step counters are not touched.  Returns the loss at entry.
+
+        The state belongs to `owner` (the solvers pass their torch.optim.LBFGS object): a call with another owner
+        than the previous one starts fresh, as a new torch.optim.LBFGS does.  With the same owner the state carries
+        on across calls - also across Adam steps or changed loss weights in between, exactly as the state of one
+        torch.optim.LBFGS object does."""
+        if self.loss_mode != "MSE":
+            raise ValueError("L-BFGS optimizes the MSE loss only (loss_mode %r)" % self.loss_mode)
+        _lbfgs.check_knobs(lr, max_iter, max_eval, history_size, line_search_fn)
+        if self._lbfgs is None or self._lbfgs.history_size != int(history_size):
+            self._lbfgs = LbfgsHistory(self.P, int(history_size), self.device)
+            self.lbfgs_reset()
+        if owner is not self._lbfgs_owner:
+            self.lbfgs_reset()
+            self._lbfgs_owner = owner
+        e_trainable = self.e_trainable
+        if self.net_e is not None:
+            self.e_trainable = False
+            self.init_vis_t()
+        try:
+            loss, info = _lbfgs.step(_EngineSpace(self, self._lbfgs), self._lbfgs_state, lr=float(lr),
+                                     max_iter=int(max_iter), max_eval=max_eval, tolerance_grad=float(tolerance_grad),
+                                     tolerance_change=float(tolerance_change), line_search_fn=line_search_fn)
+        finally:
+            self.e_trainable = e_trainable
+        self.lbfgs_info = info
+        return loss
 
     def step(self, lr):
         """loss + gradient + (all-reduce) + Adam.  With NSFNET_GRAPH=1 the launch sequence is captured

@@ -23,7 +23,7 @@ import torch.distributed as dist
 
 from . import engine as _eng
 from .net import FCNet
-from .pinn_solver import AdamHandle, _col, default_device
+from .pinn_solver import AdamHandle, _col, default_device, is_lbfgs, lbfgs_knobs
 
 
 class PysicsInformedNeuralNetwork:
@@ -298,9 +298,42 @@ class PysicsInformedNeuralNetwork:
         return self.loss, [self.loss_e, self.loss_b]
 
     def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None):
+        if is_lbfgs(optimizer):
+            self.opt = optimizer
         if self.opt is not None:
             self.opt.param_groups[0]['lr'] = lr
+        if is_lbfgs(self.opt):          # before solve_Adam's freeze schedule would replace self.opt
+            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
         return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
+
+    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None):
+        """One epoch = one torch.optim.LBFGS.step(closure) of self.opt's knobs on the main net (PinnEngine.lbfgs_step):
+        the entropy net stays frozen and the 10 000-step unfreeze schedule does not run; Adam's state is untouched.
+        Logging, checkpoints and resampling keep solve_Adam's per-epoch cadence (a resample resets the history)."""
+        self._last_log_time, self._last_log_epoch = time.time(), 0
+        if not hasattr(self, 'log_interval'):
+            self.log_interval = 100
+        rs = self._resampling
+        for epoch_id in range(num_epoch):
+            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
+                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self.global_step += 1
+            self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
+            if scheduler:
+                scheduler.step()
+            interval = self.log_interval if self.log_interval > 0 else 100
+            log_now = self.rank == 0 and (epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1)
+            save_now = self.rank == 0 and (epoch_id == 0 or epoch_id % 10000 == 0)
+            if (epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1
+                    or epoch_id % 10000 == 0):
+                # the field planes are the last TRIAL point's after a line search: evaluate the accepted one (on
+                # every rank - the evaluation all-reduces - not only where it is logged)
+                self.fwd_computing_loss_2d()
+            if log_now:
+                self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
+            if save_now:
+                self.save('model_cavity_loop%d.pth' % (epoch_id), N_HLayer=self.layers, N_neu=self.hidden_size,
+                          N_f=self.N_f)
 
     def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
         """Reference loop :440-487 incl. its schedule: the entropy net trains for exactly one

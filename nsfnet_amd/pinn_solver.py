@@ -28,6 +28,18 @@ class AdamHandle:
         return self.param_groups[0]["lr"]
 
 
+def is_lbfgs(opt):
+    return isinstance(opt, torch.optim.LBFGS)
+
+
+def lbfgs_knobs(opt):
+    """PinnEngine.lbfgs_step keywords from a torch.optim.LBFGS (its param group carries every knob)."""
+    g = opt.param_groups[0]
+    return dict(lr=float(g["lr"]), max_iter=int(g["max_iter"]), max_eval=g["max_eval"],
+                tolerance_grad=float(g["tolerance_grad"]), tolerance_change=float(g["tolerance_change"]),
+                history_size=int(g["history_size"]), line_search_fn=g["line_search_fn"])
+
+
 def _col(a):
     """numpy (N,1)/(N,) array or tensor -> contiguous float32 numpy vector."""
     if isinstance(a, torch.Tensor):
@@ -193,8 +205,39 @@ class PysicsInformedNeuralNetwork:
         return self.loss, [self.loss_e, self.loss_b]
 
     def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None):
+        if is_lbfgs(optimizer):
+            self.opt = optimizer
         self.opt.param_groups[0]['lr'] = lr
+        if is_lbfgs(self.opt):
+            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
         return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
+
+    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None):
+        """One epoch = one torch.optim.LBFGS.step(closure) of self.opt's knobs on the device (PinnEngine.lbfgs_step);
+        logging, checkpoints and resampling keep solve_Adam's per-epoch cadence (a resample resets the history)."""
+        print('--------')
+        print(num_epoch)
+        print('--------')
+        rs = self._resampling
+        log_now = save_now = False
+        for epoch_id in range(num_epoch):
+            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
+                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
+            if scheduler:
+                scheduler.step()
+            log_now = self.log_every and epoch_id % self.log_every == 0
+            save_now = self.save_every and epoch_id % self.save_every == 0
+            if log_now or save_now:
+                # the field planes are the last TRIAL point's after a line search: evaluate the accepted one
+                self.fwd_computing_loss_2d()
+            if log_now:
+                self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
+            if save_now:
+                self.save('model_cavity_loop_%d.pth' % epoch_id, N_HLayer=self.layers, N_neu=self.hidden_size,
+                          N_f=self.N_f)
+        if num_epoch > 0 and not (log_now or save_now):
+            self.fwd_computing_loss_2d()         # terms and fields of the accepted point
 
     def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
         """The reference loop (solver :240-278): loss -> backward -> Adam step; log every 1000,
