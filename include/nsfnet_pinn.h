@@ -216,6 +216,47 @@ int pinn_lbfgs_direction(void* ws, int64_t n, int history, const float* g, float
 /* Line-search probe at a trial gradient g against direction d: result[0..3] as above. */
 int pinn_lbfgs_probe(void* ws, int64_t n, int history, const float* g, const float* d, double* result, void* stream);
 
+/* ---- adaptive loss-weight balancing ----------------------------------------------------
+ * No reference counterpart: the "dynamic weights" of the NSFnets line of work, i.e. the learning-rate-
+ * annealing rule of Wang, Teng & Perdikaris (2021, Algorithm 1).  For the main net's P parameters:
+ *   g_r = grad(alpha_e L_e)  (residual loss, as today)   g_b = grad L_b  (boundary, unit weight)
+ *   g_s = grad L_s  (supervised, unit weight; only when that loss is active), all global (summed over ranks).
+ * On a balance step, for each weighted term t (b, and s when active):
+ *   lambda_hat_t = max_j |g_r,j| / ((1/P) sum_j |g_t,j|),   lambda_t <- (1 - beta) lambda_t + beta lambda_hat_t
+ * and if lambda_hat_t is not finite or its denominator is 0, lambda_t keeps its value and the skip count goes up by
+ * one.  The gradient Adam consumes is g = g_r + lambda_b g_b + lambda_s g_s.  The weights live on the device; the
+ * host never reads them on the step path.  All sums are fp64 in a fixed order, no float atomics: the results are
+ * bit-reproducible, and ranks that hold the same vectors compute the same weights.
+ *
+ * Statistics travel in per-block partials: for every block of 64 consecutive parameters b and term t (0 = r,
+ * 1 = b, 2 = s), partials[6 b + 2 t] = max|g_t| over the block (NaN-propagating) and [6 b + 2 t + 1] = sum|g_t|.
+ * Doubles of partials for n parameters: */
+int64_t pinn_balance_partials_count(int64_t n);
+/* The gradient assembly of pinn_grad_reduce with the sources in three consecutive groups: nsrc3[0] collocation
+ * sources, then nsrc3[1] boundary and nsrc3[2] supervised ones (host array of 3; total 1..4).  Each group is summed
+ * in the same fixed fp64 order as pinn_grad_reduce into its own fp32 vector out3[t] (host array of 3 device pointers).
+ * out3[t] NULL: group t not written (needs nsrc3[t] = 0).  nsrc3[t] = 0 with out3[t] given: zeros are written.
+ * Bit t of accumulate_mask adds to out3[t] instead.  partials (device, or NULL): the partials above of the values
+ * written (0 for a group not written). */
+int pinn_grad_reduce_terms(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                           float* const* out3, int accumulate_mask, double* partials, void* stream);
+/* The partials of three device vectors of n entries (vec3: host array of 3 device pointers; NULL = zeros). */
+int pinn_balance_stats(const float* const* vec3, int64_t n, double* partials, void* stream);
+/* One balance update from the partials of n parameters (one workgroup).  terms: bit 0 = update lambda_b, bit 1 =
+ * update lambda_s.  0 < beta <= 1.  record: PINN_BALANCE_RECORD doubles (device) that hold the state,
+ *   [0] max|g_r| [1] mean|g_r| [2] max|g_b| [3] mean|g_b| [4] lambda_hat_b [5] max|g_s| [6] mean|g_s|
+ *   [7] lambda_hat_s (0 for a term not updated) [8] skipped term updates [9] lambda_b [10] lambda_s
+ *   [11] balance updates made;
+ * the caller initialises [8] = [11] = 0 and [9], [10] to the configured weights.  lam (device, 2 floats) receives
+ * (float) lambda_b, (float) lambda_s. */
+#define PINN_BALANCE_RECORD 12
+int pinn_balance_update(const double* partials, int64_t n, int terms, double beta, float* lam, double* record,
+                        void* stream);
+/* g = g_r + lam[0] g_b + lam[1] g_s (fp32 fused multiply-adds in that order; gs NULL: no supervised term).  g may be
+ * g_r. */
+int pinn_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, int64_t n,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

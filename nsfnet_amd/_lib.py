@@ -55,6 +55,12 @@ SIGNATURES = {
     "pinn_lbfgs_reset": (c_int, [c_void_p, c_int64, c_int, c_void_p]),
     "pinn_lbfgs_direction": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "pinn_lbfgs_probe": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_balance_partials_count": (c_int64, [c_int64]),
+    "pinn_grad_reduce_terms": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_void_p),
+                                       ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p]),
+    "pinn_balance_stats": (c_int, [ctypes.POINTER(c_void_p), c_int64, c_void_p, c_void_p]),
+    "pinn_balance_update": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "pinn_balance_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

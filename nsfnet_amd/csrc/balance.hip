@@ -1,0 +1,180 @@
+// Adaptive loss-weight balancing: the learning-rate-annealing rule of Wang, Teng &
+// Perdikaris (2021, Algorithm 1) on the device.  Three pieces, all in a fixed order with fp64 sums and no float
+// atomics, so every result is bit-reproducible and ranks that hold the same vectors compute the same weights:
+//   reduce_terms_kernel    the gradient assembly of misc.hip with the sources split into the collocation, boundary
+//                          and supervised groups, one fp32 vector per group, optionally with per-workgroup
+//                          max|g| / sum|g| partials of what it wrote
+//   balance_stats_kernel   the same partials of three given vectors (multi-rank: after the all-reduce)
+//   balance_update_kernel  one workgroup: partials -> max|g_r|, mean|g_t| -> lambda_hat_t -> lambda_t
+//   balance_combine_kernel g = g_r + lambda_b g_b + lambda_s g_s with the weights read from device memory
+#include <cmath>
+
+#include "kernels.h"
+
+namespace {
+
+constexpr int kBlk = 64;          // parameters per partials block (one per reduce_terms_kernel workgroup)
+constexpr int kUpdThreads = 256;
+
+// NaN-propagating max of non-negative values: a NaN gradient entry must reach lambda_hat (and skip the update)
+__device__ __forceinline__ double nmax(double a, double b) { return (b > a || b != b) ? b : a; }
+
+// max and sum of |v| over the 64 lanes of a wave, in a fixed butterfly order; lane 0 holds the result
+__device__ __forceinline__ void wave_abs_stats(float v, double& mx, double& sm) {
+  mx = fabs((double)v); sm = mx;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = nmax(mx, __shfl_down(mx, off, 64));
+    sm = __dadd_rn(sm, __shfl_down(sm, off, 64));
+  }
+}
+
+__global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
+  // as reduce_kernel: 64 consecutive flat parameters per workgroup, wave w of 8 sums the partial-gradient rows
+  // w, w+8, ... of each source of a group in source order, the 8 wave sums are added in wave order
+  __shared__ double part[3][8][64];
+  const int H = a.H, HP = a.HP, L = a.L;
+  const size_t P = flat_total(H, L, a.n_out);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const size_t p = blockIdx.x * (size_t)64 + lane;
+  const bool live = p < P;
+  const ReduceLoc loc = live ? reduce_locate(p, H, HP, L, a.n_out) : ReduceLoc{-1, -1, 0};
+  const size_t SG = sg_total(HP, L);
+  int k = 0;
+  for (int t = 0; t < 3; ++t) {
+    double s = 0.0;
+    for (int j = 0; j < a.nsrc[t]; ++j, ++k)
+      if (live) s = reduce_source_add(s, a.src[k], loc, HP, SG, w);
+    part[t][w][lane] = s;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  for (int t = 0; t < 3; ++t) {
+    float v = 0.f;
+    if (a.out[t] && live) {
+      double s = part[t][0][lane];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) s += part[t][i][lane];
+      v = (a.acc_mask >> t) & 1 ? a.out[t][p] + (float)s : (float)s;
+      a.out[t][p] = v;
+    }
+    if (a.partials) {
+      double mx, sm;
+      wave_abs_stats(v, mx, sm);
+      if (lane == 0) {
+        a.partials[(size_t)blockIdx.x * 6 + 2 * t] = mx;
+        a.partials[(size_t)blockIdx.x * 6 + 2 * t + 1] = sm;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void balance_stats_kernel(const float* __restrict__ v0, const float* __restrict__ v1,
+                                                           const float* __restrict__ v2, long n,
+                                                           double* __restrict__ partials) {
+  const long p = blockIdx.x * (long)kBlk + threadIdx.x;
+  const float* v[3] = {v0, v1, v2};
+  for (int t = 0; t < 3; ++t) {
+    double mx, sm;
+    wave_abs_stats(v[t] && p < n ? v[t][p] : 0.f, mx, sm);
+    if (threadIdx.x == 0) {
+      partials[(size_t)blockIdx.x * 6 + 2 * t] = mx;
+      partials[(size_t)blockIdx.x * 6 + 2 * t + 1] = sm;
+    }
+  }
+}
+
+// record (fp64, PINN_BALANCE_RECORD entries): [0] max|g_r| [1] mean|g_r| [2] max|g_b| [3] mean|g_b| [4] lambda_hat_b
+// [5] max|g_s| [6] mean|g_s| [7] lambda_hat_s [8] skipped term updates [9] lambda_b [10] lambda_s [11] balance steps
+__global__ __launch_bounds__(kUpdThreads) void balance_update_kernel(const double* __restrict__ partials, long nblk,
+                                                                     long n, int terms, double beta,
+                                                                     float* __restrict__ lam, double* record) {
+  __shared__ double red[kUpdThreads][6];
+  const int tid = threadIdx.x;
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (long b = tid; b < nblk; b += kUpdThreads) {      // thread tid: blocks tid, tid + 256, ... in order
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      acc[2 * t] = nmax(acc[2 * t], partials[b * 6 + 2 * t]);
+      acc[2 * t + 1] += partials[b * 6 + 2 * t + 1];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) red[tid][c] = acc[c];
+  __syncthreads();
+  for (int half = kUpdThreads / 2; half > 0; half >>= 1) {   // fixed pairwise tree: thread i takes i + half
+    if (tid < half) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        red[tid][2 * t] = nmax(red[tid][2 * t], red[tid + half][2 * t]);
+        red[tid][2 * t + 1] += red[tid + half][2 * t + 1];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const double P = (double)n;
+  const double max_r = red[0][0];
+  double rec[12];
+  for (int c = 0; c < 12; ++c) rec[c] = record[c];
+  rec[0] = max_r; rec[1] = red[0][1] / P;
+  for (int t = 1; t < 3; ++t) {
+    const int base = 2 + 3 * (t - 1);                   // 2 (boundary) or 5 (supervised)
+    const double mean = red[0][2 * t + 1] / P;
+    rec[base] = red[0][2 * t]; rec[base + 1] = mean;
+    if (!((terms >> (t - 1)) & 1)) { rec[base + 2] = 0.0; continue; }
+    const double lhat = max_r / mean;
+    rec[base + 2] = lhat;
+    if (mean == 0.0 || !isfinite(lhat)) { rec[8] += 1.0; continue; }
+    rec[8 + t] = (1.0 - beta) * rec[8 + t] + beta * lhat;
+  }
+  rec[11] += 1.0;
+  for (int c = 0; c < 12; ++c) record[c] = rec[c];
+  lam[0] = (float)rec[9];
+  lam[1] = (float)rec[10];
+}
+
+__global__ void balance_combine_kernel(float* g, const float* gr, const float* __restrict__ gb,
+                                       const float* __restrict__ gs, const float* __restrict__ lam, long n) {
+  const float lb = lam[0], ls = gs ? lam[1] : 0.f;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float v = fmaf(lb, gb[i], gr[i]);
+    if (gs) v = fmaf(ls, gs[i], v);
+    g[i] = v;
+  }
+}
+
+int status() {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+}  // namespace
+
+long balance_blocks(long n) { return (n + kBlk - 1) / kBlk; }
+
+int launch_reduce_terms(const TermReduceArgs& a, hipStream_t s) {
+  size_t P = flat_total(a.H, a.L, a.n_out);
+  hipLaunchKernelGGL(reduce_terms_kernel, dim3((unsigned)((P + 63) / 64)), dim3(512), 0, s, a);
+  return status();
+}
+
+int launch_balance_stats(const float* v0, const float* v1, const float* v2, long n, double* partials, hipStream_t s) {
+  hipLaunchKernelGGL(balance_stats_kernel, dim3((unsigned)balance_blocks(n)), dim3(kBlk), 0, s, v0, v1, v2, n, partials);
+  return status();
+}
+
+int launch_balance_update(const double* partials, long n, int terms, double beta, float* lam, double* record,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(balance_update_kernel, dim3(1), dim3(kUpdThreads), 0, s, partials, balance_blocks(n), n, terms,
+                     beta, lam, record);
+  return status();
+}
+
+int launch_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, long n,
+                           hipStream_t s) {
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(balance_combine_kernel, dim3(blocks), dim3(256), 0, s, g, gr, gb, gs, lam, n);
+  return status();
+}

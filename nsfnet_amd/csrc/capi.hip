@@ -560,4 +560,62 @@ int pinn_lbfgs_probe(void* ws, int64_t n, int history, const float* g, const flo
   return rc ? hipfail(rc, "pinn_lbfgs_probe") : 0;
 }
 
+int64_t pinn_balance_partials_count(int64_t n) {
+  return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)balance_blocks((long)n) * 6;
+}
+
+int pinn_grad_reduce_terms(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                           float* const* out3, int accumulate_mask, double* partials, void* stream) {
+  if (!net || !nsrc3 || !out3) return fail(-22, "pinn_grad_reduce_terms: null argument%s");
+  TermReduceArgs r;
+  memset(&r, 0, sizeof(r));
+  int total = 0;
+  for (int t = 0; t < 3; ++t) {
+    if (nsrc3[t] < 0) return fail(-22, "pinn_grad_reduce_terms: negative source count%s");
+    if (nsrc3[t] > 0 && !out3[t]) return fail(-22, "pinn_grad_reduce_terms: a group with sources needs its output%s");
+    r.nsrc[t] = nsrc3[t]; r.out[t] = out3[t];
+    total += nsrc3[t];
+  }
+  if (total < 1 || total > 4) return fail(-22, "pinn_grad_reduce_terms: 1..4 sources in all%s");
+  if (!plans || !wss) return fail(-22, "pinn_grad_reduce_terms: null argument%s");
+  r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
+  r.acc_mask = accumulate_mask & 7; r.partials = partials;
+  for (int k = 0; k < total; ++k) {
+    pinn_plan_t p = plans[k];
+    void* ws = wss[k];
+    if (!p || !ws) return fail(-22, "pinn_grad_reduce_terms: null plan/workspace%s");
+    if (p->net.H != net->H || p->net.L != net->L || p->net.n_out != net->n_out)
+      return fail(-22, "pinn_grad_reduce_terms: plan belongs to a different net%s");
+    r.src[k].slabs = WS(p, off_slabs); r.src[k].groups = p->groups;
+    r.src[k].sg = WS(p, off_sg); r.src[k].nwg = p->grid_b;
+  }
+  int rc = launch_reduce_terms(r, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_grad_reduce_terms") : 0;
+}
+
+int pinn_balance_stats(const float* const* vec3, int64_t n, double* partials, void* stream) {
+  if (!vec3 || !partials) return fail(-22, "pinn_balance_stats: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_balance_stats: n must be 1..2^30%s");
+  int rc = launch_balance_stats(vec3[0], vec3[1], vec3[2], (long)n, partials, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_balance_stats") : 0;
+}
+
+int pinn_balance_update(const double* partials, int64_t n, int terms, double beta, float* lam, double* record,
+                        void* stream) {
+  if (!partials || !lam || !record) return fail(-22, "pinn_balance_update: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_balance_update: n must be 1..2^30%s");
+  if (terms < 0 || terms > 3) return fail(-22, "pinn_balance_update: terms must be 0..3%s");
+  if (!(beta > 0.0 && beta <= 1.0)) return fail(-22, "pinn_balance_update: beta must be in (0, 1]%s");
+  int rc = launch_balance_update(partials, (long)n, terms, beta, lam, record, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_balance_update") : 0;
+}
+
+int pinn_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, int64_t n,
+                         void* stream) {
+  if (!g || !gr || !gb || !lam) return fail(-22, "pinn_balance_combine: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_balance_combine: n must be 1..2^30%s");
+  int rc = launch_balance_combine(g, gr, gb, gs, lam, (long)n, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_balance_combine") : 0;
+}
+
 }  // extern "C"

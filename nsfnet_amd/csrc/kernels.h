@@ -99,6 +99,59 @@ struct ReduceArgs {
   float* grads; int accumulate;
 };
 
+// Where flat parameter p (state_dict order) finds its partials: a row of the dW slabs of layer `layer` (>= 1) at
+// slab_off, or entry sgi of the per-workgroup skinny accumulators (layer < 0).
+struct ReduceLoc { int sgi; int layer; size_t slab_off; };
+__device__ __forceinline__ ReduceLoc reduce_locate(size_t p, int H, int HP, int L, int n_out) {
+  ReduceLoc r{-1, -1, 0};
+  if (p < (size_t)2 * H) {
+    int o = (int)(p / 2), j = (int)(p % 2);
+    r.sgi = (j == 0 ? sg_w0x(HP, L) : sg_w0y(HP, L)) + o;
+  } else if (p < (size_t)3 * H) {
+    r.sgi = sg_db(HP, 0) + (int)(p - 2 * H);
+  } else if (p < flat_w(H, L)) {
+    size_t rel = p - (size_t)3 * H;
+    size_t per = (size_t)H * H + H;
+    int l = 1 + (int)(rel / per);
+    size_t q = rel % per;
+    if (q < (size_t)H * H) { r.layer = l; r.slab_off = (q / H) * HP + (q % H); }
+    else r.sgi = sg_db(HP, l) + (int)(q - (size_t)H * H);
+  } else {
+    size_t q = p - flat_w(H, L);
+    if (q < (size_t)n_out * H) r.sgi = sg_wout(HP, L) + (int)(q / H) * HP + (int)(q % H);
+    else r.sgi = sg_bout(HP, L) + (int)(q - (size_t)n_out * H);
+  }
+  return r;
+}
+// s + the partials of one source that wave w of 8 sums (its groups / workgroups w, w+8, ..., 4 loads in flight),
+// added one by one in that order: the fixed per-wave order of the gradient assembly.
+__device__ __forceinline__ double reduce_source_add(double s, const ReduceSrc& src, const ReduceLoc& loc, int HP,
+                                                    size_t SG, int w) {
+  const float* base; size_t stride; int n;
+  if (loc.layer >= 0) { base = src.slabs + (size_t)(loc.layer - 1) * src.groups * HP * HP + loc.slab_off; stride = (size_t)HP * HP; n = src.groups; }
+  else { base = src.sg + loc.sgi; stride = SG; n = src.nwg; }
+  int g = w;
+  for (; g + 24 < n; g += 32) {
+    float v0 = base[(size_t)g * stride], v1 = base[(size_t)(g + 8) * stride];
+    float v2 = base[(size_t)(g + 16) * stride], v3 = base[(size_t)(g + 24) * stride];
+    s += (double)v0; s += (double)v1; s += (double)v2; s += (double)v3;
+  }
+  for (; g < n; g += 8) s += (double)base[(size_t)g * stride];
+  return s;
+}
+
+// Term-split assembly (balance.hip): the sources in three consecutive groups (collocation | boundary | supervised),
+// each group summed like ReduceArgs into its own vector.  out[t] == nullptr: group t is not written (nsrc[t] must be
+// 0); nsrc[t] == 0 with out[t] given writes zeros (or leaves out[t] as it is where accumulating).  acc_mask bit t: add
+// to out[t].  partials != nullptr: per workgroup b, partials[6 b + 2 t] = max|out[t]| (NaN-propagating) and
+// [6 b + 2 t + 1] = sum|out[t]| in fp64 over its 64 parameters, of the values written (0 for an unwritten group).
+struct TermReduceArgs {
+  ReduceSrc src[4]; int nsrc[3];
+  int H, HP, L, n_out;
+  float* out[3]; int acc_mask;
+  double* partials;
+};
+
 int launch_fwd(int HP, int NS, const FwdArgs& a, int grid, hipStream_t s);
 int launch_bwd(int HP, int NS, const BwdArgs& a, int grid, hipStream_t s);
 int launch_dw(int HP, int NS, const DwArgs& a, hipStream_t s);
@@ -168,3 +221,11 @@ int launch_lbfgs_reset(void* ws, long n, long m, hipStream_t s);
 int launch_lbfgs_direction(void* ws, long n, long m, const float* g, float t_prev, float* d, double* result,
                            hipStream_t s);
 int launch_lbfgs_probe(void* ws, long n, long m, const float* g, const float* d, double* result, hipStream_t s);
+// adaptive loss-weight balancing (balance.hip)
+long balance_blocks(long n);
+int launch_reduce_terms(const TermReduceArgs& a, hipStream_t s);
+int launch_balance_stats(const float* v0, const float* v1, const float* v2, long n, double* partials, hipStream_t s);
+int launch_balance_update(const double* partials, long n, int terms, double beta, float* lam, double* record,
+                          hipStream_t s);
+int launch_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, long n,
+                           hipStream_t s);

@@ -96,42 +96,11 @@ __global__ __launch_bounds__(512) void reduce_kernel(ReduceArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const size_t p = blockIdx.x * (size_t)64 + lane;
   const bool live = p < P;
-  int sgi = -1; int layer = -1; size_t slab_off = 0;
-  if (live) {
-    if (p < (size_t)2 * H) {
-      int o = (int)(p / 2), j = (int)(p % 2);
-      sgi = (j == 0 ? sg_w0x(HP, L) : sg_w0y(HP, L)) + o;
-    } else if (p < (size_t)3 * H) {
-      sgi = sg_db(HP, 0) + (int)(p - 2 * H);
-    } else if (p < flat_w(H, L)) {
-      size_t rel = p - (size_t)3 * H;
-      size_t per = (size_t)H * H + H;
-      int l = 1 + (int)(rel / per);
-      size_t q = rel % per;
-      if (q < (size_t)H * H) { layer = l; slab_off = (q / H) * HP + (q % H); }
-      else sgi = sg_db(HP, l) + (int)(q - (size_t)H * H);
-    } else {
-      size_t q = p - flat_w(H, L);
-      if (q < (size_t)a.n_out * H) sgi = sg_wout(HP, L) + (int)(q / H) * HP + (int)(q % H);
-      else sgi = sg_bout(HP, L) + (int)(q - (size_t)a.n_out * H);
-    }
-  }
+  const ReduceLoc loc = live ? reduce_locate(p, H, HP, L, a.n_out) : ReduceLoc{-1, -1, 0};
   double s = 0.0;
   if (live) {
     const size_t SG = sg_total(HP, L);
-    for (int k = 0; k < a.nsrc; ++k) {
-      const ReduceSrc& src = a.src[k];
-      const float* base; size_t stride; int n;
-      if (layer >= 0) { base = src.slabs + (size_t)(layer - 1) * src.groups * HP * HP + slab_off; stride = (size_t)HP * HP; n = src.groups; }
-      else { base = src.sg + sgi; stride = SG; n = src.nwg; }
-      int g = w;
-      for (; g + 24 < n; g += 32) {
-        float v0 = base[(size_t)g * stride], v1 = base[(size_t)(g + 8) * stride];
-        float v2 = base[(size_t)(g + 16) * stride], v3 = base[(size_t)(g + 24) * stride];
-        s += (double)v0; s += (double)v1; s += (double)v2; s += (double)v3;
-      }
-      for (; g < n; g += 8) s += (double)base[(size_t)g * stride];
-    }
+    for (int k = 0; k < a.nsrc; ++k) s = reduce_source_add(s, a.src[k], loc, HP, SG, w);
   }
   part[w][lane] = s;
   __syncthreads();

@@ -59,6 +59,14 @@ class ResamplingConfig:
     seed: int = 0
 
 
+@dataclass
+class LossBalancingConfig:
+    """Adaptive boundary / supervised loss weights (PinnEngine.set_loss_balancing), off by default."""
+    enabled: bool = False
+    every: int = 100
+    beta: float = 0.1
+
+
 def _default_stages():
     table = [(0.05, 1e-3), (0.03, 2e-4), (0.01, 4e-5), (0.005, 1e-5), (0.002, 2e-6), (0.002, 2e-6)]
     return [TrainingStage(a, 500000, lr, "Stage %d" % (i + 1)) for i, (a, lr) in enumerate(table)]
@@ -74,6 +82,7 @@ class TrainingConfig:
     sdf_weighting: SDFWeightConfig = field(default_factory=SDFWeightConfig)
     coordinate_transform: bool = False
     resampling: ResamplingConfig = field(default_factory=ResamplingConfig)
+    loss_balancing: LossBalancingConfig = field(default_factory=LossBalancingConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -132,6 +141,9 @@ class ConfigManager:
         rs = c.training.resampling
         if rs.enabled and (rs.every < 1 or rs.pool_points < 1 or rs.k < 0 or rs.c < 0 or rs.seed < 0):
             problems.append("training.resampling: every, pool_points >= 1 and k, c, seed >= 0 required")
+        lb = c.training.loss_balancing
+        if lb.enabled and (lb.every < 1 or not 0.0 < lb.beta <= 1.0):
+            problems.append("training.loss_balancing: every >= 1 and 0 < beta <= 1 required")
         for st in c.training.training_stages:
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
@@ -159,5 +171,7 @@ class ConfigManager:
         if t.resampling.enabled:
             print("resampling : every=%d pool_points=%d k=%s c=%s seed=%d"
                   % (t.resampling.every, t.resampling.pool_points, t.resampling.k, t.resampling.c, t.resampling.seed))
+        if t.loss_balancing.enabled:
+            print("balancing  : every=%d beta=%s" % (t.loss_balancing.every, t.loss_balancing.beta))
         print("supervision: enabled=%s samples=%d weight=%s"
               % (c.supervision.enabled, c.supervision.num_samples, c.supervision.loss_weight))

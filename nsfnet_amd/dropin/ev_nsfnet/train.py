@@ -96,6 +96,9 @@ def main():
         else:
             PINN.clear_supervised_data()
             PINN.set_supervised_loss_weight(0.0)
+        lb = cfg.training.loss_balancing
+        if lb.enabled:    # after the supervised weight: the balanced weights start at the configured ones
+            PINN.set_loss_balancing(every=lb.every, beta=lb.beta)
         for st in cfg.training.training_stages:
             if rank == 0:
                 log.stage(st.name, st.alpha, st.epochs, st.lr)

@@ -347,6 +347,50 @@ def grad_reduce(net, plans, grads_out, accumulate=False):
                "pinn_grad_reduce")
 
 
+def grad_reduce_terms(net, groups, outs, acc_mask=0, partials=None):
+    """pinn_grad_reduce_terms: groups = three lists of plans (collocation, boundary, supervised), outs = three output
+    vectors (None: group not written; a written group without plans gets zeros).  acc_mask bit t: add to outs[t].
+    partials: fp64 device tensor of balance_partials_count(P) entries for the max|g| / sum|g| block partials."""
+    lib = net.lib
+    plans = [p for grp in groups for p in grp]
+    n = len(plans)
+    ns = (ctypes.c_int * 3)(*[len(grp) for grp in groups])
+    ph = (ctypes.c_void_p * max(n, 1))(*[p.handle.value for p in plans])
+    wh = (ctypes.c_void_p * max(n, 1))(*[p.ws.data_ptr() for p in plans])
+    out = (ctypes.c_void_p * 3)(*[0 if o is None else o.data_ptr() for o in outs])
+    _lib.check(lib.pinn_grad_reduce_terms(net.handle, ns, ph, wh, out, int(acc_mask), _ptr(partials), _stream()),
+               "pinn_grad_reduce_terms")
+
+
+def balance_partials(n, device):
+    """Zeroed fp64 device tensor for the block partials of n parameters."""
+    count = int(_lib.load().pinn_balance_partials_count(int(n)))
+    if count < 0:
+        raise ValueError("bad parameter count %d" % n)
+    return torch.zeros(count, dtype=torch.float64, device=device)
+
+
+def balance_stats(vecs, n, partials):
+    """Block partials of three vectors (None = zeros): pinn_balance_stats."""
+    v = (ctypes.c_void_p * 3)(*[0 if t is None else t.data_ptr() for t in vecs])
+    _lib.check(_lib.load().pinn_balance_stats(v, int(n), _ptr(partials), _stream()), "pinn_balance_stats")
+
+
+def balance_update(partials, n, terms, beta, lam, record):
+    """One balance update on the device (pinn_balance_update): record / lam are updated in place."""
+    _lib.check(_lib.load().pinn_balance_update(_ptr(partials), int(n), int(terms), float(beta), _ptr(lam), _ptr(record),
+                                               _stream()), "pinn_balance_update")
+
+
+def balance_combine(g, gr, gb, gs, lam):
+    """g = g_r + lam[0] g_b + lam[1] g_s (gs None: no supervised term): pinn_balance_combine."""
+    _lib.check(_lib.load().pinn_balance_combine(_ptr(g), _ptr(gr), _ptr(gb), _ptr(gs), _ptr(lam), g.numel(), _stream()),
+               "pinn_balance_combine")
+
+
+BALANCE_RECORD = 12      # PINN_BALANCE_RECORD
+
+
 class LbfgsHistory:
     """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
     g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
@@ -416,6 +460,17 @@ class _EngineSpace:
         self.e.flat.copy_(h)
 
 
+class _Balance:
+    """Host side of the loss balancing: the cadence (Adam updates n counted since set_loss_balancing; `done` = the
+    last n whose balance update has run) and the device tensors: lam [2] fp32, rec [BALANCE_RECORD] fp64 (the
+    state and the statistics of the last balance step), parts (block partials), buf / gb / gs (term vectors)."""
+
+    def __init__(self, every, beta):
+        self.every, self.beta = every, beta
+        self.n, self.done = 0, -1
+        self.buf = self.gb = self.gs = self.lam = self.rec = self.parts = None
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -465,6 +520,8 @@ class PinnEngine:
         self._lbfgs = None                  # LbfgsHistory (created by the first lbfgs_step)
         self._lbfgs_state = _lbfgs.LbfgsState()
         self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
+        self._bal = None                    # adaptive loss-weight balancing (set_loss_balancing; None = off)
+        self._bal_frozen = False            # lbfgs_step: the weights are held fixed
 
     # ---- views into the exchange buffer ----
     @property
@@ -616,9 +673,85 @@ class PinnEngine:
                     None if f.w is None else f.w.clone())
         return f.x.clone(), f.y.clone(), None if f.w is None else f.w.clone()
 
+    # ---- adaptive loss-weight balancing ----
+    def set_loss_balancing(self, every=0, beta=0.1):
+        """every > 0: balance the boundary (and supervised) weight by the learning-rate-annealing rule (Wang, Teng &
+        Perdikaris 2021): on Adam update n of the main net with n % every == 0 (updates counted from this call on,
+        by step() and adam_step()), lambda_t <- (1 - beta) lambda_t + beta max|g_r| / mean|g_t| from the global
+        per-term gradients, in the first evaluation for that update.  The weights live on the device and start at
+        alpha_b / alpha_s; the gradient Adam sees is g_r + lambda_b g_b + lambda_s g_s.  every = 0: off (the step
+        launches what it launches without balancing).  A call restarts the weights and the update count."""
+        every, beta = int(every), float(beta)
+        if every < 0:
+            raise ValueError("loss balancing: every must be >= 0")
+        if every > 0 and not (0.0 < beta <= 1.0):
+            raise ValueError("loss balancing: beta must be in (0, 1]")
+        self._graphs.clear()        # captured steps hold the seeds and buffers of the other mode
+        if every == 0:
+            self._bal = None
+            return
+        b = _Balance(every, beta)
+        n_ex = self.P + self.P1 + NSUMS
+        # one buffer [grads | grads_e | sums | g_b | g_s]: a balance step all-reduces its prefix in one message
+        b.buf = torch.zeros(n_ex + 2 * self.P, dtype=torch.float32, device=self.device)
+        b.buf[:n_ex].copy_(self.flat)
+        self.flat = b.buf[:n_ex]
+        b.gb, b.gs = b.buf[n_ex:n_ex + self.P], b.buf[n_ex + self.P:]
+        b.lam = torch.tensor([self.alpha_b, self.alpha_s], dtype=torch.float32).to(self.device)
+        rec = np.zeros(BALANCE_RECORD)
+        rec[9], rec[10] = self.alpha_b, self.alpha_s
+        b.rec = torch.tensor(rec, dtype=torch.float64).to(self.device)
+        b.parts = balance_partials(self.P, self.device)
+        self._bal = b
+
+    def loss_weights(self):
+        """Device tensor [lambda_b, lambda_s] (fp32) of the weights the gradient uses (the configured ones when
+        balancing is off)."""
+        if self._bal is not None:
+            return self._bal.lam
+        return torch.tensor([self.alpha_b, self.alpha_s], dtype=torch.float32).to(self.device)
+
+    def balance_info(self):
+        """The device record of the last balance step (one host read), or None when balancing is off."""
+        b = self._bal
+        if b is None:
+            return None
+        r = b.rec.cpu().tolist()
+        names = ("max_r", "mean_r", "max_b", "mean_b", "lambda_hat_b", "max_s", "mean_s", "lambda_hat_s", "skipped",
+                 "lambda_b", "lambda_s", "updates")
+        out = dict(zip(names, r))
+        out["skipped"], out["updates"] = int(out["skipped"]), int(out["updates"])
+        out.update(every=b.every, beta=b.beta, adam_updates=b.n)
+        return out
+
+    def _balance_due(self):
+        """True for the first evaluation of a balance update (n % every == 0), which it claims."""
+        b = self._bal
+        if b is None or self._bal_frozen or b.n % b.every != 0 or b.done == b.n:
+            return False
+        b.done = b.n
+        return True
+
+    def _sup_on(self):
+        return self.n_s_global > 0 and self.alpha_s != 0.0
+
+    def _reduce_terms(self, r_plans, b, s, acc_r, update):
+        """Term-split gradient assembly: g_r into grads, g_b / g_s into the balancing buffer (the partials on a
+        single-rank balance step, where the local vectors are the global ones)."""
+        bal = self._bal
+        grad_reduce_terms(self.net, [r_plans, [b], [] if s is None else [s]],
+                          [self.grads, bal.gb, bal.gs if self._sup_on() else None], acc_mask=1 if acc_r else 0,
+                          partials=bal.parts if update and self.world_size == 1 else None)
+
     # ---- one loss + gradient evaluation ----
     def loss_and_grad(self):
+        if self._bal is not None and self.loss_mode != "MSE":      # (before any stream switch)
+            raise ValueError("loss balancing needs the MSE loss (loss_mode %r)" % self.loss_mode)
+        self._loss_and_grad(self._balance_due())
+
+    def _loss_and_grad(self, update=False):
         f, b = self.plan_f, self.plan_b
+        bal = self._bal
         sums = self.sums
         sup_on = self.n_s_global > 0 and self.alpha_s != 0.0
         s = self.plan_s if sup_on else None             # None also on a rank whose supervised share is empty
@@ -644,7 +777,9 @@ class PinnEngine:
         if l2 and (self.net_e is not None or self.world_size > 1 or sup_on or isinstance(f, ChunkedResidual)):
             raise NotImplementedError("loss_mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
         try:
-            cb = 2.0 * self.alpha_b / self.n_b_global
+            # balancing: unit seeds, the weights are applied by the combine (device memory, not a launch argument)
+            wb, ws = (1.0, 1.0) if bal is not None else (self.alpha_b, self.alpha_s)
+            cb = 2.0 * wb / self.n_b_global
             if l2:      # norms first (2052 boundary points: a forward-only pass), then the adjoints alpha_b (u - u_b) / ||u - u_b||
                 b.forward(coef=(0.0, 0.0, 0.0), save=False, sums_out=sums[S_BC:S_BC + NLOSS])
                 nb = torch.sqrt(sums[S_BC:S_BC + 2]).cpu().numpy().astype(np.float64)
@@ -655,8 +790,8 @@ class PinnEngine:
             b.backward()
             if s is not None:
                 # per-output means: u,v over all supervised points, p over its finite targets (ev:399-411)
-                cs = 2.0 * self.alpha_s / self.n_s_global
-                s.forward(coef=(cs, cs, (2.0 * self.alpha_s / n_p) if n_p > 0 else 0.0), save=True,
+                cs = 2.0 * ws / self.n_s_global
+                s.forward(coef=(cs, cs, (2.0 * ws / n_p) if n_p > 0 else 0.0), save=True,
                           sums_out=sums[S_SUP:S_SUP + NLOSS])
                 s.backward()
         finally:
@@ -683,16 +818,25 @@ class PinnEngine:
                                sums_out=f.tmp_sums)
                     sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
                     ck.backward(self.Re, coef_eq, e=ek, scale=self.scale, want_ebar=self.e_trainable)
-                grad_reduce(self.net, [ck], self.grads, accumulate=k > 0)
+                if bal is None:
+                    grad_reduce(self.net, [ck], self.grads, accumulate=k > 0)
+                elif k < len(f.chunks) - 1:
+                    grad_reduce_terms(self.net, [[ck], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
             if side is not None:
                 main.wait_stream(side)
-            grad_reduce(self.net, value_plans, self.grads, accumulate=True)
+            if bal is None:
+                grad_reduce(self.net, value_plans, self.grads, accumulate=True)
+            else:
+                self._reduce_terms([f.chunks[-1]], b, s, len(f.chunks) > 1, update)
         elif not l2 and hasattr(f, "forward_backward"):      # MSE seeds: one call, the sweeps fused where the plan allows
             f.forward_backward(self.Re, coef_eq, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale,
                                want_ebar=self.e_trainable, sums_out=sums[S_EQ:S_EQ + NLOSS])
             if side is not None:
                 main.wait_stream(side)
-            grad_reduce(self.net, [f] + value_plans, self.grads)
+            if bal is None:
+                grad_reduce(self.net, [f] + value_plans, self.grads)
+            else:
+                self._reduce_terms([f], b, s, False, update)
         else:
             f.forward(self.Re, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
                       sums_out=sums[S_EQ:S_EQ + NLOSS])
@@ -702,15 +846,35 @@ class PinnEngine:
             f.backward(self.Re, coef_eq, e=e, scale=self.scale, want_ebar=self.e_trainable)
             if side is not None:
                 main.wait_stream(side)
-            grad_reduce(self.net, [f] + value_plans, self.grads)
+            if bal is None:
+                grad_reduce(self.net, [f] + value_plans, self.grads)
+            else:
+                self._reduce_terms([f], b, s, False, update)
         if self.net_e is not None:
             if self.e_trainable:
                 self.plan_e.backward(out_adj=f.ebar)
                 grad_reduce(self.net_e, [self.plan_e], self.grads_e)
             else:
                 self.grads_e.zero_()
-        if self.world_size > 1:
-            torch.distributed.all_reduce(self.flat, group=self.pg)
+        if bal is None:
+            if self.world_size > 1:
+                torch.distributed.all_reduce(self.flat, group=self.pg)
+            return
+        gs = bal.gs if sup_on else None
+        if update:
+            if self.world_size > 1:
+                # the statistics need the global term vectors: [grads (= g_r) | grads_e | sums | g_b (| g_s)] in one
+                # message, then every rank computes the same partials, weights and combine
+                n = self.flat.numel() + self.P * (2 if sup_on else 1)
+                torch.distributed.all_reduce(bal.buf[:n], group=self.pg)
+                balance_stats([self.grads, bal.gb, gs], self.P, bal.parts)
+            balance_update(bal.parts, self.P, 1 | (2 if sup_on else 0), bal.beta, bal.lam, bal.rec)
+            balance_combine(self.grads, self.grads, bal.gb, gs, bal.lam)
+        else:
+            # the combine is linear: combining before the one all-reduce gives every rank the same global g
+            balance_combine(self.grads, self.grads, bal.gb, gs, bal.lam)
+            if self.world_size > 1:
+                torch.distributed.all_reduce(self.flat, group=self.pg)
 
     def _side_stream(self, main):
         """The stream the value-mode chains run on.  Inside a graph capture it must be a stream that is
@@ -747,6 +911,11 @@ class PinnEngine:
             n_p = self._n_p_valid_global()
             loss_s = (s[S_SUP] + s[S_SUP + 1]) / self.n_s_global + (s[S_SUP + 2] / n_p if n_p > 0 else 0.0)
         out["loss_s"] = loss_s
+        if self._bal is not None:
+            lam = self._bal.lam
+            out["loss"] = lam[0] * loss_b + self.alpha_e * loss_e + lam[1] * loss_s
+            out["lambda_b"], out["lambda_s"] = lam[0], lam[1]
+            return out
         out["loss"] = self.alpha_b * loss_b + self.alpha_e * loss_e + self.alpha_s * loss_s
         return out
 
@@ -754,6 +923,8 @@ class PinnEngine:
         self.net.adam_step(self.grads, lr)
         if self.net_e is not None and self.e_trainable:
             self.net_e.adam_step(self.grads_e, lr)
+        if self._bal is not None:
+            self._bal.n += 1
 
     # ---- L-BFGS ----
     def lbfgs_reset(self):
@@ -784,12 +955,14 @@ class PinnEngine:
         if self.net_e is not None:
             self.e_trainable = False
             self.init_vis_t()
+        self._bal_frozen = True             # the objective uses the current loss weights throughout
         try:
             loss, info = _lbfgs.step(_EngineSpace(self, self._lbfgs), self._lbfgs_state, lr=float(lr),
                                      max_iter=int(max_iter), max_eval=max_eval, tolerance_grad=float(tolerance_grad),
                                      tolerance_change=float(tolerance_change), line_search_fn=line_search_fn)
         finally:
             self.e_trainable = e_trainable
+            self._bal_frozen = False
         self.lbfgs_info = info
         return loss
 
@@ -802,13 +975,16 @@ class PinnEngine:
             self.loss_and_grad()
             self.adam_step(lr)
             return
+        # with balancing on, a balance step and a plain step are separate graphs (the weights are device state)
+        update = self._balance_due()
         key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
-               self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight)
+               self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
+               self._bal is not None, update)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the
             # supervised-target census happens here), then capture
-            self.loss_and_grad()
+            self._loss_and_grad(update)
             self.adam_step(lr)
             if len(self._graphs) >= 8:
                 self._graphs.clear()
@@ -817,19 +993,23 @@ class PinnEngine:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.stream(side):
                 with torch.cuda.graph(graph, stream=side):
-                    self.loss_and_grad()
+                    self._loss_and_grad(update)
                     self.adam_step(lr)
             torch.cuda.current_stream(self.device).wait_stream(side)
-            # the capture itself does not execute; account for the host mirror it advanced
+            # the capture itself does not execute; account for the host mirrors it advanced
             self.net.adam_t -= 1
             if self.net_e is not None and self.e_trainable:
                 self.net_e.adam_t -= 1
+            if self._bal is not None:
+                self._bal.n -= 1
             self._graphs[key] = graph
             return
         g.replay()
         self.net.adam_t += 1
         if self.net_e is not None and self.e_trainable:
             self.net_e.adam_t += 1
+        if self._bal is not None:
+            self._bal.n += 1
 
     def _graphs_enabled(self):
         import os

@@ -243,6 +243,21 @@ class PysicsInformedNeuralNetwork:
         self.supervision_enabled = self.supervision_has_data and self.alpha_s != 0.0
         self.engine.alpha_s = float(self.alpha_s) if self.supervision_enabled else 0.0
 
+
+    # ---------------------------------------------------------------- adaptive loss-weight balancing
+    def set_loss_balancing(self, every=0, beta=0.1):
+        """every > 0: the boundary (and supervised) weight follows the learning-rate-annealing rule every `every` Adam updates
+        (PinnEngine.set_loss_balancing).  alpha_b stays the configured weight (it names the
+        checkpoint directory); the weight in use is lam_b().  every = 0: off."""
+        self.engine.set_loss_balancing(every, beta)
+        self._balancing = int(every) > 0
+
+    def lam_b(self):
+        """The boundary weight in use (one host read when balancing is on)."""
+        if not getattr(self, "_balancing", False):
+            return self.alpha_b
+        return float(self.engine.loss_weights()[0])
+
     def set_optimizers(self, opt):
         self.opt = opt
 
@@ -406,6 +421,10 @@ class PysicsInformedNeuralNetwork:
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))
+        if getattr(self, "_balancing", False):
+            lam = self.engine.loss_weights().cpu().tolist()
+            print('  loss weights: lambda_b=%.4e' % lam[0]
+                  + ('  lambda_s=%.4e' % lam[1] if self.supervision_total_points > 0 and self.alpha_s != 0.0 else ''))
         print('  it/s=%.2f  throughput=%.1f pts/s  lr=%.2e  Re=%s  Re_eff=%.1f  alpha_evm=%s' % (
             rate, rate * pts, self.opt.param_groups[0]['lr'], self.Re, Re_eff, self.alpha_evm))
         self._last_log_time, self._last_log_epoch = now, epoch_id
@@ -450,7 +469,7 @@ class PysicsInformedNeuralNetwork:
                              {'U_pred': u_pred.reshape(shape), 'V_pred': v_pred.reshape(shape),
                               'P_pred': p_pred.reshape(shape), 'E_pred': e_pred.reshape(shape),
                               'error_u': error_u, 'error_v': error_v, 'error_p': error_p,
-                              'lam_bcs': self.alpha_b, 'lam_equ': self.alpha_e})
+                              'lam_bcs': self.lam_b(), 'lam_equ': self.alpha_e})
         return error_u, error_v, error_p
 
     def save(self, filename, directory=None, N_HLayer=None, N_neu=None, N_f=None):

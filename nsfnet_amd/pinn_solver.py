@@ -140,6 +140,21 @@ class PysicsInformedNeuralNetwork:
             raise ValueError("every must be >= 0")
         self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
 
+
+    # ---------------------------------------------------------------- adaptive loss-weight balancing
+    def set_loss_balancing(self, every=0, beta=0.1):
+        """every > 0: the boundary weight follows the learning-rate-annealing rule every `every` Adam updates
+        (PinnEngine.set_loss_balancing).  alpha_b stays the configured weight (it names the
+        checkpoint directory); the weight in use is lam_b().  every = 0: off."""
+        self.engine.set_loss_balancing(every, beta)
+        self._balancing = int(every) > 0
+
+    def lam_b(self):
+        """The boundary weight in use (one host read when balancing is on)."""
+        if not getattr(self, "_balancing", False):
+            return self.alpha_b
+        return float(self.engine.loss_weights()[0])
+
     def set_optimizers(self, opt):
         self.opt = opt
 
@@ -274,7 +289,8 @@ class PysicsInformedNeuralNetwork:
               "epoch/num_epoch: ", epoch_id + 1, "/", num_epoch,
               "eq1_loss: %.3e " % (self.loss_eq1.item()),
               "eq2_loss: %.3e " % (self.loss_eq2.item()),
-              "eq4_loss: %.3e \n" % (self.loss_eq3.item()))
+              "eq4_loss: %.3e \n" % (self.loss_eq3.item()),
+              *(("lambda_b: %.4e" % self.lam_b(),) if getattr(self, "_balancing", False) else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):
@@ -306,7 +322,7 @@ class PysicsInformedNeuralNetwork:
             shape = (side, side) if side * side == u_pred.size else (u_pred.size, 1)
         scipy.io.savemat('cavity_result_loop_%d.mat' % (loop),
                          {'U_pred': u_pred.reshape(shape), 'V_pred': v_pred.reshape(shape),
-                          'P_pred': p_pred.reshape(shape), 'lam_bcs': self.alpha_b, 'lam_equ': self.alpha_e})
+                          'P_pred': p_pred.reshape(shape), 'lam_bcs': self.lam_b(), 'lam_equ': self.alpha_e})
         return error_u, error_v
 
     def save(self, filename, directory=None, N_HLayer=None, N_neu=None, N_f=None, lr=None):
