@@ -248,11 +248,14 @@ class ChunkedResidual:
             ws = c.ws
             self.chunks.append(c)
         self.npad = sum(c.npad for c in self.chunks)
-        self.w = None if w is None else torch.cat([c.w for c in self.chunks])
         self.tmp_sums = torch.zeros(NLOSS, dtype=torch.float32, device=net.device)
 
     def field(self, name):
         return torch.cat([c.field(name) for c in self.chunks])
+
+    @property
+    def w(self):
+        return None if self.chunks[0].w is None else torch.cat([c.w for c in self.chunks])
 
     @property
     def vis_t(self):
@@ -276,6 +279,14 @@ class ChunkedResidual:
         for (a, b), c in zip(self.bounds, self.chunks):
             out[a:b] = c.ebar[:b - a]
         return out
+
+
+def _passes(f):
+    """The passes of a collocation set as [((lo, hi), plan), ...]: one for a ResidualPlan, one per chunk for a
+    ChunkedResidual."""
+    if isinstance(f, ChunkedResidual):
+        return list(zip(f.bounds, f.chunks))
+    return [((0, f.n), f)]
 
 
 class ValuePlan(PointPlan):
@@ -512,11 +523,6 @@ class PinnEngine:
         self.n_f_global = self.n_b_global = self.n_s_global = 0
         self._n_p_local, self._n_p_valid, self._sup_stale = 0, None, False
         self.eq4_weight = 0.1
-        # 'MSE' (every script of the reference) or 'L2': 2-norms of the residual / boundary-misfit vectors
-        # (NSFnet/pinn_solver.py:202-204, 214-217; plain NSFnet, one GPU).  The same kernels run: only the adjoint
-        # coefficients change, from 2 alpha / N to alpha / ||r_k||, and the norms have to be known first - one
-        # host read of the forward sums per evaluation (no hipGraph in this mode).
-        self.loss_mode = "MSE"
         self._lbfgs = None                  # LbfgsHistory (created by the first lbfgs_step)
         self._lbfgs_state = _lbfgs.LbfgsState()
         self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
@@ -586,9 +592,10 @@ class PinnEngine:
         """vis_t_minus = alpha_evm*|e(x_f)|   (ev-NSFnet/pinn_solver.py:138-140)"""
         self.plan_e.forward(save=False)
         fresh = (self.alpha_evm * self.plan_e.pred[0].abs()).contiguous()
-        cur = self.plan_f.vis_t_minus
-        if cur is not None and not isinstance(self.plan_f, ChunkedResidual) and cur.shape == fresh.shape:
-            cur.copy_(fresh)          # in place: a captured hipGraph keeps reading / writing this allocation
+        passes = _passes(self.plan_f)
+        if all(p.vis_t_minus is not None and p.vis_t_minus.shape == (hi - lo,) for (lo, hi), p in passes):
+            for (lo, hi), p in passes:      # in place: a captured hipGraph keeps reading / writing these allocations
+                p.vis_t_minus.copy_(fresh[lo:hi])
         else:
             self._graphs.clear()
             self.plan_f.vis_t_minus = fresh
@@ -640,10 +647,10 @@ class PinnEngine:
         if not math.isfinite(S):
             raise FloatingPointError("resample: the pool's residual sum is %r (non-finite residual or coordinate in the "
                                      "pool); the collocation set is unchanged" % S)
-        chunks = list(zip(f.bounds, f.chunks)) if isinstance(f, ChunkedResidual) else [((0, f.n), f)]
+        passes = _passes(f)
         src = dict(x=pool.x, y=pool.y, w=self._pool_w, vtm=vtm0)
-        w_sums = torch.zeros(len(chunks), dtype=torch.float64, device=self.device) if f.w is not None else None
-        for j, ((lo, hi), ck) in enumerate(chunks):
+        w_sums = torch.zeros(len(passes), dtype=torch.float64, device=self.device) if f.w is not None else None
+        for j, ((lo, hi), ck) in enumerate(passes):
             dst = dict(x=ck.x, y=ck.y, w=ck.w, vtm=ck.vis_t_minus)
             resample_gather(idx, lo, hi, pool.n, src, dst, self._pool_scratch,
                             None if w_sums is None else w_sums[j:j + 1])
@@ -652,26 +659,22 @@ class PinnEngine:
                 self.plan_e.y[lo:hi].copy_(ck.y)
         if w_sums is not None:
             total = 0.0
-            for v in w_sums.cpu().tolist():          # chunk order
+            for v in w_sums.cpu().tolist():          # pass order
                 total += v
             if self.world_size > 1:
                 t = torch.tensor([total], dtype=torch.float64, device=self.device)
                 torch.distributed.all_reduce(t, group=self.pg)
                 total = float(t.item())
             mean = total / self.n_f_global
-            for _, ck in chunks:                     # mean 1 over the global set (cavity_data._compute_sdf_weights)
+            for _, ck in passes:                     # mean 1 over the global set (cavity_data._compute_sdf_weights)
                 ck.w.copy_((ck.w.double() / mean).float())
-            if isinstance(f, ChunkedResidual):
-                f.w.copy_(torch.cat([ck.w for _, ck in chunks]))
         return idx
 
     def collocation_points(self):
         """(x, y, w) of the live collocation set as fresh device tensors (w None without weights)."""
-        f = self.plan_f
-        if isinstance(f, ChunkedResidual):
-            return (torch.cat([c.x for c in f.chunks]), torch.cat([c.y for c in f.chunks]),
-                    None if f.w is None else f.w.clone())
-        return f.x.clone(), f.y.clone(), None if f.w is None else f.w.clone()
+        plans = [p for _, p in _passes(self.plan_f)]
+        return tuple(None if getattr(plans[0], k) is None else torch.cat([getattr(p, k) for p in plans])
+                     for k in ("x", "y", "w"))
 
     # ---- adaptive loss-weight balancing (DESIGN.md section 7.3) ----
     def set_loss_balancing(self, every=0, beta=0.1):
@@ -744,16 +747,25 @@ class PinnEngine:
                           partials=bal.parts if update and self.world_size == 1 else None)
 
     # ---- one loss + gradient evaluation ----
-    def loss_and_grad(self):
-        if self._bal is not None and self.loss_mode != "MSE":      # (before any stream switch)
-            raise ValueError("loss balancing needs the MSE loss (loss_mode %r)" % self.loss_mode)
-        self._loss_and_grad(self._balance_due())
+    def loss_and_grad(self, mode="MSE"):
+        """mode 'MSE' (every script of the reference) or 'L2': 2-norms of the residual / boundary-misfit vectors
+        (NSFnet/pinn_solver.py:202-204, 214-217; plain NSFnet, one GPU).  The same kernels run: only the adjoint
+        coefficients change, from 2 alpha / N to alpha / ||r_k||, and the norms have to be known first - one host read
+        of the forward sums per evaluation (no hipGraph in this mode).  Refusals come before any stream switch."""
+        if mode not in ("MSE", "L2"):
+            raise ValueError("loss mode must be 'MSE' or 'L2' (got %r)" % (mode,))
+        l2 = mode == "L2"
+        if l2 and self._bal is not None:
+            raise ValueError("loss balancing needs the MSE loss (loss mode %r)" % mode)
+        if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
+            raise NotImplementedError("loss mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
+        self._loss_and_grad(self._balance_due(), l2)
 
-    def _loss_and_grad(self, update=False):
+    def _loss_and_grad(self, update=False, l2=False):
         f, b = self.plan_f, self.plan_b
         bal = self._bal
         sums = self.sums
-        sup_on = self.n_s_global > 0 and self.alpha_s != 0.0
+        sup_on = self._sup_on()
         s = self.plan_s if sup_on else None             # None also on a rank whose supervised share is empty
         n_p = self._n_p_valid_global() if sup_on else 0
         if s is None and self._sup_stale:
@@ -773,9 +785,6 @@ class PinnEngine:
             side = self._side_stream(main)
             side.wait_stream(main)
             torch.cuda.set_stream(side)
-        l2 = self.loss_mode == "L2"
-        if l2 and (self.net_e is not None or self.world_size > 1 or sup_on or isinstance(f, ChunkedResidual)):
-            raise NotImplementedError("loss_mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
         try:
             # balancing: unit seeds, the weights are applied by the combine (device memory, not a launch argument)
             wb, ws = (1.0, 1.0) if bal is not None else (self.alpha_b, self.alpha_s)
@@ -803,53 +812,40 @@ class PinnEngine:
             e = self.plan_e.pred[0]
         c = 2.0 * self.alpha_e / self.n_f_global
         coef_eq = (c, c, c, c * self.eq4_weight if self.net_e is not None else 0.0)
-        value_plans = [b] if s is None else [b, s]
-        if isinstance(f, ChunkedResidual):
-            # one pass per chunk through the shared workspace; gradients / sums accumulate
-            sums[S_EQ:S_EQ + NLOSS].zero_()
-            for k, ((lo, hi_), ck) in enumerate(zip(f.bounds, f.chunks)):
-                ek = None if e is None else e[lo:hi_]
-                if hasattr(ck, "forward_backward"):      # (MSE seeds: known before the forward)
-                    ck.forward_backward(self.Re, coef_eq, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm,
-                                        scale=self.scale, want_ebar=self.e_trainable, sums_out=f.tmp_sums)
-                    sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
-                else:
-                    ck.forward(self.Re, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
-                               sums_out=f.tmp_sums)
-                    sums[S_EQ:S_EQ + NLOSS] += f.tmp_sums
-                    ck.backward(self.Re, coef_eq, e=ek, scale=self.scale, want_ebar=self.e_trainable)
+        # one pass per plan (several: chunks sharing one workspace, gradients and sums accumulate); every pass but
+        # the last is reduced here, the last one together with the value plans below
+        passes = _passes(f)
+        many = len(passes) > 1
+        eq_sums = sums[S_EQ:S_EQ + NLOSS]
+        if many:
+            eq_sums.zero_()
+        for k, ((lo, hi), p) in enumerate(passes):
+            ek = e[lo:hi] if e is not None and many else e
+            out = f.tmp_sums if many else eq_sums
+            if not l2 and hasattr(p, "forward_backward"):      # MSE seeds: one call, the sweeps fused where the plan allows
+                p.forward_backward(self.Re, coef_eq, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm,
+                                   scale=self.scale, want_ebar=self.e_trainable, sums_out=out)
+            else:
+                p.forward(self.Re, e=ek, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
+                          sums_out=out)
+                if l2:      # d ||eq_k|| / d theta = sum eq_k d eq_k / ||eq_k||: the reverse sweep's seeds with alpha_e / ||eq_k||
+                    ne = torch.sqrt(out[:3]).cpu().numpy().astype(np.float64)
+                    coef_eq = tuple(self.alpha_e / max(v, 1e-30) for v in ne) + (0.0,)
+                p.backward(self.Re, coef_eq, e=ek, scale=self.scale, want_ebar=self.e_trainable)
+            if many:
+                eq_sums += f.tmp_sums
+            if k < len(passes) - 1:
                 if bal is None:
-                    grad_reduce(self.net, [ck], self.grads, accumulate=k > 0)
-                elif k < len(f.chunks) - 1:
-                    grad_reduce_terms(self.net, [[ck], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
-            if side is not None:
-                main.wait_stream(side)
-            if bal is None:
-                grad_reduce(self.net, value_plans, self.grads, accumulate=True)
-            else:
-                self._reduce_terms([f.chunks[-1]], b, s, len(f.chunks) > 1, update)
-        elif not l2 and hasattr(f, "forward_backward"):      # MSE seeds: one call, the sweeps fused where the plan allows
-            f.forward_backward(self.Re, coef_eq, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale,
-                               want_ebar=self.e_trainable, sums_out=sums[S_EQ:S_EQ + NLOSS])
-            if side is not None:
-                main.wait_stream(side)
-            if bal is None:
-                grad_reduce(self.net, [f] + value_plans, self.grads)
-            else:
-                self._reduce_terms([f], b, s, False, update)
+                    grad_reduce(self.net, [p], self.grads, accumulate=k > 0)
+                else:
+                    grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
+        if side is not None:
+            main.wait_stream(side)
+        last = passes[-1][1]
+        if bal is None:
+            grad_reduce(self.net, [last, b] + ([] if s is None else [s]), self.grads, accumulate=many)
         else:
-            f.forward(self.Re, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=True,
-                      sums_out=sums[S_EQ:S_EQ + NLOSS])
-            if l2:      # d ||eq_k|| / d theta = sum eq_k d eq_k / ||eq_k||: the reverse sweep's seeds with alpha_e / ||eq_k||
-                ne = torch.sqrt(sums[S_EQ:S_EQ + 3]).cpu().numpy().astype(np.float64)
-                coef_eq = tuple(self.alpha_e / max(v, 1e-30) for v in ne) + (0.0,)
-            f.backward(self.Re, coef_eq, e=e, scale=self.scale, want_ebar=self.e_trainable)
-            if side is not None:
-                main.wait_stream(side)
-            if bal is None:
-                grad_reduce(self.net, [f] + value_plans, self.grads)
-            else:
-                self._reduce_terms([f], b, s, False, update)
+            self._reduce_terms([last], b, s, many, update)
         if self.net_e is not None:
             if self.e_trainable:
                 self.plan_e.backward(out_adj=f.ebar)
@@ -893,10 +889,11 @@ class PinnEngine:
             self._n_p_valid = n
         return self._n_p_valid
 
-    def loss_terms(self):
-        """Device tensors (no sync): dict of loss_eq1..4, loss_e, loss_b, loss_s, loss."""
+    def loss_terms(self, mode="MSE"):
+        """Device tensors (no sync): dict of loss_eq1..4, loss_e, loss_b, loss_s, loss of the sums of the last
+        evaluation, in the loss mode it ran with."""
         s = self.sums
-        if self.loss_mode == "L2":      # NSFnet/pinn_solver.py:202-204, 214-217
+        if mode == "L2":      # NSFnet/pinn_solver.py:202-204, 214-217
             eq = torch.sqrt(s[S_EQ:S_EQ + 4])
             loss_e = eq[0] + eq[1] + eq[2]
             loss_b = torch.sqrt(s[S_BC]) + torch.sqrt(s[S_BC + 1])
@@ -942,8 +939,6 @@ class PinnEngine:
         than the previous one starts fresh, as a new torch.optim.LBFGS does.  With the same owner the state carries
         on across calls - also across Adam steps or changed loss weights in between, exactly as the state of one
         torch.optim.LBFGS object does."""
-        if self.loss_mode != "MSE":
-            raise ValueError("L-BFGS optimizes the MSE loss only (loss_mode %r)" % self.loss_mode)
         _lbfgs.check_knobs(lr, max_iter, max_eval, history_size, line_search_fn)
         if self._lbfgs is None or self._lbfgs.history_size != int(history_size):
             self._lbfgs = LbfgsHistory(self.P, int(history_size), self.device)
@@ -971,7 +966,7 @@ class PinnEngine:
         once per (lr, schedule state) in a hipGraph and replayed.  Opt-in: measured on MI355X the eager
         launch sequence (~14 launches, all asynchronous) already keeps the GPU busy down to the 4x50 /
         10 k-point step (0.12 ms), and replay is 0-6 % slower; it pays only when the host is contended."""
-        if not self._graphs_enabled() or self.loss_mode != "MSE":
+        if not self._graphs_enabled():
             self.loss_and_grad()
             self.adam_step(lr)
             return

@@ -23,10 +23,10 @@ import torch.distributed as dist
 
 from . import engine as _eng
 from .net import FCNet
-from .pinn_solver import AdamHandle, _col, default_device, is_lbfgs, lbfgs_knobs
+from .pinn_solver import AdamHandle, SolverBase, _col, default_device, is_lbfgs, lbfgs_knobs
 
 
-class PysicsInformedNeuralNetwork:
+class PysicsInformedNeuralNetwork(SolverBase):
     tb_writer = None
     global_step = 0
 
@@ -182,12 +182,6 @@ class PysicsInformedNeuralNetwork:
         self.eq_weights = w
         return idx
 
-    def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
-        """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
-        if int(every) < 0:
-            raise ValueError("every must be >= 0")
-        self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
-
     def init_vis_t(self):
         self.engine.alpha_evm = float(self.alpha_evm)
         self.engine.init_vis_t()
@@ -243,24 +237,6 @@ class PysicsInformedNeuralNetwork:
         self.supervision_enabled = self.supervision_has_data and self.alpha_s != 0.0
         self.engine.alpha_s = float(self.alpha_s) if self.supervision_enabled else 0.0
 
-
-    # ---------------------------------------------------------------- adaptive loss-weight balancing
-    def set_loss_balancing(self, every=0, beta=0.1):
-        """every > 0: the boundary (and supervised) weight follows the learning-rate-annealing rule every `every` Adam updates
-        (PinnEngine.set_loss_balancing).  alpha_b stays the configured weight (it names the
-        checkpoint directory); the weight in use is lam_b().  every = 0: off."""
-        self.engine.set_loss_balancing(every, beta)
-        self._balancing = int(every) > 0
-
-    def lam_b(self):
-        """The boundary weight in use (one host read when balancing is on)."""
-        if not getattr(self, "_balancing", False):
-            return self.alpha_b
-        return float(self.engine.loss_weights()[0])
-
-    def set_optimizers(self, opt):
-        self.opt = opt
-
     def set_alpha_evm(self, alpha):
         self.alpha_evm = alpha
         self.engine.alpha_evm = float(alpha)
@@ -269,18 +245,11 @@ class PysicsInformedNeuralNetwork:
         return FCNet(num_ins=num_ins, num_outs=num_outs, num_layers=num_layers, hidden_size=hidden_size,
                      activation=torch.nn.Tanh, device=self.device)
 
-    def set_eq_training_func(self, train_data_func):
-        self.train_data_func = train_data_func
-
     # ---------------------------------------------------------------- model evaluation
     def neural_net_u(self, x, y):
         """u, v as (N,), p, e as (N,1) device tensors - the reference's mixed shapes (:284-287)."""
         u, v, p, e = self.engine.predict(_col(x), _col(y), with_e=True)
         return u, v, p.reshape(-1, 1), e.reshape(-1, 1)
-
-    def predict(self, net_params, X):
-        x, y = X
-        return self.neural_net_u(x, y)
 
     @property
     def vis_t(self):
@@ -328,10 +297,8 @@ class PysicsInformedNeuralNetwork:
         self._last_log_time, self._last_log_epoch = time.time(), 0
         if not hasattr(self, 'log_interval'):
             self.log_interval = 100
-        rs = self._resampling
         for epoch_id in range(num_epoch):
-            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
-                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self._maybe_resample(epoch_id)
             self.global_step += 1
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
             if scheduler:
@@ -359,10 +326,8 @@ class PysicsInformedNeuralNetwork:
             self.log_interval = 100
         self.freeze_evm_net(0)
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
-        rs = self._resampling
         for epoch_id in range(num_epoch):
-            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
-                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self._maybe_resample(epoch_id)
             self.global_step += 1
             self._apply_freeze_schedule(epoch_id)
             interval = self.log_interval if self.log_interval > 0 else 100
@@ -421,7 +386,7 @@ class PysicsInformedNeuralNetwork:
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))
-        if getattr(self, "_balancing", False):
+        if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]
                   + ('  lambda_s=%.4e' % lam[1] if self.supervision_total_points > 0 and self.alpha_s != 0.0 else ''))
@@ -497,6 +462,3 @@ class PysicsInformedNeuralNetwork:
         plan.forward(self.Re, e=pe.pred[0], vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.coord_scale,
                      save=False)
         return tuple(plan.field(k).reshape(-1, 1).clone() for k in ("eq1", "eq2", "eq3", "eq4"))
-
-    def divergence(self, x_star, y_star):
-        return self.neural_net_equations(x_star, y_star)[2]

@@ -54,7 +54,51 @@ def default_device():
     return torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
 
 
-class PysicsInformedNeuralNetwork:
+class SolverBase:
+    """What the plain and the ev drop-in classes share: the knobs of the features the reference does not have
+    (resampling, loss balancing) and the methods whose bodies are the same in both reference classes."""
+    _balancing = False
+
+    def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
+        """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
+
+    def _maybe_resample(self, epoch_id):
+        """The resampling cadence of solve_Adam / solve_LBFGS (set_resampling)."""
+        rs = self._resampling
+        if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
+            self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+
+    def set_loss_balancing(self, every=0, beta=0.1):
+        """every > 0: the boundary (and supervised) weight follows the learning-rate-annealing rule every `every` Adam
+        updates (PinnEngine.set_loss_balancing).  alpha_b stays the configured weight (it names
+        the checkpoint directory); the weight in use is lam_b().  every = 0: off."""
+        self.engine.set_loss_balancing(every, beta)
+        self._balancing = int(every) > 0
+
+    def lam_b(self):
+        """The boundary weight in use (one host read when balancing is on)."""
+        if not self._balancing:
+            return self.alpha_b
+        return float(self.engine.loss_weights()[0])
+
+    def set_optimizers(self, opt):
+        self.opt = opt
+
+    def set_eq_training_func(self, train_data_func):
+        self.train_data_func = train_data_func
+
+    def predict(self, net_params, X):
+        x, y = X
+        return self.neural_net_u(x, y)
+
+    def divergence(self, x_star, y_star):
+        return self.neural_net_equations(x_star, y_star)[2]
+
+
+class PysicsInformedNeuralNetwork(SolverBase):
     # training_type:  'unsupervised' | 'half-supervised'  (kept for signature compatibility)
     def __init__(self,
                  opt=None,
@@ -134,39 +178,12 @@ class PysicsInformedNeuralNetwork:
         self.x_f, self.y_f = x.reshape(-1, 1), y.reshape(-1, 1)
         return idx
 
-    def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
-        """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
-        if int(every) < 0:
-            raise ValueError("every must be >= 0")
-        self._resampling = dict(every=int(every), k=float(k), c=float(c), seed=int(seed))
-
-
-    # ---------------------------------------------------------------- adaptive loss-weight balancing
-    def set_loss_balancing(self, every=0, beta=0.1):
-        """every > 0: the boundary weight follows the learning-rate-annealing rule every `every` Adam updates
-        (PinnEngine.set_loss_balancing).  alpha_b stays the configured weight (it names the
-        checkpoint directory); the weight in use is lam_b().  every = 0: off."""
-        self.engine.set_loss_balancing(every, beta)
-        self._balancing = int(every) > 0
-
-    def lam_b(self):
-        """The boundary weight in use (one host read when balancing is on)."""
-        if not getattr(self, "_balancing", False):
-            return self.alpha_b
-        return float(self.engine.loss_weights()[0])
-
-    def set_optimizers(self, opt):
-        self.opt = opt
-
     def set_stage(self, stage):
         self.stage = stage
 
     def initialize_NN(self, num_ins=2, num_outs=4, num_layers=6, hidden_size=160):
         return FCNet(num_ins=num_ins, num_outs=num_outs, num_layers=num_layers, hidden_size=hidden_size,
                      activation=torch.nn.Tanh, device=self.device)
-
-    def set_eq_training_func(self, train_data_func):
-        self.train_data_func = train_data_func
 
     # ---------------------------------------------------------------- model evaluation
     def neural_net_u(self, x, y):
@@ -180,19 +197,9 @@ class PysicsInformedNeuralNetwork:
         plan.forward(self.Re, save=False)
         return tuple(plan.field(k).reshape(-1, 1).clone() for k in ("eq1", "eq2", "eq3"))
 
-    def predict(self, net_params, X):
-        x, y = X
-        return self.neural_net_u(x, y)
-
     # ---------------------------------------------------------------- loss / step
-    def _publish_terms(self):
-        mode = getattr(self, "_loss_mode_published", "MSE")
-        self.engine.loss_mode = mode
-        try:
-            t = self.engine.loss_terms()
-        finally:
-            self.engine.loss_mode = "MSE"
-        self._loss_mode_published = "MSE"
+    def _publish_terms(self, loss_mode="MSE"):
+        t = self.engine.loss_terms(loss_mode)
         f = self.engine.plan_f
         self.loss_eq1, self.loss_eq2, self.loss_eq3 = t["loss_eq1"], t["loss_eq2"], t["loss_eq3"]
         self.loss_e, self.loss_b, self.loss = t["loss_e"], t["loss_b"], t["loss"]
@@ -205,18 +212,12 @@ class PysicsInformedNeuralNetwork:
         """Loss of the current parameters AND its parameter gradient (the HIP pipeline fuses
         what the reference splits into this call and ``loss.backward()``, solver :197-226,252).
         Returns (loss, [loss_e, loss_b]) as 0-dim device tensors."""
-        if loss_mode not in ('MSE', 'L2'):
-            raise ValueError("loss_mode must be 'MSE' or 'L2'")
         assert self.x_f is not None and self.y_f is not None
         # 'L2' (solver :202-204, :214-217; no script of the reference selects it): 2-norms of the residual and
-        # boundary-misfit vectors instead of mean squares - same kernels, other adjoint coefficients (engine.loss_mode)
-        self.engine.loss_mode = loss_mode
-        try:
-            self.engine.loss_and_grad()
-        finally:
-            self.engine.loss_mode = 'MSE'
-            self._loss_mode_published = loss_mode
-        self._publish_terms()
+        # boundary-misfit vectors instead of mean squares - same kernels, other adjoint coefficients (an unknown
+        # mode raises ValueError)
+        self.engine.loss_and_grad(loss_mode)
+        self._publish_terms(loss_mode)
         return self.loss, [self.loss_e, self.loss_b]
 
     def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None):
@@ -233,11 +234,9 @@ class PysicsInformedNeuralNetwork:
         print('--------')
         print(num_epoch)
         print('--------')
-        rs = self._resampling
         log_now = save_now = False
         for epoch_id in range(num_epoch):
-            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
-                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self._maybe_resample(epoch_id)
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
             if scheduler:
                 scheduler.step()
@@ -262,10 +261,8 @@ class PysicsInformedNeuralNetwork:
         print('--------')
         print(num_epoch)
         print('--------')
-        rs = self._resampling
         while epoch_id < num_epoch:
-            if rs["every"] > 0 and epoch_id > 0 and epoch_id % rs["every"] == 0:
-                self.resample_collocation(rs["k"], rs["c"], rs["seed"])
+            self._maybe_resample(epoch_id)
             lr = self.opt.param_groups[0]['lr']
             log_now = self.log_every and epoch_id % self.log_every == 0
             save_now = self.save_every and epoch_id % self.save_every == 0
@@ -290,7 +287,7 @@ class PysicsInformedNeuralNetwork:
               "eq1_loss: %.3e " % (self.loss_eq1.item()),
               "eq2_loss: %.3e " % (self.loss_eq2.item()),
               "eq4_loss: %.3e \n" % (self.loss_eq3.item()),
-              *(("lambda_b: %.4e" % self.lam_b(),) if getattr(self, "_balancing", False) else ()))
+              *(("lambda_b: %.4e" % self.lam_b(),) if self._balancing else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):
@@ -342,6 +339,3 @@ class PysicsInformedNeuralNetwork:
         if getattr(self, "loss_eq1", None) is not None:
             scipy.io.savemat(save_matlab_to + 'eq_losses.mat',
                              {'eq1': self.loss_eq1.item(), 'eq2': self.loss_eq2.item(), 'eq3': self.loss_eq3.item()})
-
-    def divergence(self, x_star, y_star):
-        return self.neural_net_equations(x_star, y_star)[2]

@@ -278,9 +278,9 @@ def test_new_lbfgs_object_after_adam_starts_fresh(monkeypatch):
     assert P.engine._lbfgs_state.n_iter == 1
 
 
-def test_solver_dispatches_lbfgs_and_resample_resets(monkeypatch):
+def test_solver_dispatches_lbfgs_and_keeps_its_history(monkeypatch):
     """train(optimizer=LBFGS) runs the L-BFGS loop (the Adam path would leave the moments non-zero), the history
-    persists across train() calls and a resample resets it."""
+    persists across train() calls and lbfgs_reset clears it."""
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
     P = _gloo_solver(_gloo_case(), monkeypatch)
@@ -289,10 +289,31 @@ def test_solver_dispatches_lbfgs_and_resample_resets(monkeypatch):
     assert float(P.engine.net.m.abs().max()) == 0.0
     P.engine.lbfgs_reset()
     assert P.engine._lbfgs_state.n_iter == 0
-    with pytest.raises(ValueError, match="MSE"):
-        P.engine.loss_mode = "L2"
-        P.engine.lbfgs_step()
-    P.engine.loss_mode = "MSE"
+
+
+def test_an_l2_evaluation_does_not_change_the_lbfgs_objective(monkeypatch):
+    """The loss mode is an argument of one evaluation: an L2 fwd_computing_loss_2d before lbfgs_step leaves it on the
+    MSE loss, with the iterate and loss of a run without that call."""
+    import fakes
+    from nsfnet_amd import engine as eng
+    from nsfnet_amd import pinn_solver as ps
+    fakes.install(monkeypatch)
+    monkeypatch.setattr(eng, "LbfgsHistory", ModelHistory)
+    case = _gloo_case()
+
+    def run(l2_first):
+        torch.manual_seed(3)
+        P = ps.PysicsInformedNeuralNetwork(Re=400, layers=2, hidden_size=10, N_f=70, bc_weight=10, eq_weight=1)
+        P.set_boundary_data(X=(case["xb"], case["yb"], case["ub"], case["vb"]))
+        P.set_eq_training_data(X=(case["x"], case["y"]))
+        if l2_first:
+            P.fwd_computing_loss_2d(loss_mode="L2")
+        entry = P.engine.lbfgs_step(max_iter=3, history_size=5, line_search_fn="strong_wolfe")
+        return entry, float(P.engine.loss_terms()["loss"]), P.engine.net.params.clone()
+
+    a, b = run(False), run(True)
+    assert a[:2] == b[:2]
+    assert torch.equal(a[2], b[2])
 
 
 # ---------------------------------------------------------------- 4. ev drop-in YAML

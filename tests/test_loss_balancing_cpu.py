@@ -126,7 +126,7 @@ def test_off_restart_and_bad_arguments(monkeypatch):
             e.set_loss_balancing(**bad)
 
 
-def test_l2_is_rejected_before_the_stream_switch(monkeypatch):
+def test_l2_argument_is_rejected_before_the_stream_switch(monkeypatch):
     case = _case()
     e = _engine(monkeypatch, case)
     switched = []
@@ -135,12 +135,10 @@ def test_l2_is_rejected_before_the_stream_switch(monkeypatch):
     e._overlap = True
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: "main")
     monkeypatch.setattr(e, "_side_stream", lambda main: type("S", (), {"wait_stream": lambda self, m: None})())
-    e.loss_mode = "L2"
     with pytest.raises(ValueError, match="MSE"):
-        e.loss_and_grad()
+        e.loss_and_grad("L2")
     assert switched == []
     e.device = torch.device("cpu")
-    e.loss_mode = "MSE"
 
 
 def test_lambda_is_frozen_through_lbfgs(monkeypatch):
@@ -239,7 +237,7 @@ def test_two_rank_balancing_matches_single_process(tmp_path, monkeypatch):
 
 
 # ---------------------------------------------------------------- solvers: lam_bcs, save path, log line
-def test_solvers_write_the_current_weight_and_keep_the_configured_path(monkeypatch, tmp_path):
+def test_solvers_write_the_current_weight_keep_the_configured_path_and_refuse_l2(monkeypatch, tmp_path):
     import scipy.io
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
@@ -281,7 +279,32 @@ def test_solvers_write_the_current_weight_and_keep_the_configured_path(monkeypat
     assert len(list(tmp_path.glob("results/Re400/*lamB10*/q.pth"))) == 1
     with pytest.raises(ValueError, match="MSE"):
         Q.fwd_computing_loss_2d(loss_mode="L2")
-    assert Q.engine.loss_mode == "MSE"
+    _assert_next_published_loss_is_mse(Q)
+
+
+def _assert_next_published_loss_is_mse(P):
+    """After a refused L2 call, the next Adam epoch publishes the MSE terms, not 2-norms of the same sums."""
+    P.log_every = P.save_every = 0
+    with contextlib.redirect_stdout(io.StringIO()):
+        P.train(num_epoch=1, lr=1e-3)
+    mse, l2 = P.engine.loss_terms(), P.engine.loss_terms("L2")
+    for k in ("loss", "loss_e", "loss_b"):
+        assert float(getattr(P, k)) == float(mse[k]) != float(l2[k]), k
+
+
+def test_refused_l2_call_leaves_the_solver_on_mse(monkeypatch):
+    """A chunked collocation set refuses the L2 mode; the solver then goes on publishing MSE terms."""
+    import fakes
+    from nsfnet_amd import pinn_solver as ps
+    fakes.install(monkeypatch)
+    monkeypatch.setenv("NSFNET_CHUNK_POINTS", "128")
+    case = _case(N=300)
+    P = ps.PysicsInformedNeuralNetwork(Re=400, layers=2, hidden_size=10, N_f=70, bc_weight=10, eq_weight=1)
+    P.set_boundary_data(X=(case["xb"], case["yb"], case["ub"], case["vb"]))
+    P.set_eq_training_data(X=(case["x"].reshape(-1, 1), case["y"].reshape(-1, 1)))
+    with pytest.raises(NotImplementedError, match="L2"):
+        P.fwd_computing_loss_2d(loss_mode="L2")
+    _assert_next_published_loss_is_mse(P)
 
 
 # ---------------------------------------------------------------- ev drop-in YAML

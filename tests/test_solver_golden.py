@@ -250,3 +250,31 @@ def test_nsfnet_solver_l2_loss_mode_vs_reference(golden_dir, tmp_path, monkeypat
         assert _rel_l2(upd, g["params_after"][k].astype(np.float64) - w0) < 2e-3
     with pytest.raises(ValueError):
         P.fwd_computing_loss_2d(loss_mode='L1')
+
+
+@pytest.mark.parametrize("refusal", ["ev", "balancing"])
+def test_refused_l2_call_leaves_the_current_stream(monkeypatch, refusal):
+    """loss_and_grad('L2') refuses the ev flavour and loss balancing before it moves to the side stream: the caller's
+    current stream is the one it had, and the next MSE evaluation runs."""
+    from nsfnet_amd import engine as eng
+    from oracle import autograd_ref as ar
+    monkeypatch.delenv("NSFNET_OVERLAP_BC", raising=False)      # (the side stream is on by default)
+    dev = torch.device("cuda:0")
+    kw = dict(flavour="ev", n_hidden_e=2, hidden_e=20, alpha_evm=0.05) if refusal == "ev" else {}
+    E = eng.PinnEngine(dev, 3, 24, 400.0, alpha_b=10.0, alpha_e=1.0, **kw)
+    E.net.set_flat(ar.flat_params(ar.seeded_net(3, 3, 24, seed=5)))
+    if refusal == "ev":
+        E.net_e.set_flat(ar.flat_params(ar.seeded_net(1, 2, 20, seed=6)))
+    rng = np.random.RandomState(0)
+    E.set_collocation(rng.rand(200).astype(np.float32), rng.rand(200).astype(np.float32))
+    E.set_boundary(*(a.reshape(-1)[::16].astype(np.float32) for a in ar.cavity_boundary()))
+    if refusal == "balancing":
+        E.set_loss_balancing(every=1)
+    assert E._overlap
+    before = torch.cuda.current_stream(dev)
+    with pytest.raises(NotImplementedError if refusal == "ev" else ValueError):
+        E.loss_and_grad("L2")
+    assert torch.cuda.current_stream(dev) == before
+    E.loss_and_grad()
+    torch.cuda.synchronize()
+    assert torch.isfinite(E.loss_terms()["loss"]).item()
