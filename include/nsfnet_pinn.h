@@ -257,6 +257,31 @@ int pinn_balance_update(const double* partials, int64_t n, int terms, double bet
 int pinn_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, int64_t n,
                          void* stream);
 
+/* ---- stochastic mini-batching of the collocation term ---------------------------------
+ * No reference counterpart (its roadmap asks for "mini-batch PDE points", ev-NSFnet/README.md; its `batchsize`
+ * argument is dead).  A store of n collocation points (x, y, optional weights w, optional lagged state vis_t_minus)
+ * stays resident; every call draws a batch of b points from it (1 <= b <= n <= 2^30), stratified, one point per
+ * stratum, all in integers.  For batch slot j in [0, b):
+ *   lo = floor(j n / b),  hi = floor((j + 1) n / b)                      (64-bit arithmetic)
+ *   r  = word 0 of Philox4x32-10, counter (j_lo32, j_hi32, t_lo32, t_hi32), key (seed_lo32, rank)
+ *   idx[j] = lo + ((r * (hi - lo)) >> 32)                                (32 x 32 -> 64-bit product, high word)
+ *   dst_*[j] = src_*[idx[j]]   for x and y, and for w / vis_t_minus where given
+ * idx is strictly ascending (an ordering of the store survives) and b = n draws the identity.  When b does not
+ * divide n the strata differ by one point, so a point's inclusion probability differs by that much.
+ * t is the draw counter counter[0] in DEVICE memory: the draw reads it and advances it by one when every workgroup
+ * is done, so a captured hipGraph draws a new batch on every replay with no host scalar changing.  counter: two
+ * int64, [0] = t, [1] = scratch that is 0 between calls; the caller zeroes both to restart the sequence.
+ * src_w and dst_w (and src_vtm and dst_vtm) are both given or both NULL = absent.  The batch buffers must not
+ * overlap the store.  One launch. */
+int pinn_batch_draw(int64_t n, int64_t b, uint64_t seed, int rank, int64_t* counter,
+                    const float* src_x, const float* src_y, const float* src_w, const float* src_vtm,
+                    float* dst_x, float* dst_y, float* dst_w, float* dst_vtm, int64_t* idx, void* stream);
+/* store_vtm[idx[j]] = batch_vtm[j] for j in [0, b): the batch's updated lagged state back to the store (ev flavour).
+ * idx as written by pinn_batch_draw: distinct, so no atomics; an index outside [0, n) is skipped.  Nothing else of
+ * the store is written.  One launch. */
+int pinn_batch_scatter(const int64_t* idx, int64_t b, int64_t n, const float* batch_vtm, float* store_vtm,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

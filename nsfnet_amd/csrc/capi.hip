@@ -618,4 +618,35 @@ int pinn_balance_combine(float* g, const float* gr, const float* gb, const float
   return rc ? hipfail(rc, "pinn_balance_combine") : 0;
 }
 
+
+int pinn_batch_draw(int64_t n, int64_t b, uint64_t seed, int rank, int64_t* counter,
+                    const float* src_x, const float* src_y, const float* src_w, const float* src_vtm,
+                    float* dst_x, float* dst_y, float* dst_w, float* dst_vtm, int64_t* idx, void* stream) {
+  if (!counter || !src_x || !src_y || !dst_x || !dst_y || !idx) return fail(-22, "pinn_batch_draw: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_batch_draw: store size must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (b < 1 || b > n) return fail(-22, "pinn_batch_draw: batch size must be 1..n (got %s%ld)", "", (long)b);
+  if (rank < 0) return fail(-22, "pinn_batch_draw: rank must be >= 0%s");
+  if (!src_w != !dst_w) return fail(-22, "pinn_batch_draw: src_w and dst_w must both be given or both be NULL%s");
+  if (!src_vtm != !dst_vtm) return fail(-22, "pinn_batch_draw: src_vtm and dst_vtm must both be given or both be NULL%s");
+  BatchDrawArgs a;
+  a.n = (long)n; a.b = (long)b;
+  a.seed = (unsigned)(seed & 0xffffffffu); a.rank = (unsigned)rank;
+  a.counter = reinterpret_cast<long long*>(counter);
+  a.sx = src_x; a.sy = src_y; a.sw = src_w; a.sv = src_vtm;
+  a.dx = dst_x; a.dy = dst_y; a.dw = dst_w; a.dv = dst_vtm;
+  a.idx = reinterpret_cast<long long*>(idx);
+  int rc = launch_batch_draw(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_batch_draw") : 0;
+}
+
+int pinn_batch_scatter(const int64_t* idx, int64_t b, int64_t n, const float* batch_vtm, float* store_vtm,
+                       void* stream) {
+  if (!idx || !batch_vtm || !store_vtm) return fail(-22, "pinn_batch_scatter: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_batch_scatter: store size must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (b < 1 || b > n) return fail(-22, "pinn_batch_scatter: batch size must be 1..n (got %s%ld)", "", (long)b);
+  int rc = launch_batch_scatter(reinterpret_cast<const long long*>(idx), (long)b, (long)n, batch_vtm, store_vtm,
+                                (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_batch_scatter") : 0;
+}
+
 }  // extern "C"

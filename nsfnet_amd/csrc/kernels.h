@@ -229,3 +229,14 @@ int launch_balance_update(const double* partials, long n, int terms, double beta
                           hipStream_t s);
 int launch_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, long n,
                            hipStream_t s);
+// stochastic mini-batching of the collocation term (batch.hip)
+struct BatchDrawArgs {
+  long n, b;                               // store points, batch points (1 <= b <= n)
+  unsigned seed, rank;                     // Philox key
+  long long* counter;                      // [draw counter t, ticket of the workgroups done]
+  const float *sx, *sy, *sw, *sv;          // store x, y, w, vis_t_minus (sw / sv NULL: absent)
+  float *dx, *dy, *dw, *dv;                // batch buffers
+  long long* idx;                          // [b] drawn store indices
+};
+int launch_batch_draw(const BatchDrawArgs& a, hipStream_t s);
+int launch_batch_scatter(const long long* idx, long b, long n, const float* src, float* dst, hipStream_t s);

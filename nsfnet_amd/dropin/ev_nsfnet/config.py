@@ -67,6 +67,15 @@ class LossBalancingConfig:
     beta: float = 0.1
 
 
+@dataclass
+class BatchingConfig:
+    """Stochastic mini-batching of the collocation term (PinnEngine.set_batching), off by default.  batch_points is
+    per rank; an L-BFGS stage ignores it."""
+    enabled: bool = False
+    batch_points: int = 12000
+    seed: int = 0
+
+
 def _default_stages():
     table = [(0.05, 1e-3), (0.03, 2e-4), (0.01, 4e-5), (0.005, 1e-5), (0.002, 2e-6), (0.002, 2e-6)]
     return [TrainingStage(a, 500000, lr, "Stage %d" % (i + 1)) for i, (a, lr) in enumerate(table)]
@@ -83,6 +92,7 @@ class TrainingConfig:
     coordinate_transform: bool = False
     resampling: ResamplingConfig = field(default_factory=ResamplingConfig)
     loss_balancing: LossBalancingConfig = field(default_factory=LossBalancingConfig)
+    batching: BatchingConfig = field(default_factory=BatchingConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -144,6 +154,9 @@ class ConfigManager:
         lb = c.training.loss_balancing
         if lb.enabled and (lb.every < 1 or not 0.0 < lb.beta <= 1.0):
             problems.append("training.loss_balancing: every >= 1 and 0 < beta <= 1 required")
+        bt = c.training.batching
+        if bt.enabled and (bt.batch_points < 1 or bt.seed < 0):
+            problems.append("training.batching: batch_points >= 1 and seed >= 0 required")
         for st in c.training.training_stages:
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
@@ -173,5 +186,7 @@ class ConfigManager:
                   % (t.resampling.every, t.resampling.pool_points, t.resampling.k, t.resampling.c, t.resampling.seed))
         if t.loss_balancing.enabled:
             print("balancing  : every=%d beta=%s" % (t.loss_balancing.every, t.loss_balancing.beta))
+        if t.batching.enabled:
+            print("batching   : batch_points=%d (per rank) seed=%d" % (t.batching.batch_points, t.batching.seed))
         print("supervision: enabled=%s samples=%d weight=%s"
               % (c.supervision.enabled, c.supervision.num_samples, c.supervision.loss_weight))

@@ -99,6 +99,9 @@ def main():
         lb = cfg.training.loss_balancing
         if lb.enabled:    # after the supervised weight: the balanced weights start at the configured ones
             PINN.set_loss_balancing(every=lb.every, beta=lb.beta)
+        bt = cfg.training.batching
+        if bt.enabled:    # the collocation set is in place: it becomes the store the batches are drawn from
+            PINN.set_batching(batch_points=bt.batch_points, seed=bt.seed)
         for st in cfg.training.training_stages:
             if rank == 0:
                 log.stage(st.name, st.alpha, st.epochs, st.lr)

@@ -402,6 +402,21 @@ def balance_combine(g, gr, gb, gs, lam):
 BALANCE_RECORD = 12      # PINN_BALANCE_RECORD
 
 
+def batch_draw(store, batch, idx, n, b, seed, rank, counter):
+    """pinn_batch_draw: draw b of the n store points (stratified; counter = device [t, scratch], advanced by one) into
+    idx and gather store['x' | 'y' | 'w' | 'vtm'] at them into batch[...] (w / vtm None: absent).  One launch."""
+    _lib.check(_lib.load().pinn_batch_draw(
+        int(n), int(b), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rank), _ptr(counter), _ptr(store["x"]), _ptr(store["y"]),
+        _ptr(store.get("w")), _ptr(store.get("vtm")), _ptr(batch["x"]), _ptr(batch["y"]), _ptr(batch.get("w")),
+        _ptr(batch.get("vtm")), _ptr(idx), _stream()), "pinn_batch_draw")
+
+
+def batch_scatter(idx, b, n, batch_vtm, store_vtm):
+    """pinn_batch_scatter: store_vtm[idx[j]] = batch_vtm[j] for j in [0, b).  One launch."""
+    _lib.check(_lib.load().pinn_batch_scatter(_ptr(idx), int(b), int(n), _ptr(batch_vtm), _ptr(store_vtm), _stream()),
+               "pinn_batch_scatter")
+
+
 class LbfgsHistory:
     """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
     g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
@@ -482,6 +497,16 @@ class _Balance:
         self.buf = self.gb = self.gs = self.lam = self.rec = self.parts = None
 
 
+class _Batching:
+    """State of the stochastic mini-batching (set_batching): the batch plan f of B points (and, ev flavour, the
+    entropy net's plan e on the same x / y buffers), the device index vector idx [B] int64 and the device draw
+    counter [t, scratch]."""
+
+    def __init__(self, B, seed, rank):
+        self.B, self.seed, self.rank = B, seed, rank
+        self.f = self.e = self.idx = self.counter = None
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -528,6 +553,9 @@ class PinnEngine:
         self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
         self._bal = None                    # adaptive loss-weight balancing (set_loss_balancing; None = off)
         self._bal_frozen = False            # lbfgs_step: the weights are held fixed
+        self._batch = None                  # stochastic mini-batching (set_batching; None = off)
+        self._batch_frozen = False          # lbfgs_step: the full objective, i.e. the store
+        self._eval_batch = False            # the last evaluation ran on the batch plan (loss_terms' normalisation)
 
     # ---- views into the exchange buffer ----
     @property
@@ -547,11 +575,16 @@ class PinnEngine:
         """chunk_points (or $NSFNET_CHUNK_POINTS): process the set in passes of that many points sharing
         one activation workspace (ChunkedResidual); default: one pass, everything resident."""
         import os
-        self._graphs.clear()      # captured steps hold the old plan's pointers
-        self.lbfgs_reset()
         if chunk_points is None and os.environ.get("NSFNET_CHUNK_POINTS"):
             chunk_points = int(os.environ["NSFNET_CHUNK_POINTS"])
         n = int(np.asarray(x).size)
+        bt = self._batch
+        if bt is not None and chunk_points and n > int(chunk_points):
+            raise ValueError("mini-batching needs a resident store: chunk_points=%d with batching on" % int(chunk_points))
+        if bt is not None and bt.B > n:
+            raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points" % (bt.B, n))
+        self._graphs.clear()      # captured steps hold the old plan's pointers
+        self.lbfgs_reset()
         if chunk_points and n > int(chunk_points):
             self.plan_f = ChunkedResidual(self.net, x, y, weights, chunk_points)
         else:
@@ -560,6 +593,100 @@ class PinnEngine:
         if self.net_e is not None:
             self.plan_e = ValuePlan(self.net_e, x, y)
             self.init_vis_t()
+        self._eval_batch = False
+        if bt is not None:
+            self._make_batch_plans(bt)      # the store may have gained or lost its weights; the draw counter carries on
+
+    # ---- stochastic mini-batching of the collocation term ----
+    def set_batching(self, batch_points=0, seed=0):
+        """batch_points = B > 0: every evaluation made for Adam (step(), and loss_and_grad() followed by adam_step())
+        runs the collocation term on a fresh random batch of B of the N local collocation points, which stay
+        resident as the store.  Each evaluation (1) draws B ascending, distinct store indices on the device,
+        stratified with one point per stratum [floor(j N / B), floor((j + 1) N / B)) (Philox4x32-10, counter
+        (slot j, draw number t), key (seed, rank); t lives in device memory and advances by one per draw, so a
+        captured step draws a new batch on every replay), (2) gathers x, y, w and vis_t_minus of those points into the
+        batch plan's buffers, (3) runs the usual step on the batch plan with the collocation normalisation
+        B * world_size instead of n_f_global, and (4), ev flavour, scatters the batch's updated vis_t_minus back to
+        the store, so a point's lagged viscosity is alpha_evm |e| at its last visit.
+
+        The weights are used as gathered, without renormalising them per batch.  When B divides N every point is
+        drawn with probability B / N and the batch loss is an unbiased estimate of the full weighted mean; when it
+        does not, the strata differ by one point, and so do the inclusion probabilities (1 / floor(N / B) against
+        1 / ceil(N / B)): the estimate is biased by that much.  B = N draws the identity: the step is the full one,
+        bit for bit.  The boundary and supervised terms always use their full sets.  Multi-rank: B is per rank and
+        must be the same on all ranks; every rank draws from its own shard.
+
+        lbfgs_step, resample, init_vis_t and collocation_points keep using the store.  batch_points = 0: off.  A call
+        restarts the draw counter at 0 (set_collocation and resample do not).  Refused with ValueError: B > N, a
+        chunked store, and (in loss_and_grad) the loss mode 'L2'."""
+        B, seed = int(batch_points), int(seed)
+        if B < 0:
+            raise ValueError("mini-batching: batch_points must be >= 0")
+        if B > 0:
+            if self.plan_f is None:
+                raise RuntimeError("set_batching() needs set_collocation() first")
+            if isinstance(self.plan_f, ChunkedResidual):
+                raise ValueError("mini-batching needs a resident store: the collocation set is chunked (chunk_points)")
+            if B > self.plan_f.n:
+                raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points"
+                                 % (B, self.plan_f.n))
+        self._graphs.clear()        # captured steps hold the other plan's pointers
+        self._eval_batch = False
+        if B == 0:
+            self._batch = None
+            return
+        rank = torch.distributed.get_rank(self.pg) if self.world_size > 1 else 0
+        bt = _Batching(B, seed, rank)
+        bt.idx = torch.zeros(B, dtype=torch.int64, device=self.device)
+        bt.counter = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._make_batch_plans(bt)
+        self._batch = bt
+
+    def _make_batch_plans(self, bt):
+        """The batch plan(s) of bt.B points for the current store; the buffers are filled by every draw."""
+        z = lambda: np.zeros(bt.B, dtype=np.float32)       # one array per buffer: a host tensor may alias its source
+        bt.f = ResidualPlan(self.net, z(), z(), None if self.plan_f.w is None else z())
+        bt.e = None
+        if self.net_e is not None:
+            bt.f.vis_t_minus = torch.zeros(bt.B, dtype=torch.float32, device=self.device)
+            bt.e = ValuePlan(self.net_e, z(), z())
+            bt.e.x, bt.e.y = bt.f.x, bt.f.y         # one gather serves both nets
+
+    def batch_indices(self):
+        """Device int64 tensor [B]: the store indices of the last drawn batch (ascending, distinct); None when
+        batching is off.  It is rewritten in place by the next draw."""
+        return None if self._batch is None else self._batch.idx
+
+    def batch_info(self):
+        """dict(batch_points, store_points, seed, draws) (one host read of the device draw counter), or None when
+        batching is off."""
+        bt = self._batch
+        if bt is None:
+            return None
+        return dict(batch_points=bt.B, store_points=self.plan_f.n, seed=bt.seed, draws=int(bt.counter[0].item()))
+
+    def _batching_on(self):
+        return self._batch is not None and not self._batch_frozen
+
+    def _colloc(self):
+        """(collocation plan, entropy-net plan, global point count of the normalisation) of the next evaluation: the
+        batch plans when batching is on, else the store."""
+        if self._batching_on():
+            bt = self._batch
+            return bt.f, bt.e, bt.B * self.world_size
+        return self.plan_f, self.plan_e, self.n_f_global
+
+    @property
+    def evaluated_batch(self):
+        """True when the last evaluation ran on a drawn batch (its loss terms are the batch's)."""
+        return self._eval_batch and self._batch is not None
+
+    def eval_plans(self):
+        """(collocation plan, entropy-net plan) the last evaluation ran on: their fields, vis_t and pred are what the
+        solvers publish."""
+        if self.evaluated_batch:
+            return self._batch.f, self._batch.e
+        return self.plan_f, self.plan_e
 
     def set_boundary(self, x, y, u, v, n_global=None):
         self._graphs.clear()      # captured steps hold the old plan's pointers
@@ -644,6 +771,8 @@ class PinnEngine:
         w4 = self.eq4_weight if self.net_e is not None else 0.0
         idx, S = resample_select(pool, w4, k, c, u, f.n, self._pool_scratch)
         self.lbfgs_reset()                       # the objective changes: the history no longer describes it
+        if self._batch is not None:
+            self._graphs.clear()
         if not math.isfinite(S):
             raise FloatingPointError("resample: the pool's residual sum is %r (non-finite residual or coordinate in the "
                                      "pool); the collocation set is unchanged" % S)
@@ -747,22 +876,33 @@ class PinnEngine:
                           partials=bal.parts if update and self.world_size == 1 else None)
 
     # ---- one loss + gradient evaluation ----
-    def loss_and_grad(self, mode="MSE"):
+    def loss_and_grad(self, mode="MSE", full_batch=False):
         """mode 'MSE' (every script of the reference) or 'L2': 2-norms of the residual / boundary-misfit vectors
         (NSFnet/pinn_solver.py:202-204, 214-217; plain NSFnet, one GPU).  The same kernels run: only the adjoint
         coefficients change, from 2 alpha / N to alpha / ||r_k||, and the norms have to be known first - one host read
-        of the forward sums per evaluation (no hipGraph in this mode).  Refusals come before any stream switch."""
+        of the forward sums per evaluation (no hipGraph in this mode).  Refusals come before any stream switch.
+        full_batch: evaluate the whole store although mini-batching is on (what lbfgs_step's evaluations do)."""
         if mode not in ("MSE", "L2"):
             raise ValueError("loss mode must be 'MSE' or 'L2' (got %r)" % (mode,))
         l2 = mode == "L2"
         if l2 and self._bal is not None:
             raise ValueError("loss balancing needs the MSE loss (loss mode %r)" % mode)
+        if l2 and self._batch is not None:
+            raise ValueError("mini-batching needs the MSE loss (loss mode %r)" % mode)
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
             raise NotImplementedError("loss mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
-        self._loss_and_grad(self._balance_due(), l2)
+        frozen = self._batch_frozen
+        self._batch_frozen = frozen or bool(full_batch)
+        try:
+            self._loss_and_grad(self._balance_due(), l2)
+        finally:
+            self._batch_frozen = frozen
 
     def _loss_and_grad(self, update=False, l2=False):
-        f, b = self.plan_f, self.plan_b
+        b = self.plan_b
+        f, plan_e, n_f = self._colloc()
+        bt = self._batch if self._batching_on() else None
+        self._eval_batch = bt is not None
         bal = self._bal
         sums = self.sums
         sup_on = self._sup_on()
@@ -806,11 +946,15 @@ class PinnEngine:
         finally:
             if side is not None:
                 torch.cuda.set_stream(main)
+        if bt is not None:      # draw + gather: the batch buffers are rewritten in place, the device counter advances
+            st = self.plan_f
+            batch_draw(dict(x=st.x, y=st.y, w=st.w, vtm=st.vis_t_minus),
+                       dict(x=f.x, y=f.y, w=f.w, vtm=f.vis_t_minus), bt.idx, st.n, bt.B, bt.seed, bt.rank, bt.counter)
         e = None
         if self.net_e is not None:
-            self.plan_e.forward(save=self.e_trainable)
-            e = self.plan_e.pred[0]
-        c = 2.0 * self.alpha_e / self.n_f_global
+            plan_e.forward(save=self.e_trainable)
+            e = plan_e.pred[0]
+        c = 2.0 * self.alpha_e / n_f
         coef_eq = (c, c, c, c * self.eq4_weight if self.net_e is not None else 0.0)
         # one pass per plan (several: chunks sharing one workspace, gradients and sums accumulate); every pass but
         # the last is reduced here, the last one together with the value plans below
@@ -839,6 +983,8 @@ class PinnEngine:
                     grad_reduce(self.net, [p], self.grads, accumulate=k > 0)
                 else:
                     grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
+        if bt is not None and f.vis_t_minus is not None:      # the forward left alpha_evm |e| of the batch points there
+            batch_scatter(bt.idx, bt.B, self.plan_f.n, f.vis_t_minus, self.plan_f.vis_t_minus)
         if side is not None:
             main.wait_stream(side)
         last = passes[-1][1]
@@ -848,8 +994,8 @@ class PinnEngine:
             self._reduce_terms([last], b, s, many, update)
         if self.net_e is not None:
             if self.e_trainable:
-                self.plan_e.backward(out_adj=f.ebar)
-                grad_reduce(self.net_e, [self.plan_e], self.grads_e)
+                plan_e.backward(out_adj=f.ebar)
+                grad_reduce(self.net_e, [plan_e], self.grads_e)
             else:
                 self.grads_e.zero_()
         if bal is None:
@@ -899,7 +1045,7 @@ class PinnEngine:
             loss_b = torch.sqrt(s[S_BC]) + torch.sqrt(s[S_BC + 1])
             return dict(loss_eq1=eq[0], loss_eq2=eq[1], loss_eq3=eq[2], loss_eq4=eq[3], loss_e=loss_e, loss_b=loss_b,
                         loss_s=torch.zeros((), device=self.device), loss=self.alpha_b * loss_b + self.alpha_e * loss_e)
-        eq = s[S_EQ:S_EQ + 4] / self.n_f_global
+        eq = s[S_EQ:S_EQ + 4] / (self._batch.B * self.world_size if self._eval_batch else self.n_f_global)
         loss_e = eq[0] + eq[1] + eq[2] + (self.eq4_weight * eq[3] if self.net_e is not None else 0.0)
         loss_b = (s[S_BC] + s[S_BC + 1]) / self.n_b_global
         out = dict(loss_eq1=eq[0], loss_eq2=eq[1], loss_eq3=eq[2], loss_eq4=eq[3], loss_e=loss_e, loss_b=loss_b)
@@ -951,6 +1097,7 @@ class PinnEngine:
             self.e_trainable = False
             self.init_vis_t()
         self._bal_frozen = True             # the objective uses the current loss weights throughout
+        self._batch_frozen = True           # ... and the whole store
         try:
             loss, info = _lbfgs.step(_EngineSpace(self, self._lbfgs), self._lbfgs_state, lr=float(lr),
                                      max_iter=int(max_iter), max_eval=max_eval, tolerance_grad=float(tolerance_grad),
@@ -958,6 +1105,7 @@ class PinnEngine:
         finally:
             self.e_trainable = e_trainable
             self._bal_frozen = False
+            self._batch_frozen = False
         self.lbfgs_info = info
         return loss
 
@@ -974,7 +1122,7 @@ class PinnEngine:
         update = self._balance_due()
         key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
                self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
-               self._bal is not None, update)
+               self._bal is not None, update, self._batch.B if self._batch is not None else 0)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the
@@ -1000,6 +1148,7 @@ class PinnEngine:
             self._graphs[key] = graph
             return
         g.replay()
+        self._eval_batch = self._batching_on()
         self.net.adam_t += 1
         if self.net_e is not None and self.e_trainable:
             self.net_e.adam_t += 1

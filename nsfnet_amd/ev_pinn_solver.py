@@ -253,7 +253,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
 
     @property
     def vis_t(self):
-        f = self.engine.plan_f
+        """vis_t of the last evaluation (the batch's B values after a batch step)."""
+        f = self.engine.eval_plans()[0]
         return None if f is None else f.vis_t.reshape(-1, 1)
 
     @property
@@ -264,20 +265,20 @@ class PysicsInformedNeuralNetwork(SolverBase):
     # ---------------------------------------------------------------- loss / step
     def _publish_terms(self):
         t = self.engine.loss_terms()
-        f = self.engine.plan_f
+        f, plan_e = self.engine.eval_plans()       # the batch plans after a batch step (set_batching)
         self.loss_eq1, self.loss_eq2, self.loss_eq3, self.loss_eq4 = (t["loss_eq%d" % k] for k in (1, 2, 3, 4))
         self.loss_e, self.loss_b, self.loss_s, self.loss = t["loss_e"], t["loss_b"], t["loss_s"], t["loss"]
         self.eq1_pred, self.eq2_pred, self.eq3_pred, self.eq4_pred = (
             f.field(k).reshape(-1, 1) for k in ("eq1", "eq2", "eq3", "eq4"))
-        self.evm = self.engine.plan_e.pred[0].reshape(-1, 1)
+        self.evm = plan_e.pred[0].reshape(-1, 1)
         return t
 
-    def fwd_computing_loss_2d(self, loss_mode='MSE'):
+    def fwd_computing_loss_2d(self, loss_mode='MSE', full_batch=False):
         """Global loss AND its gradient (fused; reference :372-428 + loss.backward() :469)."""
         if loss_mode != 'MSE':
             raise NotImplementedError("only the MSE loss is implemented")
         assert self.x_f is not None and self.y_f is not None
-        self.engine.loss_and_grad()
+        self.engine.loss_and_grad(full_batch=full_batch)     # full_batch: the store although set_batching is on
         self._publish_terms()
         return self.loss, [self.loss_e, self.loss_b]
 
@@ -310,7 +311,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
                     or epoch_id % 10000 == 0):
                 # the field planes are the last TRIAL point's after a line search: evaluate the accepted one (on
                 # every rank - the evaluation all-reduces - not only where it is logged)
-                self.fwd_computing_loss_2d()
+                self.fwd_computing_loss_2d(full_batch=True)
             if log_now:
                 self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
             if save_now:
@@ -383,6 +384,9 @@ class PysicsInformedNeuralNetwork(SolverBase):
         terms = ' '.join('%s=%.3e' % (k, float(getattr(self, 'loss_' + k))) for k in ('eq1', 'eq2', 'eq3', 'eq4'))
         print('[%s] %d/%d  loss=%.4e  eq_total=%.3e boundary=%.3e  %s' % (
             self.current_stage, epoch_id + 1, num_epoch, float(self.loss), float(self.loss_e), float(self.loss_b), terms))
+        if self._batching and self.engine.evaluated_batch:
+            print('  (equation losses of the last batch: %d of %d local points)' % (
+                self.engine.batch_info()["batch_points"], self.x_f.shape[0]))
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))

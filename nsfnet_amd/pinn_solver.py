@@ -58,6 +58,7 @@ class SolverBase:
     """What the plain and the ev drop-in classes share: the knobs of the features the reference does not have
     (resampling, loss balancing) and the methods whose bodies are the same in both reference classes."""
     _balancing = False
+    _batching = False
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -77,6 +78,16 @@ class SolverBase:
         the checkpoint directory); the weight in use is lam_b().  every = 0: off."""
         self.engine.set_loss_balancing(every, beta)
         self._balancing = int(every) > 0
+
+    def set_batching(self, batch_points=0, seed=0):
+        """batch_points = B > 0: every Adam update evaluates the collocation term on a fresh random batch of B of this
+        rank's collocation points, drawn on the device (PinnEngine.set_batching); call it after
+        set_eq_training_data.  The loss terms published and logged are then those of the last batch, and eq*_pred (and
+        evm / vis_t of the ev class) have the batch's length B after a batch step; x_f, y_f stay the whole store.  An
+        L-BFGS stage ignores it (full batch).  The `batchsize` arguments of train / solve_Adam stay accepted and
+        ignored.  batch_points = 0: off."""
+        self.engine.set_batching(batch_points, seed)
+        self._batching = int(batch_points) > 0
 
     def lam_b(self):
         """The boundary weight in use (one host read when balancing is on)."""
@@ -200,7 +211,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
     # ---------------------------------------------------------------- loss / step
     def _publish_terms(self, loss_mode="MSE"):
         t = self.engine.loss_terms(loss_mode)
-        f = self.engine.plan_f
+        f, _ = self.engine.eval_plans()        # the batch plan after a batch step (set_batching)
         self.loss_eq1, self.loss_eq2, self.loss_eq3 = t["loss_eq1"], t["loss_eq2"], t["loss_eq3"]
         self.loss_e, self.loss_b, self.loss = t["loss_e"], t["loss_b"], t["loss"]
         self.eq1_pred, self.eq2_pred, self.eq3_pred = (f.field(k).reshape(-1, 1) for k in ("eq1", "eq2", "eq3"))
@@ -208,7 +219,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self.u_pred_b, self.v_pred_b = b.pred[0].reshape(-1, 1), b.pred[1].reshape(-1, 1)
         return t
 
-    def fwd_computing_loss_2d(self, loss_mode='MSE'):
+    def fwd_computing_loss_2d(self, loss_mode='MSE', full_batch=False):
         """Loss of the current parameters AND its parameter gradient (the HIP pipeline fuses
         what the reference splits into this call and ``loss.backward()``, solver :197-226,252).
         Returns (loss, [loss_e, loss_b]) as 0-dim device tensors."""
@@ -216,7 +227,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         # 'L2' (solver :202-204, :214-217; no script of the reference selects it): 2-norms of the residual and
         # boundary-misfit vectors instead of mean squares - same kernels, other adjoint coefficients (an unknown
         # mode raises ValueError)
-        self.engine.loss_and_grad(loss_mode)
+        self.engine.loss_and_grad(loss_mode, full_batch=full_batch)     # full_batch: the store although set_batching is on
         self._publish_terms(loss_mode)
         return self.loss, [self.loss_e, self.loss_b]
 
@@ -244,14 +255,14 @@ class PysicsInformedNeuralNetwork(SolverBase):
             save_now = self.save_every and epoch_id % self.save_every == 0
             if log_now or save_now:
                 # the field planes are the last TRIAL point's after a line search: evaluate the accepted one
-                self.fwd_computing_loss_2d()
+                self.fwd_computing_loss_2d(full_batch=True)
             if log_now:
                 self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
             if save_now:
                 self.save('model_cavity_loop_%d.pth' % epoch_id, N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
         if num_epoch > 0 and not (log_now or save_now):
-            self.fwd_computing_loss_2d()         # terms and fields of the accepted point
+            self.fwd_computing_loss_2d(full_batch=True)         # terms and fields of the accepted point
 
     def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
         """The reference loop (solver :240-278): loss -> backward -> Adam step; log every 1000,
@@ -287,7 +298,9 @@ class PysicsInformedNeuralNetwork(SolverBase):
               "eq1_loss: %.3e " % (self.loss_eq1.item()),
               "eq2_loss: %.3e " % (self.loss_eq2.item()),
               "eq4_loss: %.3e \n" % (self.loss_eq3.item()),
-              *(("lambda_b: %.4e" % self.lam_b(),) if self._balancing else ()))
+              *(("lambda_b: %.4e" % self.lam_b(),) if self._balancing else ()),
+              *(("(losses of the last batch of %d points)" % self.engine.batch_info()["batch_points"],)
+                if self._batching and self.engine.evaluated_batch else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

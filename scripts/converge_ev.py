@@ -11,6 +11,7 @@ viscosity state restarts from alpha*|e| as at the start of a run).
         --out gpurun_out/conv_ev --first 1 --last 2 [--resume DIR] [--epochs-scale 0.5]
         [--resample-every 5000 --pool 1000000 --rs-k 1 --rs-c 1]   (residual-based resampling, off by default)
         [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call)
+        [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,6 +42,8 @@ def main():
     ap.add_argument("--rs-seed", type=int, default=0)
     ap.add_argument("--balance-every", type=int, default=0, help="adaptive loss-weight balancing cadence (0: off)")
     ap.add_argument("--balance-beta", type=float, default=0.1)
+    ap.add_argument("--batch-points", type=int, default=0, help="stochastic mini-batching: points per Adam update (0: off)")
+    ap.add_argument("--batch-seed", type=int, default=0)
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     os.makedirs(a.out, exist_ok=True)
@@ -72,6 +75,8 @@ def main():
     P.clear_supervised_data(); P.set_supervised_loss_weight(0.0)
     if a.balance_every > 0:
         P.set_loss_balancing(every=a.balance_every, beta=a.balance_beta)
+    if a.batch_points > 0:
+        P.set_batching(batch_points=a.batch_points, seed=a.batch_seed)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     for k in range(a.first, a.last + 1):
@@ -91,7 +96,8 @@ def main():
                    resample=(dict(every=a.resample_every, pool=a.pool, k=a.rs_k, c=a.rs_c, seed=a.rs_seed)
                              if a.resample_every > 0 else None),
                    balance=(dict(every=a.balance_every, beta=a.balance_beta, lambda_b=P.lam_b())
-                            if a.balance_every > 0 else None))
+                            if a.balance_every > 0 else None),
+                   batching=(dict(batch_points=a.batch_points, seed=a.batch_seed) if a.batch_points > 0 else None))
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
