@@ -255,3 +255,42 @@ def pde_loss_and_grad_chunked(params, x, y, Re, alpha_e=1.0, vis_t=None, e=None,
     if params_e is not None:
         out["grad_e"] = grad_e
     return out
+
+
+def value_loss_and_grad_chunked(params, x, y, targets=None, coef=None, out_adj=None, chunk=8192):
+    """Value mode (boundary / supervised points, the entropy net, predict) over N points in passes of <= chunk
+    points, accumulated in fp64: forward1, the squared errors against the finite targets, backward1 of the output
+    adjoints.  targets: up to n_out arrays (None entries: no target on that channel), NaN / inf = masked.  The adjoint
+    of channel c at a point is coef[c] * (pred - target) where the target is finite and 0 where it is not (every pass
+    uses the global coef); an explicit out_adj (N,) or (N, n_out) is the seed instead.  Returns pred (N, n_out),
+    sums = [three sums of squared errors over finite targets, number of finite channel-2 targets] and grad."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    N, n_out = x.size, params[-1][0].shape[0]
+    tg = [None] * n_out
+    for c, t in enumerate(targets or ()):
+        if t is not None and c < n_out:
+            tg[c] = np.asarray(t, dtype=np.float64).reshape(-1)
+            assert tg[c].size == N
+    cf = np.zeros(n_out) if coef is None else np.asarray(coef, dtype=np.float64).reshape(-1)[:n_out]
+    seed = None if out_adj is None else np.asarray(out_adj, dtype=np.float64).reshape(N, n_out)
+    sums, grad, preds = np.zeros(4), None, []
+    for lo in range(0, N, int(chunk)):
+        hi = min(N, lo + int(chunk))
+        pred, saved = forward1(params, x[lo:hi], y[lo:hi])
+        adj = np.zeros_like(pred)
+        for c in range(n_out):
+            if tg[c] is None:
+                continue
+            ok = np.isfinite(tg[c][lo:hi])
+            d = np.where(ok, pred[:, c] - np.where(ok, tg[c][lo:hi], 0.0), 0.0)
+            sums[c] += np.sum(d * d)
+            if c == 2:
+                sums[3] += ok.sum()
+            adj[:, c] = cf[c] * d
+        if seed is not None:
+            adj = seed[lo:hi]
+        g = backward1(params, x[lo:hi], y[lo:hi], saved, adj)
+        grad = g if grad is None else grad + g
+        preds.append(pred)
+    return dict(pred=np.concatenate(preds), sums=[float(s) for s in sums], grad=grad)
