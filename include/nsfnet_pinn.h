@@ -282,6 +282,55 @@ int pinn_batch_draw(int64_t n, int64_t b, uint64_t seed, int rank, int64_t* coun
 int pinn_batch_scatter(const int64_t* idx, int64_t b, int64_t n, const float* batch_vtm, float* store_vtm,
                        void* stream);
 
+/* ---- residual-based attention weights on the collocation points -----------------------
+ * No reference counterpart (its roadmap asks for finer control of the PDE points, ev-NSFnet/README.md).  Residual-based
+ * attention (RBA; Anagnostopoulos, Toscano, Stergiopulos & Karniadakis 2024): every collocation point of the resident
+ * store carries a multiplier that grows where the residual stays large and decays where it does not.  State per
+ * local store point i (n_store of them):
+ *   lam [n_store] fp32   the attention multiplier
+ *   s   [n_store] fp32   the static weights (SDF weights); NULL = 1
+ *   w   [n_store] fp32   the effective weight the residual kernels read, w_i = s_i lam_i^2
+ * After an evaluation has written the UNWEIGHTED residual planes eq1..eq4 of its n points (the planes
+ * pinn_resample_select reads), with i = idx[j], or i = j without idx:
+ *   e2_j   = eq1^2 + eq2^2 + eq3^2 + w4 eq4^2      (w4 = the eq4 weight of the ev flavour, 0 for plain NSFnet)
+ *   r_j    = sqrt(e2_j)
+ *   rmax   = max_j r_j                              (NaN-propagating; over the points of ALL ranks)
+ *   lam_i <- gamma lam_i + eta r_j / rmax
+ *   w_i   <- s_i lam_i^2
+ * Every per-point value is computed in fp64 from the fp32 inputs, without contraction, in exactly this order
+ * (((eq1^2 + eq2^2) + eq3^2) + w4 eq4^2; gamma lam + (eta r) / rmax), and rounded to fp32 once on store; w is
+ * s (lam lam) of the STORED fp32 lam, rounded once, so w is always a function of the stored s and lam.  If rmax is
+ * not finite or is 0 nothing is written and the record's skip count goes up by one (the convention of
+ * pinn_balance_update).  0 < gamma <= 1, eta >= 0; lam stays within [0, max(lam_0, eta / (1 - gamma))].
+ *
+ * Two calls, so that a caller with several ranks can place a MAX all-reduce of the one rmax word between them.
+ * scratch: pinn_rba_scratch_bytes(n) bytes of device memory, 8-byte aligned, ZERO before the first call (both calls
+ * leave their workgroup tickets 0); sized for the largest n it is used with.  One scratch serves one stream at a
+ * time.  As doubles: [0] rmax - a NaN is stored
+ * as the positive quiet NaN, so the signed-integer order of the eight bytes is the NaN-propagating order of the
+ * values and an int64 MAX all-reduce of that word gives the global rmax; [1..4] the fp64 sums of eq1^2 .. eq4^2
+ * over the n points; then tickets and block partials.  Bytes of scratch for evaluations of up to n points
+ * (-1: n outside 1..2^30): */
+int64_t pinn_rba_scratch_bytes(int64_t n);
+/* rmax and the four unweighted sums of the n points of `fields` ([PINN_FLD_COUNT][npad] fp32, 16-byte aligned, npad a
+ * multiple of 4 and >= n) into scratch[0..4]; w4 = 0: the eq4 plane is not read and its sum is 0.  One launch: a grid-stride loop of 16-byte loads, wave reduction by
+ * shuffles, per-block partials, and the last block to finish folds them in block order.  No float atomics: every
+ * sum has a fixed order and the result is bit-reproducible. */
+int pinn_rba_stats(int64_t n, const float* fields, int64_t npad, double w4, double* scratch, void* stream);
+/* The update above with rmax = scratch[0].  idx: NULL, or the n int64 store indices of the evaluation's points as
+ * written by pinn_batch_draw (distinct, so no atomics; an index outside [0, n_store) is skipped); without idx
+ * n <= n_store.  s: NULL = 1.  lam, w (and s) must be 16-byte aligned.  record: PINN_RBA_RECORD doubles (device),
+ *   [0] rmax  [1..4] the sums of eq1^2 .. eq4^2 of this evaluation (scratch[1..4])
+ *   [5] min [6] max [7] sum of the lam values written by the last update (fp64, fixed order)  [8] their count
+ *   [9] updates made  [10] updates skipped  [11] 0;
+ * the caller zeroes it once; a skipped update rewrites [0..4] and [10] only.  One launch. */
+#define PINN_RBA_RECORD 12
+int pinn_rba_apply(int64_t n, const float* fields, int64_t npad, double w4, double gamma, double eta,
+                   const int64_t* idx, int64_t n_store, const float* s, float* lam, float* w, double* scratch,
+                   double* record, void* stream);
+/* lam_i = init, w_i = s_i init^2 for the n store points (s NULL = 1; init >= 0).  One launch. */
+int pinn_rba_fill(int64_t n, double init, const float* s, float* lam, float* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

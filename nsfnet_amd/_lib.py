@@ -64,6 +64,11 @@ SIGNATURES = {
     "pinn_batch_draw": (c_int, [c_int64, c_int64, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_batch_scatter": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "pinn_rba_scratch_bytes": (c_int64, [c_int64]),
+    "pinn_rba_stats": (c_int, [c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p]),
+    "pinn_rba_apply": (c_int, [c_int64, c_void_p, c_int64, c_double, c_double, c_double, c_void_p, c_int64, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_rba_fill": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

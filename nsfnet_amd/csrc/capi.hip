@@ -649,4 +649,55 @@ int pinn_batch_scatter(const int64_t* idx, int64_t b, int64_t n, const float* ba
   return rc ? hipfail(rc, "pinn_batch_scatter") : 0;
 }
 
+int64_t pinn_rba_scratch_bytes(int64_t n) {
+  return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)rba_scratch_bytes((long)n);
+}
+
+static int rba_planes(const char* what, int64_t n, const float* fields, int64_t npad, double w4) {
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "%s: n must be 1..2^30 (got %ld)", what, (long)n);
+  if (!fields) return fail(-22, "%s: null field planes", what);
+  if (npad < n || npad % 4 != 0) return fail(-22, "%s: npad must be >= n and a multiple of 4", what);
+  if (reinterpret_cast<uintptr_t>(fields) % 16 != 0) return fail(-22, "%s: fields must be 16-byte aligned", what);
+  if (!std::isfinite(w4) || w4 < 0.0) return fail(-22, "%s: w4 must be finite and >= 0", what);
+  return 0;
+}
+
+int pinn_rba_stats(int64_t n, const float* fields, int64_t npad, double w4, double* scratch, void* stream) {
+  if (int rc = rba_planes("pinn_rba_stats", n, fields, npad, w4)) return rc;
+  if (!scratch || reinterpret_cast<uintptr_t>(scratch) % 8 != 0) return fail(-22, "pinn_rba_stats: scratch must be given and 8-byte aligned%s");
+  int rc = launch_rba_stats((long)n, fields, (long)npad, w4, scratch, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rba_stats") : 0;
+}
+
+int pinn_rba_apply(int64_t n, const float* fields, int64_t npad, double w4, double gamma, double eta,
+                   const int64_t* idx, int64_t n_store, const float* s, float* lam, float* w, double* scratch,
+                   double* record, void* stream) {
+  if (int rc = rba_planes("pinn_rba_apply", n, fields, npad, w4)) return rc;
+  if (!lam || !w || !scratch || !record) return fail(-22, "pinn_rba_apply: null argument%s");
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 != 0) return fail(-22, "pinn_rba_apply: scratch must be 8-byte aligned%s");
+  if (n_store < 1 || n_store > (int64_t)1 << 30) return fail(-22, "pinn_rba_apply: store size must be 1..2^30 (got %s%ld)", "", (long)n_store);
+  if (!idx && n > n_store) return fail(-22, "pinn_rba_apply: without idx n must be <= n_store%s");
+  if (!(gamma > 0.0 && gamma <= 1.0)) return fail(-22, "pinn_rba_apply: gamma must be in (0, 1]%s");
+  if (!std::isfinite(eta) || eta < 0.0) return fail(-22, "pinn_rba_apply: eta must be finite and >= 0%s");
+  if (reinterpret_cast<uintptr_t>(lam) % 16 != 0 || reinterpret_cast<uintptr_t>(w) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(s) % 16 != 0)
+    return fail(-22, "pinn_rba_apply: s, lam and w must be 16-byte aligned%s");
+  if (lam == w || s == lam || s == w) return fail(-22, "pinn_rba_apply: s, lam and w must be distinct buffers%s");
+  RbaApplyArgs a;
+  a.n = (long)n; a.npad = (long)npad; a.n_store = (long)n_store;
+  a.fld = fields; a.w4 = w4; a.gamma = gamma; a.eta = eta;
+  a.idx = reinterpret_cast<const long long*>(idx);
+  a.s = s; a.lam = lam; a.w = w; a.scratch = scratch; a.record = record;
+  int rc = launch_rba_apply(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rba_apply") : 0;
+}
+
+int pinn_rba_fill(int64_t n, double init, const float* s, float* lam, float* w, void* stream) {
+  if (!lam || !w) return fail(-22, "pinn_rba_fill: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_rba_fill: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (!std::isfinite(init) || init < 0.0) return fail(-22, "pinn_rba_fill: init must be finite and >= 0%s");
+  int rc = launch_rba_fill((long)n, init, s, lam, w, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rba_fill") : 0;
+}
+
 }  // extern "C"

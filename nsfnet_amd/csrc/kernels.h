@@ -240,3 +240,18 @@ struct BatchDrawArgs {
 };
 int launch_batch_draw(const BatchDrawArgs& a, hipStream_t s);
 int launch_batch_scatter(const long long* idx, long b, long n, const float* src, float* dst, hipStream_t s);
+// residual-based attention weights on the collocation points (rba.hip)
+struct RbaApplyArgs {
+  long n, npad, n_store;                   // points of the evaluation, its plane stride, points of the store
+  const float* fld;                        // [FLD_COUNT][npad] field planes of the evaluation
+  double w4, gamma, eta;
+  const long long* idx;                    // [n] store index of evaluation point j (NULL: identity)
+  const float* s;                          // [n_store] static weights (NULL: 1)
+  float *lam, *w;                          // [n_store] attention multipliers, effective weights
+  double *scratch, *record;
+};
+long rba_blocks(long n);
+size_t rba_scratch_bytes(long n);
+int launch_rba_stats(long n, const float* fld, long npad, double w4, double* scratch, hipStream_t s);
+int launch_rba_apply(const RbaApplyArgs& a, hipStream_t s);
+int launch_rba_fill(long n, double init, const float* sw, float* lam, float* w, hipStream_t s);

@@ -76,6 +76,16 @@ class BatchingConfig:
     seed: int = 0
 
 
+@dataclass
+class ResidualAttentionConfig:
+    """Residual-based attention weights on the collocation points (PinnEngine.set_residual_attention), off by
+    default: eta = 0 is off, eta > 0 switches it on (the paper's values: eta 0.01, gamma 0.999).  lam starts at init
+    and is not saved in checkpoints; an L-BFGS stage keeps the weights fixed."""
+    eta: float = 0.0
+    gamma: float = 0.999
+    init: float = 1.0
+
+
 def _default_stages():
     table = [(0.05, 1e-3), (0.03, 2e-4), (0.01, 4e-5), (0.005, 1e-5), (0.002, 2e-6), (0.002, 2e-6)]
     return [TrainingStage(a, 500000, lr, "Stage %d" % (i + 1)) for i, (a, lr) in enumerate(table)]
@@ -93,6 +103,7 @@ class TrainingConfig:
     resampling: ResamplingConfig = field(default_factory=ResamplingConfig)
     loss_balancing: LossBalancingConfig = field(default_factory=LossBalancingConfig)
     batching: BatchingConfig = field(default_factory=BatchingConfig)
+    residual_attention: ResidualAttentionConfig = field(default_factory=ResidualAttentionConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -157,6 +168,9 @@ class ConfigManager:
         bt = c.training.batching
         if bt.enabled and (bt.batch_points < 1 or bt.seed < 0):
             problems.append("training.batching: batch_points >= 1 and seed >= 0 required")
+        ra = c.training.residual_attention
+        if not (0.0 <= ra.eta < float("inf") and 0.0 < ra.gamma <= 1.0 and 0.0 <= ra.init < float("inf")):
+            problems.append("training.residual_attention: eta >= 0, 0 < gamma <= 1 and init >= 0 required")
         for st in c.training.training_stages:
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
@@ -188,5 +202,8 @@ class ConfigManager:
             print("balancing  : every=%d beta=%s" % (t.loss_balancing.every, t.loss_balancing.beta))
         if t.batching.enabled:
             print("batching   : batch_points=%d (per rank) seed=%d" % (t.batching.batch_points, t.batching.seed))
+        if t.residual_attention.eta > 0:
+            print("attention  : eta=%s gamma=%s init=%s" % (t.residual_attention.eta, t.residual_attention.gamma,
+                                                            t.residual_attention.init))
         print("supervision: enabled=%s samples=%d weight=%s"
               % (c.supervision.enabled, c.supervision.num_samples, c.supervision.loss_weight))

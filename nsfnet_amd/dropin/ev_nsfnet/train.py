@@ -102,6 +102,9 @@ def main():
         bt = cfg.training.batching
         if bt.enabled:    # the collocation set is in place: it becomes the store the batches are drawn from
             PINN.set_batching(batch_points=bt.batch_points, seed=bt.seed)
+        ra = cfg.training.residual_attention
+        if ra.eta > 0:    # per-point attention weights on top of the SDF weights of the collocation set
+            PINN.set_residual_attention(eta=ra.eta, gamma=ra.gamma, init=ra.init)
         for st in cfg.training.training_stages:
             if rank == 0:
                 log.stage(st.name, st.alpha, st.epochs, st.lr)

@@ -417,6 +417,38 @@ def batch_scatter(idx, b, n, batch_vtm, store_vtm):
                "pinn_batch_scatter")
 
 
+RBA_RECORD = 12          # PINN_RBA_RECORD
+
+
+def rba_scratch(n, device):
+    """Zeroed device scratch of the two attention calls for evaluations of up to n points."""
+    nbytes = int(_lib.load().pinn_rba_scratch_bytes(int(n)))
+    if nbytes < 0:
+        raise ValueError("bad point count %d" % n)
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def rba_stats(plan, w4, scratch):
+    """pinn_rba_stats over the evaluated ResidualPlan `plan`: rmax into scratch[0], the unweighted sums of
+    eq1^2..eq4^2 into scratch[1:5].  One launch."""
+    _lib.check(_lib.load().pinn_rba_stats(plan.n, _ptr(plan.fields), plan.npad, float(w4), _ptr(scratch), _stream()),
+               "pinn_rba_stats")
+
+
+def rba_apply(plan, w4, gamma, eta, idx, s, lam, w, scratch, record):
+    """pinn_rba_apply: lam <- gamma lam + eta r / scratch[0] and w <- s lam^2 at the store points idx (None: the
+    plan's points are the store's), from the residual planes of the evaluated `plan`.  One launch."""
+    _lib.check(_lib.load().pinn_rba_apply(plan.n, _ptr(plan.fields), plan.npad, float(w4), float(gamma), float(eta),
+                                          _ptr(idx), lam.numel(), _ptr(s), _ptr(lam), _ptr(w), _ptr(scratch),
+                                          _ptr(record), _stream()), "pinn_rba_apply")
+
+
+def rba_fill(init, s, lam, w):
+    """pinn_rba_fill: lam = init, w = s init^2.  One launch."""
+    _lib.check(_lib.load().pinn_rba_fill(lam.numel(), float(init), _ptr(s), _ptr(lam), _ptr(w), _stream()),
+               "pinn_rba_fill")
+
+
 class LbfgsHistory:
     """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
     g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
@@ -507,6 +539,18 @@ class _Batching:
         self.f = self.e = self.idx = self.counter = None
 
 
+class _Attention:
+    """State of the residual-based attention (set_residual_attention): the device tensors lam [N] (multipliers),
+    s [N] or None (the static weights given to set_collocation), w [N] (the effective weights s lam^2, which is what
+    plan_f.w points to while the feature is on), scratch (statistics) and rec [RBA_RECORD] fp64 (the last update);
+    n_eval = local points of the last evaluation that updated."""
+
+    def __init__(self, eta, gamma, init):
+        self.eta, self.gamma, self.init = eta, gamma, init
+        self.lam = self.s = self.w = self.scratch = self.rec = None
+        self.n_eval = 0
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -556,6 +600,8 @@ class PinnEngine:
         self._batch = None                  # stochastic mini-batching (set_batching; None = off)
         self._batch_frozen = False          # lbfgs_step: the full objective, i.e. the store
         self._eval_batch = False            # the last evaluation ran on the batch plan (loss_terms' normalisation)
+        self._rba = None                    # residual-based attention (set_residual_attention; None = off)
+        self._rba_frozen = False            # lbfgs_step / full_batch: the weights are held fixed
 
     # ---- views into the exchange buffer ----
     @property
@@ -583,6 +629,8 @@ class PinnEngine:
             raise ValueError("mini-batching needs a resident store: chunk_points=%d with batching on" % int(chunk_points))
         if bt is not None and bt.B > n:
             raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points" % (bt.B, n))
+        if self._rba is not None and chunk_points and n > int(chunk_points):
+            raise ValueError("residual attention needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         self._graphs.clear()      # captured steps hold the old plan's pointers
         self.lbfgs_reset()
         if chunk_points and n > int(chunk_points):
@@ -594,8 +642,105 @@ class PinnEngine:
             self.plan_e = ValuePlan(self.net_e, x, y)
             self.init_vis_t()
         self._eval_batch = False
+        if self._rba is not None:
+            self._attach_attention()        # the new set starts at lam = init; its weights are the new s
         if bt is not None:
             self._make_batch_plans(bt)      # the store may have gained or lost its weights; the draw counter carries on
+
+    # ---- residual-based attention weights on the collocation points ----
+    def set_residual_attention(self, eta=0.0, gamma=0.999, init=1.0):
+        """eta > 0: residual-based attention (RBA; Anagnostopoulos, Toscano, Stergiopulos & Karniadakis 2024).  Every
+        local collocation point i carries a multiplier lam_i, and the weight the residual kernels read becomes
+        w_i = s_i lam_i^2 with s the static weights given to set_collocation (1 without).  After every evaluation
+        made for Adam (step(), and loss_and_grad() followed by adam_step()), from its unweighted residual planes:
+            r_j = sqrt(eq1^2 + eq2^2 + eq3^2 + eq4_weight eq4^2),  rmax = max r_j over the points of ALL ranks,
+            lam_i <- gamma lam_i + eta r_j / rmax,  w_i <- s_i lam_i^2          (fp64, rounded to fp32 on store)
+        so lam stays within [0, max(init, eta / (1 - gamma))].  An rmax that is 0 or not finite skips the update
+        (attention_info()['skipped']).  The weights evaluation k uses are those made after evaluation k - 1 - one
+        evaluation of lag, like vis_t_minus - because the fused forward + reverse sweep needs w before the residual
+        exists; w is a constant to the reverse sweep, as RBA prescribes.  With mini-batching the statistics are the
+        batch's and only the drawn points change.  Evaluations of lbfgs_step and with full_batch=True do not update:
+        the L-BFGS objective uses the current weights throughout.  resample() renormalises s and restarts lam at
+        init.  loss_terms() keeps returning the WEIGHTED terms Adam minimises; attention_info() has the unweighted
+        ones.  lam is not part of a checkpoint: a restored run restarts it at init.
+
+        eta = 0: off (plan_f.w is s again and every path launches what it launches without the feature).  A call
+        restarts lam at init; so does set_collocation.  Refused: a chunked store, gamma outside (0, 1], eta < 0,
+        init < 0 (ValueError), a call before set_collocation (RuntimeError) and, in loss_and_grad, loss mode 'L2'."""
+        eta, gamma, init = float(eta), float(gamma), float(init)
+        if not (math.isfinite(eta) and eta >= 0.0):
+            raise ValueError("residual attention: eta must be finite and >= 0")
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError("residual attention: gamma must be in (0, 1]")
+        if not (math.isfinite(init) and init >= 0.0):
+            raise ValueError("residual attention: init must be finite and >= 0")
+        if eta > 0.0:
+            if self.plan_f is None:
+                raise RuntimeError("set_residual_attention() needs set_collocation() first")
+            if isinstance(self.plan_f, ChunkedResidual):
+                raise ValueError("residual attention needs a resident store: the collocation set is chunked "
+                                 "(chunk_points)")
+        self._graphs.clear()        # captured steps hold the other weight buffer and gamma / eta
+        old = self._rba
+        if old is not None:
+            self.plan_f.w = old.s   # the static weights again (None: the set had none)
+            self._rba = None
+        if eta > 0.0:
+            self._rba = _Attention(eta, gamma, init)
+            self._attach_attention()
+        if self._batch is not None and (old is not None or eta > 0.0):
+            self._make_batch_plans(self._batch)      # the store may have gained or lost its weight buffer
+
+    def _attach_attention(self):
+        """Take plan_f's weights as s, allocate lam and the effective-weight buffer, make it plan_f.w and fill."""
+        a, f = self._rba, self.plan_f
+        a.s = f.w
+        a.lam = torch.zeros(f.n, dtype=torch.float32, device=self.device)
+        a.w = torch.zeros(f.n, dtype=torch.float32, device=self.device)
+        a.scratch = rba_scratch(f.n, self.device)
+        a.rec = torch.zeros(RBA_RECORD, dtype=torch.float64, device=self.device)
+        a.n_eval = 0
+        f.w = a.w
+        rba_fill(a.init, a.s, a.lam, a.w)
+
+    def _static_w(self):
+        """The static weights of the resident collocation set (what set_collocation was given), or None."""
+        return self._rba.s if self._rba is not None else self.plan_f.w
+
+    def attention(self):
+        """Device fp32 tensor [N]: the attention multipliers lam of the local collocation points (updated in place);
+        None when the feature is off."""
+        return None if self._rba is None else self._rba.lam
+
+    def attention_info(self):
+        """The device record of the last attention update (one host read), or None when the feature is off: rmax,
+        lam_min / lam_mean / lam_max of the multipliers that update wrote, the UNWEIGHTED loss_eq1..4 and loss_e of
+        the evaluation it followed (this rank's points), updates, skipped, and the settings."""
+        a = self._rba
+        if a is None:
+            return None
+        r = a.rec.cpu().tolist()
+        out = dict(rmax=r[0], lam_min=r[5], lam_max=r[6], lam_mean=r[7] / r[8] if r[8] > 0 else float("nan"),
+                   updates=int(r[9]), skipped=int(r[10]), eta=a.eta, gamma=a.gamma, init=a.init)
+        n = max(a.n_eval, 1)
+        for k in range(4):
+            out["loss_eq%d" % (k + 1)] = r[1 + k] / n
+        out["loss_e"] = (r[1] + r[2] + r[3] + (self.eq4_weight * r[4] if self.net_e is not None else 0.0)) / n
+        return out
+
+    def _attention_update(self, f, bt):
+        """One attention update from the residual planes the collocation pass just wrote on plan f (the batch plan
+        when bt is given: its points are the store's bt.idx).  Two launches; between them, multi-rank, the MAX
+        all-reduce of the one rmax word - as int64: the kernel stores a NaN as the positive quiet NaN, so the
+        integer order of non-negative doubles is their NaN-propagating order."""
+        a = self._rba
+        w4 = self.eq4_weight if self.net_e is not None else 0.0
+        rba_stats(f, w4, a.scratch)
+        if self.world_size > 1:
+            torch.distributed.all_reduce(a.scratch[:1].view(torch.int64), op=torch.distributed.ReduceOp.MAX,
+                                         group=self.pg)
+        rba_apply(f, w4, a.gamma, a.eta, None if bt is None else bt.idx, a.s, a.lam, a.w, a.scratch, a.rec)
+        a.n_eval = f.n
 
     # ---- stochastic mini-batching of the collocation term (DESIGN.md section 7.4) ----
     def set_batching(self, batch_points=0, seed=0):
@@ -733,7 +878,7 @@ class PinnEngine:
         flavour, a forward-only plan of the entropy net).  `weights` (pool SDF weights) must be given exactly when
         the live collocation set has weights.  A new pool does not restart the draws: the call counter that goes into
         resample()'s seed keeps counting, so refreshing the pool every stage with one seed gives fresh U values."""
-        if self.plan_f is not None and (weights is None) != (self.plan_f.w is None):
+        if self.plan_f is not None and (weights is None) != (self._static_w() is None):
             raise ValueError("pool weights must be given exactly when the collocation set has weights")
         pool = ResidualPlan(self.net, x, y, with_backward=False)
         w = None
@@ -751,12 +896,13 @@ class PinnEngine:
         vis_t0 and alpha_evm.  The live buffers are rewritten IN PLACE, so a captured step replays on the new points;
         parameters, Adam moments, the boundary / supervised plans and n_f_global are not touched.  Each rank draws from
         its own pool shard (per-rank stratification).  The weights are renormalised to mean 1 over the global selected
-        set; the entropy-net state vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-
+        set (with residual attention on: the static weights s, and lam restarts at init); the entropy-net state vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-
         ordered after the last step; one 8-byte host read.  Returns the int64 pool indices (ascending, may repeat)."""
         f, pool = self.plan_f, getattr(self, "_pool", None)
         if pool is None or f is None:
             raise RuntimeError("resample() needs set_collocation() and set_resample_pool() first")
-        if (self._pool_w is None) != (f.w is None):
+        rba = self._rba              # on: the gather and the renormalisation work on the static weights s
+        if (self._pool_w is None) != (self._static_w() is None):
             raise ValueError("pool weights must be given exactly when the collocation set has weights")
         e = vtm0 = None
         if self.net_e is not None:
@@ -778,9 +924,10 @@ class PinnEngine:
                                      "pool); the collocation set is unchanged" % S)
         passes = _passes(f)
         src = dict(x=pool.x, y=pool.y, w=self._pool_w, vtm=vtm0)
-        w_sums = torch.zeros(len(passes), dtype=torch.float64, device=self.device) if f.w is not None else None
+        wts = [rba.s] if rba is not None else [ck.w for _, ck in passes]      # (attention: one resident pass)
+        w_sums = torch.zeros(len(passes), dtype=torch.float64, device=self.device) if wts[0] is not None else None
         for j, ((lo, hi), ck) in enumerate(passes):
-            dst = dict(x=ck.x, y=ck.y, w=ck.w, vtm=ck.vis_t_minus)
+            dst = dict(x=ck.x, y=ck.y, w=wts[j], vtm=ck.vis_t_minus)
             resample_gather(idx, lo, hi, pool.n, src, dst, self._pool_scratch,
                             None if w_sums is None else w_sums[j:j + 1])
             if self.plan_e is not None:
@@ -795,12 +942,15 @@ class PinnEngine:
                 torch.distributed.all_reduce(t, group=self.pg)
                 total = float(t.item())
             mean = total / self.n_f_global
-            for _, ck in passes:                     # mean 1 over the global set (cavity_data._compute_sdf_weights)
-                ck.w.copy_((ck.w.double() / mean).float())
+            for wt in wts:                           # mean 1 over the global set (cavity_data._compute_sdf_weights)
+                wt.copy_((wt.double() / mean).float())
+        if rba is not None:                          # new points: lam = init, w = s init^2 (in place: graphs stay valid)
+            rba_fill(rba.init, rba.s, rba.lam, rba.w)
         return idx
 
     def collocation_points(self):
-        """(x, y, w) of the live collocation set as fresh device tensors (w None without weights)."""
+        """(x, y, w) of the live collocation set as fresh device tensors (w None without weights; with residual
+        attention on, w is the effective weight s lam^2)."""
         plans = [p for _, p in _passes(self.plan_f)]
         return tuple(None if getattr(plans[0], k) is None else torch.cat([getattr(p, k) for p in plans])
                      for k in ("x", "y", "w"))
@@ -889,14 +1039,17 @@ class PinnEngine:
             raise ValueError("loss balancing needs the MSE loss (loss mode %r)" % mode)
         if l2 and self._batch is not None:
             raise ValueError("mini-batching needs the MSE loss (loss mode %r)" % mode)
+        if l2 and self._rba is not None:
+            raise ValueError("residual attention needs the MSE loss (loss mode %r)" % mode)
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
             raise NotImplementedError("loss mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
-        frozen = self._batch_frozen
+        frozen, rba_frozen = self._batch_frozen, self._rba_frozen
         self._batch_frozen = frozen or bool(full_batch)
+        self._rba_frozen = rba_frozen or bool(full_batch)
         try:
             self._loss_and_grad(self._balance_due(), l2)
         finally:
-            self._batch_frozen = frozen
+            self._batch_frozen, self._rba_frozen = frozen, rba_frozen
 
     def _loss_and_grad(self, update=False, l2=False):
         b = self.plan_b
@@ -985,6 +1138,8 @@ class PinnEngine:
                     grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
         if bt is not None and f.vis_t_minus is not None:      # the forward left alpha_evm |e| of the batch points there
             batch_scatter(bt.idx, bt.B, self.plan_f.n, f.vis_t_minus, self.plan_f.vis_t_minus)
+        if self._rba is not None and not self._rba_frozen:      # the weights of the NEXT evaluation
+            self._attention_update(f, bt)
         if side is not None:
             main.wait_stream(side)
         last = passes[-1][1]
@@ -1037,7 +1192,9 @@ class PinnEngine:
 
     def loss_terms(self, mode="MSE"):
         """Device tensors (no sync): dict of loss_eq1..4, loss_e, loss_b, loss_s, loss of the sums of the last
-        evaluation, in the loss mode it ran with."""
+        evaluation, in the loss mode it ran with.  The equation terms carry the per-point weights the evaluation
+        used - with residual attention on, the effective weights s lam^2: they are what Adam minimises
+        (attention_info() has the unweighted ones)."""
         s = self.sums
         if mode == "L2":      # NSFnet/pinn_solver.py:202-204, 214-217
             eq = torch.sqrt(s[S_EQ:S_EQ + 4])
@@ -1098,6 +1255,7 @@ class PinnEngine:
             self.init_vis_t()
         self._bal_frozen = True             # the objective uses the current loss weights throughout
         self._batch_frozen = True           # ... and the whole store
+        self._rba_frozen = True             # ... and the current attention weights
         try:
             loss, info = _lbfgs.step(_EngineSpace(self, self._lbfgs), self._lbfgs_state, lr=float(lr),
                                      max_iter=int(max_iter), max_eval=max_eval, tolerance_grad=float(tolerance_grad),
@@ -1106,6 +1264,7 @@ class PinnEngine:
             self.e_trainable = e_trainable
             self._bal_frozen = False
             self._batch_frozen = False
+            self._rba_frozen = False
         self.lbfgs_info = info
         return loss
 
@@ -1122,7 +1281,8 @@ class PinnEngine:
         update = self._balance_due()
         key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
                self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
-               self._bal is not None, update, self._batch.B if self._batch is not None else 0)
+               self._bal is not None, update, self._batch.B if self._batch is not None else 0,
+               (False, 0.0, 0.0) if self._rba is None else (True, self._rba.gamma, self._rba.eta))
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the

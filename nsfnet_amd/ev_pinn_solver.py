@@ -387,6 +387,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
         if self._batching and self.engine.evaluated_batch:
             print('  (equation losses of the last batch: %d of %d local points)' % (
                 self.engine.batch_info()["batch_points"], self.x_f.shape[0]))
+        if self._attention:
+            print('  ' + self._attention_log())
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))

@@ -59,6 +59,7 @@ class SolverBase:
     (resampling, loss balancing) and the methods whose bodies are the same in both reference classes."""
     _balancing = False
     _batching = False
+    _attention = False
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -88,6 +89,23 @@ class SolverBase:
         ignored.  batch_points = 0: off."""
         self.engine.set_batching(batch_points, seed)
         self._batching = int(batch_points) > 0
+
+    def set_residual_attention(self, eta=0.0, gamma=0.999, init=1.0):
+        """eta > 0: residual-based attention weights on this rank's collocation points (PinnEngine.
+        set_residual_attention): every point carries a multiplier lam that follows
+        lam <- gamma lam + eta |r| / max|r| after each Adam evaluation, and its loss weight is (SDF weight) lam^2; call
+        it after set_eq_training_data.  The loss terms published and logged are then the weighted ones Adam minimises;
+        print_log adds the range of lam and the unweighted equation loss.  An L-BFGS stage keeps the weights fixed.
+        lam is not saved: checkpoints stay in the reference's format and a restored run restarts lam at init.
+        eta = 0: off."""
+        self.engine.set_residual_attention(eta, gamma, init)
+        self._attention = float(eta) > 0.0
+
+    def _attention_log(self):
+        """The print_log suffix of the residual attention: the lam range and the unweighted equation loss."""
+        a = self.engine.attention_info()
+        return "attention lam: min=%.3e mean=%.3e max=%.3e  unweighted loss_e=%.3e" % (
+            a["lam_min"], a["lam_mean"], a["lam_max"], a["loss_e"])
 
     def lam_b(self):
         """The boundary weight in use (one host read when balancing is on)."""
@@ -300,7 +318,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               "eq4_loss: %.3e \n" % (self.loss_eq3.item()),
               *(("lambda_b: %.4e" % self.lam_b(),) if self._balancing else ()),
               *(("(losses of the last batch of %d points)" % self.engine.batch_info()["batch_points"],)
-                if self._batching and self.engine.evaluated_batch else ()))
+                if self._batching and self.engine.evaluated_batch else ()),
+              *(("\n" + self._attention_log(),) if self._attention else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

@@ -12,6 +12,7 @@ viscosity state restarts from alpha*|e| as at the start of a run).
         [--resample-every 5000 --pool 1000000 --rs-k 1 --rs-c 1]   (residual-based resampling, off by default)
         [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call)
         [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call)
+        [--rba-eta 0.01 --rba-gamma 0.999]   (residual-based attention weights, off by default; lam restarts per call)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,6 +45,9 @@ def main():
     ap.add_argument("--balance-beta", type=float, default=0.1)
     ap.add_argument("--batch-points", type=int, default=0, help="stochastic mini-batching: points per Adam update (0: off)")
     ap.add_argument("--batch-seed", type=int, default=0)
+    ap.add_argument("--rba-eta", type=float, default=0.0, help="residual-based attention: eta (0: off; DESIGN.md 7.5)")
+    ap.add_argument("--rba-gamma", type=float, default=0.999)
+    ap.add_argument("--rba-init", type=float, default=1.0)
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     os.makedirs(a.out, exist_ok=True)
@@ -77,6 +81,8 @@ def main():
         P.set_loss_balancing(every=a.balance_every, beta=a.balance_beta)
     if a.batch_points > 0:
         P.set_batching(batch_points=a.batch_points, seed=a.batch_seed)
+    if a.rba_eta > 0:
+        P.set_residual_attention(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     for k in range(a.first, a.last + 1):
@@ -97,7 +103,11 @@ def main():
                              if a.resample_every > 0 else None),
                    balance=(dict(every=a.balance_every, beta=a.balance_beta, lambda_b=P.lam_b())
                             if a.balance_every > 0 else None),
-                   batching=(dict(batch_points=a.batch_points, seed=a.batch_seed) if a.batch_points > 0 else None))
+                   batching=(dict(batch_points=a.batch_points, seed=a.batch_seed) if a.batch_points > 0 else None),
+                   attention=(dict(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init,
+                                   **{k_: v for k_, v in P.engine.attention_info().items()
+                                      if k_ in ("lam_min", "lam_mean", "lam_max", "loss_e", "skipped")})
+                              if a.rba_eta > 0 else None))
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
