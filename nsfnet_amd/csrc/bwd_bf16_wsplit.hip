@@ -96,14 +96,7 @@ size_t bwd_wsplit_lds_bytes(int HP, int L) {
 template <int HP, int TERMS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::bwd_bytes(a.L);
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_wsplit_kernel<HP, TERMS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((bwd_wsplit_kernel<HP, TERMS>), dim3(grid), dim3(512), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, 24-bit spill, L >= 2 hidden layers (the caller checks)

@@ -219,15 +219,8 @@ size_t bwd_wide_lds_bytes(int HP, int L) { return ((size_t)HP * 64 + 4 * 64 + sg
 template <int HP, int NS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_wide_lds_bytes(HP, a.L);
-  if (lds > 163840) return -1001;
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_wide_kernel<HP, NS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((bwd_wide_kernel<HP, NS>), dim3(grid), dim3(HP * 2), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  if (lds > PINN_LDS_MAX) return -1001;
+  return launch_or_configure(&bwd_wide_kernel<HP, NS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define BWD_CASE(hp)                                                        \

@@ -21,42 +21,94 @@ static int hipfail(int rc, const char* what) {
   return fail(rc, "%s: HIP error %ld", what, (long)-rc);
 }
 
+// The environment switches, all read here.  read_switches() runs at every plan creation, and for tile_cols at net
+// creation and in pinn_net_set_precision: callers change the variables between calls in one process.
+struct Switches {
+  int sched_f, sched_b;   // $PINN_FWD_SCHED / $PINN_BWD_SCHED, each defaulting to $PINN_SCHED (default 2)
+  int wsplit, fuse;       // $PINN_WSPLIT, $PINN_FUSE (default 1; 0 opts out)
+  int stagger;            // $PINN_STAGGER (default 0)
+  int s0_skip32;          // $PINN_S0_SKIP32 (default 1; 0 opts out)
+  int verbose;            // $PINN_VERBOSE
+  int tile_cols;          // $PINN_TILE_COLS = 64 | 128 overrides pick_wide (hidden 128 / 256 only)
+};
+static int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+static Switches read_switches() {
+  const int sched = env_int("PINN_SCHED", 2);
+  return {env_int("PINN_FWD_SCHED", sched), env_int("PINN_BWD_SCHED", sched), env_int("PINN_WSPLIT", 1),
+          env_int("PINN_FUSE", 1), env_int("PINN_STAGGER", 0), env_int("PINN_S0_SKIP32", 1),
+          env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0)};
+}
+
 // precision of a kernel family: 0 = fp32-input MFMA (exact fp32), 1 = bf16x3 split, 2 = plain bf16
 struct pinn_net_s {
   int n_out, L, H, HP;
-  int wide;   // 64-column tile kernels (always for HP > 256; PINN_FORCE_WIDE=1 forces them for HP 128/256)
+  int wide;   // 64-column tile kernels (always for HP > 256; pick_wide for HP 128/256)
   int prec_fwd, prec_bwd, prec_dw;
 };
 static int terms_of(int prec) { return prec == 1 ? 3 : 1; }
 // 64-column-tile kernels: always for HP > 256; for HP == 256 in fp32 mode they are also the faster
-// choice (two workgroups per CU overlap each other's epilogue and MFMA phases): PINN_FORCE_WIDE=0 opts out.
-static int env_int(const char* name, int dflt);
+// choice (two workgroups per CU overlap each other's epilogue and MFMA phases).
 static int pick_wide(const pinn_net_s* n) {
   if (n->HP > 256) return 1;
   if (n->HP != 256 && n->HP != 128) return 0;
   const bool fp32 = !n->prec_fwd && !n->prec_bwd && !n->prec_dw;
   // measured (6x256, 360k pts): fp32 26.2 vs 29.6 ms/step in favour of 64-column tiles; bf16x3 13.4 vs 12.6 ms
   // against them.  PINN_TILE_COLS=64|128 overrides the choice (HP 128/256 only).
-  const int force = env_int("PINN_TILE_COLS", 0);
+  const int force = read_switches().tile_cols;
   if (force == 64) return 1;
   if (force == 128) return 0;
   return fp32 && n->HP == 256;
 }
 
+// Kernel families.  A plan's role (forward with / without saved activations, reverse sweep, dW, fused sweeps) runs
+// one of them, chosen once by resolve_plan; launches, LDS sizes and reported names switch over the value.
+enum Family { FAM_NONE = 0, FAM_FP32, FAM_FP32_WIDE, FAM_BF16, FAM_BF16_WIDE, FAM_PIPE, FAM_SPLIT, FAM_WSPLIT, FAM_FUSED };
+// names as pinn_plan_kernel reports them: {forward, reverse sweep, dW}.  A fused plan keeps reporting its forward and
+// reverse roles (fwd_split_kernel / bwd_split_kernel) for kernels 0 and 1, not fwdbwd_split_kernel: scripts and tests
+// key on those names, and the two kernels are still what forward-only and PINN_FUSE=0 calls launch.
+static constexpr const char* FAMILY_NAMES[][3] = {
+    {nullptr, nullptr, nullptr},
+    {"fwd_kernel", "bwd_kernel", "dw_kernel"},
+    {"fwd_wide_kernel", "bwd_wide_kernel", "dw_wide_kernel"},
+    {"fwd_bf16_kernel", "bwd_bf16_kernel", "dw_bf16_kernel"},
+    {"fwd_bf16_wide_kernel", "bwd_bf16_wide_kernel", "dw_bf16_wide_kernel"},
+    {"fwd_pipe_kernel", "bwd_pipe_kernel", nullptr},
+    {"fwd_split_kernel", "bwd_split_kernel", nullptr},
+    {"fwd_wsplit_kernel", "bwd_wsplit_kernel", nullptr},
+    {"fwdbwd_split_kernel", "fwdbwd_split_kernel", nullptr},
+};
+// the 8-wave family of one precision on this net: the only place precision and tile geometry are weighed
+static Family base_family(const pinn_net_s& n, int prec) {
+  return prec ? (n.HP > 256 ? FAM_BF16_WIDE : FAM_BF16) : n.wide ? FAM_FP32_WIDE : FAM_FP32;
+}
+
+enum { ROLE_FWD_SAVE = 0, ROLE_FWD, ROLE_BWD, ROLE_DW, ROLE_FUSED, ROLE_COUNT };
+struct Role {
+  Family family;      // FAM_NONE: the plan has no such kernel (ROLE_FUSED)
+  int grid;           // workgroups (ROLE_DW: the group count; its launcher derives the grid from DwArgs)
+  size_t lds;         // dynamic LDS bytes
+  const char* name;
+};
+
+// How the sweeps spill S and Z-bar, and what their readers recompute instead of reading.
+struct SpillFormat {
+  int s24w;              // wide bf16 residual plan (all three kernels bf16): 24-bit three-plane spill format
+  int s0_skip;           // the sweeps do not spill layer 0 (role-split pair): dw_bf16 recomputes its activations
+  int s0_skip32;         // fp32 residual plan: layer 0 not spilled, recomputed by its readers
+  int sl0; size_t sblk;  // compact spill geometry of the role-split plans (kernels.h spill_off); sblk = 0: classic layout
+};
+
 struct pinn_plan_s {
   pinn_net_s net;
   long n;
   int streams, ntiles, npad;
-  int grid_f, grid_b, groups;
-  int s24w;              // wide bf16 residual plan (all three kernels bf16): 24-bit three-plane spill format
-  int s0_skip;           // the sweeps do not spill layer 0 (role-split pair): dw_bf16 recomputes its activations
-  int s0_skip32;         // fp32 residual plan: layer 0 not spilled, recomputed by its readers (FwdArgs::s0_skip)
-  int sl0; size_t sblk;  // compact spill geometry of the role-split plans (kernels.h spill_off); sblk = 0: classic layout
+  int groups;            // dW slabs per layer
   int stagger;           // $PINN_STAGGER, read once at plan creation
-  int pipe_f, grid_fp;   // schedule of the forward with saved activations (0 8-wave, 1 pipelined, 2 role-split); grid of 1 / 2 (pairs of tiles)
-  int pipe_b;            // schedule of the reverse sweep; for 1 / 2 grid_b is the pair grid
-  int fuse;              // role-split pair: pinn_residual_forward_backward runs both sweeps of a tile in one kernel (fwdbwd_bf16_split.hip)
-  int wsplit;            // wide net (hidden > 256): role-split sweeps at 64-column tiles (fwd / bwd_bf16_wsplit.hip) instead of the 8-wave ones
+  Role role[ROLE_COUNT];
+  SpillFormat spill;
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -73,41 +125,261 @@ static int num_cus() {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}  // (declared above pick_wide)
+// per role: the LDS bytes of a family, and its launch (args.configure = 1: set the dynamic-LDS attribute of exactly
+// the kernel a launch would pick, pinn_plan_create's configure pass)
+static size_t fwd_lds(Family f, const pinn_net_s& n) {
+  switch (f) {
+    case FAM_FP32: return fwd_lds_bytes(n.HP);
+    case FAM_FP32_WIDE: return fwd_wide_lds_bytes(n.HP);
+    case FAM_BF16: return fwd_bf16_lds_bytes(n.HP, n.L, n.wide ? 64 : 128);
+    case FAM_BF16_WIDE: return fwd_bf16_wide_lds_bytes(n.HP, n.L);
+    case FAM_PIPE: return fwd_pipe_lds_bytes(n.HP, n.L);
+    case FAM_SPLIT: return fwd_split_lds_bytes(n.HP, n.L);
+    case FAM_WSPLIT: return fwd_wsplit_lds_bytes(n.HP);
+    default: return 0;
+  }
+}
+static size_t bwd_lds(Family f, const pinn_net_s& n) {
+  switch (f) {
+    case FAM_FP32: return bwd_lds_bytes(n.HP, n.L);
+    case FAM_FP32_WIDE: return bwd_wide_lds_bytes(n.HP, n.L);
+    case FAM_BF16: return bwd_bf16_lds_bytes(n.HP, n.L, n.wide ? 64 : 128);
+    case FAM_BF16_WIDE: return bwd_bf16_wide_lds_bytes(n.HP, n.L);
+    case FAM_PIPE: return bwd_pipe_lds_bytes(n.HP, n.L);
+    case FAM_SPLIT: return bwd_split_lds_bytes(n.HP, n.L);
+    case FAM_WSPLIT: return bwd_wsplit_lds_bytes(n.HP, n.L);
+    default: return 0;
+  }
+}
+static size_t dw_lds(Family f, const pinn_net_s& n) {
+  switch (f) {
+    case FAM_FP32: return dw_lds_bytes(n.HP);
+    case FAM_FP32_WIDE: return dw_wide_lds_bytes();
+    case FAM_BF16: return dw_bf16_lds_bytes(n.HP);
+    case FAM_BF16_WIDE: return dw_bf16_wide_lds_bytes();
+    default: return 0;
+  }
+}
+static int run_fwd(const pinn_plan_s* plan, const Role& r, const FwdArgs& a, hipStream_t s) {
+  const pinn_net_s& n = plan->net;
+  const int NS = plan->streams, terms = terms_of(n.prec_fwd);
+  switch (r.family) {
+    case FAM_FP32: return launch_fwd(n.HP, NS, a, r.grid, s);
+    case FAM_FP32_WIDE: return launch_fwd_wide(n.HP, NS, a, r.grid, s);
+    case FAM_BF16: return launch_fwd_bf16(n.HP, NS, terms, n.wide ? 64 : 128, a, r.grid, s);
+    case FAM_BF16_WIDE: return launch_fwd_bf16_wide(n.HP, NS, terms, a, r.grid, s);
+    case FAM_PIPE: return launch_fwd_pipe(n.HP, terms, a, r.grid, s);
+    case FAM_SPLIT: return launch_fwd_split(n.HP, terms, a, r.grid, s);
+    case FAM_WSPLIT: return launch_fwd_wsplit(n.HP, terms, a, r.grid, s);
+    default: return -1000;
+  }
+}
+static int run_bwd(const pinn_plan_s* plan, const BwdArgs& a, hipStream_t s) {
+  const pinn_net_s& n = plan->net;
+  const Role& r = plan->role[ROLE_BWD];
+  const int NS = plan->streams, terms = terms_of(n.prec_bwd);
+  switch (r.family) {
+    case FAM_FP32: return launch_bwd(n.HP, NS, a, r.grid, s);
+    case FAM_FP32_WIDE: return launch_bwd_wide(n.HP, NS, a, r.grid, s);
+    case FAM_BF16: return launch_bwd_bf16(n.HP, NS, terms, n.wide ? 64 : 128, a, r.grid, s);
+    case FAM_BF16_WIDE: return launch_bwd_bf16_wide(n.HP, NS, terms, a, r.grid, s);
+    case FAM_PIPE: return launch_bwd_pipe(n.HP, terms, a, r.grid, s);
+    case FAM_SPLIT: return launch_bwd_split(n.HP, terms, a, r.grid, s);
+    case FAM_WSPLIT: return launch_bwd_wsplit(n.HP, terms, a, r.grid, s);
+    default: return -1000;
+  }
+}
+static int run_dw(const pinn_plan_s* plan, const DwArgs& d, hipStream_t s) {
+  const pinn_net_s& n = plan->net;
+  const int NS = plan->streams, terms = terms_of(n.prec_dw);
+  switch (plan->role[ROLE_DW].family) {
+    case FAM_FP32: return launch_dw(n.HP, NS, d, s);
+    case FAM_FP32_WIDE: return launch_dw_wide(n.HP, NS, d, s);
+    case FAM_BF16: return launch_dw_bf16(n.HP, NS, terms, n.wide ? 64 : 128, d, s);
+    case FAM_BF16_WIDE: return launch_dw_bf16_wide(n.HP, NS, terms, d, s);
+    default: return -1000;
+  }
+}
+static int run_fused(const pinn_plan_s* plan, const FwdArgs& fa, const BwdArgs& ba, hipStream_t s) {
+  return launch_fwdbwd_split(plan->net.HP, terms_of(plan->net.prec_fwd), fa, ba, plan->role[ROLE_FUSED].grid, s);
+}
 
-// kernel-family dispatch (precision x tile geometry), shared by the launches and by pinn_plan_create's
-// configure pass (args.configure = 1: set the dynamic-LDS attribute of exactly the kernel a launch would pick)
-static int dispatch_fwd(const pinn_plan_s* plan, const FwdArgs& a, hipStream_t s, bool pipe = false) {
-  const pinn_net_s& n = plan->net;
-  const int cols = n.wide ? 64 : 128, NS = plan->streams;
-  if (pipe && plan->wsplit) return launch_fwd_wsplit(n.HP, terms_of(n.prec_fwd), a, plan->grid_fp, s);
-  if (pipe) return plan->pipe_f == 2 ? launch_fwd_split(n.HP, terms_of(n.prec_fwd), a, plan->grid_fp, s)
-                                     : launch_fwd_pipe(n.HP, terms_of(n.prec_fwd), a, plan->grid_fp, s);
-  if (n.prec_fwd)
-    return n.HP > 256 ? launch_fwd_bf16_wide(n.HP, NS, terms_of(n.prec_fwd), a, plan->grid_f, s)
-                      : launch_fwd_bf16(n.HP, NS, terms_of(n.prec_fwd), cols, a, plan->grid_f, s);
-  return n.wide ? launch_fwd_wide(n.HP, NS, a, plan->grid_f, s) : launch_fwd(n.HP, NS, a, plan->grid_f, s);
+// Resolves a plan: tiles, one Role per kernel role, the spill format and the workspace layout.  Pure host arithmetic
+// (no HIP call) on the net, the point and stream counts, the compute-unit count and the switches.
+static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw) {
+  p->net = net;
+  p->n = n_points; p->streams = streams;
+  const bool wide = net.wide != 0;
+  const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
+  p->ntiles = (int)((n_points + per_tile - 1) / per_tile);
+  p->npad = p->ntiles * per_tile;
+  const int HP = net.HP, L = net.L, NW = HP / 32;
+  auto bpc = [&](size_t lds) {
+    int b = (int)(PINN_LDS_MAX / lds);
+    int bw = NW >= 8 ? (wide && NW == 8 ? 2 : 1) : 8 / NW;
+    if (b > bw) b = bw;
+    return b < 1 ? 1 : b;
+  };
+  auto role = [&](int which, Family f, int grid, size_t lds, int name_col) {
+    p->role[which] = Role{f, grid, lds, FAMILY_NAMES[f][name_col]};
+  };
+  // the 8-wave kernels: what forward-only calls (save = 0) and value plans always run.  A plan whose 8-wave forward
+  // or reverse kernel does not fit in LDS is refused, whatever schedule its sweeps would take.
+  const Family f8 = base_family(net, net.prec_fwd), b8 = base_family(net, net.prec_bwd), d8 = base_family(net, net.prec_dw);
+  const size_t lds_f = fwd_lds(f8, net), lds_b = bwd_lds(b8, net), lds_d = dw_lds(d8, net);
+  if (lds_b > PINN_LDS_MAX || lds_f > PINN_LDS_MAX) return fail(-22, "pinn_plan_create: this depth x width needs more than 160 KiB of LDS%s");
+  int grid_f = cus * bpc(lds_f);
+  if (grid_f > p->ntiles) grid_f = p->ntiles;
+  int grid_b = cus * bpc(lds_b);
+  if (grid_b > p->ntiles) grid_b = p->ntiles;
+  const int grid_fp = cus < (p->ntiles + 1) / 2 ? cus : (p->ntiles + 1) / 2;   // pipelined / role-split kernels: pairs of tiles
+  // Schedule of the hidden-256 bf16 sweeps in residual mode: 0 = 8-wave kernels (fwd_bf16 / bwd_bf16), 1 = one wave
+  // per SIMD, two tiles per wave (fwd_bf16_pipe / bwd_bf16_pipe), 2 = two wave groups in opposite phases
+  // (fwd_bf16_split / bwd_bf16_split).  $PINN_FWD_SCHED / $PINN_BWD_SCHED choose per sweep, $PINN_SCHED both.
+  // Default 2.  Round-2 measurements at 6x256 / 360k points (ms): forward 2.84 / 2.65 / 2.47, reverse sweep
+  // 3.75 / 3.40 / 3.22 - the schedules end close to each other because all of them wait on the spill traffic
+  // (DESIGN.md section 4.3).
+  const bool pipe_shape = HP == 256 && !wide && streams == 4 && L >= 2;
+  int sf = sw.sched_f, sb = sw.sched_b;
+  if (!pipe_shape || !net.prec_fwd) sf = 0;
+  if (!pipe_shape || !net.prec_bwd) sb = 0;
+  if (sf == 2 && fwd_lds(FAM_SPLIT, net) > PINN_LDS_MAX) sf = 1;
+  if (sf == 1 && fwd_lds(FAM_PIPE, net) > PINN_LDS_MAX) sf = 0;
+  if (sb == 2 && bwd_lds(FAM_SPLIT, net) > PINN_LDS_MAX) sb = 1;
+  if (sb == 1 && bwd_lds(FAM_PIPE, net) > PINN_LDS_MAX) sb = 0;
+  if (sf < 0 || sf > 2) sf = 0;
+  if (sb < 0 || sb > 2) sb = 0;
+  SpillFormat& sp = p->spill;
+  // The role-split sweeps do not spill layer 0 (its saved activations are one FMA pair and one tanh of the point: the
+  // reverse sweep and dw_bf16 recompute them), so they only come as a pair, and with the bf16 dW kernel; a request for
+  // one of them alone runs that sweep on schedule 1.
+  sp.s0_skip = sf == 2 && sb == 2 && net.prec_dw;
+  if (!sp.s0_skip) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
+  // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
+  sp.s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
+  // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
+  // K region must fit twice in the 512-element image rows); $PINN_WSPLIT=0 keeps the 8-wave kernels.
+  const bool wsplit = sp.s24w && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
+                      bwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX;
+  // The fused sweeps need the role-split pair on both sides, in one precision, and fit in LDS up to 7 hidden layers at hidden 256; deeper
+  // nets keep the two launches.  $PINN_FUSE=0 keeps them too (same-build A/B).
+  const bool fuse = sf == 2 && sb == 2 && sp.s0_skip && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
+                    fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
+  p->stagger = sw.stagger;
+  if (sw.verbose)
+    fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
+            (long)n_points, streams, HP, L, net.prec_fwd, net.prec_bwd, net.prec_dw, (int)wide, sf, sb);
+  const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
+  const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
+  role(ROLE_FWD, f8, grid_f, lds_f, 0);
+  role(ROLE_FWD_SAVE, fs, fs == f8 ? grid_f : grid_fp, fwd_lds(fs, net), 0);
+  role(ROLE_BWD, bs, bs == b8 ? grid_b : grid_fp, bwd_lds(bs, net), 1);
+  role(ROLE_FUSED, fuse ? FAM_FUSED : FAM_NONE, grid_fp, fuse ? fwdbwd_split_lds_bytes(HP, L) : 0, 0);
+  if (L > 1) {
+    int g = cus * bpc(lds_d) / (L - 1);
+    if (g < 1) g = 1;
+    if (g > p->ntiles) g = p->ntiles;
+    p->groups = g;
+  } else {
+    p->groups = 0;
+  }
+  role(ROLE_DW, d8, p->groups, lds_d, 2);
+  const int grid_part = p->role[ROLE_FWD].grid > p->role[ROLE_FWD_SAVE].grid ? p->role[ROLE_FWD].grid : p->role[ROLE_FWD_SAVE].grid;
+  size_t off = 0;
+  p->off_partials = off; off = align_up(off + (size_t)grid_part * PINN_NLOSS * 4, 256);
+  p->off_oadj = off;     off = align_up(off + (size_t)4 * p->npad * 4, 256);
+  p->bytes_fwd = off;
+  p->off_sg = off;       off = align_up(off + (size_t)p->role[ROLE_BWD].grid * sg_total(HP, L) * 4, 256);
+  p->off_slabs = off;    off = align_up(off + (size_t)(L - 1) * p->groups * HP * HP * 4, 256);
+  const size_t ablk = (size_t)HP * (wide ? 64 : PINN_TILE_COLS);
+  // The role-split pair writes three 16-byte planes per register quad and no layer 0: its S and Z-bar are sized for
+  // exactly that, (L - 1) blocks of 3/4 of the classic HP x 128 floats per tile (5.5 instead of 8.9 GB each at
+  // 6x256 / 360 000 points).  Every other plan keeps the classic [tile][L][HP x columns] layout.
+  sp.s0_skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0;
+  sp.sl0 = sp.s0_skip ? 1 : 0;
+  sp.sblk = sp.s0_skip ? ablk / 4 * 3 : 0;
+  const size_t spill_tile = sp.s0_skip ? (size_t)(L - 1) * sp.sblk : (size_t)L * ablk;      // floats per tile
+  // (+1 tile: the pipelined kernels work on PAIRS of tiles; an odd count's dummy partner spills into this scratch block)
+  p->off_S = off;        off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
+  p->off_Zb = off;       off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
+  p->bytes_all = off;
+  return 0;
 }
-static int dispatch_bwd(const pinn_plan_s* plan, const BwdArgs& a, hipStream_t s) {
-  const pinn_net_s& n = plan->net;
-  const int cols = n.wide ? 64 : 128, NS = plan->streams;
-  if (plan->wsplit) return launch_bwd_wsplit(n.HP, terms_of(n.prec_bwd), a, plan->grid_b, s);
-  if (plan->pipe_b == 2) return launch_bwd_split(n.HP, terms_of(n.prec_bwd), a, plan->grid_b, s);
-  if (plan->pipe_b) return launch_bwd_pipe(n.HP, terms_of(n.prec_bwd), a, plan->grid_b, s);
-  if (n.prec_bwd)
-    return n.HP > 256 ? launch_bwd_bf16_wide(n.HP, NS, terms_of(n.prec_bwd), a, plan->grid_b, s)
-                      : launch_bwd_bf16(n.HP, NS, terms_of(n.prec_bwd), cols, a, plan->grid_b, s);
-  return n.wide ? launch_bwd_wide(n.HP, NS, a, plan->grid_b, s) : launch_bwd(n.HP, NS, a, plan->grid_b, s);
+
+// The spill format as each argument block carries it.  FwdArgs / BwdArgs::s0_skip is the fp32 kind of layer-0
+// recompute only (the role-split sweeps never write layer 0 and need no flag for it); DwArgs::s0_skip is either kind:
+// the dW kernel recomputes layer 0's activations whichever sweep left them out.
+static void stamp_spill(FwdArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip32; }
+static void stamp_spill(BwdArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip32; }
+static void stamp_spill(DwArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip || f.s0_skip32; }
+
+// workspace carving (ws == null: the configure pass, which launches nothing)
+static float* ws_at(void* ws, size_t off) { return ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off) : nullptr; }
+#define WS(p, off) ws_at(ws, (p)->off)
+
+// The argument blocks, each filled in one place.  A value plan's spill format is all zeros, and the residual-only
+// (value-only) fields stay zero in value (residual) mode.
+static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y, int save, float scale) {
+  FwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
+  a.prep = prep; a.S = save ? WS(plan, off_S) : nullptr;
+  a.scale = scale;
+  a.partials = WS(plan, off_partials);
+  stamp_spill(a, plan->spill);
+  return a;
 }
-static int dispatch_dw(const pinn_plan_s* plan, const DwArgs& d, hipStream_t s) {
-  const pinn_net_s& n = plan->net;
-  if (n.prec_dw && n.HP > 256) return launch_dw_bf16_wide(n.HP, plan->streams, terms_of(n.prec_dw), d, s);
-  if (n.prec_dw) return launch_dw_bf16(n.HP, plan->streams, terms_of(n.prec_dw), n.wide ? 64 : 128, d, s);
-  if (n.wide) return launch_dw_wide(n.HP, plan->streams, d, s);
-  return launch_dw(n.HP, plan->streams, d, s);
+static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
+                                 const float* e, const float* w, float* vis_t_minus, float* vis_t_out, float* fields,
+                                 float Re, float vis_t0, float alpha_evm, float coord_scale, int save, bool stagger) {
+  FwdArgs a = fwd_args(plan, ws, prep, x, y, save, coord_scale);
+  a.fld = fields; a.e = e; a.w = w; a.vtm = vis_t_minus; a.vis_used = vis_t_out;
+  a.inv_re = 1.0f / Re; a.vis_t0 = vis_t0; a.alpha_evm = alpha_evm;
+  a.stagger = stagger && plan->ntiles > 4 * plan->role[ROLE_FWD].grid ? plan->stagger : 0;
+  return a;
+}
+static BwdArgs bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y, float scale) {
+  BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
+  a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
+  a.scale = scale;
+  a.sg = WS(plan, off_sg);
+  stamp_spill(a, plan->spill);
+  return a;
+}
+static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
+                                 const float* e, const float* w, const float* vis_t, const float* fields,
+                                 const float* coef_eq4, float Re, float coord_scale, float* ebar_out) {
+  BwdArgs a = bwd_args(plan, ws, prep, x, y, coord_scale);
+  a.fld = fields; a.e = e; a.w = w; a.vis_used = vis_t;
+  for (int k = 0; k < 4; ++k) a.coef_eq[k] = coef_eq4[k];
+  a.inv_re = 1.0f / Re; a.ebar = ebar_out;
+  return a;
+}
+static DwArgs dw_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y) {
+  DwArgs d;
+  memset(&d, 0, sizeof(d));
+  d.S = WS(plan, off_S); d.Zb = WS(plan, off_Zb);
+  d.ntiles = plan->ntiles; d.L = plan->net.L; d.groups = plan->groups;
+  d.slabs = WS(plan, off_slabs);
+  d.x = x; d.y = y; d.prep = prep; d.n = (int)plan->n;
+  stamp_spill(d, plan->spill);
+  return d;
+}
+
+// Raise the dynamic-LDS limit of every kernel the plan may launch, on the CURRENT device.
+static int configure_plan(const pinn_plan_s* p) {
+  FwdArgs fa = fwd_args(p, nullptr, nullptr, nullptr, nullptr, 0, 1.f);
+  BwdArgs ba = bwd_args(p, nullptr, nullptr, nullptr, nullptr, 1.f);
+  DwArgs da = dw_args(p, nullptr, nullptr, nullptr, nullptr);
+  fa.configure = ba.configure = da.configure = 1;
+  int rc = run_fwd(p, p->role[ROLE_FWD], fa, nullptr);
+  if (!rc && p->role[ROLE_FWD_SAVE].family != p->role[ROLE_FWD].family) rc = run_fwd(p, p->role[ROLE_FWD_SAVE], fa, nullptr);
+  if (!rc) rc = run_bwd(p, ba, nullptr);
+  if (!rc && p->role[ROLE_FUSED].family) rc = run_fused(p, fa, ba, nullptr);
+  if (!rc) rc = run_dw(p, da, nullptr);
+  return rc;
 }
 
 extern "C" {
@@ -154,110 +426,15 @@ int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t*
   if (n_points < 1 || n_points > (int64_t)1 << 30) return fail(-22, "pinn_plan_create: bad point count %s%ld", "", (long)n_points);
   pinn_plan_s* p = new (std::nothrow) pinn_plan_s;
   if (!p) return fail(-12, "pinn_plan_create: out of host memory%s");
-  p->net = *net;
-  p->n = n_points; p->streams = streams;
-  const bool wide = net->wide != 0;
-  const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
-  p->ntiles = (int)((n_points + per_tile - 1) / per_tile);
-  p->npad = p->ntiles * per_tile;
-  const int HP = net->HP, L = net->L, NW = HP / 32;
-  const int cus = num_cus();
-  auto bpc = [&](size_t lds) {
-    int b = (int)(163840 / lds);
-    int bw = NW >= 8 ? (wide && NW == 8 ? 2 : 1) : 8 / NW;
-    if (b > bw) b = bw;
-    return b < 1 ? 1 : b;
-  };
-  const int cols = wide ? 64 : 128;
-  const bool wbf = HP > 256;   // wide bf16 kernels
-  const size_t lds_f = net->prec_fwd ? (wbf ? fwd_bf16_wide_lds_bytes(HP, L) : fwd_bf16_lds_bytes(HP, L, cols)) : wide ? fwd_wide_lds_bytes(HP) : fwd_lds_bytes(HP);
-  const size_t lds_b = net->prec_bwd ? (wbf ? bwd_bf16_wide_lds_bytes(HP, L) : bwd_bf16_lds_bytes(HP, L, cols)) : wide ? bwd_wide_lds_bytes(HP, L) : bwd_lds_bytes(HP, L);
-  const size_t lds_d = net->prec_dw ? (wbf ? dw_bf16_wide_lds_bytes() : dw_bf16_lds_bytes(HP)) : wide ? dw_wide_lds_bytes() : dw_lds_bytes(HP);
-  if (lds_b > 163840 || lds_f > 163840) { delete p; return fail(-22, "pinn_plan_create: this depth x width needs more than 160 KiB of LDS%s"); }
-  p->grid_f = cus * bpc(lds_f);
-  if (p->grid_f > p->ntiles) p->grid_f = p->ntiles;
-  // (forward-only calls, save = 0, always take the 8-wave kernel)
-  // Schedule of the hidden-256 bf16 sweeps in residual mode: 0 = 8-wave kernels (fwd_bf16 / bwd_bf16), 1 = one wave
-  // per SIMD, two tiles per wave (fwd_bf16_pipe / bwd_bf16_pipe), 2 = two wave groups in opposite phases
-  // (fwd_bf16_split / bwd_bf16_split).  $PINN_FWD_SCHED / $PINN_BWD_SCHED choose per sweep, $PINN_SCHED both.
-  // Default 2.  Round-2 measurements at 6x256 / 360k points (ms): forward 2.84 / 2.65 / 2.47, reverse sweep
-  // 3.75 / 3.40 / 3.22 - the schedules end close to each other because all of them wait on the spill traffic
-  // (DESIGN.md section 4.3).
-  const bool pipe_shape = HP == 256 && !wide && streams == 4 && L >= 2;
-  const int sched_all = env_int("PINN_SCHED", 2);
-  int sf = env_int("PINN_FWD_SCHED", sched_all), sb = env_int("PINN_BWD_SCHED", sched_all);
-  if (!pipe_shape || !net->prec_fwd) sf = 0;
-  if (!pipe_shape || !net->prec_bwd) sb = 0;
-  if (sf == 2 && fwd_split_lds_bytes(HP, L) > 163840) sf = 1;
-  if (sf == 1 && fwd_pipe_lds_bytes(HP, L) > 163840) sf = 0;
-  if (sb == 2 && bwd_split_lds_bytes(HP, L) > 163840) sb = 1;
-  if (sb == 1 && bwd_pipe_lds_bytes(HP, L) > 163840) sb = 0;
-  p->pipe_f = sf < 0 || sf > 2 ? 0 : sf;
-  p->pipe_b = sb < 0 || sb > 2 ? 0 : sb;
-  // The role-split sweeps do not spill layer 0 (its saved activations are one FMA pair and one tanh of the point: the
-  // reverse sweep and dw_bf16 recompute them), so they only come as a pair, and with the bf16 dW kernel; a request for
-  // one of them alone runs that sweep on schedule 1.
-  p->s0_skip = p->pipe_f == 2 && p->pipe_b == 2 && net->prec_dw;
-  // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
-  p->s24w = HP > 256 && streams == 4 && net->prec_fwd && net->prec_bwd && net->prec_dw;
-  if (!p->s0_skip) { if (p->pipe_f == 2) p->pipe_f = 1; if (p->pipe_b == 2) p->pipe_b = 1; }
-  // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
-  // K region must fit twice in the 512-element image rows); $PINN_WSPLIT=0 keeps the 8-wave kernels.  Forward-only
-  // calls (save = 0) always take the 8-wave kernel.
-  p->wsplit = p->s24w && L >= 2 && env_int("PINN_WSPLIT", 1) != 0 && fwd_wsplit_lds_bytes(HP) <= PINN_LDS_MAX &&
-              bwd_wsplit_lds_bytes(HP, L) <= PINN_LDS_MAX;
-  p->grid_fp = cus < (p->ntiles + 1) / 2 ? cus : (p->ntiles + 1) / 2;
-  // The fused sweeps need the role-split pair on both sides, in one precision, and fit in LDS up to 7 hidden layers at hidden 256; deeper
-  // nets keep the two launches.  $PINN_FUSE=0 keeps them too (same-build A/B).
-  p->fuse = p->pipe_f == 2 && p->pipe_b == 2 && p->s0_skip && net->prec_fwd == net->prec_bwd && env_int("PINN_FUSE", 1) != 0 &&
-            fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
-  p->stagger = env_int("PINN_STAGGER", 0);
-  if (env_int("PINN_VERBOSE", 0))
-    fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
-            (long)n_points, streams, HP, L, net->prec_fwd, net->prec_bwd, net->prec_dw, (int)wide, p->pipe_f, p->pipe_b);
-  p->grid_b = cus * bpc(lds_b);
-  if (p->grid_b > p->ntiles) p->grid_b = p->ntiles;
-  if (p->pipe_b || p->wsplit) p->grid_b = p->grid_fp;
-  if (L > 1) {
-    int g = cus * bpc(lds_d) / (L - 1);
-    if (g < 1) g = 1;
-    if (g > p->ntiles) g = p->ntiles;
-    p->groups = g;
-  } else {
-    p->groups = 0;
-  }
-  size_t off = 0;
-  p->off_partials = off; off = align_up(off + (size_t)(p->grid_f > p->grid_fp ? p->grid_f : p->grid_fp) * PINN_NLOSS * 4, 256);
-  p->off_oadj = off;     off = align_up(off + (size_t)4 * p->npad * 4, 256);
-  p->bytes_fwd = off;
-  p->off_sg = off;       off = align_up(off + (size_t)p->grid_b * sg_total(HP, L) * 4, 256);
-  p->off_slabs = off;    off = align_up(off + (size_t)(L - 1) * p->groups * HP * HP * 4, 256);
-  const size_t ablk = (size_t)HP * (wide ? 64 : PINN_TILE_COLS);
-  // The role-split pair writes three 16-byte planes per register quad and no layer 0: its S and Z-bar are sized for
-  // exactly that, (L - 1) blocks of 3/4 of the classic HP x 128 floats per tile (5.5 instead of 8.9 GB each at
-  // 6x256 / 360 000 points).  Every other plan keeps the classic [tile][L][HP x columns] layout.
-  p->s0_skip32 = streams == 4 && L >= 2 && !net->prec_fwd && !net->prec_bwd && !net->prec_dw && env_int("PINN_S0_SKIP32", 1) != 0;
-  p->sl0 = p->s0_skip ? 1 : 0;
-  p->sblk = p->s0_skip ? ablk / 4 * 3 : 0;
-  const size_t spill_tile = p->s0_skip ? (size_t)(L - 1) * p->sblk : (size_t)L * ablk;      // floats per tile
-  // (+1 tile: the pipelined kernels work on PAIRS of tiles; an odd count's dummy partner spills into this scratch block)
-  p->off_S = off;        off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
-  p->off_Zb = off;       off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
-  p->bytes_all = off;
-  // Raise the dynamic-LDS limit of the kernels this plan will launch, on the CURRENT device.  It is per-device
-  // state of the HIP runtime and idempotent; doing it here, per plan, keeps the launch path free of cached
-  // "already configured" flags (no global mutable state; a process may drive several devices and threads).
+  int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches());
+  if (rc) { delete p; return rc; }
+  // The dynamic-LDS limit is per-device state of the HIP runtime and idempotent to raise; doing it here, per plan,
+  // keeps the launch path free of cached "already configured" flags (no global mutable state; a process may drive
+  // several devices and threads).
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess) { ndev = 0; (void)hipGetLastError(); }
   if (ndev > 0) {     // (a host without a device can still size workspaces; it cannot launch anyway)
-    FwdArgs fa; memset(&fa, 0, sizeof(fa)); fa.L = L; fa.configure = 1;
-    BwdArgs ba; memset(&ba, 0, sizeof(ba)); ba.L = L; ba.configure = 1;
-    DwArgs da;  memset(&da, 0, sizeof(da)); da.L = L; da.groups = p->groups; da.configure = 1; da.s0_skip = p->s0_skip; da.s24 = p->s24w;
-    int rc = dispatch_fwd(p, fa, nullptr);
-    if (!rc && (p->pipe_f || p->wsplit)) rc = dispatch_fwd(p, fa, nullptr, true);
-    if (!rc) rc = dispatch_bwd(p, ba, nullptr);
-    if (!rc && p->fuse) rc = launch_fwdbwd_split(HP, terms_of(net->prec_fwd), fa, ba, p->grid_fp, nullptr);
-    if (!rc) rc = dispatch_dw(p, da, nullptr);
+    rc = configure_plan(p);
     if (rc) { delete p; return hipfail(rc, "pinn_plan_create(kernel attributes)"); }
   }
   *out = p;
@@ -267,22 +444,19 @@ int pinn_plan_destroy(pinn_plan_t plan) { delete plan; return 0; }
 int64_t pinn_plan_padded_points(pinn_plan_t plan) { return plan ? plan->npad : -1; }
 const char* pinn_plan_kernel(pinn_plan_t plan, int which) {
   if (!plan || which < 0 || which > 2) return nullptr;
-  const pinn_net_s& n = plan->net;
-  const bool wbf = n.HP > 256;
-  if (which == 0 && plan->wsplit) return "fwd_wsplit_kernel";
-  if (which == 1 && plan->wsplit) return "bwd_wsplit_kernel";
-  if (which == 0) return plan->pipe_f == 2 ? "fwd_split_kernel" : plan->pipe_f ? "fwd_pipe_kernel" : n.prec_fwd ? (wbf ? "fwd_bf16_wide_kernel" : "fwd_bf16_kernel")
-                                      : n.wide ? "fwd_wide_kernel" : "fwd_kernel";
-  if (which == 1) return plan->pipe_b == 2 ? "bwd_split_kernel" : plan->pipe_b ? "bwd_pipe_kernel" : n.prec_bwd ? (wbf ? "bwd_bf16_wide_kernel" : "bwd_bf16_kernel")
-                                      : n.wide ? "bwd_wide_kernel" : "bwd_kernel";
-  return n.prec_dw ? (wbf ? "dw_bf16_wide_kernel" : "dw_bf16_kernel") : n.wide ? "dw_wide_kernel" : "dw_kernel";
+  return plan->role[which == 0 ? ROLE_FWD_SAVE : which == 1 ? ROLE_BWD : ROLE_DW].name;
 }
 int64_t pinn_plan_workspace_bytes(pinn_plan_t plan, int with_backward) {
   if (!plan) return -1;
   return (int64_t)(with_backward ? plan->bytes_all : plan->bytes_fwd);
 }
 
-#define WS(p, off) reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (p)->off)
+// the loss sums over the partials that a forward (or fused) launch of role `r` left, one row per workgroup
+static int run_loss_sums(const Role& r, const FwdArgs& a, float* loss_sums, hipStream_t s, const char* what) {
+  if (!loss_sums) return 0;
+  int rc = launch_loss_sums(a.partials, r.grid, loss_sums, s);
+  return rc ? hipfail(rc, what) : 0;
+}
 
 int pinn_residual_forward(pinn_plan_t plan, void* ws, const float* prep,
                           const float* x, const float* y, const float* e, const float* w,
@@ -292,36 +466,16 @@ int pinn_residual_forward(pinn_plan_t plan, void* ws, const float* prep,
   if (!plan || !ws || !prep || !x || !y || !fields) return fail(-22, "pinn_residual_forward: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_residual_forward: plan is not a residual (4-stream) plan%s");
   if (!(Re > 0.f)) return fail(-22, "pinn_residual_forward: Re must be > 0%s");
-  FwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
-  a.prep = prep; a.S = save ? WS(plan, off_S) : nullptr;
-  a.fld = fields; a.e = e; a.w = w; a.vtm = vis_t_minus; a.vis_used = vis_t_out;
-  a.inv_re = 1.0f / Re; a.vis_t0 = vis_t0; a.alpha_evm = alpha_evm; a.scale = coord_scale;
-  a.s24 = plan->s24w;
-  a.partials = WS(plan, off_partials);
-  a.stagger = plan->ntiles > 4 * plan->grid_f ? plan->stagger : 0;
-  a.sl0 = plan->sl0; a.sblk = plan->sblk; a.s0_skip = plan->s0_skip32;
-  const bool pipe = (plan->pipe_f || plan->wsplit) && save;
-  int rc = dispatch_fwd(plan, a, (hipStream_t)stream, pipe);
+  const FwdArgs a = residual_fwd_args(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,
+                                      coord_scale, save, true);
+  const Role& r = plan->role[save ? ROLE_FWD_SAVE : ROLE_FWD];
+  int rc = run_fwd(plan, r, a, (hipStream_t)stream);
   if (rc) return hipfail(rc, "pinn_residual_forward");
-  if (loss_sums) {
-    rc = launch_loss_sums(a.partials, pipe ? plan->grid_fp : plan->grid_f, loss_sums, (hipStream_t)stream);
-    if (rc) return hipfail(rc, "pinn_residual_forward(loss sums)");
-  }
-  return 0;
+  return run_loss_sums(r, a, loss_sums, (hipStream_t)stream, "pinn_residual_forward(loss sums)");
 }
 
 static int run_dw_and_stash(pinn_plan_t plan, void* ws, const float* prep, const float* x, const float* y, hipStream_t s) {
-  DwArgs d;
-  memset(&d, 0, sizeof(d));
-  d.S = WS(plan, off_S); d.Zb = WS(plan, off_Zb);
-  d.ntiles = plan->ntiles; d.L = plan->net.L; d.groups = plan->groups;
-  d.slabs = WS(plan, off_slabs);
-  d.configure = 0;
-  d.s0_skip = plan->s0_skip || plan->s0_skip32; d.s24 = plan->s24w; d.x = x; d.y = y; d.prep = prep; d.n = (int)plan->n;
-  d.sl0 = plan->sl0; d.sblk = plan->sblk;
-  return dispatch_dw(plan, d, s);
+  return run_dw(plan, dw_args(plan, ws, prep, x, y), s);
 }
 
 int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
@@ -330,19 +484,10 @@ int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
                                   float Re, float coord_scale, float* ebar_out, int phases, void* stream) {
   if (!plan || !ws || !prep || !x || !y || !fields || !coef_eq4) return fail(-22, "pinn_residual_backward: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_residual_backward: plan is not a residual (4-stream) plan%s");
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
-  a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
-  a.fld = fields; a.e = e; a.w = w; a.vis_used = vis_t;
-  for (int k = 0; k < 4; ++k) a.coef_eq[k] = coef_eq4[k];
-  a.inv_re = 1.0f / Re; a.scale = coord_scale; a.ebar = ebar_out;
-  a.s24 = plan->s24w;
-  a.sl0 = plan->sl0; a.sblk = plan->sblk; a.s0_skip = plan->s0_skip32;
-  a.sg = WS(plan, off_sg);
+  const BwdArgs a = residual_bwd_args(plan, ws, prep, x, y, e, w, vis_t, fields, coef_eq4, Re, coord_scale, ebar_out);
   int rc = 0;
   if (phases & 1) {
-    rc = dispatch_bwd(plan, a, (hipStream_t)stream);
+    rc = run_bwd(plan, a, (hipStream_t)stream);
     if (rc) return hipfail(rc, "pinn_residual_backward");
   }
   if (phases & 2) rc = run_dw_and_stash(plan, ws, prep, x, y, (hipStream_t)stream);
@@ -364,40 +509,23 @@ int pinn_residual_forward_backward(pinn_plan_t plan, void* ws, const float* prep
                                    float coord_scale, float* loss_sums, float* ebar_out, void* stream) {
   if (!plan || !ws || !prep || !x || !y || !fields || !coef_eq4) return fail(-22, "pinn_residual_forward_backward: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_residual_forward_backward: plan is not a residual (4-stream) plan%s");
-  if (!plan->fuse) {
+  if (!plan->role[ROLE_FUSED].family) {
     int rc = pinn_residual_forward(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,
                                    coord_scale, 1, loss_sums, stream);
     return rc ? rc : pinn_residual_backward(plan, ws, prep, x, y, e, w, vis_t_out, fields, coef_eq4, Re, coord_scale,
                                             ebar_out, stream);
   }
   if (!(Re > 0.f)) return fail(-22, "pinn_residual_forward_backward: Re must be > 0%s");
-  // the argument blocks of the two launches it replaces (pinn_residual_forward, save = 1 / pinn_residual_backward)
-  FwdArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.x = x; fa.y = y; fa.n = (int)plan->n; fa.ntiles = plan->ntiles; fa.L = plan->net.L; fa.n_out = plan->net.n_out;
-  fa.prep = prep; fa.S = WS(plan, off_S);
-  fa.fld = fields; fa.e = e; fa.w = w; fa.vtm = vis_t_minus; fa.vis_used = vis_t_out;
-  fa.inv_re = 1.0f / Re; fa.vis_t0 = vis_t0; fa.alpha_evm = alpha_evm; fa.scale = coord_scale;
-  fa.s24 = plan->s24w;
-  fa.partials = WS(plan, off_partials);
-  fa.sl0 = plan->sl0; fa.sblk = plan->sblk; fa.s0_skip = plan->s0_skip32;
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
-  a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
-  a.fld = fields; a.e = e; a.w = w; a.vis_used = vis_t_out;
-  for (int k = 0; k < 4; ++k) a.coef_eq[k] = coef_eq4[k];
-  a.inv_re = 1.0f / Re; a.scale = coord_scale; a.ebar = ebar_out;
-  a.s24 = plan->s24w;
-  a.sl0 = plan->sl0; a.sblk = plan->sblk; a.s0_skip = plan->s0_skip32;
-  a.sg = WS(plan, off_sg);
+  // the argument blocks of the two launches it replaces (pinn_residual_forward, save = 1 / pinn_residual_backward),
+  // except that the fused kernel never staggers its workgroups
+  const FwdArgs fa = residual_fwd_args(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,
+                                       coord_scale, 1, false);
+  const BwdArgs a = residual_bwd_args(plan, ws, prep, x, y, e, w, vis_t_out, fields, coef_eq4, Re, coord_scale, ebar_out);
   hipStream_t s = (hipStream_t)stream;
-  int rc = launch_fwdbwd_split(plan->net.HP, terms_of(plan->net.prec_fwd), fa, a, plan->grid_fp, s);
+  int rc = run_fused(plan, fa, a, s);
   if (rc) return hipfail(rc, "pinn_residual_forward_backward");
-  if (loss_sums) {
-    rc = launch_loss_sums(fa.partials, plan->grid_fp, loss_sums, s);
-    if (rc) return hipfail(rc, "pinn_residual_forward_backward(loss sums)");
-  }
+  rc = run_loss_sums(plan->role[ROLE_FUSED], fa, loss_sums, s, "pinn_residual_forward_backward(loss sums)");
+  if (rc) return rc;
   rc = run_dw_and_stash(plan, ws, prep, x, y, s);
   return rc ? hipfail(rc, "pinn_residual_forward_backward(dW)") : 0;
 }
@@ -408,42 +536,44 @@ int pinn_value_forward(pinn_plan_t plan, void* ws, const float* prep,
                        int save, float* loss_sums, void* stream) {
   if (!plan || !ws || !prep || !x || !y) return fail(-22, "pinn_value_forward: null argument%s");
   if (plan->streams != 1) return fail(-22, "pinn_value_forward: plan is not a value (1-stream) plan%s");
-  FwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
-  a.prep = prep; a.S = save ? WS(plan, off_S) : nullptr;
+  FwdArgs a = fwd_args(plan, ws, prep, x, y, save, 1.f);
   for (int c = 0; c < 3; ++c) {
     a.pred[c] = (pred3 && c < a.n_out) ? pred3[c] : nullptr;
     a.tgt[c] = (tgt3 && c < a.n_out) ? tgt3[c] : nullptr;
     a.coef[c] = coef3 ? coef3[c] : 0.f;
   }
   a.oadj = save ? WS(plan, off_oadj) : nullptr;
-  a.scale = 1.f;
-  a.partials = WS(plan, off_partials);
-  int rc = dispatch_fwd(plan, a, (hipStream_t)stream);
+  const Role& r = plan->role[ROLE_FWD];
+  int rc = run_fwd(plan, r, a, (hipStream_t)stream);
   if (rc) return hipfail(rc, "pinn_value_forward");
-  if (loss_sums) {
-    rc = launch_loss_sums(a.partials, plan->grid_f, loss_sums, (hipStream_t)stream);
-    if (rc) return hipfail(rc, "pinn_value_forward(loss sums)");
-  }
-  return 0;
+  return run_loss_sums(r, a, loss_sums, (hipStream_t)stream, "pinn_value_forward(loss sums)");
 }
 
 int pinn_value_backward(pinn_plan_t plan, void* ws, const float* prep,
                         const float* x, const float* y, const float* out_adj, void* stream) {
   if (!plan || !ws || !prep || !x || !y) return fail(-22, "pinn_value_backward: null argument%s");
   if (plan->streams != 1) return fail(-22, "pinn_value_backward: plan is not a value (1-stream) plan%s");
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.n = (int)plan->n; a.ntiles = plan->ntiles; a.L = plan->net.L; a.n_out = plan->net.n_out;
-  a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
+  BwdArgs a = bwd_args(plan, ws, prep, x, y, 1.f);
   a.oadj = out_adj ? out_adj : WS(plan, off_oadj);
-  a.scale = 1.f;
-  a.sg = WS(plan, off_sg);
-  int rc = dispatch_bwd(plan, a, (hipStream_t)stream);
+  int rc = run_bwd(plan, a, (hipStream_t)stream);
   if (rc) return hipfail(rc, "pinn_value_backward");
   rc = run_dw_and_stash(plan, ws, prep, x, y, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_value_backward(dW)") : 0;
+}
+
+// the partial-sum sources of a gradient assembly: each plan's dW slabs and per-workgroup skinny accumulators
+static int reduce_sources(const char* who, const pinn_net_s* net, int nsrc, const pinn_plan_t* plans, void* const* wss,
+                          ReduceSrc* src) {
+  for (int k = 0; k < nsrc; ++k) {
+    pinn_plan_t p = plans[k];
+    void* ws = wss[k];
+    if (!p || !ws) return fail(-22, "%s: null plan/workspace", who);
+    if (p->net.H != net->H || p->net.L != net->L || p->net.n_out != net->n_out)  // (precision may differ)
+      return fail(-22, "%s: plan belongs to a different net", who);
+    src[k].slabs = WS(p, off_slabs); src[k].groups = p->groups;
+    src[k].sg = WS(p, off_sg); src[k].nwg = p->role[ROLE_BWD].grid;
+  }
+  return 0;
 }
 
 int pinn_grad_reduce(pinn_net_t net, int nsrc, const pinn_plan_t* plans, void* const* wss,
@@ -454,15 +584,7 @@ int pinn_grad_reduce(pinn_net_t net, int nsrc, const pinn_plan_t* plans, void* c
   memset(&r, 0, sizeof(r));
   r.nsrc = nsrc; r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
   r.grads = grads; r.accumulate = accumulate;
-  for (int k = 0; k < nsrc; ++k) {
-    pinn_plan_t p = plans[k];
-    void* ws = wss[k];
-    if (!p || !ws) return fail(-22, "pinn_grad_reduce: null plan/workspace%s");
-    if (p->net.H != net->H || p->net.L != net->L || p->net.n_out != net->n_out)  // (precision may differ)
-      return fail(-22, "pinn_grad_reduce: plan belongs to a different net%s");
-    r.src[k].slabs = WS(p, off_slabs); r.src[k].groups = p->groups;
-    r.src[k].sg = WS(p, off_sg); r.src[k].nwg = p->grid_b;
-  }
+  if (int rc = reduce_sources("pinn_grad_reduce", net, nsrc, plans, wss, r.src)) return rc;
   int rc = launch_reduce(r, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_grad_reduce") : 0;
 }
@@ -580,15 +702,7 @@ int pinn_grad_reduce_terms(pinn_net_t net, const int* nsrc3, const pinn_plan_t* 
   if (!plans || !wss) return fail(-22, "pinn_grad_reduce_terms: null argument%s");
   r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
   r.acc_mask = accumulate_mask & 7; r.partials = partials;
-  for (int k = 0; k < total; ++k) {
-    pinn_plan_t p = plans[k];
-    void* ws = wss[k];
-    if (!p || !ws) return fail(-22, "pinn_grad_reduce_terms: null plan/workspace%s");
-    if (p->net.H != net->H || p->net.L != net->L || p->net.n_out != net->n_out)
-      return fail(-22, "pinn_grad_reduce_terms: plan belongs to a different net%s");
-    r.src[k].slabs = WS(p, off_slabs); r.src[k].groups = p->groups;
-    r.src[k].sg = WS(p, off_sg); r.src[k].nwg = p->grid_b;
-  }
+  if (int rc = reduce_sources("pinn_grad_reduce_terms", net, total, plans, wss, r.src)) return rc;
   int rc = launch_reduce_terms(r, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_grad_reduce_terms") : 0;
 }

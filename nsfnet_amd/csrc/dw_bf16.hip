@@ -312,14 +312,7 @@ template <int HP, int NS, int TERMS, int PPL, bool P24 = false>
 static int launch_one(const DwArgs& a, hipStream_t s) {
   if (!P24 && HP == 256 && NS == 4 && PPL == 32 && a.s0_skip) return launch_one<HP, NS, TERMS, PPL, HP == 256 && NS == 4 && PPL == 32>(a, s);
   size_t lds = lds_bytes_t<HP>();
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((dw_bf16_kernel<HP, NS, TERMS, PPL, P24>), dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 template <int HP, int PPL>

@@ -191,15 +191,8 @@ size_t dw_bf16_wide_lds_bytes() { return DI::BYTES; }
 template <int NS, int TERMS, bool P24 = false>
 static int launch_one(int HP, const DwArgs& a, hipStream_t s) {
   if (!P24 && NS == 4 && a.s24) return launch_one<NS, TERMS, NS == 4>(HP, a, s);
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bf16_wide_kernel<NS, TERMS, P24>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
   const int nblk = (HP / 32 + 7) / 8;
-  hipLaunchKernelGGL((dw_bf16_wide_kernel<NS, TERMS, P24>), dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a, HP);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&dw_bf16_wide_kernel<NS, TERMS, P24>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
 }
 
 int launch_dw_bf16_wide(int HP, int NS, int terms, const DwArgs& a, hipStream_t s) {

@@ -136,17 +136,11 @@ int launch_dw_wide(int HP, int NS, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
   const int T = HP / 32, nblk = (T + 7) / 8;
   size_t lds = dw_wide_lds_bytes();
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_wide_kernel<4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_wide_kernel<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
   dim3 grid(a.groups, a.L - 1, nblk * nblk);
-  if (NS == 4) hipLaunchKernelGGL((dw_wide_kernel<4>), grid, dim3(512), lds, s, a, HP);
-  else hipLaunchKernelGGL((dw_wide_kernel<1>), grid, dim3(512), lds, s, a, HP);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  if (a.configure) {   // raises the limit of both stream counts' kernels, whichever the plan has
+    int rc = launch_or_configure(&dw_wide_kernel<4>, grid, dim3(512), lds, s, 1, a, HP);
+    return rc ? rc : launch_or_configure(&dw_wide_kernel<1>, grid, dim3(512), lds, s, 1, a, HP);
+  }
+  return NS == 4 ? launch_or_configure(&dw_wide_kernel<4>, grid, dim3(512), lds, s, 0, a, HP)
+                 : launch_or_configure(&dw_wide_kernel<1>, grid, dim3(512), lds, s, 0, a, HP);
 }

@@ -326,14 +326,7 @@ size_t fwd_bf16_lds_bytes(int HP, int L, int cols) {
 template <int HP, int NS, int TERMS, int COLS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_bf16_kernel<HP, NS, TERMS, COLS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((fwd_bf16_kernel<HP, NS, TERMS, COLS>), dim3(grid), dim3(HP * 2), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 template <int HP, int COLS>

@@ -127,14 +127,7 @@ size_t fwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitLds<256>::byte
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitLds<HP>::bytes(a.L);
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_split_kernel<HP, TERMS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((fwd_split_kernel<HP, TERMS>), dim3(grid), dim3(2 * HP), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&fwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations, L >= 2 hidden layers, HP = 256 (the caller checks)

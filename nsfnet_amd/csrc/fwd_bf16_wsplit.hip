@@ -110,14 +110,7 @@ size_t fwd_wsplit_lds_bytes(int HP) {
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::fwd_bytes();
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_wsplit_kernel<HP, TERMS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((fwd_wsplit_kernel<HP, TERMS>), dim3(grid), dim3(512), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations in the 24-bit format, L >= 2 hidden layers (the caller checks)

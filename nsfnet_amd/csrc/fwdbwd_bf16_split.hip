@@ -221,14 +221,7 @@ size_t fwdbwd_split_lds_bytes(int HP, int L) { (void)HP; return FusedLds<256>::b
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = FusedLds<HP>::bytes(a.L);
-  if (a.configure) {   // pinn_plan_create: raise the kernel's dynamic-LDS limit on the current device
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwdbwd_split_kernel<HP, TERMS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
-    return e == hipSuccess ? 0 : -(int)e;
-  }
-  hipLaunchKernelGGL((fwdbwd_split_kernel<HP, TERMS>), dim3(grid), dim3(2 * HP), lds, s, fa, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
 }
 
 // residual mode, MSE seeds, role-split plan (HP = 256, s0_skip, compact 24-bit spill; the caller checks)

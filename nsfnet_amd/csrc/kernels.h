@@ -16,6 +16,16 @@ __device__ __forceinline__ gf32x4* pin_base(const void* q) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
   return (gf32x4*)(((unsigned long long)hi << 32) | lo);
 }
+// The host tail of every sweep and dW launcher.  configure != 0 (pinn_plan_create's configure pass): launch nothing,
+// raise the kernel's dynamic-LDS limit on the current device.  Otherwise launch.  Returns 0 or -(the HIP error).
+template <typename... Params, typename... Args>
+static int launch_or_configure(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t s, int configure,
+                               const Args&... args) {
+  if (configure)
+    return -(int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  return -(int)hipGetLastError();
+}
 #endif
 
 // Field planes written by the residual forward and read by the backward
