@@ -331,6 +331,68 @@ int pinn_rba_apply(int64_t n, const float* fields, int64_t npad, double w4, doub
 /* lam_i = init, w_i = s_i init^2 for the n store points (s NULL = 1; init >= 0).  One launch. */
 int pinn_rba_fill(int64_t n, double init, const float* s, float* lam, float* w, void* stream);
 
+/* ---- learning-rate schedules and global-norm gradient clipping for Adam ----------------
+ * The reference documents a per-stage `scheduler` key (Constant | MultiStepLR | CosineAnnealingLR,
+ * ev-NSFnet/AGENTS.md:44,66) that steps a torch.optim.lr_scheduler on the host.  Here the schedule position is an
+ * epoch counter e in DEVICE memory, like the step count of pinn_adam_step_dev, and the learning rate of epoch e is
+ * computed inside the update kernel from launch constants, so one captured step serves a whole stage.  e is a counter
+ * of its own, not Adam's t: re-creating Adam (t = 0, zero moments) leaves the schedule position alone.
+ *
+ * lr_e, in fp64, from lr0 and a pinn_lr_schedule_t s (the closed forms of torch.optim.lr_scheduler):
+ *   PINN_LR_CONSTANT     lr0
+ *   PINN_LR_MULTISTEP    lr0 gamma^k,  k = number of the n_milestones (<= PINN_LR_MAX_MILESTONES) milestones <= e
+ *   PINN_LR_STEP         lr0 gamma^floor(e / step_size)
+ *   PINN_LR_EXPONENTIAL  lr0 gamma^e
+ *   PINN_LR_COSINE       eta_min + (lr0 - eta_min) (1 + cos(pi e / t_max)) / 2      (continues past t_max)
+ * times, when W = warmup_epochs > 0, the linear warm-up factor warmup_start + (1 - warmup_start) min(e, W) / W.
+ * Every operation is an fp64 operation in the order written, without contraction.  The update rounds lr_e to fp32
+ * once and uses that value exactly where pinn_adam_step_dev uses its lr.
+ * Limits: gamma > 0 and finite; milestones >= 0 and non-decreasing; step_size >= 1 (STEP); t_max >= 1 (COSINE);
+ * warmup_epochs >= 0; 0 <= warmup_start <= 1; eta_min finite.  Fields a kind does not use are ignored. */
+enum { PINN_LR_CONSTANT = 0, PINN_LR_MULTISTEP = 1, PINN_LR_STEP = 2, PINN_LR_EXPONENTIAL = 3, PINN_LR_COSINE = 4 };
+#define PINN_LR_MAX_MILESTONES 16
+typedef struct {
+  int32_t kind;                                   /* PINN_LR_* */
+  int32_t n_milestones;
+  int64_t milestones[PINN_LR_MAX_MILESTONES];
+  int64_t step_size, t_max, warmup_epochs;
+  double gamma, eta_min, warmup_start;
+} pinn_lr_schedule_t;
+/* lr_e on the host, by the formula above (NaN: null or invalid schedule, or e < 0; see pinn_last_error). */
+double pinn_lr_schedule_value(const pinn_lr_schedule_t* schedule, double lr0, int64_t e);
+
+/* Squared global gradient norm: the fp64 sum of the squares of all entries of up to two fp32 vectors (g1 NULL with
+ * n1 = 0: one vector) into scratch[0].  One launch: a grid-stride loop of 16-byte loads (4-byte loads of the same
+ * quads where a vector is not 16-byte aligned - the grouping, and so the result, does not depend on alignment), fp64
+ * accumulation, wave reduction by shuffles, per-block partials (at most 256 blocks per vector, vector 0's numbered
+ * before vector 1's), and the last block to finish folds them in a fixed order: its thread t adds partials t and
+ * t + 256, then a pairwise tree combines the 256 thread sums.  No float atomics: the result is bit-reproducible,
+ * and ranks that hold the same all-reduced gradient get the same value.  A NaN entry gives NaN.
+ * scratch: pinn_grad_sqnorm_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (the
+ * call leaves its workgroup ticket 0); one scratch serves one stream at a time.  As doubles: [0] the sum, [1] the
+ * ticket, then block partials. */
+int64_t pinn_grad_sqnorm_scratch_bytes(void);
+int pinn_grad_sqnorm(const float* g0, int64_t n0, const float* g1, int64_t n1, double* scratch, void* stream);
+
+/* pinn_adam_step_dev with the learning rate of epoch e = epoch[0] (one int64 in device memory) in place of lr, and,
+ * when sqnorm is given, with every gradient entry multiplied first by the clip_grad_norm_ coefficient
+ *   coef = min(1, max_norm / (sqrt(sqnorm[0]) + 1e-6))      (fp64, rounded to fp32 once; a NaN norm gives NaN)
+ * in fp32, as its own rounded operation.  grads is only read.  sqnorm NULL: no clipping (max_norm is ignored, coef
+ * is 1 and the gradient is used as it is); otherwise max_norm > 0.  With schedule PINN_LR_CONSTANT, no warm-up and no
+ * clipping the result equals pinn_adam_step_dev's bit for bit.
+ * When its last workgroup is done the call increments step_counter[0] (two int64 words as for pinn_adam_step_dev)
+ * and, with advance != 0, epoch[0]; then it writes record (PINN_OPTIM_RECORD doubles, device; the caller zeroes it
+ * once):
+ *   [0] the epoch e used  [1] lr_e used (the fp32 value)  [2] the total norm sqrt(sqnorm[0]) (0 without clipping)
+ *   [3] coef (the fp32 value)  [4] updates clipped so far (coef < 1)  [5] updates made;
+ * [4] and [5] count the calls with advance != 0 only.  Several nets updated in one step must share lr_e and coef:
+ * call with advance = 0 for all but the last, which advances the epoch once.  One launch. */
+#define PINN_OPTIM_RECORD 6
+int pinn_adam_step_sched(float* params, const float* grads, float* m, float* v, int64_t n,
+                         const pinn_lr_schedule_t* schedule, double lr0, float beta1, float beta2, float eps,
+                         int64_t* step_counter, int64_t* epoch, int advance, const double* sqnorm, double max_norm,
+                         double* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

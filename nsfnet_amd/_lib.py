@@ -69,7 +69,20 @@ SIGNATURES = {
     "pinn_rba_apply": (c_int, [c_int64, c_void_p, c_int64, c_double, c_double, c_double, c_void_p, c_int64, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_rba_fill": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_lr_schedule_value": (c_double, [c_void_p, c_double, c_int64]),
+    "pinn_grad_sqnorm_scratch_bytes": (c_int64, []),
+    "pinn_grad_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pinn_adam_step_sched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_float, c_float,
+                                     c_float, c_void_p, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
 }
+
+
+class LrScheduleStruct(ctypes.Structure):
+    """pinn_lr_schedule_t"""
+    _fields_ = [("kind", ctypes.c_int32), ("n_milestones", ctypes.c_int32), ("milestones", c_int64 * 16),
+                ("step_size", c_int64), ("t_max", c_int64), ("warmup_epochs", c_int64),
+                ("gamma", c_double), ("eta_min", c_double), ("warmup_start", c_double)]
+
 
 _lib = None
 

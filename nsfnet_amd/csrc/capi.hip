@@ -8,6 +8,7 @@
 
 #include "../../include/nsfnet_pinn.h"
 #include "kernels.h"
+#include "optim.h"
 
 static_assert((int)PINN_FLD_COUNT == (int)FLD_COUNT, "field plane enum mismatch");
 
@@ -812,6 +813,76 @@ int pinn_rba_fill(int64_t n, double init, const float* s, float* lam, float* w, 
   if (!std::isfinite(init) || init < 0.0) return fail(-22, "pinn_rba_fill: init must be finite and >= 0%s");
   int rc = launch_rba_fill((long)n, init, s, lam, w, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_rba_fill") : 0;
+}
+
+// ---------------------------------------------------------------------------
+// learning-rate schedules and gradient clipping for Adam (optim.hip)
+// ---------------------------------------------------------------------------
+static int check_schedule(const char* what, const pinn_lr_schedule_t* s) {
+  if (!s) return fail(-22, "%s: null schedule", what);
+  if (s->kind < PINN_LR_CONSTANT || s->kind > PINN_LR_COSINE) return fail(-22, "%s: unknown schedule kind %ld", what, (long)s->kind);
+  if (s->warmup_epochs < 0) return fail(-22, "%s: warmup_epochs must be >= 0", what);
+  if (s->warmup_epochs > 0 && !(s->warmup_start >= 0.0 && s->warmup_start <= 1.0))
+    return fail(-22, "%s: warmup_start must be in [0, 1]", what);
+  if (s->kind == PINN_LR_CONSTANT) return 0;
+  if (s->kind == PINN_LR_COSINE) {
+    if (s->t_max < 1) return fail(-22, "%s: t_max must be >= 1", what);
+    if (!std::isfinite(s->eta_min)) return fail(-22, "%s: eta_min must be finite", what);
+    return 0;
+  }
+  if (!(s->gamma > 0.0) || !std::isfinite(s->gamma)) return fail(-22, "%s: gamma must be finite and > 0", what);
+  if (s->kind == PINN_LR_STEP && s->step_size < 1) return fail(-22, "%s: step_size must be >= 1", what);
+  if (s->kind == PINN_LR_MULTISTEP) {
+    if (s->n_milestones < 0 || s->n_milestones > PINN_LR_MAX_MILESTONES)
+      return fail(-22, "%s: at most 16 milestones (got %ld)", what, (long)s->n_milestones);
+    for (int i = 0; i < s->n_milestones; ++i)
+      if (s->milestones[i] < 0 || (i > 0 && s->milestones[i] < s->milestones[i - 1]))
+        return fail(-22, "%s: milestones must be >= 0 and non-decreasing", what);
+  }
+  return 0;
+}
+
+double pinn_lr_schedule_value(const pinn_lr_schedule_t* schedule, double lr0, int64_t e) {
+  if (check_schedule("pinn_lr_schedule_value", schedule)) return NAN;
+  if (e < 0) { fail(-22, "pinn_lr_schedule_value: e must be >= 0%s"); return NAN; }
+  return lr_schedule_value(*schedule, lr0, (long long)e);
+}
+
+int64_t pinn_grad_sqnorm_scratch_bytes(void) { return (int64_t)grad_sqnorm_scratch_bytes(); }
+
+int pinn_grad_sqnorm(const float* g0, int64_t n0, const float* g1, int64_t n1, double* scratch, void* stream) {
+  if (!g0 || !scratch) return fail(-22, "pinn_grad_sqnorm: null argument%s");
+  if (n0 < 1 || n0 > (int64_t)1 << 30) return fail(-22, "pinn_grad_sqnorm: n0 must be 1..2^30 (got %s%ld)", "", (long)n0);
+  if (n1 < 0 || n1 > (int64_t)1 << 30) return fail(-22, "pinn_grad_sqnorm: n1 must be 0..2^30 (got %s%ld)", "", (long)n1);
+  if ((n1 > 0) != (g1 != nullptr)) return fail(-22, "pinn_grad_sqnorm: g1 must be given exactly when n1 > 0%s");
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 != 0) return fail(-22, "pinn_grad_sqnorm: scratch must be 8-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(g0) % 4 != 0 || reinterpret_cast<uintptr_t>(g1) % 4 != 0)
+    return fail(-22, "pinn_grad_sqnorm: the vectors must be 4-byte aligned%s");
+  int rc = launch_grad_sqnorm(g0, (long)n0, g1, (long)n1, scratch, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_grad_sqnorm") : 0;
+}
+
+int pinn_adam_step_sched(float* params, const float* grads, float* m, float* v, int64_t n,
+                         const pinn_lr_schedule_t* schedule, double lr0, float beta1, float beta2, float eps,
+                         int64_t* step_counter, int64_t* epoch, int advance, const double* sqnorm, double max_norm,
+                         double* record, void* stream) {
+  if (!params || !grads || !m || !v || !step_counter || !epoch || !record)
+    return fail(-22, "pinn_adam_step_sched: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_adam_step_sched: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (int rc = check_schedule("pinn_adam_step_sched", schedule)) return rc;
+  if (!std::isfinite(lr0)) return fail(-22, "pinn_adam_step_sched: lr0 must be finite%s");
+  if (sqnorm && !(max_norm > 0.0)) return fail(-22, "pinn_adam_step_sched: max_norm must be > 0 when sqnorm is given%s");
+  if (reinterpret_cast<uintptr_t>(sqnorm) % 8 != 0 || reinterpret_cast<uintptr_t>(record) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(epoch) % 8 != 0)
+    return fail(-22, "pinn_adam_step_sched: epoch, sqnorm and record must be 8-byte aligned%s");
+  AdamSchedArgs a;
+  a.p = params; a.g = grads; a.m = m; a.v = v; a.n = (long)n;
+  a.sched = *schedule; a.lr0 = lr0; a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  a.step_counter = reinterpret_cast<long long*>(step_counter);
+  a.epoch = reinterpret_cast<long long*>(epoch);
+  a.advance = advance != 0; a.sq = sqnorm; a.max_norm = max_norm; a.record = record;
+  int rc = launch_adam_sched(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_adam_step_sched") : 0;
 }
 
 }  // extern "C"

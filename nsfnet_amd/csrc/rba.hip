@@ -20,6 +20,7 @@
 //                      min / max / sum of the lam values it wrote, folded the same way, go to the record
 //   rba_fill_kernel    lam = init, w = s init^2
 #include "kernels.h"
+#include "xwg_fold.h"
 
 namespace {
 
@@ -39,16 +40,6 @@ __device__ __forceinline__ double nmax(double a, double b) { return (b > a || b 
 __device__ __forceinline__ double e2_of(float e1, float e2, float e3, float e4, double w4) {
   double s = __dadd_rn(__dadd_rn(sq(e1), sq(e2)), sq(e3));
   return __dadd_rn(s, __dmul_rn(w4, sq(e4)));       // w4 = 0: e4 is 0 as well (the plane is not read)
-}
-
-// block partials cross workgroups (and XCDs, whose L2s are private) inside one launch: agent-scope accesses
-__device__ __forceinline__ void put(double* p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double get(const double* p) {
-  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p),
-                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
 // op 0: sum, 1: NaN-propagating max, 2: min, 3: max
@@ -72,21 +63,6 @@ __device__ __forceinline__ double block_fold(double v, double* red) {
   if (threadIdx.x == 0)
     for (int i = 1; i < kThreads / 64; ++i) t = comb<OP>(t, red[i]);
   return t;
-}
-
-// True in every thread of the last workgroup to get here, after which it may read what the others put()
-__device__ __forceinline__ bool last_block(double* ticket_word, int* flag) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ticket_word);
-    __threadfence();
-    const bool last = atomicAdd(ticket, 1ull) == (unsigned long long)gridDim.x - 1;
-    if (last) *ticket = 0;                          // 0 between calls
-    __threadfence();
-    *flag = last;
-  }
-  __syncthreads();
-  return *flag != 0;
 }
 
 // the four residual values of points base .. base + 3 (base % 4 == 0 and base < n <= npad, npad % 4 == 0: in bounds)

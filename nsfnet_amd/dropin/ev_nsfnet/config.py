@@ -32,6 +32,24 @@ class TrainingStage:
     optimizer: str = "adam"             # adam | lbfgs (lbfgs: epochs = L-BFGS iterations, lr = step scale)
     history_size: int = 100             # lbfgs only
     line_search: str = "strong_wolfe"   # lbfgs only: strong_wolfe | none
+    # adam only: the learning-rate schedule of the stage, computed on the device (PinnEngine.set_lr_schedule).  lr is
+    # its base rate and the stage's first update is epoch 0.
+    scheduler: str = "constant"         # constant | multistep | step | exponential | cosine
+    milestones: List[int] = field(default_factory=list)    # multistep: at most 16, ascending
+    gamma: float = 0.1                  # multistep / step / exponential
+    step_size: int = 1                  # step
+    t_max: int = 0                      # cosine; 0 = the stage's epochs
+    eta_min: float = 0.0                # cosine
+    warmup_epochs: int = 0              # > 0: linear warm-up from warmup_start * lr over that many updates
+    warmup_start: float = 0.0
+
+    def schedule_args(self, epochs_scale=1.0):
+        """Keyword arguments of nsfnet_amd.schedule.LrSchedule for this stage, every count scaled like epochs."""
+        n = lambda v, lo: max(lo, int(v * epochs_scale))
+        epochs = n(self.epochs, 1)
+        return dict(kind=self.scheduler, milestones=tuple(n(m, 0) for m in self.milestones), gamma=self.gamma,
+                    step_size=n(self.step_size, 1), t_max=n(self.t_max, 1) if self.t_max > 0 else epochs,
+                    eta_min=self.eta_min, warmup_epochs=n(self.warmup_epochs, 0), warmup_start=self.warmup_start)
 
 
 @dataclass
@@ -77,6 +95,13 @@ class BatchingConfig:
 
 
 @dataclass
+class GradClipConfig:
+    """Global-norm gradient clipping of the Adam updates (PinnEngine.set_grad_clipping), off by default: max_norm = 0
+    is off.  An L-BFGS stage ignores it."""
+    max_norm: float = 0.0
+
+
+@dataclass
 class ResidualAttentionConfig:
     """Residual-based attention weights on the collocation points (PinnEngine.set_residual_attention), off by
     default: eta = 0 is off, eta > 0 switches it on (the paper's values: eta 0.01, gamma 0.999).  lam starts at init
@@ -84,6 +109,9 @@ class ResidualAttentionConfig:
     eta: float = 0.0
     gamma: float = 0.999
     init: float = 1.0
+
+
+SCHEDULERS = ("constant", "multistep", "step", "exponential", "cosine")
 
 
 def _default_stages():
@@ -104,6 +132,7 @@ class TrainingConfig:
     loss_balancing: LossBalancingConfig = field(default_factory=LossBalancingConfig)
     batching: BatchingConfig = field(default_factory=BatchingConfig)
     residual_attention: ResidualAttentionConfig = field(default_factory=ResidualAttentionConfig)
+    grad_clip: GradClipConfig = field(default_factory=GradClipConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -129,7 +158,13 @@ def _fill(obj, data):
         if key == "training_stages":
             setattr(obj, key, [TrainingStage(float(s["alpha"]), int(s["epochs"]), float(s["lr"]), str(s["name"]),
                                              str(s.get("optimizer", "adam")), int(s.get("history_size", 100)),
-                                             str(s.get("line_search", "strong_wolfe")))
+                                             str(s.get("line_search", "strong_wolfe")),
+                                             scheduler=str(s.get("scheduler", "constant")),
+                                             milestones=[int(m) for m in (s.get("milestones") or [])],
+                                             gamma=float(s.get("gamma", 0.1)), step_size=int(s.get("step_size", 1)),
+                                             t_max=int(s.get("t_max", 0)), eta_min=float(s.get("eta_min", 0.0)),
+                                             warmup_epochs=int(s.get("warmup_epochs", 0)),
+                                             warmup_start=float(s.get("warmup_start", 0.0)))
                                for s in (val or [])])
         elif is_dataclass(cur):
             _fill(cur, val)
@@ -171,7 +206,28 @@ class ConfigManager:
         ra = c.training.residual_attention
         if not (0.0 <= ra.eta < float("inf") and 0.0 < ra.gamma <= 1.0 and 0.0 <= ra.init < float("inf")):
             problems.append("training.residual_attention: eta >= 0, 0 < gamma <= 1 and init >= 0 required")
+        gc = c.training.grad_clip
+        if not 0.0 <= gc.max_norm < float("inf"):
+            problems.append("training.grad_clip: max_norm >= 0 and finite required")
         for st in c.training.training_stages:
+            if st.scheduler not in SCHEDULERS:
+                problems.append("stage %s: scheduler must be one of %s (got %r)" % (st.name, " | ".join(SCHEDULERS),
+                                                                                   st.scheduler))
+            elif st.scheduler != "constant" and st.optimizer == "lbfgs":
+                problems.append("stage %s: an lbfgs stage takes no scheduler (got %r)" % (st.name, st.scheduler))
+            if st.scheduler in ("multistep", "step", "exponential") and not 0.0 < st.gamma < float("inf"):
+                problems.append("stage %s: gamma must be finite and > 0" % st.name)
+            if st.scheduler == "multistep" and (len(st.milestones) > 16 or any(m < 0 for m in st.milestones) or any(
+                    b < a for a, b in zip(st.milestones, st.milestones[1:]))):
+                problems.append("stage %s: milestones must be at most 16, >= 0 and ascending" % st.name)
+            if st.scheduler == "step" and st.step_size < 1:
+                problems.append("stage %s: step_size must be >= 1" % st.name)
+            if st.scheduler == "cosine" and (st.t_max < 0 or not abs(st.eta_min) < float("inf")):
+                problems.append("stage %s: t_max >= 0 (0 = the stage's epochs) and a finite eta_min required" % st.name)
+            if st.warmup_epochs < 0 or not 0.0 <= st.warmup_start <= 1.0:
+                problems.append("stage %s: warmup_epochs >= 0 and 0 <= warmup_start <= 1 required" % st.name)
+            if st.warmup_epochs > 0 and st.optimizer == "lbfgs":
+                problems.append("stage %s: an lbfgs stage takes no warm-up" % st.name)
             if st.epochs < 0 or st.lr <= 0:
                 problems.append("stage %s: epochs >= 0 and lr > 0 required" % st.name)
             if st.optimizer not in ("adam", "lbfgs"):
@@ -205,5 +261,15 @@ class ConfigManager:
         if t.residual_attention.eta > 0:
             print("attention  : eta=%s gamma=%s init=%s" % (t.residual_attention.eta, t.residual_attention.gamma,
                                                             t.residual_attention.init))
+        if t.grad_clip.max_norm > 0:
+            print("grad clip  : max_norm=%s" % t.grad_clip.max_norm)
+        for st in t.training_stages:
+            if st.scheduler != "constant" or st.warmup_epochs > 0:
+                a = st.schedule_args()
+                print("scheduler  : %s: %s%s" % (st.name, st.scheduler, "".join(
+                    " %s=%s" % (k, a[k]) for k in {"multistep": ("milestones", "gamma"), "step": ("step_size", "gamma"),
+                                                   "exponential": ("gamma",), "cosine": ("t_max", "eta_min"),
+                                                   "constant": ()}[st.scheduler]
+                    + (("warmup_epochs", "warmup_start") if st.warmup_epochs > 0 else ()))))
         print("supervision: enabled=%s samples=%d weight=%s"
               % (c.supervision.enabled, c.supervision.num_samples, c.supervision.loss_weight))

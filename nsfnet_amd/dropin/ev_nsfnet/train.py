@@ -15,6 +15,7 @@ import torch.distributed as dist
 import cavity_data as cavity
 import pinn_solver as psolver
 from nsfnet_amd.pinn_solver import AdamHandle
+from nsfnet_amd.schedule import LrSchedule
 from config import ConfigManager
 from logger import get_logger
 
@@ -27,6 +28,30 @@ def setup_distributed():
     torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
     dist.init_process_group(backend=os.environ.get("NSFNET_DIST_BACKEND", "nccl"))
     return True
+
+
+def run_stages(PINN, stages, epochs_scale, rank, log, star=None):
+    """The staged schedule: per stage alpha_evm, then `epochs` (scaled) L-BFGS iterations or Adam updates at `lr`; an
+    Adam stage with a scheduler or a warm-up runs under that device schedule, every count scaled like the epochs."""
+    for st in stages:
+        if rank == 0:
+            log.stage(st.name, st.alpha, st.epochs, st.lr)
+        PINN.current_stage = st.name
+        PINN.set_alpha_evm(st.alpha)
+        epochs = max(1, int(st.epochs * epochs_scale))
+        if st.optimizer == "lbfgs":     # one epoch = one L-BFGS iteration of the main net, lr = step scale
+            # max_eval: room for the line search (torch's default for max_iter = 1 is one evaluation)
+            opt = torch.optim.LBFGS(PINN.net.parameters(), lr=st.lr, max_iter=1, max_eval=25,
+                                    history_size=st.history_size,
+                                    line_search_fn=None if st.line_search == "none" else st.line_search)
+            PINN.train(num_epoch=epochs, lr=st.lr, optimizer=opt)
+            PINN.set_optimizers(AdamHandle(st.lr))      # a later adam stage runs Adam again
+        elif st.scheduler != "constant" or st.warmup_epochs > 0:    # lr is the base rate, the stage starts at epoch 0
+            PINN.train(num_epoch=epochs, lr=st.lr, scheduler=LrSchedule(**st.schedule_args(epochs_scale)))
+        else:
+            PINN.train(num_epoch=epochs, lr=st.lr)
+        if rank == 0 and star is not None:
+            PINN.evaluate(*star)
 
 
 def main():
@@ -105,23 +130,10 @@ def main():
         ra = cfg.training.residual_attention
         if ra.eta > 0:    # per-point attention weights on top of the SDF weights of the collocation set
             PINN.set_residual_attention(eta=ra.eta, gamma=ra.gamma, init=ra.init)
-        for st in cfg.training.training_stages:
-            if rank == 0:
-                log.stage(st.name, st.alpha, st.epochs, st.lr)
-            PINN.current_stage = st.name
-            PINN.set_alpha_evm(st.alpha)
-            epochs = max(1, int(st.epochs * args.epochs_scale))
-            if st.optimizer == "lbfgs":     # one epoch = one L-BFGS iteration of the main net, lr = step scale
-                # max_eval: room for the line search (torch's default for max_iter = 1 is one evaluation)
-                opt = torch.optim.LBFGS(PINN.net.parameters(), lr=st.lr, max_iter=1, max_eval=25,
-                                        history_size=st.history_size,
-                                        line_search_fn=None if st.line_search == "none" else st.line_search)
-                PINN.train(num_epoch=epochs, lr=st.lr, optimizer=opt)
-                PINN.set_optimizers(AdamHandle(st.lr))      # a later adam stage runs Adam again
-            else:
-                PINN.train(num_epoch=epochs, lr=st.lr)
-            if rank == 0 and star is not None:
-                PINN.evaluate(*star)
+        gc = cfg.training.grad_clip
+        if gc.max_norm > 0:   # global-norm clipping of every Adam update, on the device
+            PINN.set_grad_clipping(max_norm=gc.max_norm)
+        run_stages(PINN, cfg.training.training_stages, args.epochs_scale, rank, log, star)
         if rank == 0:
             log.header("training completed")
     finally:

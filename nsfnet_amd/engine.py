@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from . import lbfgs as _lbfgs
+from . import schedule as _schedule
 
 NLOSS = 8
 FLD = dict(u=0, v=1, u_x=2, u_y=3, v_x=4, v_y=5, eq1=6, eq2=7, eq3=8, eq4=9, p=10)
@@ -135,6 +136,18 @@ class DeviceNet:
         _lib.check(self.lib.pinn_adam_step_dev(_ptr(self.params), _ptr(grads), _ptr(self.m), _ptr(self.v),
                                                self.num_params, lr, betas[0], betas[1], eps,
                                                _ptr(self.adam_t_dev), _stream()), "pinn_adam_step_dev")
+        self.prepare()
+
+    def adam_step_sched(self, grads, lr0, opt, advance, betas=(0.9, 0.999), eps=1e-8):
+        """adam_step with the learning rate of the device epoch counter opt.epoch under opt's schedule (lr0 = its
+        base rate) and, when opt.max_norm > 0, the gradient scaled by the clipping coefficient of the squared norm in
+        opt.scratch (pinn_adam_step_sched).  advance: this call moves the epoch counter on."""
+        self.adam_t += 1
+        _lib.check(self.lib.pinn_adam_step_sched(
+            _ptr(self.params), _ptr(grads), _ptr(self.m), _ptr(self.v), self.num_params, ctypes.byref(opt.cstruct),
+            float(lr0), betas[0], betas[1], eps, _ptr(self.adam_t_dev), _ptr(opt.epoch), 1 if advance else 0,
+            _ptr(opt.scratch if opt.max_norm > 0.0 else None), float(opt.max_norm), _ptr(opt.rec), _stream()),
+            "pinn_adam_step_sched")
         self.prepare()
 
 
@@ -449,6 +462,20 @@ def rba_fill(init, s, lam, w):
                "pinn_rba_fill")
 
 
+OPTIM_RECORD = 6         # PINN_OPTIM_RECORD
+
+
+def grad_sqnorm_scratch(device):
+    """Zeroed device scratch of grad_sqnorm."""
+    return torch.zeros(int(_lib.load().pinn_grad_sqnorm_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def grad_sqnorm(g0, g1, scratch):
+    """pinn_grad_sqnorm: the fp64 sum of squares of g0 and (not None) g1 into scratch[0], fixed order.  One launch."""
+    _lib.check(_lib.load().pinn_grad_sqnorm(_ptr(g0), g0.numel(), _ptr(g1), 0 if g1 is None else g1.numel(),
+                                            _ptr(scratch), _stream()), "pinn_grad_sqnorm")
+
+
 class LbfgsHistory:
     """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
     g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
@@ -551,6 +578,25 @@ class _Attention:
         self.n_eval = 0
 
 
+class _Optim:
+    """State of the device learning-rate schedule and gradient clipping (set_lr_schedule / set_grad_clipping): the
+    schedule (an LrSchedule; constant while only clipping is on) with its C struct, max_norm (0 = no clipping) and the
+    device tensors epoch [1] int64 (the schedule position e), rec [OPTIM_RECORD] fp64 (the last update) and scratch
+    (the squared norm and its partials)."""
+
+    def __init__(self, device):
+        self.user_spec, self.max_norm = None, 0.0
+        self.epoch = torch.zeros(1, dtype=torch.int64, device=device)
+        self.rec = torch.zeros(OPTIM_RECORD, dtype=torch.float64, device=device)
+        self.scratch = grad_sqnorm_scratch(device)
+        self.set_spec(None)
+
+    def set_spec(self, spec):
+        self.user_spec = spec
+        self.spec = spec if spec is not None else _schedule.LrSchedule()
+        self.cstruct = self.spec.c_struct()
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -602,6 +648,7 @@ class PinnEngine:
         self._eval_batch = False            # the last evaluation ran on the batch plan (loss_terms' normalisation)
         self._rba = None                    # residual-based attention (set_residual_attention; None = off)
         self._rba_frozen = False            # lbfgs_step / full_batch: the weights are held fixed
+        self._opt = None                    # device lr schedule / gradient clipping (set_lr_schedule, set_grad_clipping)
 
     # ---- views into the exchange buffer ----
     @property
@@ -1220,11 +1267,76 @@ class PinnEngine:
         return out
 
     def adam_step(self, lr):
-        self.net.adam_step(self.grads, lr)
-        if self.net_e is not None and self.e_trainable:
-            self.net_e.adam_step(self.grads_e, lr)
+        """Adam on the gradient of the last evaluation.  With a device schedule or clipping on, lr is the schedule's
+        base rate lr0; every trainable net uses the lr_e and the clipping coefficient of the same epoch."""
+        o = self._opt
+        with_e = self.net_e is not None and self.e_trainable
+        if o is None:
+            self.net.adam_step(self.grads, lr)
+            if with_e:
+                self.net_e.adam_step(self.grads_e, lr)
+        else:
+            if o.max_norm > 0.0:        # the gradient Adam consumes: all-reduced, combined
+                grad_sqnorm(self.grads, self.grads_e if with_e else None, o.scratch)
+            if with_e:
+                self.net_e.adam_step_sched(self.grads_e, lr, o, advance=False)
+            self.net.adam_step_sched(self.grads, lr, o, advance=True)        # last: it moves the epoch on
         if self._bal is not None:
             self._bal.n += 1
+
+    # ---- device learning-rate schedule and gradient clipping (DESIGN.md section 7.6) ----
+    def set_lr_schedule(self, spec=None):
+        """spec = an LrSchedule: the Adam updates of step() and adam_step(lr) use the rate lr_e = spec.value(lr, e) of a
+        schedule position e kept in device memory (the update kernel computes it in fp64 from launch constants and
+        rounds it to fp32 once) - lr is the base rate lr0, and e advances by one per update, so a captured step
+        serves a whole stage.  e is not Adam's step count: reset_adam (the ev freeze schedule) leaves it alone, and
+        so does lbfgs_step.  A call restarts e at 0; reset_lr_schedule(e) sets it.  None: off (with clipping off
+        too, adam_step makes exactly the calls it makes without the feature)."""
+        if spec is not None and not isinstance(spec, _schedule.LrSchedule):
+            raise TypeError("set_lr_schedule: an LrSchedule or None (got %r)" % (spec,))
+        self._graphs.clear()        # captured steps hold the other schedule's launch constants
+        if spec is None and (self._opt is None or self._opt.max_norm == 0.0):
+            self._opt = None
+            return
+        if self._opt is None:
+            self._opt = _Optim(self.device)
+        self._opt.set_spec(spec)
+        self._opt.epoch.zero_()
+
+    def reset_lr_schedule(self, e=0):
+        """Set the schedule position to e (in place: captured steps stay valid)."""
+        if int(e) < 0:
+            raise ValueError("reset_lr_schedule: e must be >= 0")
+        if self._opt is not None:
+            self._opt.epoch.fill_(int(e))
+
+    def set_grad_clipping(self, max_norm=0.0):
+        """max_norm > 0: before every Adam update the gradient is scaled by min(1, max_norm / (||g|| + 1e-6)), the
+        formula of torch.nn.utils.clip_grad_norm_, with ||g|| the 2-norm over all trainable nets of the gradient Adam
+        is about to consume (after the all-reduce and the loss-balancing combine; every rank computes the same
+        value).  One more launch per step, a fixed-order fp64 sum; the scaling happens inside the update, so `grads`
+        stays the raw gradient.  A non-finite norm propagates into the parameters, as in torch.  0: off."""
+        max_norm = float(max_norm)
+        if not (max_norm >= 0.0 and math.isfinite(max_norm)):
+            raise ValueError("gradient clipping: max_norm must be finite and >= 0")
+        self._graphs.clear()
+        if max_norm == 0.0 and (self._opt is None or self._opt.user_spec is None):
+            self._opt = None
+            return
+        if self._opt is None:
+            self._opt = _Optim(self.device)
+        self._opt.max_norm = max_norm
+
+    def optimizer_info(self):
+        """The device record of the last scheduled / clipped update (one host read), or None with both off: epoch
+        (the position e it used), lr (the fp32 lr_e), grad_norm and clip_coef (0 and 1 without clipping), clipped
+        (updates with coef < 1 so far), updates, next_epoch, and the settings."""
+        o = self._opt
+        if o is None:
+            return None
+        r = torch.cat([o.rec, o.epoch.to(torch.float64)]).cpu().tolist()
+        return dict(epoch=int(r[0]), lr=r[1], grad_norm=r[2], clip_coef=r[3], clipped=int(r[4]), updates=int(r[5]),
+                    next_epoch=int(r[6]), schedule=o.user_spec, max_norm=o.max_norm)
 
     # ---- L-BFGS (DESIGN.md section 7.2) ----
     def lbfgs_reset(self):
@@ -1283,6 +1395,8 @@ class PinnEngine:
                self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
                self._bal is not None, update, self._batch.B if self._batch is not None else 0,
                (False, 0.0, 0.0) if self._rba is None else (True, self._rba.gamma, self._rba.eta))
+        if self._opt is not None:       # lr is the base rate lr0: the rate of each update is device state
+            key += (self._opt.spec.key(), self._opt.max_norm)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the

@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine as _eng
+from . import schedule as _schedule
 from .net import FCNet
 from .pinn_solver import AdamHandle, SolverBase, _col, default_device, is_lbfgs, lbfgs_knobs
 
@@ -302,7 +303,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
             self._maybe_resample(epoch_id)
             self.global_step += 1
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
-            if scheduler:
+            if scheduler is not None and not isinstance(scheduler, _schedule.LrSchedule):
                 scheduler.step()
             interval = self.log_interval if self.log_interval > 0 else 100
             log_now = self.rank == 0 and (epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1)
@@ -325,6 +326,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self._last_log_time, self._last_log_epoch = time.time(), 0
         if not hasattr(self, 'log_interval'):
             self.log_interval = 100
+        scheduler = self._begin_adam_stage(scheduler)
         self.freeze_evm_net(0)
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
         for epoch_id in range(num_epoch):
@@ -335,10 +337,10 @@ class PysicsInformedNeuralNetwork(SolverBase):
             log_now = self.rank == 0 and (epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1)
             save_now = self.rank == 0 and (epoch_id == 0 or epoch_id % 10000 == 0)
             if fused and not (log_now or save_now):
-                self.engine.step(self.opt.param_groups[0]['lr'])
+                self.engine.step(self._adam_lr())
             else:
                 loss, losses = loss_func()
-                self.engine.adam_step(self.opt.param_groups[0]['lr'])
+                self.engine.adam_step(self._adam_lr())
             if scheduler:
                 scheduler.step()
             if log_now:
@@ -392,6 +394,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))
+        if self.engine._opt is not None:
+            print('  ' + self._optimizer_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]

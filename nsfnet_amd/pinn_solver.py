@@ -13,6 +13,7 @@ import scipy.io
 import torch
 
 from . import engine as _eng
+from . import schedule as _schedule
 from .net import FCNet
 
 
@@ -60,6 +61,9 @@ class SolverBase:
     _balancing = False
     _batching = False
     _attention = False
+    _lr_schedule = None         # set_lr_schedule: the LrSchedule of every Adam stage without a scheduler= of its own
+    _clipping = False
+    _lr0 = None                 # the base rate of the running Adam stage while a device schedule is on
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -106,6 +110,61 @@ class SolverBase:
         a = self.engine.attention_info()
         return "attention lam: min=%.3e mean=%.3e max=%.3e  unweighted loss_e=%.3e" % (
             a["lam_min"], a["lam_mean"], a["lam_max"], a["loss_e"])
+
+    def set_lr_schedule(self, spec=None):
+        """spec = an nsfnet_amd.schedule.LrSchedule: every Adam stage (train / solve_Adam) that is not given a
+        scheduler= of its own runs under it, computed on the device (PinnEngine.set_lr_schedule; DESIGN.md section
+        7.6): update e of the stage uses spec.value(lr, e) with lr the stage's rate, and every stage starts at e = 0.
+        An L-BFGS stage ignores it.  None: off."""
+        if spec is not None and not isinstance(spec, _schedule.LrSchedule):
+            raise TypeError("set_lr_schedule: an LrSchedule or None (got %r)" % (spec,))
+        self._lr_schedule = spec
+        self.engine.set_lr_schedule(spec)
+
+    def set_grad_clipping(self, max_norm=0.0):
+        """max_norm > 0: every Adam update scales its gradient to a global 2-norm of at most max_norm, on the device
+        (PinnEngine.set_grad_clipping; the formula of torch.nn.utils.clip_grad_norm_).  print_log adds the norm and
+        the number of clipped updates.  An L-BFGS stage ignores it.  0: off."""
+        self.engine.set_grad_clipping(max_norm)
+        self._clipping = float(max_norm) > 0.0
+
+    def _begin_adam_stage(self, scheduler):
+        """Resolve solve_Adam's scheduler= argument.  An LrSchedule, or a torch.optim.lr_scheduler object of type
+        MultiStepLR, StepLR, ExponentialLR or CosineAnnealingLR (translated once, from its own attributes), becomes
+        the device schedule of this stage: an LrSchedule starts at e = 0 with the stage's rate as lr0, a torch object
+        at e = its last_epoch with its base_lrs[0].  Returns the object whose step() the loop still calls - the torch
+        one, so that its param_groups[0]['lr'] stays right, although the engine no longer consumes that value - or
+        None.  Anything else is returned as it is and works as it always did: the loop reads the rate it sets."""
+        lr0, e0, spec, stepper = self.opt.param_groups[0]['lr'], 0, self._lr_schedule, scheduler
+        if isinstance(scheduler, _schedule.LrSchedule):
+            spec, stepper = scheduler, None
+        elif scheduler is not None:
+            tr = _schedule.from_torch(scheduler)
+            if tr is not None:
+                spec, lr0, e0 = tr
+            else:
+                spec = None         # a host schedule the device does not know: the old path
+        o = self.engine._opt
+        if spec is not (o.user_spec if o is not None else None):
+            self.engine.set_lr_schedule(spec)
+        self.engine.reset_lr_schedule(e0)
+        self._lr0 = lr0 if spec is not None else None      # None: the loop passes the handle's current rate through
+        return stepper
+
+    def _adam_lr(self):
+        """The rate solve_Adam hands to the engine: the stage's base rate under a device schedule, else the optimizer
+        handle's current one (with clipping alone that one is the base rate of a constant schedule)."""
+        return self._lr0 if self._lr0 is not None else self.opt.param_groups[0]['lr']
+
+    def _optimizer_log(self):
+        """The print_log suffix of the device schedule / clipping: lr_e of the last update and, with clipping on, the
+        gradient norm and the clipped count (one host read, at log points only)."""
+        i = self.engine.optimizer_info()
+        out = "device lr=%.6e (epoch %d)" % (i["lr"], i["epoch"])
+        if self._clipping:
+            out += "  grad_norm=%.3e clip_coef=%.3e clipped=%d/%d" % (i["grad_norm"], i["clip_coef"], i["clipped"],
+                                                                     i["updates"])
+        return out
 
     def lam_b(self):
         """The boundary weight in use (one host read when balancing is on)."""
@@ -267,7 +326,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         for epoch_id in range(num_epoch):
             self._maybe_resample(epoch_id)
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
-            if scheduler:
+            if scheduler is not None and not isinstance(scheduler, _schedule.LrSchedule):
                 scheduler.step()
             log_now = self.log_every and epoch_id % self.log_every == 0
             save_now = self.save_every and epoch_id % self.save_every == 0
@@ -286,13 +345,14 @@ class PysicsInformedNeuralNetwork(SolverBase):
         """The reference loop (solver :240-278): loss -> backward -> Adam step; log every 1000,
         checkpoint every 10000 (incl. step 0).  Adam moments persist across calls."""
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
+        scheduler = self._begin_adam_stage(scheduler)
         epoch_id = 0
         print('--------')
         print(num_epoch)
         print('--------')
         while epoch_id < num_epoch:
             self._maybe_resample(epoch_id)
-            lr = self.opt.param_groups[0]['lr']
+            lr = self._adam_lr()
             log_now = self.log_every and epoch_id % self.log_every == 0
             save_now = self.save_every and epoch_id % self.save_every == 0
             if fused and not (log_now or save_now):
@@ -319,7 +379,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("lambda_b: %.4e" % self.lam_b(),) if self._balancing else ()),
               *(("(losses of the last batch of %d points)" % self.engine.batch_info()["batch_points"],)
                 if self._batching and self.engine.evaluated_batch else ()),
-              *(("\n" + self._attention_log(),) if self._attention else ()))
+              *(("\n" + self._attention_log(),) if self._attention else ()),
+              *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

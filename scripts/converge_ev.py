@@ -13,6 +13,9 @@ viscosity state restarts from alpha*|e| as at the start of a run).
         [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call)
         [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call)
         [--rba-eta 0.01 --rba-gamma 0.999]   (residual-based attention weights, off by default; lam restarts per call)
+        [--scheduler cosine --eta-min-factor 0.01 --warmup-epochs 1000]   (device learning-rate schedule of every stage,
+                                                  off by default; counts scale with --epochs-scale, each stage starts at 0)
+        [--grad-clip 1.0]   (global-norm gradient clipping of the Adam updates, off by default)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,8 +51,18 @@ def main():
     ap.add_argument("--rba-eta", type=float, default=0.0, help="residual-based attention: eta (0: off; DESIGN.md 7.5)")
     ap.add_argument("--rba-gamma", type=float, default=0.999)
     ap.add_argument("--rba-init", type=float, default=1.0)
+    ap.add_argument("--scheduler", choices=("constant", "multistep", "step", "exponential", "cosine"), default="constant",
+                    help="learning-rate schedule of every stage, on the device (DESIGN.md 7.6); lr0 = the stage's lr")
+    ap.add_argument("--milestones", type=int, nargs="*", default=[], help="multistep: epochs of a stage at full scale")
+    ap.add_argument("--gamma", type=float, default=0.1, help="multistep / step / exponential")
+    ap.add_argument("--step-size", type=int, default=100000, help="step: epochs at full scale")
+    ap.add_argument("--eta-min-factor", type=float, default=0.0, help="cosine: eta_min = this times the stage's lr")
+    ap.add_argument("--warmup-epochs", type=int, default=0, help="linear warm-up, epochs at full scale")
+    ap.add_argument("--warmup-start", type=float, default=0.0)
+    ap.add_argument("--grad-clip", type=float, default=0.0, help="max global gradient norm of an Adam update (0: off)")
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
+    from nsfnet_amd.schedule import LrSchedule
     os.makedirs(a.out, exist_ok=True)
     dns = os.path.abspath(a.dns)
     res = None if a.resume is None else os.path.abspath(a.resume)
@@ -83,6 +96,8 @@ def main():
         P.set_batching(batch_points=a.batch_points, seed=a.batch_seed)
     if a.rba_eta > 0:
         P.set_residual_attention(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init)
+    if a.grad_clip > 0:
+        P.set_grad_clipping(a.grad_clip)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     for k in range(a.first, a.last + 1):
@@ -91,7 +106,13 @@ def main():
         P.current_stage = "Stage %d" % k
         P.set_alpha_evm(alpha)
         t0 = time.time()
-        P.train(num_epoch=n, lr=lr)
+        sched = None
+        if a.scheduler != "constant" or a.warmup_epochs > 0:
+            c = lambda v, lo: max(lo, int(v * a.epochs_scale))
+            sched = LrSchedule(a.scheduler, milestones=[c(m, 0) for m in a.milestones], gamma=a.gamma,
+                               step_size=c(a.step_size, 1), t_max=n, eta_min=a.eta_min_factor * lr,
+                               warmup_epochs=c(a.warmup_epochs, 0), warmup_start=a.warmup_start)
+        P.train(num_epoch=n, lr=lr, scheduler=sched)
         torch.cuda.synchronize()
         dt = time.time() - t0
         eu, ev = P.evaluate(*star)[:2]
@@ -107,7 +128,10 @@ def main():
                    attention=(dict(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init,
                                    **{k_: v for k_, v in P.engine.attention_info().items()
                                       if k_ in ("lam_min", "lam_mean", "lam_max", "loss_e", "skipped")})
-                              if a.rba_eta > 0 else None))
+                              if a.rba_eta > 0 else None),
+                   optimizer=({k_: (v if k_ != "schedule" else (None if v is None else v.key()))
+                               for k_, v in P.engine.optimizer_info().items()}
+                              if P.engine.optimizer_info() is not None else None))
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
