@@ -233,8 +233,10 @@ def test_config5_shape_ev_8x400_with_4x40_entropy_net(prec):
 
 @pytest.mark.parametrize("H,L", [(400, 8), (288, 3), (512, 2), (330, 4)])
 def test_wide_nets_bf16x3_sweeps(H, L):
-    """hidden > 256 in bf16x3 mode: fwd_bf16_wide / bwd_bf16_wide (two 32-feature blocks per wave; odd block
-    counts: 288 = 9, 330 -> 352 = 11) + the fp32 dW kernel, against the fp64 oracle at the bf16x3 bar."""
+    """hidden > 256 in bf16x3 mode: the wide bf16 sweeps (role-split up to 448, fwd_bf16_wide / bwd_bf16_wide at 512;
+    two 32-feature blocks per wave; odd block counts: 288 = 9, 330 -> 352 = 11) + dw_bf16_wide_kernel on the 24-bit
+    spill, against the fp64 oracle at the bf16x3 bar.  (The fp32 dW kernel behind fwd_bf16_wide / bwd_bf16_wide, on
+    the fp32-plane spill, is a case of test_kernel_pairings.py.)"""
     eng = _engine_mod()
     dev = torch.device("cuda:0")
     N, Re = 300, 2000.0

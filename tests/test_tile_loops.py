@@ -95,10 +95,13 @@ def pick_n(cus, families, n_hidden):
     raise AssertionError("no point count found")
 
 
-def families_of(names, hidden, fp32):
-    """(tile, paired, bpc) of the forward and reverse sweeps a plan launches, from its kernel names."""
-    t, b = tile_points(hidden, fp32), bpc_max(hidden, fp32)
-    return [(t, k in PAIRED, b) for k in names[:2]]
+def families_of(names, hidden, fp32, tile=None):
+    """(tile, paired, bpc) of the forward and reverse sweeps a plan launches, from its kernel names.  tile: the points
+    per tile where precision alone does not tell them (a precision triple, $PINN_TILE_COLS)."""
+    if tile is None:
+        tile = tile_points(hidden, fp32)
+    b = bpc_max(hidden, tile == 16)
+    return [(tile, k in PAIRED, b) for k in names[:2]]
 
 
 SPLIT_256 = (32, True, 1)       # role-split sweeps, hidden 256, bf16 modes
@@ -222,10 +225,10 @@ def _oracle(key, L, H, flat, x, y, Re, **kw):
     return _ORACLE[key]
 
 
-def _case(monkeypatch, L, H, prec, flat, x, y, Re, names, env=(), flat_e=None, w=None, scale=1.0):
+def _case(monkeypatch, L, H, prec, flat, x, y, Re, names, env=(), flat_e=None, w=None, scale=1.0, tile=None):
     from nsfnet_amd import engine as eng
     for k in ("PINN_SCHED", "PINN_FWD_SCHED", "PINN_BWD_SCHED", "PINN_WSPLIT", "PINN_TILE_COLS", "PINN_STAGGER",
-              "NSFNET_CHUNK_POINTS"):
+              "PINN_FUSE", "PINN_S0_SKIP32", "NSFNET_CHUNK_POINTS"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env:
         monkeypatch.setenv(k, v)
@@ -241,9 +244,10 @@ def _case(monkeypatch, L, H, prec, flat, x, y, Re, names, env=(), flat_e=None, w
     # the geometry this case is for: the intended kernel families, each of them looping
     n, cus, fp32 = x.size, _cus(), prec == "fp32"
     assert E.plan_f.kernel_names() == names
-    tile = tile_points(H, fp32)
+    if tile is None:
+        tile = tile_points(H, fp32)
     assert E.plan_f.npad == -(-n // tile) * tile
-    for fam in families_of(names, H, fp32):
+    for fam in families_of(names, H, fp32, tile):
         assert loop_violations(n, cus, *fam, L) == [], (fam, loop_violations(n, cus, *fam, L))
     out = dict(vtm0=E.plan_f.vis_t_minus.cpu().numpy().astype(np.float64) if ev else None)
     E.loss_and_grad()
