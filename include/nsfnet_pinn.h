@@ -393,6 +393,34 @@ int pinn_adam_step_sched(float* params, const float* grads, float* m, float* v, 
                          int64_t* step_counter, int64_t* epoch, int advance, const double* sqnorm, double max_norm,
                          double* record, void* stream);
 
+/* ---- random weight factorization of the dense layers ------------------------------------
+ * Every Linear layer l = 0..L of a net (the first and the output layer included) gets its weight as
+ * W_l = diag(g_l) V_l with a trainable scale factor s_l,i per ROW and g_l,i = fp32(exp((double) s_l,i)), rounded once
+ * (RWF; Wang, Wang, Sankaran & Perdikaris 2022).  The factorisation is a reparametrisation between the optimizer and
+ * pinn_net_prepare: no sweep, dW or prepare kernel knows about it.  With P = pinn_net_num_params and R = sum of the
+ * layers' row counts = L * hidden + n_out, the trainable vector theta has P + R fp32 entries: the first P in
+ * state_dict order with V_l where W_l stands (biases as they are), then the R scale factors, layers ascending and
+ * rows ascending.  The optimizers (pinn_adam_step*, pinn_lbfgs_*) and pinn_grad_sqnorm take theta and its gradient
+ * like any other vector of P + R entries.
+ *   split    V_l[i,j] = W_l[i,j] / g_l,i (one fp32 division), b_l and s copied.  params is only read: the caller
+ *            keeps using it until the first update, so turning the factorisation on changes no evaluation.
+ *   compose  W_l[i,j] = g_l,i V_l[i,j] (one rounded fp32 multiply), b_l copied: params as pinn_net_prepare reads it.
+ *   grad     from the effective gradient G (d loss / d params, P entries):
+ *              dV[i,j] = g_i G_W[i,j] (one rounded fp32 multiply),  db = G_b,
+ *              ds_i    = fp32( (double) g_i * sum_j (double) V[i,j] (double) G_W[i,j] ).
+ *            The sum is fp64, not contracted, in a fixed order: one wave per row, lane t adds j = t, t + 64, ...
+ *            ascending, the lanes are combined by a shuffle-down tree with offsets 32, 16, ..., 1.  No atomics, no
+ *            scratch: the result is bit-reproducible.
+ * One launch each.  All vectors are device memory, 4-byte aligned; an output must not overlap an input.
+ * Number of scale factors R of a net (-1: null net): */
+int64_t pinn_rwf_rows(pinn_net_t net);
+/* theta [P + R] from params [P] and s [R]. */
+int pinn_rwf_split(pinn_net_t net, const float* params, const float* s, float* theta, void* stream);
+/* params [P] from theta [P + R]. */
+int pinn_rwf_compose(pinn_net_t net, const float* theta, float* params, void* stream);
+/* gtheta [P + R] = d loss / d theta from theta [P + R] and grads [P] = d loss / d params. */
+int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float* gtheta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,10 @@ SIGNATURES = {
     "pinn_grad_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "pinn_adam_step_sched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_float, c_float,
                                      c_float, c_void_p, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
+    "pinn_rwf_rows": (c_int64, [c_void_p]),
+    "pinn_rwf_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_rwf_compose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_rwf_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

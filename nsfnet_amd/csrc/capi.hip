@@ -9,6 +9,7 @@
 #include "../../include/nsfnet_pinn.h"
 #include "kernels.h"
 #include "optim.h"
+#include "rwf.h"
 
 static_assert((int)PINN_FLD_COUNT == (int)FLD_COUNT, "field plane enum mismatch");
 
@@ -883,6 +884,57 @@ int pinn_adam_step_sched(float* params, const float* grads, float* m, float* v, 
   a.advance = advance != 0; a.sq = sqnorm; a.max_norm = max_norm; a.record = record;
   int rc = launch_adam_sched(a, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_adam_step_sched") : 0;
+}
+
+// ---------------------------------------------------------------------------
+// random weight factorization of the dense layers (rwf.hip)
+// ---------------------------------------------------------------------------
+static RwfNet rwf_net(const pinn_net_s* net) {
+  RwfNet n;
+  n.H = net->H; n.L = net->L; n.n_out = net->n_out;
+  return n;
+}
+static bool misaligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 != 0; }
+// [a, a + na) and [b, b + nb) floats share an entry
+static bool overlap(const float* a, size_t na, const float* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + 4 * nb && b0 < a0 + 4 * na;
+}
+
+int64_t pinn_rwf_rows(pinn_net_t net) { return net ? (int64_t)rwf_rows(rwf_net(net)) : -1; }
+
+int pinn_rwf_split(pinn_net_t net, const float* params, const float* s, float* theta, void* stream) {
+  if (!net || !params || !s || !theta) return fail(-22, "pinn_rwf_split: null argument%s");
+  if (misaligned4(params) || misaligned4(s) || misaligned4(theta))
+    return fail(-22, "pinn_rwf_split: the vectors must be 4-byte aligned%s");
+  const RwfNet n = rwf_net(net);
+  const size_t P = flat_total(n.H, n.L, n.n_out), R = (size_t)rwf_rows(n);
+  if (overlap(theta, P + R, params, P) || overlap(theta, P + R, s, R))
+    return fail(-22, "pinn_rwf_split: theta must not overlap params or s%s");
+  int rc = launch_rwf_split(n, params, s, theta, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rwf_split") : 0;
+}
+
+int pinn_rwf_compose(pinn_net_t net, const float* theta, float* params, void* stream) {
+  if (!net || !theta || !params) return fail(-22, "pinn_rwf_compose: null argument%s");
+  if (misaligned4(theta) || misaligned4(params)) return fail(-22, "pinn_rwf_compose: the vectors must be 4-byte aligned%s");
+  const RwfNet n = rwf_net(net);
+  const size_t P = flat_total(n.H, n.L, n.n_out), R = (size_t)rwf_rows(n);
+  if (overlap(theta, P + R, params, P)) return fail(-22, "pinn_rwf_compose: params must not overlap theta%s");
+  int rc = launch_rwf_compose(n, theta, params, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rwf_compose") : 0;
+}
+
+int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float* gtheta, void* stream) {
+  if (!net || !theta || !grads || !gtheta) return fail(-22, "pinn_rwf_grad: null argument%s");
+  if (misaligned4(theta) || misaligned4(grads) || misaligned4(gtheta))
+    return fail(-22, "pinn_rwf_grad: the vectors must be 4-byte aligned%s");
+  const RwfNet n = rwf_net(net);
+  const size_t P = flat_total(n.H, n.L, n.n_out), R = (size_t)rwf_rows(n);
+  if (overlap(gtheta, P + R, theta, P + R) || overlap(gtheta, P + R, grads, P))
+    return fail(-22, "pinn_rwf_grad: gtheta must not overlap theta or grads%s");
+  int rc = launch_rwf_grad(n, theta, grads, gtheta, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_rwf_grad") : 0;
 }
 
 }  // extern "C"

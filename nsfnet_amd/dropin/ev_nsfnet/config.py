@@ -111,6 +111,18 @@ class ResidualAttentionConfig:
     init: float = 1.0
 
 
+@dataclass
+class WeightFactorizationConfig:
+    """Random weight factorization of every Linear layer of both nets, W = diag(exp(s)) V with s ~ Normal(mean, std)
+    drawn from a generator of its own seeded with `seed` (PinnEngine.set_weight_factorization).  The key is absent by
+    default; `training.weight_factorization: {mean, std, seed}` (any subset, or an empty mapping) switches it on.  The
+    paper recommends mean 0.5 or 1.0 with std 0.1."""
+    enabled: bool = False
+    mean: float = 0.5
+    std: float = 0.1
+    seed: int = 0
+
+
 SCHEDULERS = ("constant", "multistep", "step", "exponential", "cosine")
 
 
@@ -133,6 +145,7 @@ class TrainingConfig:
     batching: BatchingConfig = field(default_factory=BatchingConfig)
     residual_attention: ResidualAttentionConfig = field(default_factory=ResidualAttentionConfig)
     grad_clip: GradClipConfig = field(default_factory=GradClipConfig)
+    weight_factorization: WeightFactorizationConfig = field(default_factory=WeightFactorizationConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -166,6 +179,10 @@ def _fill(obj, data):
                                              warmup_epochs=int(s.get("warmup_epochs", 0)),
                                              warmup_start=float(s.get("warmup_start", 0.0)))
                                for s in (val or [])])
+        elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
+            if val is not None and val is not False:
+                cur.enabled = True
+                _fill(cur, val)
         elif is_dataclass(cur):
             _fill(cur, val)
         else:
@@ -209,6 +226,9 @@ class ConfigManager:
         gc = c.training.grad_clip
         if not 0.0 <= gc.max_norm < float("inf"):
             problems.append("training.grad_clip: max_norm >= 0 and finite required")
+        wf = c.training.weight_factorization
+        if wf.enabled and not (abs(wf.mean) < float("inf") and 0.0 <= wf.std < float("inf") and wf.seed >= 0):
+            problems.append("training.weight_factorization: finite mean, finite std >= 0 and seed >= 0 required")
         for st in c.training.training_stages:
             if st.scheduler not in SCHEDULERS:
                 problems.append("stage %s: scheduler must be one of %s (got %r)" % (st.name, " | ".join(SCHEDULERS),
@@ -263,6 +283,9 @@ class ConfigManager:
                                                             t.residual_attention.init))
         if t.grad_clip.max_norm > 0:
             print("grad clip  : max_norm=%s" % t.grad_clip.max_norm)
+        if t.weight_factorization.enabled:
+            print("weight fact: mean=%s std=%s seed=%d" % (t.weight_factorization.mean, t.weight_factorization.std,
+                                                            t.weight_factorization.seed))
         for st in t.training_stages:
             if st.scheduler != "constant" or st.warmup_epochs > 0:
                 a = st.schedule_args()

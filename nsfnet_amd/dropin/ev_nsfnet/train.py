@@ -133,6 +133,9 @@ def main():
         gc = cfg.training.grad_clip
         if gc.max_norm > 0:   # global-norm clipping of every Adam update, on the device
             PINN.set_grad_clipping(max_norm=gc.max_norm)
+        wf = cfg.training.weight_factorization
+        if wf.enabled:        # W = diag(exp(s)) V on every layer of both nets; the optimizers act on (V, b, s)
+            PINN.set_weight_factorization(mean=wf.mean, std=wf.std, seed=wf.seed)
         run_stages(PINN, cfg.training.training_stages, args.epochs_scale, rank, log, star)
         if rank == 0:
             log.header("training completed")

@@ -61,7 +61,13 @@ def resolve_precision(precision=None):
 
 class DeviceNet:
     """One FCNet on the device: flat fp32 parameters in reference state_dict order
-    (NSFnet/net.py:36-46) plus their MFMA-fragment-ordered copy."""
+    (NSFnet/net.py:36-46) plus their MFMA-fragment-ordered copy.
+
+    With the random weight factorization on (set_factorization) the trainable vector is
+    theta = [params with V where W stands | s] of num_train = num_params + rwf_rows entries: the Adam entry points
+    update theta (m and v have its size) with gtheta, the gradient rwf_grad makes of the effective one, and rebuild
+    params from it (compose) before prepare.  params stays what prepare, state_dict and every plan read."""
+    theta = gtheta = None       # the factorization is off
 
     def __init__(self, n_out, n_hidden, hidden, device, precision=None):
         self.lib = _lib.load()
@@ -119,6 +125,73 @@ class DeviceNet:
         if flat.numel() != self.num_params:
             raise ValueError("expected %d parameters, got %d" % (self.num_params, flat.numel()))
         self.params.copy_(flat.to(self.device))
+        if self.theta is not None:      # params is exactly what was given; V follows from it and the current s
+            self._rwf_split(self.theta[self.num_params:].clone())
+        self.prepare()
+
+    # ---- random weight factorization ----
+    @property
+    def rwf_rows(self):
+        """Number of scale factors: one per row of every Linear layer."""
+        return self.n_hidden * self.hidden + self.n_out
+
+    @property
+    def num_train(self):
+        """Entries of the vector the optimizers update."""
+        return self.num_params + (self.rwf_rows if self.theta is not None else 0)
+
+    @property
+    def trainable(self):
+        """The vector the optimizers update: theta with the factorization on, else params."""
+        return self.params if self.theta is None else self.theta
+
+    def set_factorization(self, s):
+        """s = fp32 [rwf_rows] (layers ascending, rows ascending): theta = split(params, s); params itself is not
+        rewritten before the first update.  None: off (params stays as composed).  Either way Adam starts afresh, with
+        moments of the trainable vector's size."""
+        if s is None:
+            self.theta = self.gtheta = None
+        else:
+            s = torch.as_tensor(s, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if s.numel() != self.rwf_rows:
+                raise ValueError("expected %d scale factors, got %d" % (self.rwf_rows, s.numel()))
+            n = self.num_params + self.rwf_rows
+            self.theta = torch.zeros(n, dtype=torch.float32, device=self.device)
+            self.gtheta = torch.zeros(n, dtype=torch.float32, device=self.device)
+            self._rwf_split(s)
+        self.m = torch.zeros_like(self.trainable)
+        self.v = torch.zeros_like(self.trainable)
+        self.reset_adam()
+
+    def _rwf_split(self, s):
+        _lib.check(self.lib.pinn_rwf_split(self.handle, _ptr(self.params), _ptr(s), _ptr(self.theta), _stream()),
+                   "pinn_rwf_split")
+
+    def compose(self):
+        """params = the effective weights of theta."""
+        _lib.check(self.lib.pinn_rwf_compose(self.handle, _ptr(self.theta), _ptr(self.params), _stream()),
+                   "pinn_rwf_compose")
+
+    def rwf_grad(self, grads):
+        """gtheta = d loss / d theta from the effective gradient; returns it."""
+        _lib.check(self.lib.pinn_rwf_grad(self.handle, _ptr(self.theta), _ptr(grads), _ptr(self.gtheta), _stream()),
+                   "pinn_rwf_grad")
+        return self.gtheta
+
+    def factors(self):
+        """The per-layer scale factors s as views of theta (updated in place); None when off."""
+        if self.theta is None:
+            return None
+        out, off = [], self.num_params
+        for rows, _ in layer_shapes(self.n_out, self.n_hidden, self.hidden):
+            out.append(self.theta[off:off + rows])
+            off += rows
+        return out
+
+    def update_params(self):
+        """After an update of the trainable vector: compose (factorization on) and re-layout."""
+        if self.theta is not None:
+            self.compose()
         self.prepare()
 
     def prepare(self):
@@ -131,24 +204,26 @@ class DeviceNet:
 
     def adam_step(self, grads, lr, betas=(0.9, 0.999), eps=1e-8):
         """One Adam update + weight re-layout.  The step count lives on the device so the call is
-        identical every step (hipGraph-capturable)."""
+        identical every step (hipGraph-capturable).  Factorization on: grads is gtheta, the update is theta's."""
         self.adam_t += 1
-        _lib.check(self.lib.pinn_adam_step_dev(_ptr(self.params), _ptr(grads), _ptr(self.m), _ptr(self.v),
-                                               self.num_params, lr, betas[0], betas[1], eps,
+        x = self.trainable
+        _lib.check(self.lib.pinn_adam_step_dev(_ptr(x), _ptr(grads), _ptr(self.m), _ptr(self.v),
+                                               x.numel(), lr, betas[0], betas[1], eps,
                                                _ptr(self.adam_t_dev), _stream()), "pinn_adam_step_dev")
-        self.prepare()
+        self.update_params()
 
     def adam_step_sched(self, grads, lr0, opt, advance, betas=(0.9, 0.999), eps=1e-8):
         """adam_step with the learning rate of the device epoch counter opt.epoch under opt's schedule (lr0 = its
         base rate) and, when opt.max_norm > 0, the gradient scaled by the clipping coefficient of the squared norm in
         opt.scratch (pinn_adam_step_sched).  advance: this call moves the epoch counter on."""
         self.adam_t += 1
+        x = self.trainable
         _lib.check(self.lib.pinn_adam_step_sched(
-            _ptr(self.params), _ptr(grads), _ptr(self.m), _ptr(self.v), self.num_params, ctypes.byref(opt.cstruct),
+            _ptr(x), _ptr(grads), _ptr(self.m), _ptr(self.v), x.numel(), ctypes.byref(opt.cstruct),
             float(lr0), betas[0], betas[1], eps, _ptr(self.adam_t_dev), _ptr(opt.epoch), 1 if advance else 0,
             _ptr(opt.scratch if opt.max_norm > 0.0 else None), float(opt.max_norm), _ptr(opt.rec), _stream()),
             "pinn_adam_step_sched")
-        self.prepare()
+        self.update_params()
 
 
 class PointPlan:
@@ -512,36 +587,49 @@ class LbfgsHistory:
 
 class _EngineSpace:
     """The vector space of lbfgs.step over a PinnEngine: x = the main net's parameters, g = grads (the kept copies
-    are the whole exchange buffer, so the loss sums of an accepted point come back with its gradient)."""
+    are the whole exchange buffer, so the loss sums of an accepted point come back with its gradient).  With the
+    weight factorization on, x = theta and g = gtheta (kept beside the exchange buffer)."""
 
     def __init__(self, engine, hist):
         self.e, self.h = engine, hist
+        self.rwf = engine.net.theta is not None
+
+    def _g(self):
+        return self.e.net.gtheta if self.rwf else self.e.grads
 
     def evaluate(self):
         e = self.e
         e.loss_and_grad()
         loss = e.loss_terms()["loss"]
-        r = self.h.probe(e.grads)
+        if self.rwf:
+            e.net.rwf_grad(e.grads)
+        r = self.h.probe(self._g())
         v = torch.cat([loss.reshape(1).to(torch.float64), r[:4]]).cpu().tolist()      # the one readback
         return v[0], v[1], v[4]
 
     def direction(self, t_prev):
         if t_prev > 0 and float(np.float32(t_prev)) == 0.0:
             t_prev = -1.0            # below fp32 range: a zero step (torch's s = t d rounds to 0, the pair is rejected)
-        r = self.h.direction(self.e.grads, t_prev).cpu().tolist()
+        r = self.h.direction(self._g(), t_prev).cpu().tolist()
         return r[0], r[1], r[2], r[3]
 
     def save_x(self):
-        self.h.x0.copy_(self.e.net.params)
+        self.h.x0.copy_(self.e.net.trainable)
 
     def set_x(self, t):
-        torch.add(self.h.x0, self.h.d, alpha=float(t), out=self.e.net.params)     # in place: captured steps stay valid
-        self.e.net.prepare()
+        torch.add(self.h.x0, self.h.d, alpha=float(t), out=self.e.net.trainable)  # in place: captured steps stay valid
+        self.e.net.update_params()
 
     def keep(self):
+        if self.rwf:
+            return self.e.flat.clone(), self.e.net.gtheta.clone()
         return self.e.flat.clone()
 
     def restore(self, h):
+        if self.rwf:
+            self.e.flat.copy_(h[0])
+            self.e.net.gtheta.copy_(h[1])
+            return
         self.e.flat.copy_(h)
 
 
@@ -649,6 +737,7 @@ class PinnEngine:
         self._rba = None                    # residual-based attention (set_residual_attention; None = off)
         self._rba_frozen = False            # lbfgs_step / full_batch: the weights are held fixed
         self._opt = None                    # device lr schedule / gradient clipping (set_lr_schedule, set_grad_clipping)
+        self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
 
     # ---- views into the exchange buffer ----
     @property
@@ -1271,18 +1360,101 @@ class PinnEngine:
         base rate lr0; every trainable net uses the lr_e and the clipping coefficient of the same epoch."""
         o = self._opt
         with_e = self.net_e is not None and self.e_trainable
+        g, ge = self.grads, self.grads_e
+        if self._rwf is not None:       # the chain rule from the effective gradient (all-reduced, combined) to d theta
+            g = self.net.rwf_grad(g)
+            if with_e:
+                ge = self.net_e.rwf_grad(ge)
         if o is None:
-            self.net.adam_step(self.grads, lr)
+            self.net.adam_step(g, lr)
             if with_e:
-                self.net_e.adam_step(self.grads_e, lr)
+                self.net_e.adam_step(ge, lr)
         else:
-            if o.max_norm > 0.0:        # the gradient Adam consumes: all-reduced, combined
-                grad_sqnorm(self.grads, self.grads_e if with_e else None, o.scratch)
+            if o.max_norm > 0.0:        # the gradient Adam consumes: all-reduced, combined (, transformed)
+                grad_sqnorm(g, ge if with_e else None, o.scratch)
             if with_e:
-                self.net_e.adam_step_sched(self.grads_e, lr, o, advance=False)
-            self.net.adam_step_sched(self.grads, lr, o, advance=True)        # last: it moves the epoch on
+                self.net_e.adam_step_sched(ge, lr, o, advance=False)
+            self.net.adam_step_sched(g, lr, o, advance=True)        # last: it moves the epoch on
         if self._bal is not None:
             self._bal.n += 1
+
+    # ---- random weight factorization of the dense layers (DESIGN.md section 7.7) ----
+    def _nets(self):
+        return [("net", self.net)] + ([("net_e", self.net_e)] if self.net_e is not None else [])
+
+    def set_weight_factorization(self, mean=0.5, std=0.1, seed=0, factors=None):
+        """Random weight factorization (RWF; Wang, Wang, Sankaran & Perdikaris 2022): every Linear layer of every net
+        - the first and the output layer included, on the ev flavour both nets - gets its weight as
+        W = diag(exp(s)) V with s (one fp32 scale factor per row) and V both trainable.  The optimizers then act on
+        theta = [params with V where W stands | s] with d loss / d theta: Adam's moments, the clipping norm and the
+        L-BFGS vectors all have theta's size.  Per Adam update and trainable net this costs two small launches, both
+        captured in the step graph: the chain rule from the effective gradient (after the all-reduce and the
+        loss-balancing combine, whose statistics stay those of the effective term gradients) and the compose that
+        rebuilds `params`, which prepare, state_dict, predict and every plan keep reading.
+
+        s ~ Normal(mean, std), drawn on the host from np.random.Generator(np.random.Philox(key=seed)): the main net
+        first, layers ascending and rows ascending, then the entropy net from the same generator.  The global numpy
+        and torch generators are not consumed, and every rank draws the same s.  factors: the s to use instead of a
+        draw, as weight_factors() returns them (per net a list of per-layer tensors, or one flat vector).  V = W / g
+        by one fp32 division; `params` is not rewritten before the first update, so the first evaluation is
+        bit-identical to the one without the feature.
+
+        mean = None: off; `params` stays as composed.  Every call re-creates Adam (t = 0, zero moments), forgets the
+        L-BFGS history and clears the captured graphs; the schedule position is left alone.  load_state_dict with
+        the feature on sets `params` exactly and re-splits with the current s."""
+        self._graphs.clear()        # captured steps hold the other vectors' pointers
+        self._lbfgs = None          # the history is sized on the trainable vector
+        self.lbfgs_reset()
+        if mean is None and factors is None:
+            self._rwf = None
+            for _, net in self._nets():
+                net.set_factorization(None)
+            return
+        given = {}
+        if factors is not None:
+            for name, net in self._nets():
+                if name not in factors:
+                    raise ValueError("weight factorization: factors has no entry %r" % name)
+                f = factors[name]
+                if isinstance(f, (list, tuple)):
+                    f = torch.cat([torch.as_tensor(a, dtype=torch.float32).reshape(-1).cpu() for a in f])
+                given[name] = torch.as_tensor(f, dtype=torch.float32).reshape(-1)
+            mean = std = seed = None
+        else:
+            mean, std, seed = float(mean), float(std), int(seed)
+            if not (math.isfinite(mean) and math.isfinite(std) and std >= 0.0):
+                raise ValueError("weight factorization: mean must be finite, std finite and >= 0")
+            rng = np.random.Generator(np.random.Philox(key=seed))
+            for name, net in self._nets():
+                given[name] = torch.from_numpy(rng.normal(mean, std, size=net.rwf_rows).astype(np.float32))
+        for name, net in self._nets():
+            net.set_factorization(given[name])
+        self._rwf = dict(mean=mean, std=std, seed=seed)
+
+    def weight_factors(self):
+        """dict(net=[s_0, ..., s_L][, net_e=[...]]): the per-layer scale factors s as fp32 device tensors, views of
+        theta that the updates rewrite in place; None when the feature is off."""
+        if self._rwf is None:
+            return None
+        return {name: net.factors() for name, net in self._nets()}
+
+    def factorization_info(self):
+        """One host read: dict(n_train=[per net], layers={net name: [dict(min, max, mean) of g = fp32(exp(s)) per
+        layer]}, mean, std, seed); None when the feature is off."""
+        if self._rwf is None:
+            return None
+        nets = self._nets()
+        s = torch.cat([net.theta[net.num_params:] for _, net in nets]).cpu().numpy()
+        out = dict(self._rwf, n_train=[net.num_train for _, net in nets], layers={})
+        off = 0
+        for name, net in nets:
+            rows = []
+            for r, _ in layer_shapes(net.n_out, net.n_hidden, net.hidden):
+                g = np.exp(s[off:off + r].astype(np.float64)).astype(np.float32)
+                rows.append(dict(min=float(g.min()), max=float(g.max()), mean=float(g.astype(np.float64).mean())))
+                off += r
+            out["layers"][name] = rows
+        return out
 
     # ---- device learning-rate schedule and gradient clipping (DESIGN.md section 7.6) ----
     def set_lr_schedule(self, spec=None):
@@ -1356,7 +1528,7 @@ class PinnEngine:
         torch.optim.LBFGS object does."""
         _lbfgs.check_knobs(lr, max_iter, max_eval, history_size, line_search_fn)
         if self._lbfgs is None or self._lbfgs.history_size != int(history_size):
-            self._lbfgs = LbfgsHistory(self.P, int(history_size), self.device)
+            self._lbfgs = LbfgsHistory(self.net.num_train, int(history_size), self.device)
             self.lbfgs_reset()
         if owner is not self._lbfgs_owner:
             self.lbfgs_reset()
@@ -1397,6 +1569,8 @@ class PinnEngine:
                (False, 0.0, 0.0) if self._rba is None else (True, self._rba.gamma, self._rba.eta))
         if self._opt is not None:       # lr is the base rate lr0: the rate of each update is device state
             key += (self._opt.spec.key(), self._opt.max_norm)
+        if self._rwf is not None:
+            key += ("rwf",)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the

@@ -460,6 +460,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         os.makedirs(save_results_to, exist_ok=True)
         torch.save(self.net.state_dict(), save_results_to + filename)
         torch.save(self.net_1.state_dict(), save_results_to + filename + '_evm')
+        self.save_weight_factors(save_results_to + filename)
 
     def neural_net_equations(self, x, y):
         """eq1..eq4 at arbitrary points, forward only, with vis_t = vis_t0 as the reference does

@@ -128,6 +128,37 @@ class SolverBase:
         self.engine.set_grad_clipping(max_norm)
         self._clipping = float(max_norm) > 0.0
 
+    def set_weight_factorization(self, mean=0.5, std=0.1, seed=0, factors=None):
+        """Random weight factorization of every Linear layer, W = diag(exp(s)) V with s and V trainable
+        (PinnEngine.set_weight_factorization): s ~ Normal(mean, std) from a generator of its own
+        seeded with `seed`, or the given `factors`.  Adam and L-BFGS then act on (V, b, s).  Checkpoints keep the
+        reference's format - state_dict() is the effective weights - and save() adds the scale factors as a sidecar
+        <checkpoint>_rwf, which load() reads back.  mean = None: off."""
+        self.engine.set_weight_factorization(mean, std, seed, factors)
+
+    def save_weight_factors(self, path):
+        """Write the sidecar of the checkpoint at `path`: {net name: flat fp32 s} as path + '_rwf' (torch.save).  With
+        the factorization off nothing is written."""
+        f = self.engine.weight_factors()
+        if f is not None:
+            torch.save({name: torch.cat([a.detach().reshape(-1) for a in layers]).cpu() for name, layers in f.items()},
+                       path + '_rwf')
+
+    def load(self, path, path_evm=None):
+        """Load a checkpoint written by save(): the main net's state_dict at `path` and, for the ev class, the entropy
+        net's at path_evm (default <path>_evm when that file exists).  When the sidecar <path>_rwf is present the
+        weight factorization is turned on with its scale factors (the effective weights are the checkpoint's exactly);
+        without it the factorization state of this solver is left as it is."""
+        self.net.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+        net_1 = getattr(self, "net_1", None)
+        if net_1 is not None:
+            if path_evm is None and os.path.exists(path + '_evm'):
+                path_evm = path + '_evm'
+            if path_evm is not None:
+                net_1.load_state_dict(torch.load(path_evm, map_location="cpu", weights_only=True))
+        if os.path.exists(path + '_rwf'):
+            self.engine.set_weight_factorization(factors=torch.load(path + '_rwf', map_location="cpu", weights_only=True))
+
     def _begin_adam_stage(self, scheduler):
         """Resolve solve_Adam's scheduler= argument.  An LrSchedule, or a torch.optim.lr_scheduler object of type
         MultiStepLR, StepLR, ExponentialLR or CosineAnnealingLR (translated once, from its own attributes), becomes
@@ -427,6 +458,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         save_results_to = directory + relative_path
         os.makedirs(save_results_to, exist_ok=True)
         torch.save(self.net.state_dict(), save_results_to + filename)
+        self.save_weight_factors(save_results_to + filename)
         save_matlab_to = directory + '/loss/'
         os.makedirs(save_matlab_to, exist_ok=True)
         if getattr(self, "loss_eq1", None) is not None:

@@ -60,6 +60,12 @@ def main():
     ap.add_argument("--warmup-epochs", type=int, default=0, help="linear warm-up, epochs at full scale")
     ap.add_argument("--warmup-start", type=float, default=0.0)
     ap.add_argument("--grad-clip", type=float, default=0.0, help="max global gradient norm of an Adam update (0: off)")
+    ap.add_argument("--rwf", action="store_true",
+                    help="random weight factorization W = diag(exp(s)) V of every layer of both nets (DESIGN.md 7.7); a "
+                         "resumed slice takes up the net.pth_rwf the previous one wrote")
+    ap.add_argument("--rwf-mean", type=float, default=0.5)
+    ap.add_argument("--rwf-std", type=float, default=0.1)
+    ap.add_argument("--rwf-seed", type=int, default=0)
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     from nsfnet_amd.schedule import LrSchedule
@@ -98,6 +104,12 @@ def main():
         P.set_residual_attention(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init)
     if a.grad_clip > 0:
         P.set_grad_clipping(a.grad_clip)
+    if a.rwf:
+        side = None if res is None else os.path.join(res, "net.pth_rwf")
+        if side is not None and os.path.exists(side):       # carry the trained scale factors across slices
+            P.set_weight_factorization(factors=torch.load(side, map_location="cpu", weights_only=True))
+        else:
+            P.set_weight_factorization(mean=a.rwf_mean, std=a.rwf_std, seed=a.rwf_seed)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     for k in range(a.first, a.last + 1):
@@ -137,6 +149,7 @@ def main():
         print("STAGE", json.dumps(rec), flush=True)
         torch.save(P.net.state_dict(), "net.pth")
         torch.save(P.net_1.state_dict(), "net_evm.pth")
+        P.save_weight_factors("net.pth")                 # net.pth_rwf with --rwf, nothing without
 
 
 if __name__ == "__main__":
