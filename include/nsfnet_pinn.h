@@ -257,6 +257,44 @@ int pinn_balance_update(const double* partials, int64_t n, int terms, double bet
 int pinn_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, int64_t n,
                          void* stream);
 
+/* ---- conflict-free combination of the per-term gradients --------------------------------
+ * No reference counterpart: ConFIG (Liu, Chu & Thuerey, "ConFIG: Towards Conflict-free Training of Physics Informed
+ * Neural Networks", ICLR 2025), the stateless alternative to the balancing above.  With g_t the global gradient of
+ * loss term t of the main net's P parameters, weights baked in (r = alpha_e L_e, b = alpha_b L_b, s = alpha_s L_s;
+ * m = 2 terms, or 3 with the supervised loss), the gradient Adam consumes is the one with equal positive projection
+ * on every term's unit gradient, its length the sum of the terms' projections on it:
+ *   A_ij = g_i . g_j    n_t = sqrt(A_tt)    M_ij = A_ij / (n_i n_j)    solve M c = 1
+ *   k_t = (sum_i n_i / sum_i c_i) c_t / n_t                           g = sum_t k_t g_t
+ * (two terms: k_t = (n_r + n_b) / (2 n_t)).  There is no state besides counters.  Guards, decided on the device:
+ * a term with n_t = 0 leaves the set (one term left: g is that term, k = 1; none: g = 0, k = 0); a non-finite Gram
+ * entry, det(M) <= 1e-10, sum c <= 0 or a non-finite c_t make the step fall back to the plain sum k = (1, 1, 1),
+ * which is the gradient without this feature.  All sums are fp64 in a fixed order, no float atomics: the results
+ * are bit-reproducible, and ranks that hold the same vectors compute the same coefficients.
+ *
+ * Statistics travel in per-block partials: for every block b of 64 consecutive parameters, partials[6 b + 0..5] =
+ * the dot products rr, bb, ss, rb, rs, bs over the block (exact fp64 products of the fp32 entries).  Doubles of
+ * partials for n parameters (= pinn_balance_partials_count; -1: n outside 1..2^30): */
+int64_t pinn_confgrad_partials_count(int64_t n);
+/* pinn_grad_reduce_terms that also writes the Gram partials of the three vectors it wrote (an unwritten group counts
+ * as zeros) to gram_partials (device, or NULL: exactly pinn_grad_reduce_terms).  One launch either way. */
+int pinn_grad_reduce_terms_gram(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                                float* const* out3, int accumulate_mask, double* partials, double* gram_partials,
+                                void* stream);
+/* The Gram partials of three device vectors of n entries (vec3: host array of 3 device pointers; NULL = zeros). */
+int pinn_confgrad_gram(const float* const* vec3, int64_t n, double* partials, void* stream);
+/* The coefficients from the partials of n parameters (one workgroup).  nterms: 2 (r, b) or 3 (r, b, s).  coef
+ * (device, 3 floats) receives (float) k_r, k_b, k_s.  record: PINN_CONFGRAD_RECORD doubles (device),
+ *   [0] n_r [1] n_b [2] n_s   [3] cos_rb [4] cos_rs [5] cos_bs (0 for a pair outside the set)   [6] k_r [7] k_b [8] k_s
+ *   [9] |g| = sum n / sqrt(sum c) (fallback: the norm of the plain sum)
+ *   [10] steps made   [11] fallbacks   [12] terms dropped for a zero norm (counted per step and term);
+ * [0..9] are overwritten, [10..12] accumulate: the caller zeroes them to start. */
+#define PINN_CONFGRAD_RECORD 13
+int pinn_confgrad_coef(const double* partials, int64_t n, int nterms, float* coef, double* record, void* stream);
+/* g = coef[0] g_r + coef[1] g_b + coef[2] g_s: one fp32 product, then fp32 fused multiply-adds in that order (gs
+ * NULL: no supervised term).  g may be g_r. */
+int pinn_confgrad_combine(float* g, const float* gr, const float* gb, const float* gs, const float* coef, int64_t n,
+                          void* stream);
+
 /* ---- stochastic mini-batching of the collocation term ---------------------------------
  * No reference counterpart (its roadmap asks for "mini-batch PDE points", ev-NSFnet/README.md; its `batchsize`
  * argument is dead).  A store of n collocation points (x, y, optional weights w, optional lagged state vis_t_minus)

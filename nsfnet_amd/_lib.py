@@ -61,6 +61,13 @@ SIGNATURES = {
     "pinn_balance_stats": (c_int, [ctypes.POINTER(c_void_p), c_int64, c_void_p, c_void_p]),
     "pinn_balance_update": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "pinn_balance_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pinn_confgrad_partials_count": (c_int64, [c_int64]),
+    "pinn_grad_reduce_terms_gram": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_void_p),
+                                            ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p,
+                                            c_void_p]),
+    "pinn_confgrad_gram": (c_int, [ctypes.POINTER(c_void_p), c_int64, c_void_p, c_void_p]),
+    "pinn_confgrad_coef": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "pinn_confgrad_combine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pinn_batch_draw": (c_int, [c_int64, c_int64, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_batch_scatter": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -3,7 +3,8 @@
 // atomics, so every result is bit-reproducible and ranks that hold the same vectors compute the same weights:
 //   reduce_terms_kernel    the gradient assembly of misc.hip with the sources split into the collocation, boundary
 //                          and supervised groups, one fp32 vector per group, optionally with per-workgroup
-//                          max|g| / sum|g| partials of what it wrote
+//                          max|g| / sum|g| partials of what it wrote (and, on request, the Gram partials of
+//                          confgrad.hip)
 //   balance_stats_kernel   the same partials of three given vectors (multi-rank: after the all-reduce)
 //   balance_update_kernel  one workgroup: partials -> max|g_r|, mean|g_t| -> lambda_hat_t -> lambda_t
 //   balance_combine_kernel g = g_r + lambda_b g_b + lambda_s g_s with the weights read from device memory
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
   }
   __syncthreads();
   if (w != 0) return;
+  float vt[3];
   for (int t = 0; t < 3; ++t) {
     float v = 0.f;
     if (a.out[t] && live) {
@@ -66,7 +68,9 @@ __global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
         a.partials[(size_t)blockIdx.x * 6 + 2 * t + 1] = sm;
       }
     }
+    vt[t] = v;
   }
+  if (a.gram) wave_gram(vt[0], vt[1], vt[2], lane, a.gram + (size_t)blockIdx.x * 6);   // confgrad.hip's statistics
 }
 
 __global__ __launch_bounds__(64) void balance_stats_kernel(const float* __restrict__ v0, const float* __restrict__ v1,

@@ -688,25 +688,37 @@ int64_t pinn_balance_partials_count(int64_t n) {
   return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)balance_blocks((long)n) * 6;
 }
 
-int pinn_grad_reduce_terms(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
-                           float* const* out3, int accumulate_mask, double* partials, void* stream) {
-  if (!net || !nsrc3 || !out3) return fail(-22, "pinn_grad_reduce_terms: null argument%s");
+static int reduce_terms(const char* what, pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                        float* const* out3, int accumulate_mask, double* partials, double* gram, void* stream) {
+  if (!net || !nsrc3 || !out3) return fail(-22, "%s: null argument", what);
   TermReduceArgs r;
   memset(&r, 0, sizeof(r));
   int total = 0;
   for (int t = 0; t < 3; ++t) {
-    if (nsrc3[t] < 0) return fail(-22, "pinn_grad_reduce_terms: negative source count%s");
-    if (nsrc3[t] > 0 && !out3[t]) return fail(-22, "pinn_grad_reduce_terms: a group with sources needs its output%s");
+    if (nsrc3[t] < 0) return fail(-22, "%s: negative source count", what);
+    if (nsrc3[t] > 0 && !out3[t]) return fail(-22, "%s: a group with sources needs its output", what);
     r.nsrc[t] = nsrc3[t]; r.out[t] = out3[t];
     total += nsrc3[t];
   }
-  if (total < 1 || total > 4) return fail(-22, "pinn_grad_reduce_terms: 1..4 sources in all%s");
-  if (!plans || !wss) return fail(-22, "pinn_grad_reduce_terms: null argument%s");
+  if (total < 1 || total > 4) return fail(-22, "%s: 1..4 sources in all", what);
+  if (!plans || !wss) return fail(-22, "%s: null argument", what);
   r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
-  r.acc_mask = accumulate_mask & 7; r.partials = partials;
-  if (int rc = reduce_sources("pinn_grad_reduce_terms", net, total, plans, wss, r.src)) return rc;
+  r.acc_mask = accumulate_mask & 7; r.partials = partials; r.gram = gram;
+  if (int rc = reduce_sources(what, net, total, plans, wss, r.src)) return rc;
   int rc = launch_reduce_terms(r, (hipStream_t)stream);
-  return rc ? hipfail(rc, "pinn_grad_reduce_terms") : 0;
+  return rc ? hipfail(rc, what) : 0;
+}
+
+int pinn_grad_reduce_terms(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                           float* const* out3, int accumulate_mask, double* partials, void* stream) {
+  return reduce_terms("pinn_grad_reduce_terms", net, nsrc3, plans, wss, out3, accumulate_mask, partials, nullptr, stream);
+}
+
+int pinn_grad_reduce_terms_gram(pinn_net_t net, const int* nsrc3, const pinn_plan_t* plans, void* const* wss,
+                                float* const* out3, int accumulate_mask, double* partials, double* gram_partials,
+                                void* stream) {
+  return reduce_terms("pinn_grad_reduce_terms_gram", net, nsrc3, plans, wss, out3, accumulate_mask, partials,
+                      gram_partials, stream);
 }
 
 int pinn_balance_stats(const float* const* vec3, int64_t n, double* partials, void* stream) {
@@ -734,6 +746,30 @@ int pinn_balance_combine(float* g, const float* gr, const float* gb, const float
   return rc ? hipfail(rc, "pinn_balance_combine") : 0;
 }
 
+int64_t pinn_confgrad_partials_count(int64_t n) { return pinn_balance_partials_count(n); }
+
+int pinn_confgrad_gram(const float* const* vec3, int64_t n, double* partials, void* stream) {
+  if (!vec3 || !partials) return fail(-22, "pinn_confgrad_gram: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_confgrad_gram: n must be 1..2^30%s");
+  int rc = launch_confgrad_gram(vec3[0], vec3[1], vec3[2], (long)n, partials, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_confgrad_gram") : 0;
+}
+
+int pinn_confgrad_coef(const double* partials, int64_t n, int nterms, float* coef, double* record, void* stream) {
+  if (!partials || !coef || !record) return fail(-22, "pinn_confgrad_coef: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_confgrad_coef: n must be 1..2^30%s");
+  if (nterms < 2 || nterms > 3) return fail(-22, "pinn_confgrad_coef: nterms must be 2 or 3%s");
+  int rc = launch_confgrad_coef(partials, (long)n, nterms, coef, record, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_confgrad_coef") : 0;
+}
+
+int pinn_confgrad_combine(float* g, const float* gr, const float* gb, const float* gs, const float* coef, int64_t n,
+                          void* stream) {
+  if (!g || !gr || !gb || !coef) return fail(-22, "pinn_confgrad_combine: null argument%s");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_confgrad_combine: n must be 1..2^30%s");
+  int rc = launch_confgrad_combine(g, gr, gb, gs, coef, (long)n, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_confgrad_combine") : 0;
+}
 
 int pinn_batch_draw(int64_t n, int64_t b, uint64_t seed, int rank, int64_t* counter,
                     const float* src_x, const float* src_y, const float* src_w, const float* src_vtm,

@@ -155,12 +155,32 @@ __device__ __forceinline__ double reduce_source_add(double s, const ReduceSrc& s
 // 0); nsrc[t] == 0 with out[t] given writes zeros (or leaves out[t] as it is where accumulating).  acc_mask bit t: add
 // to out[t].  partials != nullptr: per workgroup b, partials[6 b + 2 t] = max|out[t]| (NaN-propagating) and
 // [6 b + 2 t + 1] = sum|out[t]| in fp64 over its 64 parameters, of the values written (0 for an unwritten group).
+// gram != nullptr (confgrad.hip): per workgroup b, gram[6 b + c] = the fp64 dot products rr, bb, ss, rb, rs, bs over
+// its 64 parameters of the values written (r, b, s = out[0..2]; 0 for an unwritten group).
 struct TermReduceArgs {
   ReduceSrc src[4]; int nsrc[3];
   int H, HP, L, n_out;
   float* out[3]; int acc_mask;
   double* partials;
+  double* gram;
 };
+
+// The six dot products of the 64 (r, b, s) a full wave holds, one triple per lane: exact fp64 products of the fp32
+// values, summed in the fixed butterfly order of balance.hip's wave_abs_stats; lane 0 writes out[0..5] = rr bb ss rb rs bs.
+__device__ __forceinline__ void wave_gram(float r, float b, float s, int lane, double* __restrict__ out) {
+  const double dr = r, db = b, ds = s;
+  double q[6] = {__dmul_rn(dr, dr), __dmul_rn(db, db), __dmul_rn(ds, ds),
+                 __dmul_rn(dr, db), __dmul_rn(dr, ds), __dmul_rn(db, ds)};
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) q[c] = __dadd_rn(q[c], __shfl_down(q[c], off, 64));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) out[c] = q[c];
+  }
+}
 
 int launch_fwd(int HP, int NS, const FwdArgs& a, int grid, hipStream_t s);
 int launch_bwd(int HP, int NS, const BwdArgs& a, int grid, hipStream_t s);
@@ -239,6 +259,11 @@ int launch_balance_update(const double* partials, long n, int terms, double beta
                           hipStream_t s);
 int launch_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, long n,
                            hipStream_t s);
+// conflict-free combination of the per-term gradients (confgrad.hip); partials: balance_blocks(n) * 6 doubles
+int launch_confgrad_gram(const float* v0, const float* v1, const float* v2, long n, double* partials, hipStream_t s);
+int launch_confgrad_coef(const double* partials, long n, int nterms, float* coef, double* record, hipStream_t s);
+int launch_confgrad_combine(float* g, const float* gr, const float* gb, const float* gs, const float* coef, long n,
+                            hipStream_t s);
 // stochastic mini-batching of the collocation term (batch.hip)
 struct BatchDrawArgs {
   long n, b;                               // store points, batch points (1 <= b <= n)

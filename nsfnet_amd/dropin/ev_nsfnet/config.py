@@ -86,6 +86,13 @@ class LossBalancingConfig:
 
 
 @dataclass
+class ConflictFreeGradientsConfig:
+    """Conflict-free combination of the per-term gradients, ConFIG (PinnEngine.set_conflict_free_gradients), off by
+    default.  Not together with loss_balancing; an L-BFGS stage uses the plain sum."""
+    enabled: bool = False
+
+
+@dataclass
 class BatchingConfig:
     """Stochastic mini-batching of the collocation term (PinnEngine.set_batching), off by default.  batch_points is
     per rank; an L-BFGS stage ignores it."""
@@ -142,6 +149,7 @@ class TrainingConfig:
     coordinate_transform: bool = False
     resampling: ResamplingConfig = field(default_factory=ResamplingConfig)
     loss_balancing: LossBalancingConfig = field(default_factory=LossBalancingConfig)
+    conflict_free_gradients: ConflictFreeGradientsConfig = field(default_factory=ConflictFreeGradientsConfig)
     batching: BatchingConfig = field(default_factory=BatchingConfig)
     residual_attention: ResidualAttentionConfig = field(default_factory=ResidualAttentionConfig)
     grad_clip: GradClipConfig = field(default_factory=GradClipConfig)
@@ -217,6 +225,9 @@ class ConfigManager:
         lb = c.training.loss_balancing
         if lb.enabled and (lb.every < 1 or not 0.0 < lb.beta <= 1.0):
             problems.append("training.loss_balancing: every >= 1 and 0 < beta <= 1 required")
+        if lb.enabled and c.training.conflict_free_gradients.enabled:
+            problems.append("training.conflict_free_gradients and training.loss_balancing both decide how the term "
+                            "gradients are combined: enable one of them")
         bt = c.training.batching
         if bt.enabled and (bt.batch_points < 1 or bt.seed < 0):
             problems.append("training.batching: batch_points >= 1 and seed >= 0 required")
@@ -276,6 +287,8 @@ class ConfigManager:
                   % (t.resampling.every, t.resampling.pool_points, t.resampling.k, t.resampling.c, t.resampling.seed))
         if t.loss_balancing.enabled:
             print("balancing  : every=%d beta=%s" % (t.loss_balancing.every, t.loss_balancing.beta))
+        if t.conflict_free_gradients.enabled:
+            print("conflict-free gradients: on (ConFIG)")
         if t.batching.enabled:
             print("batching   : batch_points=%d (per rank) seed=%d" % (t.batching.batch_points, t.batching.seed))
         if t.residual_attention.eta > 0:

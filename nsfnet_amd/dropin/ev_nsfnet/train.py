@@ -124,6 +124,8 @@ def main():
         lb = cfg.training.loss_balancing
         if lb.enabled:    # after the supervised weight: the balanced weights start at the configured ones
             PINN.set_loss_balancing(every=lb.every, beta=lb.beta)
+        if cfg.training.conflict_free_gradients.enabled:    # the term gradients combined by the ConFIG rule
+            PINN.set_conflict_free_gradients(True)
         bt = cfg.training.batching
         if bt.enabled:    # the collocation set is in place: it becomes the store the batches are drawn from
             PINN.set_batching(batch_points=bt.batch_points, seed=bt.seed)

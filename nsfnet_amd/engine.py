@@ -446,10 +446,12 @@ def grad_reduce(net, plans, grads_out, accumulate=False):
                "pinn_grad_reduce")
 
 
-def grad_reduce_terms(net, groups, outs, acc_mask=0, partials=None):
+def grad_reduce_terms(net, groups, outs, acc_mask=0, partials=None, gram=None):
     """pinn_grad_reduce_terms: groups = three lists of plans (collocation, boundary, supervised), outs = three output
     vectors (None: group not written; a written group without plans gets zeros).  acc_mask bit t: add to outs[t].
-    partials: fp64 device tensor of balance_partials_count(P) entries for the max|g| / sum|g| block partials."""
+    partials: fp64 device tensor of balance_partials_count(P) entries for the max|g| / sum|g| block partials.
+    gram: fp64 device tensor of confgrad_partials(P) entries for the Gram block partials
+    (pinn_grad_reduce_terms_gram, the same single launch)."""
     lib = net.lib
     plans = [p for grp in groups for p in grp]
     n = len(plans)
@@ -457,6 +459,10 @@ def grad_reduce_terms(net, groups, outs, acc_mask=0, partials=None):
     ph = (ctypes.c_void_p * max(n, 1))(*[p.handle.value for p in plans])
     wh = (ctypes.c_void_p * max(n, 1))(*[p.ws.data_ptr() for p in plans])
     out = (ctypes.c_void_p * 3)(*[0 if o is None else o.data_ptr() for o in outs])
+    if gram is not None:
+        _lib.check(lib.pinn_grad_reduce_terms_gram(net.handle, ns, ph, wh, out, int(acc_mask), _ptr(partials),
+                                                   _ptr(gram), _stream()), "pinn_grad_reduce_terms_gram")
+        return
     _lib.check(lib.pinn_grad_reduce_terms(net.handle, ns, ph, wh, out, int(acc_mask), _ptr(partials), _stream()),
                "pinn_grad_reduce_terms")
 
@@ -488,6 +494,36 @@ def balance_combine(g, gr, gb, gs, lam):
 
 
 BALANCE_RECORD = 12      # PINN_BALANCE_RECORD
+
+
+def confgrad_partials(n, device):
+    """Zeroed fp64 device tensor for the Gram block partials of n parameters."""
+    count = int(_lib.load().pinn_confgrad_partials_count(int(n)))
+    if count < 0:
+        raise ValueError("bad parameter count %d" % n)
+    return torch.zeros(count, dtype=torch.float64, device=device)
+
+
+def confgrad_gram(vecs, n, partials):
+    """Gram block partials rr, bb, ss, rb, rs, bs of three vectors (None = zeros): pinn_confgrad_gram."""
+    v = (ctypes.c_void_p * 3)(*[0 if t is None else t.data_ptr() for t in vecs])
+    _lib.check(_lib.load().pinn_confgrad_gram(v, int(n), _ptr(partials), _stream()), "pinn_confgrad_gram")
+
+
+def confgrad_coef(partials, n, nterms, coef, record):
+    """The ConFIG coefficients of nterms (2 or 3) terms on the device (pinn_confgrad_coef): coef [3] fp32 is
+    written, record is updated in place."""
+    _lib.check(_lib.load().pinn_confgrad_coef(_ptr(partials), int(n), int(nterms), _ptr(coef), _ptr(record), _stream()),
+               "pinn_confgrad_coef")
+
+
+def confgrad_combine(g, gr, gb, gs, coef):
+    """g = coef[0] g_r + coef[1] g_b + coef[2] g_s (gs None: no supervised term): pinn_confgrad_combine."""
+    _lib.check(_lib.load().pinn_confgrad_combine(_ptr(g), _ptr(gr), _ptr(gb), _ptr(gs), _ptr(coef), g.numel(),
+                                                 _stream()), "pinn_confgrad_combine")
+
+
+CONFGRAD_RECORD = 13     # PINN_CONFGRAD_RECORD
 
 
 def batch_draw(store, batch, idx, n, b, seed, rank, counter):
@@ -644,6 +680,15 @@ class _Balance:
         self.buf = self.gb = self.gs = self.lam = self.rec = self.parts = None
 
 
+class _ConflictFree:
+    """Device tensors of the conflict-free gradient combination (set_conflict_free_gradients): buf / gb / gs (the
+    exchange buffer with the term vectors behind it), parts (Gram block partials), coef [3] fp32 and rec
+    [CONFGRAD_RECORD] fp64 (the statistics of the last step and the counters)."""
+
+    def __init__(self):
+        self.buf = self.gb = self.gs = self.parts = self.coef = self.rec = None
+
+
 class _Batching:
     """State of the stochastic mini-batching (set_batching): the batch plan f of B points (and, ev flavour, the
     entropy net's plan e on the same x / y buffers), the device index vector idx [B] int64 and the device draw
@@ -731,6 +776,8 @@ class PinnEngine:
         self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
         self._bal = None                    # adaptive loss-weight balancing (set_loss_balancing; None = off)
         self._bal_frozen = False            # lbfgs_step: the weights are held fixed
+        self._cfg = None                    # conflict-free combination (set_conflict_free_gradients; None = off)
+        self._cfg_frozen = False            # lbfgs_step: the plain sum, the gradient of the objective
         self._batch = None                  # stochastic mini-batching (set_batching; None = off)
         self._batch_frozen = False          # lbfgs_step: the full objective, i.e. the store
         self._eval_batch = False            # the last evaluation ran on the batch plan (loss_terms' normalisation)
@@ -1104,6 +1151,9 @@ class PinnEngine:
             raise ValueError("loss balancing: every must be >= 0")
         if every > 0 and not (0.0 < beta <= 1.0):
             raise ValueError("loss balancing: beta must be in (0, 1]")
+        if every > 0 and self._cfg is not None:
+            raise ValueError("loss balancing and conflict-free gradients both decide how the term gradients are "
+                             "combined: switch set_conflict_free_gradients off first")
         self._graphs.clear()        # captured steps hold the seeds and buffers of the other mode
         if every == 0:
             self._bal = None
@@ -1153,6 +1203,53 @@ class PinnEngine:
     def _sup_on(self):
         return self.n_s_global > 0 and self.alpha_s != 0.0
 
+    # ---- conflict-free combination of the per-term gradients ----
+    def set_conflict_free_gradients(self, enabled=True):
+        """enabled: every evaluation on the Adam path combines the global per-term gradients g_r (collocation), g_b
+        (boundary) and - with the supervised loss active - g_s by the ConFIG rule (Liu, Chu & Thuerey 2025): the
+        direction with equal positive projection on every term's unit gradient, as long as the sum of the terms'
+        projections on it; for two terms g = (|g_r| + |g_b|) / 2 (g_r / |g_r| + g_b / |g_b|).  The terms keep the
+        configured alpha_e, alpha_b and alpha_s; the rule has no state, so no weight can drift, and loss_terms() stays
+        the alpha-weighted sum.  Per step and rank this is the term-split assembly (which also writes the Gram
+        statistics), a one-workgroup coefficient kernel and a combine; several ranks all-reduce the term vectors
+        [grads | grads_e | sums | g_b (| g_s)] in one message every step, since the rule is not linear.  Parallel,
+        anti-parallel or non-finite terms fall back to the plain sum (conflict_info() counts them).  lbfgs_step
+        evaluates with the plain sum: the combined direction is not the gradient of an objective.  Not together with
+        set_loss_balancing or the L2 loss mode.  Off (the default): the step launches what it launches without the
+        feature.  A call restarts the counters."""
+        if enabled and self._bal is not None:
+            raise ValueError("conflict-free gradients and loss balancing both decide how the term gradients are "
+                             "combined: switch set_loss_balancing off first")
+        self._graphs.clear()        # captured steps hold the launches and buffers of the other mode
+        if not enabled:
+            self._cfg = None
+            return
+        c = _ConflictFree()
+        n_ex = self.P + self.P1 + NSUMS
+        # one buffer [grads | grads_e | sums | g_b | g_s]: several ranks all-reduce its used prefix in one message
+        c.buf = torch.zeros(n_ex + 2 * self.P, dtype=torch.float32, device=self.device)
+        c.buf[:n_ex].copy_(self.flat)
+        self.flat = c.buf[:n_ex]
+        c.gb, c.gs = c.buf[n_ex:n_ex + self.P], c.buf[n_ex + self.P:]
+        c.coef = torch.ones(3, dtype=torch.float32, device=self.device)
+        c.rec = torch.zeros(CONFGRAD_RECORD, dtype=torch.float64, device=self.device)
+        c.parts = confgrad_partials(self.P, self.device)
+        self._cfg = c
+
+    def conflict_info(self):
+        """The device record of the last conflict-free combination (one host read), or None when the feature is
+        off: the term norms n_*, their cosines, the coefficients k_* of g = sum k_t g_t, |g|, and the counters
+        steps, fallbacks (plain-sum steps) and dropped (zero-norm terms left out)."""
+        c = self._cfg
+        if c is None:
+            return None
+        names = ("n_r", "n_b", "n_s", "cos_rb", "cos_rs", "cos_bs", "k_r", "k_b", "k_s", "norm", "steps", "fallbacks",
+                 "dropped")
+        out = dict(zip(names, c.rec.cpu().tolist()))
+        for k in ("steps", "fallbacks", "dropped"):
+            out[k] = int(out[k])
+        return out
+
     def _reduce_terms(self, r_plans, b, s, acc_r, update):
         """Term-split gradient assembly: g_r into grads, g_b / g_s into the balancing buffer (the partials on a
         single-rank balance step, where the local vectors are the global ones)."""
@@ -1173,6 +1270,8 @@ class PinnEngine:
         l2 = mode == "L2"
         if l2 and self._bal is not None:
             raise ValueError("loss balancing needs the MSE loss (loss mode %r)" % mode)
+        if l2 and self._cfg is not None:
+            raise ValueError("conflict-free gradients need the MSE loss (loss mode %r)" % mode)
         if l2 and self._batch is not None:
             raise ValueError("mini-batching needs the MSE loss (loss mode %r)" % mode)
         if l2 and self._rba is not None:
@@ -1193,6 +1292,7 @@ class PinnEngine:
         bt = self._batch if self._batching_on() else None
         self._eval_batch = bt is not None
         bal = self._bal
+        cfg = None if self._cfg_frozen else self._cfg     # conflict-free combination (never together with bal)
         sums = self.sums
         sup_on = self._sup_on()
         s = self.plan_s if sup_on else None             # None also on a rank whose supervised share is empty
@@ -1268,7 +1368,7 @@ class PinnEngine:
             if many:
                 eq_sums += f.tmp_sums
             if k < len(passes) - 1:
-                if bal is None:
+                if bal is None and cfg is None:
                     grad_reduce(self.net, [p], self.grads, accumulate=k > 0)
                 else:
                     grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
@@ -1279,7 +1379,13 @@ class PinnEngine:
         if side is not None:
             main.wait_stream(side)
         last = passes[-1][1]
-        if bal is None:
+        if cfg is not None:
+            # g_r into grads, alpha_b g_b / alpha_s g_s behind the exchange buffer; one rank: the local vectors are the
+            # global ones and the assembly writes their Gram partials too
+            grad_reduce_terms(self.net, [[last], [b], [] if s is None else [s]],
+                              [self.grads, cfg.gb, cfg.gs if sup_on else None], acc_mask=1 if many else 0,
+                              gram=cfg.parts if self.world_size == 1 else None)
+        elif bal is None:
             grad_reduce(self.net, [last, b] + ([] if s is None else [s]), self.grads, accumulate=many)
         else:
             self._reduce_terms([last], b, s, many, update)
@@ -1289,6 +1395,17 @@ class PinnEngine:
                 grad_reduce(self.net_e, [plan_e], self.grads_e)
             else:
                 self.grads_e.zero_()
+        if cfg is not None:
+            gs = cfg.gs if sup_on else None
+            if self.world_size > 1:
+                # the rule is not linear: it needs the global term vectors, [grads (= g_r) | grads_e | sums | g_b
+                # (| g_s)] in one message; then every rank computes the same partials, coefficients and combine
+                n = self.flat.numel() + self.P * (2 if sup_on else 1)
+                torch.distributed.all_reduce(cfg.buf[:n], group=self.pg)
+                confgrad_gram([self.grads, cfg.gb, gs], self.P, cfg.parts)
+            confgrad_coef(cfg.parts, self.P, 3 if sup_on else 2, cfg.coef, cfg.rec)
+            confgrad_combine(self.grads, self.grads, cfg.gb, gs, cfg.coef)
+            return
         if bal is None:
             if self.world_size > 1:
                 torch.distributed.all_reduce(self.flat, group=self.pg)
@@ -1485,9 +1602,9 @@ class PinnEngine:
     def set_grad_clipping(self, max_norm=0.0):
         """max_norm > 0: before every Adam update the gradient is scaled by min(1, max_norm / (||g|| + 1e-6)), the
         formula of torch.nn.utils.clip_grad_norm_, with ||g|| the 2-norm over all trainable nets of the gradient Adam
-        is about to consume (after the all-reduce and the loss-balancing combine; every rank computes the same
-        value).  One more launch per step, a fixed-order fp64 sum; the scaling happens inside the update, so `grads`
-        stays the raw gradient.  A non-finite norm propagates into the parameters, as in torch.  0: off."""
+        is about to consume (after the all-reduce and the loss-balancing or conflict-free combine; every rank computes
+        the same value).  One more launch per step, a fixed-order fp64 sum; the scaling happens inside the update, so
+        `grads` stays the raw gradient.  A non-finite norm propagates into the parameters, as in torch.  0: off."""
         max_norm = float(max_norm)
         if not (max_norm >= 0.0 and math.isfinite(max_norm)):
             raise ValueError("gradient clipping: max_norm must be finite and >= 0")
@@ -1538,6 +1655,7 @@ class PinnEngine:
             self.e_trainable = False
             self.init_vis_t()
         self._bal_frozen = True             # the objective uses the current loss weights throughout
+        self._cfg_frozen = True             # ... and its own gradient: the plain sum of the terms
         self._batch_frozen = True           # ... and the whole store
         self._rba_frozen = True             # ... and the current attention weights
         try:
@@ -1547,6 +1665,7 @@ class PinnEngine:
         finally:
             self.e_trainable = e_trainable
             self._bal_frozen = False
+            self._cfg_frozen = False
             self._batch_frozen = False
             self._rba_frozen = False
         self.lbfgs_info = info
@@ -1571,6 +1690,8 @@ class PinnEngine:
             key += (self._opt.spec.key(), self._opt.max_norm)
         if self._rwf is not None:
             key += ("rwf",)
+        if self._cfg is not None:
+            key += ("confgrad",)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the

@@ -396,6 +396,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))
         if self.engine._opt is not None:
             print('  ' + self._optimizer_log())
+        if self._confgrad:
+            print('  ' + self._confgrad_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]

@@ -59,6 +59,7 @@ class SolverBase:
     """What the plain and the ev drop-in classes share: the knobs of the features the reference does not have
     (resampling, loss balancing) and the methods whose bodies are the same in both reference classes."""
     _balancing = False
+    _confgrad = False
     _batching = False
     _attention = False
     _lr_schedule = None         # set_lr_schedule: the LrSchedule of every Adam stage without a scheduler= of its own
@@ -83,6 +84,21 @@ class SolverBase:
         the checkpoint directory); the weight in use is lam_b().  every = 0: off."""
         self.engine.set_loss_balancing(every, beta)
         self._balancing = int(every) > 0
+
+    def set_conflict_free_gradients(self, enabled=True):
+        """enabled: every Adam update combines the per-term gradients (equations, boundary, supervised) by the ConFIG
+        rule - equal positive projection on every term's unit gradient - instead of adding them
+        (PinnEngine.set_conflict_free_gradients).  The configured weights stay in the terms and
+        in the logged loss; print_log adds the term norms, their cosine and the coefficients.  An L-BFGS stage uses the
+        plain sum.  Not together with set_loss_balancing.  False: off."""
+        self.engine.set_conflict_free_gradients(enabled)
+        self._confgrad = bool(enabled)
+
+    def _confgrad_log(self):
+        """The print_log suffix of the conflict-free combination (one host read, at log points only)."""
+        i = self.engine.conflict_info()
+        return "conflict-free: |g_r|=%.3e |g_b|=%.3e |g_s|=%.3e cos_rb=%+.3f k=(%.3e, %.3e, %.3e) fallbacks=%d/%d" % (
+            i["n_r"], i["n_b"], i["n_s"], i["cos_rb"], i["k_r"], i["k_b"], i["k_s"], i["fallbacks"], i["steps"])
 
     def set_batching(self, batch_points=0, seed=0):
         """batch_points = B > 0: every Adam update evaluates the collocation term on a fresh random batch of B of this
@@ -411,6 +427,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("(losses of the last batch of %d points)" % self.engine.batch_info()["batch_points"],)
                 if self._batching and self.engine.evaluated_batch else ()),
               *(("\n" + self._attention_log(),) if self._attention else ()),
+              *(("\n" + self._confgrad_log(),) if self._confgrad else ()),
               *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()))
 
     # ---------------------------------------------------------------- evaluation / io

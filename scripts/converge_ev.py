@@ -11,6 +11,7 @@ viscosity state restarts from alpha*|e| as at the start of a run).
         --out gpurun_out/conv_ev --first 1 --last 2 [--resume DIR] [--epochs-scale 0.5]
         [--resample-every 5000 --pool 1000000 --rs-k 1 --rs-c 1]   (residual-based resampling, off by default)
         [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call)
+        [--confgrad]   (conflict-free combination of the per-term gradients, off by default; stateless)
         [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call)
         [--rba-eta 0.01 --rba-gamma 0.999]   (residual-based attention weights, off by default; lam restarts per call)
         [--scheduler cosine --eta-min-factor 0.01 --warmup-epochs 1000]   (device learning-rate schedule of every stage,
@@ -46,6 +47,8 @@ def main():
     ap.add_argument("--rs-seed", type=int, default=0)
     ap.add_argument("--balance-every", type=int, default=0, help="adaptive loss-weight balancing cadence (0: off)")
     ap.add_argument("--balance-beta", type=float, default=0.1)
+    ap.add_argument("--confgrad", action="store_true",
+                    help="conflict-free combination of the per-term gradients, ConFIG (DESIGN.md 7.8); not with --balance-every")
     ap.add_argument("--batch-points", type=int, default=0, help="stochastic mini-batching: points per Adam update (0: off)")
     ap.add_argument("--batch-seed", type=int, default=0)
     ap.add_argument("--rba-eta", type=float, default=0.0, help="residual-based attention: eta (0: off; DESIGN.md 7.5)")
@@ -98,6 +101,8 @@ def main():
     P.clear_supervised_data(); P.set_supervised_loss_weight(0.0)
     if a.balance_every > 0:
         P.set_loss_balancing(every=a.balance_every, beta=a.balance_beta)
+    if a.confgrad:
+        P.set_conflict_free_gradients(True)
     if a.batch_points > 0:
         P.set_batching(batch_points=a.batch_points, seed=a.batch_seed)
     if a.rba_eta > 0:
@@ -136,6 +141,7 @@ def main():
                              if a.resample_every > 0 else None),
                    balance=(dict(every=a.balance_every, beta=a.balance_beta, lambda_b=P.lam_b())
                             if a.balance_every > 0 else None),
+                   confgrad=(P.engine.conflict_info() if a.confgrad else None),
                    batching=(dict(batch_points=a.batch_points, seed=a.batch_seed) if a.batch_points > 0 else None),
                    attention=(dict(eta=a.rba_eta, gamma=a.rba_gamma, init=a.rba_init,
                                    **{k_: v for k_, v in P.engine.attention_info().items()
