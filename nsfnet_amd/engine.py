@@ -8,8 +8,10 @@ The step implemented is the reference's solve_Adam loop body
 (NSFnet/pinn_solver.py:250-254, ev-NSFnet/pinn_solver.py:456-472):
 loss (BC MSE + PDE residual MSE [+ supervised MSE]) -> d loss/d theta -> Adam.
 """
+import contextlib
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -49,7 +51,6 @@ PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2}
 def resolve_precision(precision=None):
     """'fp32' | 'bf16x3' | 'bf16' or a (fwd, bwd, dw) triple of those; default from
     $NSFNET_PRECISION, else fp32 (the bit-exact fp32 MFMA path)."""
-    import os
     if precision is None:
         precision = os.environ.get("NSFNET_PRECISION", "fp32")
     if isinstance(precision, str):
@@ -669,24 +670,78 @@ class _EngineSpace:
         self.e.flat.copy_(h)
 
 
-class _Balance:
+class _TermCombiner:
+    """What the rules that combine the per-term gradients share: buf = [grads | grads_e | sums | g_b | g_s], the
+    engine's exchange buffer (content kept; engine.flat becomes the view of it) with the term vectors gb / gs behind
+    it, so several ranks all-reduce the used prefix in one message.  A rule tells _loss_and_grad what the final
+    term-split assembly writes besides the vectors (assembly) and makes the gradient of g_r, g_b and g_s (finish)."""
+    unit_seeds = False      # the boundary / supervised adjoints carry alpha_b / alpha_s
+
+    def __init__(self, engine):
+        n_ex = engine.flat.numel()
+        self.buf = torch.zeros(n_ex + 2 * engine.P, dtype=torch.float32, device=engine.device)
+        self.buf[:n_ex].copy_(engine.flat)
+        engine.flat = self.buf[:n_ex]
+        self.gb, self.gs = self.buf[n_ex:n_ex + engine.P], self.buf[n_ex + engine.P:]
+
+    def _allreduce_terms(self, e, sup_on):
+        """The global term vectors [grads (= g_r) | grads_e | sums | g_b (| g_s)], in one message."""
+        torch.distributed.all_reduce(self.buf[:e.flat.numel() + e.P * (2 if sup_on else 1)], group=e.pg)
+
+
+class _Balance(_TermCombiner):
     """Host side of the loss balancing: the cadence (Adam updates n counted since set_loss_balancing; `done` = the
     last n whose balance update has run) and the device tensors: lam [2] fp32, rec [BALANCE_RECORD] fp64 (the
     state and the statistics of the last balance step), parts (block partials), buf / gb / gs (term vectors)."""
+    unit_seeds = True       # the weights are applied by the combine (device memory, not a launch argument)
 
-    def __init__(self, every, beta):
+    def __init__(self, engine, every, beta):
+        super().__init__(engine)
         self.every, self.beta = every, beta
         self.n, self.done = 0, -1
-        self.buf = self.gb = self.gs = self.lam = self.rec = self.parts = None
+        self.lam = torch.tensor([engine.alpha_b, engine.alpha_s], dtype=torch.float32).to(engine.device)
+        rec = np.zeros(BALANCE_RECORD)
+        rec[9], rec[10] = engine.alpha_b, engine.alpha_s
+        self.rec = torch.tensor(rec, dtype=torch.float64).to(engine.device)
+        self.parts = balance_partials(engine.P, engine.device)
+
+    def assembly(self, e, update):      # one rank: the local vectors are the global ones, their partials come along
+        return dict(partials=self.parts if update and e.world_size == 1 else None)
+
+    def finish(self, e, update, sup_on):
+        gs = self.gs if sup_on else None
+        if update:
+            if e.world_size > 1:
+                self._allreduce_terms(e, sup_on)
+                balance_stats([e.grads, self.gb, gs], e.P, self.parts)
+            balance_update(self.parts, e.P, 1 | (2 if sup_on else 0), self.beta, self.lam, self.rec)
+        balance_combine(e.grads, e.grads, self.gb, gs, self.lam)
+        if not update and e.world_size > 1:
+            # the combine is linear: combining before the one all-reduce gives every rank the same global g
+            torch.distributed.all_reduce(e.flat, group=e.pg)
 
 
-class _ConflictFree:
+class _ConflictFree(_TermCombiner):
     """Device tensors of the conflict-free gradient combination (set_conflict_free_gradients): buf / gb / gs (the
-    exchange buffer with the term vectors behind it), parts (Gram block partials), coef [3] fp32 and rec
-    [CONFGRAD_RECORD] fp64 (the statistics of the last step and the counters)."""
+    exchange buffer with the term vectors alpha_b g_b / alpha_s g_s behind it), parts (Gram block partials), coef [3]
+    fp32 and rec [CONFGRAD_RECORD] fp64 (the statistics of the last step and the counters)."""
 
-    def __init__(self):
-        self.buf = self.gb = self.gs = self.parts = self.coef = self.rec = None
+    def __init__(self, engine):
+        super().__init__(engine)
+        self.coef = torch.ones(3, dtype=torch.float32, device=engine.device)
+        self.rec = torch.zeros(CONFGRAD_RECORD, dtype=torch.float64, device=engine.device)
+        self.parts = confgrad_partials(engine.P, engine.device)
+
+    def assembly(self, e, update):      # one rank: the local vectors are the global ones, their Gram partials too
+        return dict(gram=self.parts if e.world_size == 1 else None)
+
+    def finish(self, e, update, sup_on):
+        gs = self.gs if sup_on else None
+        if e.world_size > 1:        # the rule is not linear: every rank computes it from the global vectors
+            self._allreduce_terms(e, sup_on)
+            confgrad_gram([e.grads, self.gb, gs], e.P, self.parts)
+        confgrad_coef(self.parts, e.P, 3 if sup_on else 2, self.coef, self.rec)
+        confgrad_combine(e.grads, e.grads, self.gb, gs, self.coef)
 
 
 class _Batching:
@@ -730,6 +785,13 @@ class _Optim:
         self.cstruct = self.spec.c_struct()
 
 
+# What an evaluation is made for.  Each mode holds what the one before it holds, and more:
+EVAL_ADAM = 0           # an Adam step: a fresh batch, attention and balance updates, the conflict-free combination
+EVAL_FULL_BATCH = 1     # loss_and_grad(full_batch=True): the whole store, the attention weights held
+EVAL_LBFGS = 2          # the L-BFGS objective: also the loss weights held, and its own gradient (the plain sum)
+_SAME_MODE = contextlib.nullcontext()       # (an evaluation that asks for nothing: no generator on the step's path)
+
+
 class PinnEngine:
     """The per-step hot path for one rank.
 
@@ -759,14 +821,12 @@ class PinnEngine:
             self.net_e = None
         self.e_trainable = False
         self.pg, self.world_size = process_group, int(world_size)
-        P = self.net.num_params + (self.net_e.num_params if self.net_e else 0)
-        self.flat = torch.zeros(P + NSUMS, dtype=torch.float32, device=self.device)
         self.P, self.P1 = self.net.num_params, (self.net_e.num_params if self.net_e else 0)
+        self.flat = torch.zeros(self.P + self.P1 + NSUMS, dtype=torch.float32, device=self.device)
         self.plan_f = self.plan_b = self.plan_s = self.plan_e = None
         self._graphs = {}
         self._side = None
         self._resample_calls = 0        # resample() calls so far: part of each call's seed, kept across pools
-        import os
         self._overlap = os.environ.get("NSFNET_OVERLAP_BC", "1") not in ("0", "", "false")
         self.n_f_global = self.n_b_global = self.n_s_global = 0
         self._n_p_local, self._n_p_valid, self._sup_stale = 0, None, False
@@ -774,17 +834,35 @@ class PinnEngine:
         self._lbfgs = None                  # LbfgsHistory (created by the first lbfgs_step)
         self._lbfgs_state = _lbfgs.LbfgsState()
         self._lbfgs_owner = None            # what the state belongs to (lbfgs_step's `owner`)
+        self._mode = EVAL_ADAM              # what the evaluations are made for (_evaluating)
         self._bal = None                    # adaptive loss-weight balancing (set_loss_balancing; None = off)
-        self._bal_frozen = False            # lbfgs_step: the weights are held fixed
         self._cfg = None                    # conflict-free combination (set_conflict_free_gradients; None = off)
-        self._cfg_frozen = False            # lbfgs_step: the plain sum, the gradient of the objective
         self._batch = None                  # stochastic mini-batching (set_batching; None = off)
-        self._batch_frozen = False          # lbfgs_step: the full objective, i.e. the store
         self._eval_batch = False            # the last evaluation ran on the batch plan (loss_terms' normalisation)
         self._rba = None                    # residual-based attention (set_residual_attention; None = off)
-        self._rba_frozen = False            # lbfgs_step / full_batch: the weights are held fixed
+        self._pool = self._pool_w = self._pool_e = self._pool_scratch = None     # set_resample_pool
         self._opt = None                    # device lr schedule / gradient clipping (set_lr_schedule, set_grad_clipping)
         self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
+
+    # ---- what the evaluations are made for ----
+    @contextlib.contextmanager
+    def _evaluating(self, mode):
+        """Evaluate in `mode` (or the current one, where that holds more); the previous mode comes back on exit."""
+        prev, self._mode = self._mode, max(self._mode, mode)
+        try:
+            yield
+        finally:
+            self._mode = prev
+
+    # what the mode holds, option by option (read-only)
+    _bal_frozen = _cfg_frozen = property(lambda self: self._mode == EVAL_LBFGS)
+    _batch_frozen = _rba_frozen = property(lambda self: self._mode != EVAL_ADAM)
+
+    def _rank(self):
+        return torch.distributed.get_rank(self.pg) if self.world_size > 1 else 0
+
+    def _w4(self):      # the weight of eq4 (the plain flavour has none)
+        return self.eq4_weight if self.net_e is not None else 0.0
 
     # ---- views into the exchange buffer ----
     @property
@@ -803,7 +881,6 @@ class PinnEngine:
     def set_collocation(self, x, y, weights=None, n_global=None, chunk_points=None):
         """chunk_points (or $NSFNET_CHUNK_POINTS): process the set in passes of that many points sharing
         one activation workspace (ChunkedResidual); default: one pass, everything resident."""
-        import os
         if chunk_points is None and os.environ.get("NSFNET_CHUNK_POINTS"):
             chunk_points = int(os.environ["NSFNET_CHUNK_POINTS"])
         n = int(np.asarray(x).size)
@@ -916,8 +993,7 @@ class PinnEngine:
         when bt is given: its points are the store's bt.idx).  Two launches; between them, multi-rank, the MAX
         all-reduce of the one rmax word - as int64: the kernel stores a NaN as the positive quiet NaN, so the
         integer order of non-negative doubles is their NaN-propagating order."""
-        a = self._rba
-        w4 = self.eq4_weight if self.net_e is not None else 0.0
+        a, w4 = self._rba, self._w4()
         rba_stats(f, w4, a.scratch)
         if self.world_size > 1:
             torch.distributed.all_reduce(a.scratch[:1].view(torch.int64), op=torch.distributed.ReduceOp.MAX,
@@ -963,8 +1039,7 @@ class PinnEngine:
         if B == 0:
             self._batch = None
             return
-        rank = torch.distributed.get_rank(self.pg) if self.world_size > 1 else 0
-        bt = _Batching(B, seed, rank)
+        bt = _Batching(B, seed, self._rank())
         bt.idx = torch.zeros(B, dtype=torch.int64, device=self.device)
         bt.counter = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._make_batch_plans(bt)
@@ -994,7 +1069,7 @@ class PinnEngine:
         return dict(batch_points=bt.B, store_points=self.plan_f.n, seed=bt.seed, draws=int(bt.counter[0].item()))
 
     def _batching_on(self):
-        return self._batch is not None and not self._batch_frozen
+        return self._batch is not None and self._mode == EVAL_ADAM
 
     def _colloc(self):
         """(collocation plan, entropy-net plan, global point count of the normalisation) of the next evaluation: the
@@ -1079,9 +1154,10 @@ class PinnEngine:
         vis_t0 and alpha_evm.  The live buffers are rewritten IN PLACE, so a captured step replays on the new points;
         parameters, Adam moments, the boundary / supervised plans and n_f_global are not touched.  Each rank draws from
         its own pool shard (per-rank stratification).  The weights are renormalised to mean 1 over the global selected
-        set (with residual attention on: the static weights s, and lam restarts at init); the entropy-net state vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-
-        ordered after the last step; one 8-byte host read.  Returns the int64 pool indices (ascending, may repeat)."""
-        f, pool = self.plan_f, getattr(self, "_pool", None)
+        set (with residual attention on: the static weights s, and lam restarts at init); the entropy-net state
+        vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-ordered after the last step; one
+        8-byte host read.  Returns the int64 pool indices (ascending, may repeat)."""
+        f, pool = self.plan_f, self._pool
         if pool is None or f is None:
             raise RuntimeError("resample() needs set_collocation() and set_resample_pool() first")
         rba = self._rba              # on: the gather and the renormalisation work on the static weights s
@@ -1094,11 +1170,9 @@ class PinnEngine:
             vtm0 = (self.alpha_evm * e.abs()).contiguous()       # init_vis_t at the pool points
             pool.vis_t_minus = vtm0.clone()                        # (the forward overwrites its state argument)
         pool.forward(self.Re, e=e, vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.scale, save=False)
-        rank = torch.distributed.get_rank(self.pg) if self.world_size > 1 else 0
-        u = np.random.default_rng([int(seed), self._resample_calls, rank]).random()     # (calls counted per engine)
+        u = np.random.default_rng([int(seed), self._resample_calls, self._rank()]).random()     # (calls counted per engine)
         self._resample_calls += 1
-        w4 = self.eq4_weight if self.net_e is not None else 0.0
-        idx, S = resample_select(pool, w4, k, c, u, f.n, self._pool_scratch)
+        idx, S = resample_select(pool, self._w4(), k, c, u, f.n, self._pool_scratch)
         self.lbfgs_reset()                       # the objective changes: the history no longer describes it
         if self._batch is not None:
             self._graphs.clear()
@@ -1158,19 +1232,7 @@ class PinnEngine:
         if every == 0:
             self._bal = None
             return
-        b = _Balance(every, beta)
-        n_ex = self.P + self.P1 + NSUMS
-        # one buffer [grads | grads_e | sums | g_b | g_s]: a balance step all-reduces its prefix in one message
-        b.buf = torch.zeros(n_ex + 2 * self.P, dtype=torch.float32, device=self.device)
-        b.buf[:n_ex].copy_(self.flat)
-        self.flat = b.buf[:n_ex]
-        b.gb, b.gs = b.buf[n_ex:n_ex + self.P], b.buf[n_ex + self.P:]
-        b.lam = torch.tensor([self.alpha_b, self.alpha_s], dtype=torch.float32).to(self.device)
-        rec = np.zeros(BALANCE_RECORD)
-        rec[9], rec[10] = self.alpha_b, self.alpha_s
-        b.rec = torch.tensor(rec, dtype=torch.float64).to(self.device)
-        b.parts = balance_partials(self.P, self.device)
-        self._bal = b
+        self._bal = _Balance(self, every, beta)
 
     def loss_weights(self):
         """Device tensor [lambda_b, lambda_s] (fp32) of the weights the gradient uses (the configured ones when
@@ -1195,7 +1257,7 @@ class PinnEngine:
     def _balance_due(self):
         """True for the first evaluation of a balance update (n % every == 0), which it claims."""
         b = self._bal
-        if b is None or self._bal_frozen or b.n % b.every != 0 or b.done == b.n:
+        if b is None or self._mode == EVAL_LBFGS or b.n % b.every != 0 or b.done == b.n:
             return False
         b.done = b.n
         return True
@@ -1224,17 +1286,7 @@ class PinnEngine:
         if not enabled:
             self._cfg = None
             return
-        c = _ConflictFree()
-        n_ex = self.P + self.P1 + NSUMS
-        # one buffer [grads | grads_e | sums | g_b | g_s]: several ranks all-reduce its used prefix in one message
-        c.buf = torch.zeros(n_ex + 2 * self.P, dtype=torch.float32, device=self.device)
-        c.buf[:n_ex].copy_(self.flat)
-        self.flat = c.buf[:n_ex]
-        c.gb, c.gs = c.buf[n_ex:n_ex + self.P], c.buf[n_ex + self.P:]
-        c.coef = torch.ones(3, dtype=torch.float32, device=self.device)
-        c.rec = torch.zeros(CONFGRAD_RECORD, dtype=torch.float64, device=self.device)
-        c.parts = confgrad_partials(self.P, self.device)
-        self._cfg = c
+        self._cfg = _ConflictFree(self)
 
     def conflict_info(self):
         """The device record of the last conflict-free combination (one host read), or None when the feature is
@@ -1250,14 +1302,6 @@ class PinnEngine:
             out[k] = int(out[k])
         return out
 
-    def _reduce_terms(self, r_plans, b, s, acc_r, update):
-        """Term-split gradient assembly: g_r into grads, g_b / g_s into the balancing buffer (the partials on a
-        single-rank balance step, where the local vectors are the global ones)."""
-        bal = self._bal
-        grad_reduce_terms(self.net, [r_plans, [b], [] if s is None else [s]],
-                          [self.grads, bal.gb, bal.gs if self._sup_on() else None], acc_mask=1 if acc_r else 0,
-                          partials=bal.parts if update and self.world_size == 1 else None)
-
     # ---- one loss + gradient evaluation ----
     def loss_and_grad(self, mode="MSE", full_batch=False):
         """mode 'MSE' (every script of the reference) or 'L2': 2-norms of the residual / boundary-misfit vectors
@@ -1268,31 +1312,23 @@ class PinnEngine:
         if mode not in ("MSE", "L2"):
             raise ValueError("loss mode must be 'MSE' or 'L2' (got %r)" % (mode,))
         l2 = mode == "L2"
-        if l2 and self._bal is not None:
-            raise ValueError("loss balancing needs the MSE loss (loss mode %r)" % mode)
-        if l2 and self._cfg is not None:
-            raise ValueError("conflict-free gradients need the MSE loss (loss mode %r)" % mode)
-        if l2 and self._batch is not None:
-            raise ValueError("mini-batching needs the MSE loss (loss mode %r)" % mode)
-        if l2 and self._rba is not None:
-            raise ValueError("residual attention needs the MSE loss (loss mode %r)" % mode)
+        for state, needs in ((self._bal, "loss balancing needs"), (self._cfg, "conflict-free gradients need"),
+                             (self._batch, "mini-batching needs"), (self._rba, "residual attention needs")):
+            if l2 and state is not None:
+                raise ValueError("%s the MSE loss (loss mode %r)" % (needs, mode))
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
             raise NotImplementedError("loss mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
-        frozen, rba_frozen = self._batch_frozen, self._rba_frozen
-        self._batch_frozen = frozen or bool(full_batch)
-        self._rba_frozen = rba_frozen or bool(full_batch)
-        try:
+        with self._evaluating(EVAL_FULL_BATCH) if full_batch else _SAME_MODE:
             self._loss_and_grad(self._balance_due(), l2)
-        finally:
-            self._batch_frozen, self._rba_frozen = frozen, rba_frozen
 
     def _loss_and_grad(self, update=False, l2=False):
         b = self.plan_b
         f, plan_e, n_f = self._colloc()
         bt = self._batch if self._batching_on() else None
         self._eval_batch = bt is not None
-        bal = self._bal
-        cfg = None if self._cfg_frozen else self._cfg     # conflict-free combination (never together with bal)
+        comb = self._bal        # the rule that combines the term gradients; None: the plain sum
+        if comb is None and self._mode != EVAL_LBFGS:       # (never both; the L-BFGS objective has its own gradient)
+            comb = self._cfg
         sums = self.sums
         sup_on = self._sup_on()
         s = self.plan_s if sup_on else None             # None also on a rank whose supervised share is empty
@@ -1315,8 +1351,7 @@ class PinnEngine:
             side.wait_stream(main)
             torch.cuda.set_stream(side)
         try:
-            # balancing: unit seeds, the weights are applied by the combine (device memory, not a launch argument)
-            wb, ws = (1.0, 1.0) if bal is not None else (self.alpha_b, self.alpha_s)
+            wb, ws = (1.0, 1.0) if comb is not None and comb.unit_seeds else (self.alpha_b, self.alpha_s)
             cb = 2.0 * wb / self.n_b_global
             if l2:      # norms first (2052 boundary points: a forward-only pass), then the adjoints alpha_b (u - u_b) / ||u - u_b||
                 b.forward(coef=(0.0, 0.0, 0.0), save=False, sums_out=sums[S_BC:S_BC + NLOSS])
@@ -1344,7 +1379,7 @@ class PinnEngine:
             plan_e.forward(save=self.e_trainable)
             e = plan_e.pred[0]
         c = 2.0 * self.alpha_e / n_f
-        coef_eq = (c, c, c, c * self.eq4_weight if self.net_e is not None else 0.0)
+        coef_eq = (c, c, c, c * self._w4())
         # one pass per plan (several: chunks sharing one workspace, gradients and sums accumulate); every pass but
         # the last is reduced here, the last one together with the value plans below
         passes = _passes(f)
@@ -1368,63 +1403,33 @@ class PinnEngine:
             if many:
                 eq_sums += f.tmp_sums
             if k < len(passes) - 1:
-                if bal is None and cfg is None:
+                if comb is None:
                     grad_reduce(self.net, [p], self.grads, accumulate=k > 0)
                 else:
                     grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
         if bt is not None and f.vis_t_minus is not None:      # the forward left alpha_evm |e| of the batch points there
             batch_scatter(bt.idx, bt.B, self.plan_f.n, f.vis_t_minus, self.plan_f.vis_t_minus)
-        if self._rba is not None and not self._rba_frozen:      # the weights of the NEXT evaluation
+        if self._rba is not None and self._mode == EVAL_ADAM:      # the weights of the NEXT evaluation
             self._attention_update(f, bt)
         if side is not None:
             main.wait_stream(side)
         last = passes[-1][1]
-        if cfg is not None:
-            # g_r into grads, alpha_b g_b / alpha_s g_s behind the exchange buffer; one rank: the local vectors are the
-            # global ones and the assembly writes their Gram partials too
-            grad_reduce_terms(self.net, [[last], [b], [] if s is None else [s]],
-                              [self.grads, cfg.gb, cfg.gs if sup_on else None], acc_mask=1 if many else 0,
-                              gram=cfg.parts if self.world_size == 1 else None)
-        elif bal is None:
+        if comb is None:
             grad_reduce(self.net, [last, b] + ([] if s is None else [s]), self.grads, accumulate=many)
-        else:
-            self._reduce_terms([last], b, s, many, update)
+        else:       # g_r into grads, g_b / g_s behind the exchange buffer
+            grad_reduce_terms(self.net, [[last], [b], [] if s is None else [s]],
+                              [self.grads, comb.gb, comb.gs if sup_on else None], acc_mask=1 if many else 0,
+                              **comb.assembly(self, update))
         if self.net_e is not None:
             if self.e_trainable:
                 plan_e.backward(out_adj=f.ebar)
                 grad_reduce(self.net_e, [plan_e], self.grads_e)
             else:
                 self.grads_e.zero_()
-        if cfg is not None:
-            gs = cfg.gs if sup_on else None
-            if self.world_size > 1:
-                # the rule is not linear: it needs the global term vectors, [grads (= g_r) | grads_e | sums | g_b
-                # (| g_s)] in one message; then every rank computes the same partials, coefficients and combine
-                n = self.flat.numel() + self.P * (2 if sup_on else 1)
-                torch.distributed.all_reduce(cfg.buf[:n], group=self.pg)
-                confgrad_gram([self.grads, cfg.gb, gs], self.P, cfg.parts)
-            confgrad_coef(cfg.parts, self.P, 3 if sup_on else 2, cfg.coef, cfg.rec)
-            confgrad_combine(self.grads, self.grads, cfg.gb, gs, cfg.coef)
-            return
-        if bal is None:
-            if self.world_size > 1:
-                torch.distributed.all_reduce(self.flat, group=self.pg)
-            return
-        gs = bal.gs if sup_on else None
-        if update:
-            if self.world_size > 1:
-                # the statistics need the global term vectors: [grads (= g_r) | grads_e | sums | g_b (| g_s)] in one
-                # message, then every rank computes the same partials, weights and combine
-                n = self.flat.numel() + self.P * (2 if sup_on else 1)
-                torch.distributed.all_reduce(bal.buf[:n], group=self.pg)
-                balance_stats([self.grads, bal.gb, gs], self.P, bal.parts)
-            balance_update(bal.parts, self.P, 1 | (2 if sup_on else 0), bal.beta, bal.lam, bal.rec)
-            balance_combine(self.grads, self.grads, bal.gb, gs, bal.lam)
-        else:
-            # the combine is linear: combining before the one all-reduce gives every rank the same global g
-            balance_combine(self.grads, self.grads, bal.gb, gs, bal.lam)
-            if self.world_size > 1:
-                torch.distributed.all_reduce(self.flat, group=self.pg)
+        if comb is not None:
+            comb.finish(self, update, sup_on)
+        elif self.world_size > 1:
+            torch.distributed.all_reduce(self.flat, group=self.pg)
 
     def _side_stream(self, main):
         """The stream the value-mode chains run on.  Inside a graph capture it must be a stream that is
@@ -1434,7 +1439,7 @@ class PinnEngine:
         return self._side
 
     def _n_p_valid_global(self):
-        if getattr(self, "_n_p_valid", None) is None:
+        if self._n_p_valid is None:
             n = int(self._n_p_local)
             if self.world_size > 1:
                 tt = torch.tensor([n], dtype=torch.int64, device=self.device)
@@ -1460,7 +1465,7 @@ class PinnEngine:
         loss_b = (s[S_BC] + s[S_BC + 1]) / self.n_b_global
         out = dict(loss_eq1=eq[0], loss_eq2=eq[1], loss_eq3=eq[2], loss_eq4=eq[3], loss_e=loss_e, loss_b=loss_b)
         loss_s = torch.zeros((), device=self.device)
-        if self.n_s_global > 0 and self.alpha_s != 0.0:
+        if self._sup_on():
             n_p = self._n_p_valid_global()
             loss_s = (s[S_SUP] + s[S_SUP + 1]) / self.n_s_global + (s[S_SUP + 2] / n_p if n_p > 0 else 0.0)
         out["loss_s"] = loss_s
@@ -1494,6 +1499,14 @@ class PinnEngine:
             self.net.adam_step_sched(g, lr, o, advance=True)        # last: it moves the epoch on
         if self._bal is not None:
             self._bal.n += 1
+
+    def _count_updates(self, d):
+        """Move the host mirrors of the update count (what adam_step advances) by d = +1 / -1."""
+        self.net.adam_t += d
+        if self.net_e is not None and self.e_trainable:
+            self.net_e.adam_t += d
+        if self._bal is not None:
+            self._bal.n += d
 
     # ---- random weight factorization of the dense layers (DESIGN.md section 7.7) ----
     def _nets(self):
@@ -1654,20 +1667,14 @@ class PinnEngine:
         if self.net_e is not None:
             self.e_trainable = False
             self.init_vis_t()
-        self._bal_frozen = True             # the objective uses the current loss weights throughout
-        self._cfg_frozen = True             # ... and its own gradient: the plain sum of the terms
-        self._batch_frozen = True           # ... and the whole store
-        self._rba_frozen = True             # ... and the current attention weights
+        space = _EngineSpace(self, self._lbfgs)
         try:
-            loss, info = _lbfgs.step(_EngineSpace(self, self._lbfgs), self._lbfgs_state, lr=float(lr),
-                                     max_iter=int(max_iter), max_eval=max_eval, tolerance_grad=float(tolerance_grad),
-                                     tolerance_change=float(tolerance_change), line_search_fn=line_search_fn)
+            with self._evaluating(EVAL_LBFGS):      # the objective: one set of points, weights and terms throughout
+                loss, info = _lbfgs.step(space, self._lbfgs_state, lr=float(lr), max_iter=int(max_iter),
+                                         max_eval=max_eval, tolerance_grad=float(tolerance_grad),
+                                         tolerance_change=float(tolerance_change), line_search_fn=line_search_fn)
         finally:
             self.e_trainable = e_trainable
-            self._bal_frozen = False
-            self._cfg_frozen = False
-            self._batch_frozen = False
-            self._rba_frozen = False
         self.lbfgs_info = info
         return loss
 
@@ -1682,16 +1689,7 @@ class PinnEngine:
             return
         # with balancing on, a balance step and a plain step are separate graphs (the weights are device state)
         update = self._balance_due()
-        key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
-               self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
-               self._bal is not None, update, self._batch.B if self._batch is not None else 0,
-               (False, 0.0, 0.0) if self._rba is None else (True, self._rba.gamma, self._rba.eta))
-        if self._opt is not None:       # lr is the base rate lr0: the rate of each update is device state
-            key += (self._opt.spec.key(), self._opt.max_norm)
-        if self._rwf is not None:
-            key += ("rwf",)
-        if self._cfg is not None:
-            key += ("confgrad",)
+        key = self._graph_key(lr, update)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the
@@ -1708,24 +1706,25 @@ class PinnEngine:
                     self._loss_and_grad(update)
                     self.adam_step(lr)
             torch.cuda.current_stream(self.device).wait_stream(side)
-            # the capture itself does not execute; account for the host mirrors it advanced
-            self.net.adam_t -= 1
-            if self.net_e is not None and self.e_trainable:
-                self.net_e.adam_t -= 1
-            if self._bal is not None:
-                self._bal.n -= 1
+            self._count_updates(-1)      # the capture itself does not execute
             self._graphs[key] = graph
             return
         g.replay()
         self._eval_batch = self._batching_on()
-        self.net.adam_t += 1
-        if self.net_e is not None and self.e_trainable:
-            self.net_e.adam_t += 1
-        if self._bal is not None:
-            self._bal.n += 1
+        self._count_updates(1)
+
+    def _graph_key(self, lr, update):
+        """What a captured step depends on besides device memory: the launch constants of the engine and of every
+        option that is on (lr is the base rate lr0 under a schedule: the rate of each update is device state)."""
+        bt, a, o = self._batch, self._rba, self._opt
+        key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
+               self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
+               self._bal is not None, update, 0 if bt is None else bt.B,
+               (False, 0.0, 0.0) if a is None else (True, a.gamma, a.eta))
+        key += () if o is None else (o.spec.key(), o.max_norm)
+        return key + (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
 
     def _graphs_enabled(self):
-        import os
         flag = os.environ.get("NSFNET_GRAPH")
         return flag is not None and flag not in ("0", "", "false", "False") and self.device.type == "cuda"
 
