@@ -8,6 +8,7 @@
 // the weight-gradient GEMM (dw.hip), and the skinny gradients (all biases, layer 0,
 // output layer) are reduced in-kernel.
 #include "kernels.h"
+#include "spill_io.h"
 #include "point_stage.h"
 #include "reduce_util.h"
 
@@ -52,23 +53,18 @@ __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
       }
     }
     for (int l = L - 1; l >= 0; --l) {
-      const float* Sl = a.S + ((size_t)tile * L + l) * act_block(HP);
-      float* Zl = a.Zb + ((size_t)tile * L + l) * act_block(HP);
+      const float* Sl = a.S + spill_off<act_block(HP), 0>(a.spill, tile, l, L);
+      float* Zl = a.Zb + spill_off<act_block(HP), 0>(a.spill, tile, l, L);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * 32 + col);
-        const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
         f32x4 s0, s1, s2, s3;
-        if (NS == 4 && l == 0 && a.s0_skip) {      // not spilled: the forward's own fmaf chain and tanhf, bit for bit
+        if (NS == 4 && l == 0 && a.spill.skip0) {      // not stored: recomputed as the forward computed it
           const int o0 = ob + 8 * g + 4 * h;
-          s1 = *reinterpret_cast<const f32x4*>(P + prep_w0x(HP) + o0); s2 = *reinterpret_cast<const f32x4*>(P + prep_w0y(HP) + o0);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(P + prep_b0(HP) + o0);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s0[e] = tanhf(fmaf(s1[e], px[0], fmaf(s2[e], py[0], b4[e])));
-          s3 = f32x4{0.f, 0.f, 0.f, 0.f};
+          layer0_saved(*reinterpret_cast<const f32x4*>(P + prep_w0x(HP) + o0), *reinterpret_cast<const f32x4*>(P + prep_w0y(HP) + o0),
+                       *reinterpret_cast<const f32x4*>(P + prep_b0(HP) + o0), px[0], py[0], TanhLibm(), s0, s1, s2, s3);
         } else {
-          s0 = __builtin_nontemporal_load(pin_base(S4 + 0 * (HP / 4) * 32) + so); s1 = __builtin_nontemporal_load(pin_base(S4 + 1 * (HP / 4) * 32) + so);
-          s2 = __builtin_nontemporal_load(pin_base(S4 + 2 * (HP / 4) * 32) + so); s3 = __builtin_nontemporal_load(pin_base(S4 + 3 * (HP / 4) * 32) + so);
+          load_quad4(Sl, (HP / 4) * 32, so, s0, s1, s2, s3);
         }
         f32x4 z0, z1, z2, z3;
         float dbq[4], wq0[4], wq1[4], wq2[4], dxq[4], dyq[4];
@@ -141,11 +137,7 @@ __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
             if (l == 0) { lds_add(&sgacc[sg_w0x(HP, L) + o], dx); lds_add(&sgacc[sg_w0y(HP, L) + o], dy); }
           }
         }
-        if (l > 0) {
-          const f32x4* Z4 = reinterpret_cast<const f32x4*>(Zl);
-          __builtin_nontemporal_store(z0, pin_base(Z4 + 0 * (HP / 4) * 32) + so); __builtin_nontemporal_store(z1, pin_base(Z4 + 1 * (HP / 4) * 32) + so);
-          __builtin_nontemporal_store(z2, pin_base(Z4 + 2 * (HP / 4) * 32) + so); __builtin_nontemporal_store(z3, pin_base(Z4 + 3 * (HP / 4) * 32) + so);
-        }
+        if (l > 0) store_quad4(Zl, (HP / 4) * 32, so, z0, z1, z2, z3);
       }
       if (l == 0) break;
       __syncthreads();
@@ -199,6 +191,7 @@ size_t bwd_lds_bytes(int HP, int L) { return ((size_t)HP * 128 + 4 * 128 + sg_to
 template <int HP, int NS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_lds_bytes(HP, a.L);
+  if (!spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   return launch_or_configure(&bwd_kernel<HP, NS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

@@ -72,8 +72,8 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
         }
       }
       asm volatile("" ::: "memory");
-      const float* Sl = a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS);
-      float* Zl = a.Zb + ((size_t)tile * L + l) * ((size_t)HP * COLS);
+      const float* Sl = a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
+      float* Zl = a.Zb + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
 
       // residual mode: tanh adjoint of one register quad (features ob+8g+4h+e, column pp), all streams
       auto adj_quad = [&](int g, const f32x4& ga, const f32x4& gx, const f32x4& gy, const f32x4& gd) {
@@ -81,9 +81,8 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
         // 64-bit add pair (every VALU instruction of the epilogue costs its full issue time)
         const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
         constexpr size_t PLQ = (size_t)(HP / 4) * PPL;          // f32x4 per plane
-        auto plane = [&](const float* base, int k) { return pin_base(reinterpret_cast<const f32x4*>(base) + k * PLQ); };
-        f32x4 s0 = __builtin_nontemporal_load(plane(Sl, 0) + so), s1 = __builtin_nontemporal_load(plane(Sl, 1) + so);
-        f32x4 s2 = __builtin_nontemporal_load(plane(Sl, 2) + so), s3 = __builtin_nontemporal_load(plane(Sl, 3) + so);
+        f32x4 s0, s1, s2, s3;
+        load_quad4(Sl, PLQ, so, s0, s1, s2, s3);
         f32x4 z0, z1, z2, z3;
         // branch-free chain for the four features (the layer-specific skinny-gradient terms follow below,
         // once per quad: a branch per element splits this into blocks the scheduler cannot pack)
@@ -154,8 +153,7 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
           split4(z3[0], z3[1], z3[2], z3[3], vh, vl);
           *reinterpret_cast<u32x2*>(Xb + 3 * XI::PLANE * 2 + off) = vh;
           if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
-          __builtin_nontemporal_store(z0, plane(Zl, 0) + so); __builtin_nontemporal_store(z1, plane(Zl, 1) + so);
-          __builtin_nontemporal_store(z2, plane(Zl, 2) + so); __builtin_nontemporal_store(z3, plane(Zl, 3) + so);
+          store_quad4(Zl, PLQ, so, z0, z1, z2, z3);
         }
       };
 
@@ -315,6 +313,7 @@ size_t bwd_bf16_lds_bytes(int HP, int L, int cols) {
 template <int HP, int NS, int TERMS, int COLS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
+  if (!spill_is(a.spill, act_block(HP, COLS), IN_CLASSIC)) return -1000;
   return launch_or_configure(&bwd_bf16_kernel<HP, NS, TERMS, COLS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

@@ -129,8 +129,8 @@ __global__ __launch_bounds__(HP, 1) void bwd_pipe_kernel(BwdArgs a) {
     };
     // ------------- epilogue state -------------
     const int tileS = tileE < a.ntiles ? tileE : 0;      // the dummy partner of an odd tile count reads tile 0's (finite) S
-    const float* const Sl = a.S + ((size_t)tileS * L + lE) * ((size_t)HP * COLS);
-    float* const Zl = a.Zb + ((size_t)tileE * L + lE) * ((size_t)HP * COLS);
+    const float* const Sl = a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tileS, lE, L);
+    float* const Zl = a.Zb + spill_off<act_block(HP, COLS), 0>(a.spill, tileE, lE, L);
     float oc[3][4];                                       // output adjoints of this lane's point: [output][stream]
     if (first) {
 #pragma unroll
@@ -328,6 +328,7 @@ size_t bwd_pipe_lds_bytes(int HP, int L) { return PipeBwdLds<256>::bytes(L); }
 template <int HP, int TERMS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = PipeBwdLds<HP>::bytes(a.L);
+  if (!spill_is(a.spill, act_block(HP), IN_CLASSIC)) return -1000;
   return launch_or_configure(&bwd_pipe_kernel<HP, TERMS>, dim3(grid), dim3(HP), lds, s, a.configure, a);
 }
 

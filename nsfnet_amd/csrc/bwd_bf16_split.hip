@@ -52,8 +52,8 @@ __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
   SW sw(ldsb, P, woutL, w0L, w, lane0);
 
   // the dummy partner of an odd tile count reads tile 0's (finite) S
-  auto S_of = [&](int tile, int l) { return a.S + spill_off(tile < a.ntiles ? tile : 0, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
-  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS)>(a.spill, tile < a.ntiles ? tile : 0, l, L); };
+  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off<act_block(HP, COLS)>(a.spill, tile, l, L); };
   // ---- output adjoints of a tile (point_stage.h) into the group's LDS block; zero for the dummy partner tile ----
   auto seeds = [&](int tile, float& px, float& py) {
     const int col = lane0 & 31;
@@ -116,6 +116,7 @@ size_t bwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitBwdLds<256>::b
 template <int HP, int TERMS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitBwdLds<HP>::bytes(a.L);
+  if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
   return launch_or_configure(&bwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 

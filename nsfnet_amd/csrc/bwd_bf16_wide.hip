@@ -79,8 +79,8 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel
           }
       }
       asm volatile("" ::: "memory");
-      const float* Sl = a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS);
-      float* Zl = a.Zb + ((size_t)tile * L + l) * ((size_t)HP * COLS);
+      const float* Sl = a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
+      float* Zl = a.Zb + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         if (m >= mcount) continue;
@@ -99,17 +99,8 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel
           for (int gq = 0; gq < 2; ++gq) {
             const int g = gq + 2 * hi;
             const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
-            const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
             f32x4 s0, s1, s2, s3;
-            if (a.s24) {      // 24-bit three-plane spill (bf16_util.h pack24)
-              u32x4 pk[3];
-#pragma unroll
-              for (int k = 0; k < 3; ++k) pk[k] = __builtin_bit_cast(u32x4, __builtin_nontemporal_load(pin_base(S4 + k * (HP / 4) * PPL) + so));
-              s0 = unpack24_plane(pk, 0); s1 = unpack24_plane(pk, 1); s2 = unpack24_plane(pk, 2); s3 = unpack24_plane(pk, 3);
-            } else {
-              s0 = __builtin_nontemporal_load(pin_base(S4 + 0 * (HP / 4) * PPL) + so); s1 = __builtin_nontemporal_load(pin_base(S4 + 1 * (HP / 4) * PPL) + so);
-              s2 = __builtin_nontemporal_load(pin_base(S4 + 2 * (HP / 4) * PPL) + so); s3 = __builtin_nontemporal_load(pin_base(S4 + 3 * (HP / 4) * PPL) + so);
-            }
+            load_quad(a.spill.quad, Sl, (HP / 4) * PPL, so, s0, s1, s2, s3);
             f32x4 z0, z1, z2, z3;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -178,16 +169,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel
               split4(z3[0], z3[1], z3[2], z3[3], vh, vl);
               *reinterpret_cast<u32x2*>(Xb + 3 * XI::PLANE * 2 + off) = vh;
               if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
-              const f32x4* Z4 = reinterpret_cast<const f32x4*>(Zl);
-              if (a.s24) {
-                u32x4 pk[3];
-                pack24_quad(z0, z1, z2, z3, pk);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[k]), pin_base(Z4 + k * (HP / 4) * PPL) + so);
-              } else {
-                __builtin_nontemporal_store(z0, pin_base(Z4 + 0 * (HP / 4) * PPL) + so); __builtin_nontemporal_store(z1, pin_base(Z4 + 1 * (HP / 4) * PPL) + so);
-                __builtin_nontemporal_store(z2, pin_base(Z4 + 2 * (HP / 4) * PPL) + so); __builtin_nontemporal_store(z3, pin_base(Z4 + 3 * (HP / 4) * PPL) + so);
-              }
+              store_quad(a.spill.quad, Zl, (HP / 4) * PPL, so, z0, z1, z2, z3);
             }
           }
         } else {
@@ -332,6 +314,7 @@ size_t bwd_bf16_wide_lds_bytes(int HP, int L) {
 template <int HP, int NS, int TERMS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_bf16_wide_lds_bytes(HP, a.L);
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
   return launch_or_configure(&bwd_bf16_wide_kernel<HP, NS, TERMS>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
 }
 

@@ -36,8 +36,8 @@ __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
   SW sw(ldsb, P, P + prep_wout(HP, L), P + prep_w0x(HP), grp, w, lane0);
 
   // the dummy partner of an odd tile count reads tile 0's (finite) S
-  auto S_of = [&](int tile, int l) { return a.S + ((size_t)(tile < a.ntiles ? tile : 0) * L + l) * ((size_t)HP * COLS); };
-  auto Z_of = [&](int tile, int l) { return a.Zb + ((size_t)tile * L + l) * ((size_t)HP * COLS); };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile < a.ntiles ? tile : 0, l, L); };
+  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L); };
   // ---- output adjoints of a tile (point_stage.h) into the group's LDS block; zero for the dummy partner tile ----
   auto seeds = [&](int tile, float& px, float& py) {
     const int col = lane0 & 31;
@@ -96,6 +96,7 @@ size_t bwd_wsplit_lds_bytes(int HP, int L) {
 template <int HP, int TERMS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::bwd_bytes(a.L);
+  if (!spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
   return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 

@@ -3,6 +3,7 @@
 // ev-NSFnet/pinn_solver.py:469); tile geometry and the v_permlane16_swap stream exchange
 // as in fwd_wide.hip.
 #include "kernels.h"
+#include "spill_io.h"
 #include "point_stage.h"
 #include "reduce_util.h"
 
@@ -59,8 +60,8 @@ __global__ __launch_bounds__(HP * 2) void bwd_wide_kernel(BwdArgs a) {
 #pragma unroll
         for (int q = 0; q < PRE; ++q) wq[q] = wf[q * 64];
       }
-      const float* Sl = a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS);
-      float* Zl = a.Zb + ((size_t)tile * L + l) * ((size_t)HP * COLS);
+      const float* Sl = a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
+      float* Zl = a.Zb + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L);
       if (NS == 4) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -75,7 +76,9 @@ __global__ __launch_bounds__(HP * 2) void bwd_wide_kernel(BwdArgs a) {
           const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
           const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
           f32x4 s0, s1, s2, s3;
-          if (l == 0 && a.s0_skip) {      // not spilled: the forward's own fmaf chain and tanhf, bit for bit
+          // Layer 0 not stored: layer0_saved, written out.  This epilogue's chain rule below is contracted differently (and the
+          // gradient's low bits move) when its inputs arrive through the shared helpers, so it keeps its own text.
+          if (l == 0 && a.spill.skip0) {
             const int o0 = ob + 8 * g + 4 * h;
             s1 = *reinterpret_cast<const f32x4*>(P + prep_w0x(HP) + o0); s2 = *reinterpret_cast<const f32x4*>(P + prep_w0y(HP) + o0);
             const f32x4 b4 = *reinterpret_cast<const f32x4*>(P + prep_b0(HP) + o0);
@@ -220,6 +223,7 @@ template <int HP, int NS>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_wide_lds_bytes(HP, a.L);
   if (lds > PINN_LDS_MAX) return -1001;
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   return launch_or_configure(&bwd_wide_kernel<HP, NS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

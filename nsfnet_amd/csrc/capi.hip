@@ -19,7 +19,7 @@ static int fail(int code, const char* fmt, const char* a = "", long b = 0) {
   return code;
 }
 static int hipfail(int rc, const char* what) {
-  if (rc == -1000) return fail(-22, "%s: unsupported hidden width (code %ld)", what, (long)rc);
+  if (rc == -1000) return fail(-22, "%s: unsupported hidden width or spill layout (code %ld)", what, (long)rc);
   return fail(rc, "%s: HIP error %ld", what, (long)-rc);
 }
 
@@ -82,25 +82,32 @@ static constexpr const char* FAMILY_NAMES[][3] = {
     {"fwd_wsplit_kernel", "bwd_wsplit_kernel", nullptr},
     {"fwdbwd_split_kernel", "fwdbwd_split_kernel", nullptr},
 };
+// The spill layouts (spill.h) each family's kernels implement in residual mode: {S the forward writes, S the reverse
+// sweep reads and Z-bar it writes, S and Z-bar the dW kernel reads}.  resolve_plan checks every role of a plan against
+// this table and the launchers check again what they are handed; value mode is SPILL_CLASSIC in every 8-wave family.
+static constexpr unsigned FAMILY_SPILLS[][3] = {
+    {0, 0, 0},
+    {IN_CLASSIC | IN_SKIP0, IN_CLASSIC | IN_SKIP0, IN_CLASSIC | IN_SKIP0},
+    {IN_CLASSIC | IN_SKIP0, IN_CLASSIC | IN_SKIP0, IN_CLASSIC | IN_SKIP0},
+    {IN_CLASSIC, IN_CLASSIC, IN_CLASSIC | IN_P24_COMPACT},      // (dw_bf16 reads the compact layout at hidden 256 / 128 columns)
+    {IN_CLASSIC | IN_P24_WIDE, IN_CLASSIC | IN_P24_WIDE, IN_CLASSIC | IN_P24_WIDE},
+    {IN_CLASSIC, IN_CLASSIC, 0},
+    {IN_P24_COMPACT, IN_P24_COMPACT, 0},
+    {IN_P24_WIDE, IN_P24_WIDE, 0},
+    {IN_P24_COMPACT, IN_P24_COMPACT, 0},
+};
 // the 8-wave family of one precision on this net: the only place precision and tile geometry are weighed
 static Family base_family(const pinn_net_s& n, int prec) {
   return prec ? (n.HP > 256 ? FAM_BF16_WIDE : FAM_BF16) : n.wide ? FAM_FP32_WIDE : FAM_FP32;
 }
 
 enum { ROLE_FWD_SAVE = 0, ROLE_FWD, ROLE_BWD, ROLE_DW, ROLE_FUSED, ROLE_COUNT };
+static constexpr int ROLE_SPILL_COL[ROLE_COUNT] = {0, -1, 1, 2, 0};      // the role's column of FAMILY_SPILLS (ROLE_FWD saves nothing)
 struct Role {
   Family family;      // FAM_NONE: the plan has no such kernel (ROLE_FUSED)
   int grid;           // workgroups (ROLE_DW: the group count; its launcher derives the grid from DwArgs)
   size_t lds;         // dynamic LDS bytes
   const char* name;
-};
-
-// How the sweeps spill S and Z-bar, and what their readers recompute instead of reading.
-struct SpillFormat {
-  int s24w;              // wide bf16 residual plan (all three kernels bf16): 24-bit three-plane spill format
-  int s0_skip;           // the sweeps do not spill layer 0 (role-split pair): dw_bf16 recomputes its activations
-  int s0_skip32;         // fp32 residual plan: layer 0 not spilled, recomputed by its readers
-  int sl0; size_t sblk;  // compact spill geometry of the role-split plans (kernels.h spill_off); sblk = 0: classic layout
 };
 
 struct pinn_plan_s {
@@ -110,7 +117,7 @@ struct pinn_plan_s {
   int groups;            // dW slabs per layer
   int stagger;           // $PINN_STAGGER, read once at plan creation
   Role role[ROLE_COUNT];
-  SpillFormat spill;
+  Spill spill;           // how the sweeps spill S and Z-bar, and what their readers recompute instead (spill.h)
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -251,21 +258,20 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   if (sb == 1 && bwd_lds(FAM_PIPE, net) > PINN_LDS_MAX) sb = 0;
   if (sf < 0 || sf > 2) sf = 0;
   if (sb < 0 || sb > 2) sb = 0;
-  SpillFormat& sp = p->spill;
   // The role-split sweeps do not spill layer 0 (its saved activations are one FMA pair and one tanh of the point: the
   // reverse sweep and dw_bf16 recompute them), so they only come as a pair, and with the bf16 dW kernel; a request for
   // one of them alone runs that sweep on schedule 1.
-  sp.s0_skip = sf == 2 && sb == 2 && net.prec_dw;
-  if (!sp.s0_skip) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
+  const bool split_pair = sf == 2 && sb == 2 && net.prec_dw;
+  if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
-  sp.s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
+  const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
   // K region must fit twice in the 512-element image rows); $PINN_WSPLIT=0 keeps the 8-wave kernels.
-  const bool wsplit = sp.s24w && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
+  const bool wsplit = s24w && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
                       bwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX;
   // The fused sweeps need the role-split pair on both sides, in one precision, and fit in LDS up to 7 hidden layers at hidden 256; deeper
   // nets keep the two launches.  $PINN_FUSE=0 keeps them too (same-build A/B).
-  const bool fuse = sf == 2 && sb == 2 && sp.s0_skip && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
+  const bool fuse = sf == 2 && sb == 2 && split_pair && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
                     fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
   p->stagger = sw.stagger;
   if (sw.verbose)
@@ -293,14 +299,18 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   p->bytes_fwd = off;
   p->off_sg = off;       off = align_up(off + (size_t)p->role[ROLE_BWD].grid * sg_total(HP, L) * 4, 256);
   p->off_slabs = off;    off = align_up(off + (size_t)(L - 1) * p->groups * HP * HP * 4, 256);
-  const size_t ablk = (size_t)HP * (wide ? 64 : PINN_TILE_COLS);
-  // The role-split pair writes three 16-byte planes per register quad and no layer 0: its S and Z-bar are sized for
-  // exactly that, (L - 1) blocks of 3/4 of the classic HP x 128 floats per tile (5.5 instead of 8.9 GB each at
-  // 6x256 / 360 000 points).  Every other plan keeps the classic [tile][L][HP x columns] layout.
-  sp.s0_skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0;
-  sp.sl0 = sp.s0_skip ? 1 : 0;
-  sp.sblk = sp.s0_skip ? ablk / 4 * 3 : 0;
-  const size_t spill_tile = sp.s0_skip ? (size_t)(L - 1) * sp.sblk : (size_t)L * ablk;      // floats per tile
+  // The spill layout (spill.h).  The role-split pair writes three 16-byte planes per register quad and no layer 0: its
+  // S and Z-bar are sized for exactly that, (L - 1) blocks of 3/4 of the classic HP x 128 floats per tile (5.5 instead
+  // of 8.9 GB each at 6x256 / 360 000 points).  Every other plan keeps [tile][L][HP x columns] blocks: an fp32 residual
+  // plan without layer 0 in them ($PINN_S0_SKIP32=0 opts out), a wide all-bf16 residual plan in the 24-bit format.
+  const size_t ablk = act_block(HP, wide ? 64 : PINN_TILE_COLS);
+  const bool skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0;
+  p->spill = spill_make(split_pair ? SPILL_P24_COMPACT : s24w ? SPILL_P24_WIDE : skip32 ? SPILL_SKIP0 : SPILL_CLASSIC, ablk);
+  for (int r = 0; r < ROLE_COUNT; ++r)
+    if (ROLE_SPILL_COL[r] >= 0 && p->role[r].family && (r != ROLE_DW || p->groups) &&
+        !spill_is(p->spill, ablk, FAMILY_SPILLS[p->role[r].family][ROLE_SPILL_COL[r]]))
+      return fail(-5, "pinn_plan_create: internal error: %s does not implement the plan's spill layout", p->role[r].name);
+  const size_t spill_tile = spill_tile_floats(p->spill, L);
   // (+1 tile: the pipelined kernels work on PAIRS of tiles; an odd count's dummy partner spills into this scratch block)
   p->off_S = off;        off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
   p->off_Zb = off;       off = align_up(off + (size_t)(p->ntiles + 1) * spill_tile * 4, 256);
@@ -308,18 +318,11 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   return 0;
 }
 
-// The spill format as each argument block carries it.  FwdArgs / BwdArgs::s0_skip is the fp32 kind of layer-0
-// recompute only (the role-split sweeps never write layer 0 and need no flag for it); DwArgs::s0_skip is either kind:
-// the dW kernel recomputes layer 0's activations whichever sweep left them out.
-static void stamp_spill(FwdArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip32; }
-static void stamp_spill(BwdArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip32; }
-static void stamp_spill(DwArgs& a, const SpillFormat& f) { a.s24 = f.s24w; a.sl0 = f.sl0; a.sblk = f.sblk; a.s0_skip = f.s0_skip || f.s0_skip32; }
-
 // workspace carving (ws == null: the configure pass, which launches nothing)
 static float* ws_at(void* ws, size_t off) { return ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off) : nullptr; }
 #define WS(p, off) ws_at(ws, (p)->off)
 
-// The argument blocks, each filled in one place.  A value plan's spill format is all zeros, and the residual-only
+// The argument blocks, each filled in one place.  Each carries the plan's spill descriptor, and the residual-only
 // (value-only) fields stay zero in value (residual) mode.
 static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y, int save, float scale) {
   FwdArgs a;
@@ -328,7 +331,7 @@ static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.prep = prep; a.S = save ? WS(plan, off_S) : nullptr;
   a.scale = scale;
   a.partials = WS(plan, off_partials);
-  stamp_spill(a, plan->spill);
+  a.spill = plan->spill;
   return a;
 }
 static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -347,7 +350,7 @@ static BwdArgs bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.prep = prep; a.S = WS(plan, off_S); a.Zb = WS(plan, off_Zb);
   a.scale = scale;
   a.sg = WS(plan, off_sg);
-  stamp_spill(a, plan->spill);
+  a.spill = plan->spill;
   return a;
 }
 static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -366,7 +369,7 @@ static DwArgs dw_args(const pinn_plan_s* plan, void* ws, const float* prep, cons
   d.ntiles = plan->ntiles; d.L = plan->net.L; d.groups = plan->groups;
   d.slabs = WS(plan, off_slabs);
   d.x = x; d.y = y; d.prep = prep; d.n = (int)plan->n;
-  stamp_spill(d, plan->spill);
+  d.spill = plan->spill;
   return d;
 }
 

@@ -12,6 +12,7 @@
 // A_{l-1} (the four activation streams of layer l-1) is recomputed on the fly from the
 // saved (t, z_x, z_y, z_D) instead of being stored a second time.
 #include "kernels.h"
+#include "spill_io.h"
 
 template <int T> struct DwCfg;
 template <> struct DwCfg<1> { static constexpr int TM = 1, TN = 1; };
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
 
   f32x4 zr[4], sr[4];
-  const bool rec = NS == 4 && a.s0_skip && l == 1;      // (uniform per workgroup)
+  const bool rec = NS == 4 && a.spill.skip0 && l == 1;      // (uniform per workgroup)
   f32x4 wx4 = {0.f, 0.f, 0.f, 0.f}, wy4 = wx4, b4 = wx4;
   if (rec) {
     const f32x4* w0 = reinterpret_cast<const f32x4*>(a.prep + prep_w0x(HP));
@@ -59,29 +60,25 @@ __global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
   }
   auto gload = [&](int ch) {
     const int tile = t0 + (ch >> 2), c = ch & 3;
-    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + ((size_t)tile * a.L + l) * act_block(HP)) + 8 * c;
-    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + ((size_t)tile * a.L + (l - 1)) * act_block(HP)) + 8 * c;
+    const float* Zg = a.Zb + spill_off<act_block(HP), 0>(a.spill, tile, l, a.L) + 32 * c;
+    const float* Sg = a.S + spill_off<act_block(HP), 0>(a.spill, tile, l - 1, a.L) + 32 * c;
     const unsigned lo_ = (unsigned)(og * 32 + p);
-    if (rec) {      // layer-1 workgroups, layer 0 not spilled (DwArgs::s0_skip): only the point travels
-#pragma unroll
-      for (int s = 0; s < 4; ++s) zr[s] = __builtin_nontemporal_load(pin_base(Zg + (size_t)s * (HP / 4) * 32) + lo_);
+    if (rec) {      // layer-1 workgroups, layer 0 not stored (Spill::skip0): only the point travels
+      load_planes<4>(Zg, (HP / 4) * 32, lo_, zr);
       const int pt = tile * 32 + 8 * c + p;
       sr[0][0] = pt < a.n ? a.x[pt] : 0.f; sr[0][1] = pt < a.n ? a.y[pt] : 0.f;
       return;
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      zr[s] = __builtin_nontemporal_load(pin_base(Zg + (size_t)s * (HP / 4) * 32) + lo_);
-      sr[s] = __builtin_nontemporal_load(pin_base(Sg + (size_t)s * (HP / 4) * 32) + lo_);
-    }
+    for (int s = 0; s < 4; ++s) { zr[s] = load_plane(Zg, (HP / 4) * 32, s, lo_); sr[s] = load_plane(Sg, (HP / 4) * 32, s, lo_); }
   };
   auto lstore = [&](int buf) {
     f32x4 a0, a1, a2, a3;
-    if (rec) {      // the forward's own fmaf chain and tanhf (fwd.hip layer 0), bit for bit
+    if (rec) {      // layer 0 as the forward computed it (fwd.hip)
       const float px = sr[0][0], py = sr[0][1];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float t = tanhf(fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e]))), zx = wx4[e], zy = wy4[e];
+        float t = layer0_t(wx4[e], wy4[e], b4[e], px, py, TanhLibm()), zx = wx4[e], zy = wy4[e];
         float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         a0[e] = t; a1[e] = d1 * zx; a2[e] = d1 * zy; a3[e] = d2 * (zx * zx + zy * zy) + d1 * 0.f;
       }
@@ -152,6 +149,7 @@ int dw_threads(int HP) { return HP * 2; }
 template <int HP, int NS>
 static int launch_one(const DwArgs& a, hipStream_t s) {
   size_t lds = dw_lds_bytes(HP);
+  if (!spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   return launch_or_configure(&dw_kernel<HP, NS>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
 }
 

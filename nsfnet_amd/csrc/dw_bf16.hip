@@ -38,13 +38,16 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 }
 
 // PPL = points per plane of a tile: 32 (128-column tiles) or 16 (64-column tiles)
-// REC: the activations are layer 0's and were not spilled (DwArgs::s0_skip) - recomputed from the point.  A template
-// parameter, not a run-time flag: the steady-state loop must stay one basic block (see below).
+// REC: the activations are layer 0's and were not stored (Spill::skip0) - recomputed from the point.  P24: S and Z-bar
+// are in the 24-bit format (Spill::quad).  Template parameters, not run-time flags: the steady-state loop must stay one
+// basic block (see below).  The fp32 format with an unstored layer 0 has no reader here: no plan pairs SPILL_SKIP0 with
+// a bf16 dW kernel, and the launcher refuses it.
 template <int HP, int NS, int TERMS, int PPL, bool REC, bool P24>
 __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
   constexpr int CPT = PPL / 8;                 // 32-column chunks per tile
-  constexpr size_t ABLK = (size_t)HP * 4 * PPL; // floats per (tile, layer) activation block
+  constexpr size_t ABLK = act_block(HP, 4 * PPL);
   using DI = DwImg<HP>;
+  static_assert(P24 || !REC, "no fp32-format reader that recomputes layer 0");
   constexpr int T = HP / 32;
   constexpr int TM = DwCfgB<T>::TM, TN = DwCfgB<T>::TN;
   constexpr int WN = T / TN;
@@ -71,8 +74,8 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
   // other buffer - that VALU / ds_write work can sit in the MFMA shadow (4 VALU per MFMA are free on gfx950,
   // and a partner wave's VALU does NOT overlap this wave's MFMAs: tests/micro/mfma_valu_*.hip) - and then
   // requests chunk ch+2 into the registers it has just freed.
-  // Layer-0 activations that the role-split forward did not spill (DwArgs::s0_skip): recomputed from the point with the
-  // forward's own two FMAs and tanh; the point travels in sr[0][0..1] instead of the four saved quads.
+  // Layer-0 activations that the forward did not store: recomputed from the point as the forward computed them
+  // (layer0_t); the point travels in the raw set instead of the saved quads.
   constexpr bool rec = REC;
   f32x4 wx4 = {0.f, 0.f, 0.f, 0.f}, wy4 = wx4, b4 = wx4;
   if (rec) {
@@ -80,7 +83,7 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
     wx4 = w0[og]; wy4 = w0[HP / 4 + og]; b4 = w0[2 * (HP / 4) + og];
   }
   f32x4 zrA[4], srA[4];
-  // P24: S and Z-bar arrive in the 24-bit spill format of the role-split sweeps (bf16_util.h pack24): THREE 16-byte
+  // P24: S and Z-bar arrive in the 24-bit spill format of the role-split sweeps (spill_io.h pack24): THREE 16-byte
   // planes per quad (hi16 of streams 0-1, hi16 of streams 2-3, lo8 of all four) instead of four, same plane geometry,
   // same coalescing; unpacked at the head of the conversion.
   // Two raw sets (A, B): with the 24-bit format TWO chunks are in flight per workgroup (PINN_DWDEPTH 2) - one chunk in
@@ -93,39 +96,23 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
 #ifndef PINN_ABL
 #define PINN_ABL 0      // timing-only (scripts/abl_build.py): 512 = the last hidden layer's Z-bar is not streamed (one resident block re-read)
 #endif
-    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + spill_off(((PINN_ABL & 512) && l == a.L - 1) ? 0 : tile, l, a.L, a.sl0, a.sblk, ABLK)) + 8 * c;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) R.z[k] = __builtin_bit_cast(u32x4, __builtin_nontemporal_load(pin_base(Zg + (size_t)k * (HP / 4) * PPL) + lo_));
+    load_quad24(a.Zb + spill_off<ABLK>(a.spill, ((PINN_ABL & 512) && l == a.L - 1) ? 0 : tile, l, a.L) + 32 * c, (HP / 4) * PPL, lo_, R.z);
     if (rec) {
       const int pt = tile * PPL + 8 * c + p;
       R.px = pt < a.n ? a.x[pt] : 0.f; R.py = pt < a.n ? a.y[pt] : 0.f;
     } else {
-      const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + spill_off(tile, l - 1, a.L, a.sl0, a.sblk, ABLK)) + 8 * c;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) R.s[k] = __builtin_bit_cast(u32x4, __builtin_nontemporal_load(pin_base(Sg + (size_t)k * (HP / 4) * PPL) + lo_));
+      load_quad24(a.S + spill_off<ABLK>(a.spill, tile, l - 1, a.L) + 32 * c, (HP / 4) * PPL, lo_, R.s);
     }
   };
   auto gload = [&](int ch, f32x4 (&zr)[4], f32x4 (&sr)[4]) {
     if (P24) { gload24(ch, rawA); return; }
     const int tile = t0 + ch / CPT, c = ch % CPT;
-    if (rec) {
-      const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + ((size_t)tile * a.L + l) * ABLK) + 8 * c;
-      const unsigned lo_ = (unsigned)(og * PPL + p);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) zr[s] = __builtin_nontemporal_load(pin_base(Zg + (size_t)s * (HP / 4) * PPL) + lo_);
-      const int pt = tile * PPL + 8 * c + p;
-      sr[0][0] = pt < a.n ? a.x[pt] : 0.f; sr[0][1] = pt < a.n ? a.y[pt] : 0.f;
-      return;
-    }
-    // (tile, layer, plane, chunk) bases are uniform: pinned to scalar registers, one 32-bit lane offset
-    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + ((size_t)tile * a.L + l) * ABLK) + 8 * c;
-    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + ((size_t)tile * a.L + (l - 1)) * ABLK) + 8 * c;
     const unsigned lo_ = (unsigned)(og * PPL + p);
+    // (tile, layer, plane, chunk) bases are uniform: pinned to scalar registers, one 32-bit lane offset
+    const float* Zg = a.Zb + spill_off<ABLK, 0>(a.spill, tile, l, a.L) + 32 * c;
+    const float* Sg = a.S + spill_off<ABLK, 0>(a.spill, tile, l - 1, a.L) + 32 * c;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      zr[s] = __builtin_nontemporal_load(pin_base(Zg + (size_t)s * (HP / 4) * PPL) + lo_);
-      sr[s] = __builtin_nontemporal_load(pin_base(Sg + (size_t)s * (HP / 4) * PPL) + lo_);
-    }
+    for (int s = 0; s < 4; ++s) { zr[s] = load_plane(Zg, (HP / 4) * PPL, s, lo_); sr[s] = load_plane(Sg, (HP / 4) * PPL, s, lo_); }
   };
   auto lstore_r = [&](int buf, f32x4 (&zr)[4], f32x4 (&sr)[4], const Raw24& R) {
     if (P24) {
@@ -137,10 +124,10 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
     }
     f32x4 av[4];
     if (rec) {
-      const float px = P24 ? R.px : sr[0][0], py = P24 ? R.py : sr[0][1];
+      const float px = R.px, py = R.py;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float t = fast_tanh(fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e]))), zx = wx4[e], zy = wy4[e];
+        const float t = layer0_t(wx4[e], wy4[e], b4[e], px, py, TanhFast()), zx = wx4[e], zy = wy4[e];
         const float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * (zx * zx + zy * zy);
       }
@@ -290,10 +277,10 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
       }
 }
 
-// P24 = the plan's sweeps are the role-split pair (DwArgs::s0_skip): 24-bit spill format, layer 0 not spilled
-template <int HP, int NS, int TERMS, int PPL, bool P24>
+// P24: 24-bit format; REC0: layer 0 is not stored, so the layer-1 workgroups recompute it
+template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0>
 __global__ __launch_bounds__(HP * 2) void dw_bf16_kernel(DwArgs a) {
-  if (P24 && blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, P24, P24>(a);
+  if (REC0 && blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, REC0, P24>(a);
   else dw_bf16_body<HP, NS, TERMS, PPL, false, P24>(a);
 }
 
@@ -308,11 +295,22 @@ size_t dw_bf16_lds_bytes(int HP) {
   }
 }
 
-template <int HP, int NS, int TERMS, int PPL, bool P24 = false>
-static int launch_one(const DwArgs& a, hipStream_t s) {
-  if (!P24 && HP == 256 && NS == 4 && PPL == 32 && a.s0_skip) return launch_one<HP, NS, TERMS, PPL, HP == 256 && NS == 4 && PPL == 32>(a, s);
+template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0>
+static int launch_fmt(const DwArgs& a, hipStream_t s) {
   size_t lds = lds_bytes_t<HP>();
-  return launch_or_configure(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24, REC0>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
+}
+// The two formats this kernel reads: SPILL_CLASSIC, and - where the role-split pair runs, hidden 256 at 128-column
+// tiles in residual mode - SPILL_P24_COMPACT.  The 24-bit reader follows the quad field, the recompute the layer-0 field.
+template <int HP, int NS, int TERMS, int PPL>
+static int launch_one(const DwArgs& a, hipStream_t s) {
+  constexpr bool CAN_COMPACT = HP == 256 && NS == 4 && PPL == 32;
+  if (!spill_is(a.spill, act_block(HP, 4 * PPL), CAN_COMPACT ? IN_CLASSIC | IN_P24_COMPACT : IN_CLASSIC)) return -1000;
+  const bool p24 = a.spill.quad == SPILL_QUAD_P24, rec0 = a.spill.skip0 != 0;
+  if constexpr (CAN_COMPACT) {
+    if (p24 && rec0) return launch_fmt<HP, NS, TERMS, PPL, true, true>(a, s);
+  }
+  return p24 || rec0 ? -1000 : launch_fmt<HP, NS, TERMS, PPL, false, false>(a, s);
 }
 
 template <int HP, int PPL>

@@ -21,11 +21,11 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 }
 }  // namespace
 
-// P24: S / Z-bar in the 24-bit three-plane spill format (DwArgs::s24; residual mode only) - a template parameter, the
+// P24: S / Z-bar in the 24-bit three-plane spill format (Spill::quad; residual mode only) - a template parameter, the
 // steady-state loop must stay one basic block
 template <int NS, int TERMS, bool P24>
 __global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
-  constexpr int TM = 4, TN = 2, WN = 4, PPL = 16, COLS = 64, CPT = PPL / 8;
+  constexpr int TM = 4, TN = 2, WN = 4, PPL = 16, CPT = PPL / 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, i32 = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -38,7 +38,6 @@ __global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
   const int p = tid & 7, og = tid >> 3;
   const int ogz = bi * 64 + og, oga = bj * 64 + og;
   const bool vz = ogz < HP / 4, va = oga < HP / 4;
-  const size_t blk = (size_t)HP * COLS;
   // accumulator tiles of this wave that lie inside the matrix (uniform per wave)
   bool live[TM][TN];
 #pragma unroll
@@ -58,8 +57,8 @@ __global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
   u32x4 zp[3], sp[3];
   auto gload = [&](int ch) {
     const int tile = t0 + ch / CPT, c = ch % CPT;
-    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + ((size_t)tile * a.L + l) * blk) + 8 * c;
-    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + ((size_t)tile * a.L + (l - 1)) * blk) + 8 * c;
+    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + spill_off<0, 0>(a.spill, tile, l, a.L)) + 8 * c;
+    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + spill_off<0, 0>(a.spill, tile, l - 1, a.L)) + 8 * c;
     const unsigned loz = (unsigned)(ogz * PPL + p), loa = (unsigned)(oga * PPL + p);
     if (P24) {
 #pragma unroll
@@ -190,7 +189,8 @@ size_t dw_bf16_wide_lds_bytes() { return DI::BYTES; }
 
 template <int NS, int TERMS, bool P24 = false>
 static int launch_one(int HP, const DwArgs& a, hipStream_t s) {
-  if (!P24 && NS == 4 && a.s24) return launch_one<NS, TERMS, NS == 4>(HP, a, s);
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
+  if (!P24 && NS == 4 && a.spill.quad == SPILL_QUAD_P24) return launch_one<NS, TERMS, NS == 4>(HP, a, s);
   const int nblk = (HP / 32 + 7) / 8;
   return launch_or_configure(&dw_bf16_wide_kernel<NS, TERMS, P24>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
 }

@@ -3,10 +3,11 @@
 // single block (8 waves x 4x2 accumulator tiles, split-K over tiles, one slab per group).
 // Tiles are 64 columns (16 points x 4 planes), see fwd_wide.hip.
 #include "kernels.h"
+#include "spill_io.h"
 
 template <int NS>
 __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
-  constexpr int TM = 4, TN = 2, WN = 4, LDW = 260, CH = 32, PPL = 16, COLS = 64;
+  constexpr int TM = 4, TN = 2, WN = 4, LDW = 260, CH = 32, PPL = 16;
   extern __shared__ float lds[];
   float* Zs = lds;
   float* As = lds + 2 * CH * LDW;
@@ -21,7 +22,6 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
   const int p = tid & 7, og = tid >> 3;
   const int ogz = bi * 64 + og, oga = bj * 64 + og;
   const bool vz = ogz < HP / 4, va = oga < HP / 4;
-  const size_t blk = (size_t)HP * COLS;
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
 
   f32x4 zr[4], sr[4];
-  const bool rec = NS == 4 && a.s0_skip && l == 1;      // layer-1 workgroups, layer 0 not spilled (uniform per workgroup)
+  const bool rec = NS == 4 && a.spill.skip0 && l == 1;      // layer-1 workgroups, layer 0 not stored (uniform per workgroup)
   f32x4 wx4 = {0.f, 0.f, 0.f, 0.f}, wy4 = wx4, b4 = wx4;
   if (rec && va) {
     const f32x4* w0 = reinterpret_cast<const f32x4*>(a.prep + prep_w0x(HP));
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
   }
   auto gload = [&](int ch) {
     const int tile = t0 + ch / (PPL / 8), c = ch % (PPL / 8);
-    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + ((size_t)tile * a.L + l) * blk) + 8 * c;
-    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + ((size_t)tile * a.L + (l - 1)) * blk) + 8 * c;
+    const f32x4* Zg = reinterpret_cast<const f32x4*>(a.Zb + spill_off<0, 0>(a.spill, tile, l, a.L)) + 8 * c;
+    const f32x4* Sg = reinterpret_cast<const f32x4*>(a.S + spill_off<0, 0>(a.spill, tile, l - 1, a.L)) + 8 * c;
     const unsigned loz = (unsigned)(ogz * PPL + p), loa = (unsigned)(oga * PPL + p);
     if (rec) {
 #pragma unroll
@@ -58,11 +58,11 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
   };
   auto lstore = [&](int buf) {
     f32x4 a0, a1, a2, a3;
-    if (rec) {      // the forward's own fmaf chain and tanhf (fwd_wide.hip layer 0), bit for bit; padded features: all zero
+    if (rec) {      // layer 0 as the forward computed it (fwd_wide.hip); padded features: all zero
       const float px = sr[0][0], py = sr[0][1];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float t = va ? tanhf(fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e]))) : 0.f, zx = wx4[e], zy = wy4[e];
+        float t = va ? layer0_t(wx4[e], wy4[e], b4[e], px, py, TanhLibm()) : 0.f, zx = wx4[e], zy = wy4[e];
         float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         a0[e] = t; a1[e] = d1 * zx; a2[e] = d1 * zy; a3[e] = d2 * (zx * zx + zy * zy);
       }
@@ -136,6 +136,7 @@ int launch_dw_wide(int HP, int NS, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
   const int T = HP / 32, nblk = (T + 7) / 8;
   size_t lds = dw_wide_lds_bytes();
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   dim3 grid(a.groups, a.L - 1, nblk * nblk);
   if (a.configure) {   // raises the limit of both stream counts' kernels, whichever the plan has
     int rc = launch_or_configure(&dw_wide_kernel<4>, grid, dim3(512), lds, s, 1, a, HP);

@@ -13,6 +13,7 @@
 // the four 32-column blocks (= the four streams of 32 points), so the tanh chain rule
 // that mixes the four streams of one (point, feature) is lane-local on the accumulators.
 #include "kernels.h"
+#include "spill_io.h"
 #include "point_stage.h"
 
 template <int HP, int NS>
@@ -53,17 +54,17 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
         int o = ob + mfma_row(r, h);
         float wx = P[prep_w0x(HP) + o], wy = P[prep_w0y(HP) + o], b = P[prep_b0(HP) + o];
         if (NS == 4) {
-          acc[0][r] = fmaf(wx, px[0], fmaf(wy, py[0], b));
+          acc[0][r] = layer0_z(wx, wy, b, px[0], py[0]);
           acc[1][r] = wx; acc[2][r] = wy; acc[3][r] = 0.f;
         } else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j][r] = fmaf(wx, px[j], fmaf(wy, py[j], b));
+          for (int j = 0; j < 4; ++j) acc[j][r] = layer0_z(wx, wy, b, px[j], py[j]);
         }
       }
     }
     for (int l = 0; l < L; ++l) {
       // ------------- tanh + chain rule on the accumulators; save; restage in LDS -------------
-      float* Sl = a.S ? a.S + ((size_t)tile * L + l) * act_block(HP) : nullptr;
+      float* Sl = a.S ? a.S + spill_off<act_block(HP), 0>(a.spill, tile, l, L) : nullptr;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 s0, s1, s2, s3;
@@ -86,13 +87,9 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
             s0[e] = t0; s1[e] = t1; s2[e] = t2; s3[e] = t3;
           }
         }
-        if (Sl && !(NS == 4 && l == 0 && a.s0_skip)) {      // (layer 0 is recomputed by its readers: FwdArgs::s0_skip)
+        if (Sl && !(NS == 4 && l == 0 && a.spill.skip0)) {      // (layer 0 is recomputed by its readers: Spill::skip0)
           const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * 32 + col);
-          const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
-          __builtin_nontemporal_store(s0, pin_base(S4 + 0 * (HP / 4) * 32) + so);   // streamed once: nontemporal
-          __builtin_nontemporal_store(s1, pin_base(S4 + 1 * (HP / 4) * 32) + so);
-          __builtin_nontemporal_store(s2, pin_base(S4 + 2 * (HP / 4) * 32) + so);
-          __builtin_nontemporal_store(s3, pin_base(S4 + 3 * (HP / 4) * 32) + so);
+          store_quad4(Sl, (HP / 4) * 32, so, s0, s1, s2, s3);
         }
       }
       __syncthreads();
@@ -178,6 +175,7 @@ size_t fwd_lds_bytes(int HP) { return ((size_t)HP * 128 + (size_t)(HP / 32) * 4 
 template <int HP, int NS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_lds_bytes(HP);
+  if (a.S && !spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   return launch_or_configure(&fwd_kernel<HP, NS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

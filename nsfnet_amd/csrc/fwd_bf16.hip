@@ -73,12 +73,12 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
         int o = ob + mfma_row(r, h);
         float wx = P[prep_w0x(HP) + o], wy = P[prep_w0y(HP) + o], b = P[prep_b0(HP) + o];
         if (NS == 4) {
-          float z = fmaf(wx, px[0], fmaf(wy, py[0], b));
+          float z = layer0_z(wx, wy, b, px[0], py[0]);
           if (COLS == 128) { acc[0][r] = z; acc[1][r] = wx; acc[2 % NTL][r] = wy; acc[3 % NTL][r] = 0.f; }
           else { acc[0][r] = hi ? wx : z; acc[1][r] = hi ? 0.f : wy; }
         } else {
 #pragma unroll
-          for (int j = 0; j < NTL; ++j) acc[j][r] = fmaf(wx, px[j], fmaf(wy, py[j], b));
+          for (int j = 0; j < NTL; ++j) acc[j][r] = layer0_z(wx, wy, b, px[j], py[j]);
         }
       }
     }
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
         }
       }
       asm volatile("" ::: "memory");
-      float* Sl = a.S ? a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS) : nullptr;
+      float* Sl = a.S ? a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L) : nullptr;
       // one register quad (4 consecutive features `o4*4..`, one column) of the four planes:
       // restage as bf16 hi/lo (8 bytes at [pp][chunk] + 8h per plane) and spill the saved values
       auto emit = [&](int g, const f32x4& a0, const f32x4& a1, const f32x4& a2, const f32x4& a3,
@@ -122,12 +122,8 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
           // saddr + voffset form instead of a 64-bit VALU address per plane
           const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
           constexpr size_t PLQ = (size_t)(HP / 4) * PPL;          // f32x4 per plane
-          const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
           // streamed once: nontemporal keeps the spill out of L2's way (measured -3 % on the kernel)
-          __builtin_nontemporal_store(s0, pin_base(S4 + 0 * PLQ) + so);
-          __builtin_nontemporal_store(s1, pin_base(S4 + 1 * PLQ) + so);
-          __builtin_nontemporal_store(s2, pin_base(S4 + 2 * PLQ) + so);
-          __builtin_nontemporal_store(s3, pin_base(S4 + 3 * PLQ) + so);
+          store_quad4(Sl, PLQ, so, s0, s1, s2, s3);
         }
       };
       auto chain = [&](float z, float zx, float zy, float zd, int e, f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3,
@@ -326,6 +322,7 @@ size_t fwd_bf16_lds_bytes(int HP, int L, int cols) {
 template <int HP, int NS, int TERMS, int COLS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
+  if (a.S && !spill_is(a.spill, act_block(HP, COLS), IN_CLASSIC)) return -1000;
   return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(HP, 1) void fwd_pipe_kernel(FwdArgs a) {
       }
     };
     // ------------- epilogue state -------------
-    float* const Sl = a.S + ((size_t)tileE * L + lE) * ((size_t)HP * COLS);
+    float* const Sl = a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tileE, lE, L);
     const float* const bE = biasL + (size_t)lE * HP;
     float po[3][4];
 #pragma unroll
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(HP, 1) void fwd_pipe_kernel(FwdArgs a) {
         float z, zx, zy, zd;
         if (e == 0) { b4 = b4n; if (first) { wx4 = wx4n; wy4 = wy4n; } }
         if (first) {
-          z = fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e])); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
+          z = layer0_z(wx4[e], wy4[e], b4[e], px, py); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
         } else {
           z = acc_read(accE[fb][0][r]) + b4[e]; zx = acc_read(accE[fb][1][r]); zy = acc_read(accE[fb][2][r]);
           zd = acc_read(accE[fb][3][r]);
@@ -367,6 +367,7 @@ size_t fwd_pipe_lds_bytes(int HP, int L) { (void)HP; return PipeLds<256>::bytes(
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = PipeLds<HP>::bytes(a.L);
+  if (a.S && !spill_is(a.spill, act_block(HP), IN_CLASSIC)) return -1000;
   return launch_or_configure(&fwd_pipe_kernel<HP, TERMS>, dim3(grid), dim3(HP), lds, s, a.configure, a);
 }
 

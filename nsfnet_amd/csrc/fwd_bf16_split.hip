@@ -83,7 +83,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
   auto bias = [&](int l) {      // bias rows from LDS
     return [=](int, int, int o, int) { return *reinterpret_cast<const f32x4*>(biasL + (size_t)l * HP + o); };
   };
-  auto S_of = [&](int tile, int l) { return a.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS)>(a.spill, tile, l, L); };
   auto none = [](auto&&...) {};      // no kernel work in this hook
 
   // Program of a group, one op per phase: per tile E0 M1 E1 ... M_{L-1} E_{L-1} (2L - 1 phases, four barriers each);
@@ -127,6 +127,7 @@ size_t fwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitLds<256>::byte
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitLds<HP>::bytes(a.L);
+  if (a.S && !spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
   return launch_or_configure(&fwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 

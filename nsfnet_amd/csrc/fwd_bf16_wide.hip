@@ -62,11 +62,11 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
           int o = ob + mfma_row(r, h);
           float wx = P[prep_w0x(HP) + o], wy = P[prep_w0y(HP) + o], b = P[prep_b0(HP) + o];
           if (NS == 4) {
-            float z = fmaf(wx, px[0], fmaf(wy, py[0], b));
+            float z = layer0_z(wx, wy, b, px[0], py[0]);
             acc[m][0][r] = hi ? wx : z; acc[m][1][r] = hi ? 0.f : wy;
           } else {
 #pragma unroll
-            for (int j = 0; j < NTL; ++j) acc[m][j][r] = fmaf(wx, px[j], fmaf(wy, py[j], b));
+            for (int j = 0; j < NTL; ++j) acc[m][j][r] = layer0_z(wx, wy, b, px[j], py[j]);
           }
         }
       }
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
           }
       }
       asm volatile("" ::: "memory");
-      float* Sl = a.S ? a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS) : nullptr;
+      float* Sl = a.S ? a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L) : nullptr;
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         if (m >= mcount) continue;
@@ -134,18 +134,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
             if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
             if (Sl) {
               const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
-              const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
-              if (a.s24) {      // 24-bit three-plane spill (bf16_util.h pack24): three instructions instead of four
-                u32x4 pk[3];
-                pack24_quad(s0, s1, s2, s3, pk);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(__builtin_bit_cast(f32x4, pk[k]), pin_base(S4 + k * (HP / 4) * PPL) + so);
-              } else {
-                __builtin_nontemporal_store(s0, pin_base(S4 + 0 * (HP / 4) * PPL) + so);
-                __builtin_nontemporal_store(s1, pin_base(S4 + 1 * (HP / 4) * PPL) + so);
-                __builtin_nontemporal_store(s2, pin_base(S4 + 2 * (HP / 4) * PPL) + so);
-                __builtin_nontemporal_store(s3, pin_base(S4 + 3 * (HP / 4) * PPL) + so);
-              }
+              store_quad(a.spill.quad, Sl, (HP / 4) * PPL, so, s0, s1, s2, s3);
             }
           }
         } else {
@@ -317,6 +306,7 @@ int fwd_bf16_wide_threads(int HP) { return ((HP / 32 + 1) / 2) * 64; }
 template <int HP, int NS, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP>(a.L);
+  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
   return launch_or_configure(&fwd_bf16_wide_kernel<HP, NS, TERMS>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
 }
 

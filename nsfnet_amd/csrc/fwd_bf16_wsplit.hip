@@ -65,7 +65,7 @@ __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
     }
     if (ptile >= 0 && ptile < a.ntiles && q == 1) residual_point_stage<PPL, COLS>(a, outvG, ptile, gtid, npad, lsum);
   };
-  auto S_of = [&](int tile, int l) { return a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS); };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L); };
   auto none = [](auto&&...) {};      // no kernel work in this hook
 
   // Program of a group: per tile E0 M1 E1 ... M_{L-1} E_{L-1}; group 1 runs it one phase behind group 0
@@ -110,6 +110,7 @@ size_t fwd_wsplit_lds_bytes(int HP) {
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::fwd_bytes();
+  if (a.S && !spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
   return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 

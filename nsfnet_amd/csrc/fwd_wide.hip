@@ -9,6 +9,7 @@
 // every lane owns all four streams of 8 of the 16 accumulator rows.  With up to 16 waves per
 // workgroup a wave has 128 VGPRs, so the weight slice streams through a small register ring.
 #include "kernels.h"
+#include "spill_io.h"
 #include "point_stage.h"
 
 template <int HP, int NS>
@@ -49,11 +50,11 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
         int o = ob + mfma_row(r, h);
         float wx = P[prep_w0x(HP) + o], wy = P[prep_w0y(HP) + o], b = P[prep_b0(HP) + o];
         if (NS == 4) {            // tile 0: streams (value | d/dx), tile 1: streams (d/dy | Laplacian)
-          acc[0][r] = hi ? wx : fmaf(wx, px[0], fmaf(wy, py[0], b));
+          acc[0][r] = hi ? wx : layer0_z(wx, wy, b, px[0], py[0]);
           acc[1][r] = hi ? 0.f : wy;
         } else {
-          acc[0][r] = fmaf(wx, px[0], fmaf(wy, py[0], b));
-          acc[1][r] = fmaf(wx, px[1], fmaf(wy, py[1], b));
+          acc[0][r] = layer0_z(wx, wy, b, px[0], py[0]);
+          acc[1][r] = layer0_z(wx, wy, b, px[1], py[1]);
         }
       }
     }
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
 #pragma unroll
         for (int q = 0; q < PRE; ++q) wq[q] = wf[q * 64];
       }
-      float* Sl = a.S ? a.S + ((size_t)tile * L + l) * ((size_t)HP * COLS) : nullptr;
+      float* Sl = a.S ? a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L) : nullptr;
       if (NS == 4) {
         // lanes 0-15 keep register rows 0-7, lanes 16-31 rows 8-15; both get all four streams
 #pragma unroll
@@ -91,13 +92,9 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
             Xo[48] = d2 * (zx * zx + zy * zy) + d1 * zd;
             s0[e] = t; s1[e] = zx; s2[e] = zy; s3[e] = zd;
           }
-          if (Sl && !(l == 0 && a.s0_skip)) {      // (layer 0 is recomputed by its readers: FwdArgs::s0_skip)
+          if (Sl && !(l == 0 && a.spill.skip0)) {      // (layer 0 is recomputed by its readers: Spill::skip0)
             const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
-            const f32x4* S4 = reinterpret_cast<const f32x4*>(Sl);
-            __builtin_nontemporal_store(s0, pin_base(S4 + 0 * (HP / 4) * PPL) + so);
-            __builtin_nontemporal_store(s1, pin_base(S4 + 1 * (HP / 4) * PPL) + so);
-            __builtin_nontemporal_store(s2, pin_base(S4 + 2 * (HP / 4) * PPL) + so);
-            __builtin_nontemporal_store(s3, pin_base(S4 + 3 * (HP / 4) * PPL) + so);
+            store_quad4(Sl, (HP / 4) * PPL, so, s0, s1, s2, s3);
           }
         }
       } else {
@@ -189,6 +186,7 @@ size_t fwd_wide_lds_bytes(int HP) { return ((size_t)HP * 64 + (size_t)(HP / 32) 
 template <int HP, int NS>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_wide_lds_bytes(HP);
+  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   return launch_or_configure(&fwd_wide_kernel<HP, NS>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 

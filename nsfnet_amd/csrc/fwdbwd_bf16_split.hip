@@ -72,9 +72,9 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
   // The dummy partner of an odd tile count reads its OWN S (the +1 scratch block its forward just wrote), not tile 0's as
   // bwd_bf16_split.hip does: here tile 0 may still be in its forward on another workgroup.  Its output adjoints are zero,
   // so its z-bars are zeros either way.
-  auto S_of = [&](int tile, int l) { return a.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
-  auto Sw_of = [&](int tile, int l) { return fa.S + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
-  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off(tile, l, L, a.sl0, a.sblk, (size_t)HP * COLS); };
+  auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS)>(a.spill, tile, l, L); };
+  auto Sw_of = [&](int tile, int l) { return fa.S + spill_off<act_block(HP, COLS)>(a.spill, tile, l, L); };
+  auto Z_of = [&](int tile, int l) { return a.Zb + spill_off<act_block(HP, COLS)>(a.spill, tile, l, L); };
   auto none = [](auto&&...) {};      // no kernel work in this hook
 
   // ---------------- point stage + output adjoints of column col (start of XB) ----------------
@@ -221,10 +221,11 @@ size_t fwdbwd_split_lds_bytes(int HP, int L) { (void)HP; return FusedLds<256>::b
 template <int HP, int TERMS>
 static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = FusedLds<HP>::bytes(a.L);
+  if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT) || !spill_is(fa.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
   return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
 }
 
-// residual mode, MSE seeds, role-split plan (HP = 256, s0_skip, compact 24-bit spill; the caller checks)
+// residual mode, MSE seeds, role-split plan (HP = 256, SPILL_P24_COMPACT)
 int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
   return terms == 3 ? launch_one<256, 3>(fa, a, grid, s) : launch_one<256, 1>(fa, a, grid, s);

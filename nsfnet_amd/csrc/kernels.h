@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "layout.h"
+#include "spill.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -39,7 +40,7 @@ struct FwdArgs {
   int L;            // hidden layers
   int n_out;        // 3 (u,v,p) or 1 (e)
   const float* prep;
-  float* S;         // [tile][L][HP*128] saved (t, z_x, z_y, z_D) or null
+  float* S;         // saved (t, z_x, z_y, z_D) per (tile, layer) block (spill.h) or null
   // residual mode (4 streams)
   float* fld;       // [FLD_COUNT][npad]
   const float* e;   // entropy-net output per point or null
@@ -55,26 +56,15 @@ struct FwdArgs {
   float* partials;       // [grid][PINN_NLOSS]
   int stagger;           // start offset unit (x 4096 cycles x (block*5 mod 8)); 0 = off
   int configure;         // 1: do not launch, only raise the kernel's dynamic-LDS limit (pinn_plan_create)
-  int s24;               // wide bf16 residual kernels: S / Z-bar in the 24-bit three-plane spill format (bf16_util.h pack24)
-  // role-split sweeps (compact spill): block (tile, layer l) of S / Z-bar starts at ((size_t)tile * (L - sl0) + (l - sl0)) * sblk
-  // floats - only what the sweeps write is allocated: three 16-byte planes, no layer 0 (sl0 = 1)
-  int sl0; size_t sblk;
-  // fp32 kernels, residual mode: layer 0's saved activations are not spilled - (tanh(w0x x + w0y y + b0), w0x, w0y, 0)
-  // are recomputed where they are read (the reverse sweep's layer-0 epilogue, the layer-1 workgroups of the dW kernel)
-  // with the forward's own fmaf chain and tanhf: the same values, a sixth of S at six layers neither written nor read twice
-  int s0_skip;
+  Spill spill;           // the plan's S / Z-bar format (spill.h)
 };
-// float offset of the spill block of (tile, layer l); `sblk` == 0 selects the classic [tile][L][HP x columns] layout
-PINN_HD size_t spill_off(int tile, int l, int L, int sl0, size_t sblk, size_t classic) {
-  return sblk ? ((size_t)tile * (L - sl0) + (l > sl0 ? l - sl0 : 0)) * sblk : ((size_t)tile * L + l) * classic;
-}
 
 struct BwdArgs {
   const float* x; const float* y;
   int n, ntiles, L, n_out;
   const float* prep;
   const float* S;
-  float* Zb;             // [tile][L][HP*128] z-adjoints (layers 1..L-1 used)
+  float* Zb;             // z-adjoints per (tile, layer) block (layers 1..L-1 used)
   // residual mode
   const float* fld; const float* e; const float* w; const float* vis_used;
   float coef_eq[4];      // 2*alpha_e*c_k/N_total
@@ -84,9 +74,7 @@ struct BwdArgs {
   const float* oadj;     // [4][npad]
   float* sg;             // [grid][sg_total]
   int configure;         // see FwdArgs
-  int s24;               // see FwdArgs
-  int sl0; size_t sblk;  // see FwdArgs
-  int s0_skip;           // see FwdArgs
+  Spill spill;           // see FwdArgs
 };
 
 struct DwArgs {
@@ -94,12 +82,10 @@ struct DwArgs {
   int ntiles, L, groups;
   float* slabs;          // [(L-1)][groups][HP*HP]
   int configure;         // see FwdArgs
-  // Layer-0 activations recomputed instead of read (the role-split sweeps do not spill them: they are one FMA and one
-  // tanh of the point, fwd_bf16_split.hip): the points, the prepared parameters (w0x | w0y | b0 lead them) and n.
-  int s0_skip;
-  int s24;               // see FwdArgs (dw_bf16_wide)
+  // where the plan does not store layer 0 (Spill::skip0), the layer-1 workgroups recompute its activations: the
+  // points, the prepared parameters (w0x | w0y | b0 lead them) and n
   const float* x; const float* y; const float* prep; int n;
-  int sl0; size_t sblk;  // see FwdArgs
+  Spill spill;           // see FwdArgs
 };
 
 struct ReduceSrc { const float* slabs; int groups; const float* sg; int nwg; };

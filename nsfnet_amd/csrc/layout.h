@@ -58,8 +58,8 @@ PINN_HD int sg_total(int HP, int L) { return L * HP + 6 * HP + 4; }
 // row of a 32x32 MFMA accumulator register r (0..15) for lane half h (lane>>5)
 PINN_HD int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// number of floats in one (tile, layer) activation block
-PINN_HD size_t act_block(int HP) { return (size_t)HP * PINN_TILE_COLS; }
+// number of floats in one (tile, layer) activation block of four fp32 planes (spill.h: `ablk`)
+PINN_HD constexpr size_t act_block(int HP, int cols = PINN_TILE_COLS) { return (size_t)HP * cols; }
 
 // flat (state_dict order) parameter offsets: layer_0.weight (H,2), layer_0.bias (H),
 // layer_l.weight (H,H), layer_l.bias (H) ..., layer_L.weight (n_out,H), layer_L.bias (n_out)

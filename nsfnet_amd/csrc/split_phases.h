@@ -33,7 +33,7 @@ struct SplitWave {
   // weight-fragment ring [feature block][k-step % RING].  It lives across phases: the first WPRE k-steps of an M / G
   // phase are requested during the last quad of the E phase before it, so no M / G phase opens with an L2 round trip.
   u32x4 wh[2][RING], wl[2][RING];
-  u32x4 sq[SQ + 1][3];                    // saved-activation quads in flight, 24-bit format (bf16_util.h pack24)
+  u32x4 sq[SQ + 1][3];                    // saved-activation quads in flight, 24-bit format (spill_io.h pack24)
   u32x4 skeep[8][3];                      // S_{L-1} kept in registers from the forward to the reverse epilogue (KEEP)
   bool have_parked = false;               // the last E phase parked region 3 (reverse sweep: G dumps it in quarter 0)
 
@@ -186,7 +186,7 @@ struct SplitWave {
           const int r = 4 * g + e;
           float z, zx, zy, zd;
           if (first) {
-            z = fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e])); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
+            z = layer0_z(wx4[e], wy4[e], b4[e], px, py); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
           } else {
             z = acc[fb][0][r] + b4[e]; zx = acc[fb][1][r]; zy = acc[fb][2][r]; zd = acc[fb][3][r];
           }
@@ -276,12 +276,9 @@ struct SplitWave {
         }
         f32x4 sc[4];
         if (last) {
-          // layer 0 is not spilled: same two FMAs and tanh as the forward, bit for bit
-          const f32x4 wx4 = *reinterpret_cast<const f32x4*>(w0L + o), wy4 = *reinterpret_cast<const f32x4*>(w0L + HP + o);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(w0L + 2 * HP + o);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[0][e] = fast_tanh(fmaf(wx4[e], pxE, fmaf(wy4[e], pyE, b4[e])));
-          sc[1] = wx4; sc[2] = wy4; sc[3] = f32x4{0.f, 0.f, 0.f, 0.f};
+          // layer 0 is not stored: recomputed as the forward computed it
+          layer0_saved(*reinterpret_cast<const f32x4*>(w0L + o), *reinterpret_cast<const f32x4*>(w0L + HP + o),
+                       *reinterpret_cast<const f32x4*>(w0L + 2 * HP + o), pxE, pyE, TanhFast(), sc[0], sc[1], sc[2], sc[3]);
         } else if (first && KEEP) {
 #pragma unroll
           for (int p = 0; p < 4; ++p) {

@@ -188,7 +188,7 @@ struct WSplitWave {
         const int r = 4 * k + e;
         float z, zx, zy, zd;
         if (first) {
-          z = fmaf(wx4[e], px, fmaf(wy4[e], py, b4[e])); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
+          z = layer0_z(wx4[e], wy4[e], b4[e], px, py); zx = wx4[e]; zy = wy4[e]; zd = 0.f;
         } else {
           z = acc[bq][0][r] + b4[e]; zx = acc[bq][0][r + 8]; zy = acc[bq][1][r]; zd = acc[bq][1][r + 8];
         }
@@ -306,12 +306,9 @@ struct WSplitWave {
       const int bq = item_bq(i), k = item_k(i), o = quad_o(bq, k, hi, h);
       f32x4 sc[4];
       if (last) {
-        // layer 0: same two FMAs and tanh as the forward, bit for bit
-        const f32x4 wx4 = *reinterpret_cast<const f32x4*>(w0 + o), wy4 = *reinterpret_cast<const f32x4*>(w0 + HP + o);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(w0 + 2 * HP + o);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sc[0][e] = fast_tanh(fmaf(wx4[e], pxE, fmaf(wy4[e], pyE, b4[e])));
-        sc[1] = wx4; sc[2] = wy4; sc[3] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // layer 0: recomputed as the forward computed it (stored too in this layout, but not read back here)
+        layer0_saved(*reinterpret_cast<const f32x4*>(w0 + o), *reinterpret_cast<const f32x4*>(w0 + HP + o),
+                     *reinterpret_cast<const f32x4*>(w0 + 2 * HP + o), pxE, pyE, TanhFast(), sc[0], sc[1], sc[2], sc[3]);
       } else {
 #pragma unroll
         for (int p = 0; p < 4; ++p) sc[p] = unpack24_plane(sq[i % (SQ + 1)], p);

@@ -32,7 +32,7 @@ def split(x):
 
 
 def round24(x):
-    """The 24-bit spill: add 0x80 to the integer image, drop the low byte (bf16_util.h pack24)."""
+    """The 24-bit spill: add 0x80 to the integer image, drop the low byte (spill_io.h pack24)."""
     u = np.ascontiguousarray(x, dtype=F).view(np.uint32)
     return ((u + np.uint32(0x80)) & np.uint32(0xFFFFFF00)).view(F)
 

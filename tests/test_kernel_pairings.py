@@ -2,8 +2,8 @@
 
 pinn_plan_create pairs a forward sweep, a reverse sweep and a dW kernel from the three precisions and the schedule
 switches.  The kernels of a plan meet only in the S / Z-bar spill of the workspace, so every pairing is a contract
-between kernels of different files: the layout (spill_off, sl0, sblk), the format (fp32 planes or the 24-bit
-three-plane format) and whether layer 0 is spilled or recomputed by its readers.  tests/test_plan_census.py fingerprints
+between kernels of different files: the layout (csrc/spill.h: block size, first stored layer), the format (fp32 planes or
+the 24-bit three-plane format) and whether layer 0 is spilled or recomputed by its readers.  tests/test_plan_census.py fingerprints
 which kernels a plan names; it cannot tell whether they agree on what lies in the spill.  test_tile_loops.py runs three
 pairings of the 6x256 net and two of the 4x400 net at looping point counts; this module runs the others a precision
 triple or a switch selects - the pipelined sweeps, fp32 sweeps reading what bf16 sweeps spilled and the reverse, each
@@ -61,7 +61,7 @@ ROWS_256 = [
          (("PINN_FWD_SCHED", "0"), ("PINN_BWD_SCHED", "1"))),
     # the 64-column bf16 kernels: 16-point tiles, up to two workgroups per CU
     _row(X3, ("fwd_bf16_kernel", "bwd_bf16_kernel", "dw_bf16_kernel"), 16, (("PINN_TILE_COLS", "64"),)),
-    # the 128-column fp32 kernels, layer 0 recomputed by its readers (s0_skip32) and spilled
+    # the 128-column fp32 kernels, layer 0 recomputed by its readers (SPILL_SKIP0) and spilled
     _row(F32, ("fwd_kernel", "bwd_kernel", "dw_kernel"), 32, (("PINN_TILE_COLS", "128"),)),
     _row(F32, ("fwd_kernel", "bwd_kernel", "dw_kernel"), 32, (("PINN_TILE_COLS", "128"), ("PINN_S0_SKIP32", "0"))),
     # the unfused role-split pair: the default pairing of 8x256

@@ -115,7 +115,7 @@ def test_mixed_schedules_share_the_fp32_spill_layout(monkeypatch, fs, bs):
 
 @pytest.mark.parametrize("H,L,N", [(128, 4, 333), (256, 3, 150), (50, 2, 40)])
 def test_fp32_layer0_recompute_matches_the_spilled_version(monkeypatch, H, L, N):
-    """fp32 mode does not spill layer 0 (FwdArgs::s0_skip): the reverse sweep and the layer-1 workgroups of the dW kernel
+    """fp32 mode does not spill layer 0 (Spill::skip0): the reverse sweep and the layer-1 workgroups of the dW kernel
     recompute (tanh(w0x x + w0y y + b0), w0x, w0y, 0) with the forward's own fmaf chain and tanhf.  The loss sums (forward
     only) must be BITWISE those of the spilled version ($PINN_S0_SKIP32=0); the gradient agrees to fp32 rounding (the
     compiler specialises the layer-0 epilogue for z_D = 0 and contracts a few products differently), in the narrow and in

@@ -1,4 +1,4 @@
-"""The 24-bit spill format of the role-split / wide bf16 sweeps (nsfnet_amd/csrc/bf16_util.h pack24 / unpack24), checked on
+"""The 24-bit spill format of the role-split / wide bf16 sweeps (nsfnet_amd/csrc/spill_io.h pack24 / unpack24), checked on
 the CPU: the v_perm_b32 byte selectors are read from the header and emulated, so a changed constant fails here before it
 reaches a GPU.  (The end-to-end statement - the kernels with this format against the fp64 oracle - is the GPU suite.)"""
 import os
@@ -6,7 +6,7 @@ import re
 
 import numpy as np
 
-HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nsfnet_amd", "csrc", "bf16_util.h")
+HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nsfnet_amd", "csrc", "spill_io.h")
 
 
 def v_perm_b32(s0, s1, sel):
@@ -27,7 +27,7 @@ def v_perm_b32(s0, s1, sel):
 
 def _selectors():
     src = open(HDR).read()
-    body = src[src.index("void pack24("):src.index("// tanh for the bf16 modes")]
+    body = src[src.index("void pack24("):src.index("// a register quad's four planes")]
     sels = [int(m, 16) for m in re.findall(r"0x([0-9a-fA-F]{8})u", body)]
     # pack24: hi pair selector (twice), two lo selectors; unpack24: four selectors
     assert len(sels) >= 8, sels
@@ -60,7 +60,7 @@ def test_pack24_round_trip_is_round_to_24_bits():
 def test_pack24_keeps_the_nans_and_infinities_arithmetic_produces():
     """A diverged activation must still poison the reverse sweep after the spill.  Pinned: +-infinity, the hardware's
     quiet NaNs and every quiet NaN with a payload below 0x7fff80 keep their class; the largest finite value rounds up to
-    infinity.  Documented in bf16_util.h and NOT guarded (three VALU per value in the hottest loop): an all-ones payload
+    infinity.  Documented in spill_io.h and NOT guarded (three VALU per value in the hottest loop): an all-ones payload
     carries into the exponent and reads back as zero - no instruction of the sweeps produces such a NaN."""
     hi_a, hi_b, lo_a, lo_b, u0, u1, u2, u3 = _selectors()
     cases = [0x7fc00000, 0xffc00000, 0x7fc00001, 0xffd12345, 0x7fff7f7f, 0x7f800000, 0xff800000, 0x7f7fffff]
