@@ -4,10 +4,11 @@
 // hi/lo split operands (bf16_util.h); the z-adjoint tile lives in LDS as
 // X[hi|lo][plane][col][k] bf16 (swizzled); Zb spilled to HBM stays fp32 (layout.h).
 // COLS = 128 / 64: tile geometry as in fwd_bf16.hip.
+// Everything of the tile program lives here except what wave8_bodies.h holds for the four 8-wave bf16 sweeps: the quad
+// restage and the closing flush of the skinny gradients.
 #include "kernels.h"
 #include "point_stage.h"
-#include "bf16_util.h"
-#include "reduce_util.h"
+#include "wave8_bodies.h"
 
 template <int HP, int NS, int TERMS, int COLS>
 __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
@@ -140,19 +141,10 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
         }
         if (l > 0) {
           const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-          u32x2 vh, vl;
-          split4(z0[0], z0[1], z0[2], z0[3], vh, vl);
-          *reinterpret_cast<u32x2*>(Xb + 0 * XI::PLANE * 2 + off) = vh;
-          if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 0 * XI::PLANE * 2 + off) = vl;
-          split4(z1[0], z1[1], z1[2], z1[3], vh, vl);
-          *reinterpret_cast<u32x2*>(Xb + 1 * XI::PLANE * 2 + off) = vh;
-          if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 1 * XI::PLANE * 2 + off) = vl;
-          split4(z2[0], z2[1], z2[2], z2[3], vh, vl);
-          *reinterpret_cast<u32x2*>(Xb + 2 * XI::PLANE * 2 + off) = vh;
-          if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 2 * XI::PLANE * 2 + off) = vl;
-          split4(z3[0], z3[1], z3[2], z3[3], vh, vl);
-          *reinterpret_cast<u32x2*>(Xb + 3 * XI::PLANE * 2 + off) = vh;
-          if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
+          restage<XI, TERMS>(Xb, 0, off, z0);
+          restage<XI, TERMS>(Xb, 1, off, z1);
+          restage<XI, TERMS>(Xb, 2, off, z2);
+          restage<XI, TERMS>(Xb, 3, off, z3);
           store_quad4(Zl, PLQ, so, z0, z1, z2, z3);
         }
       };
@@ -211,10 +203,7 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
             }
             if (l > 0) {
               const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-              u32x2 vh, vl;
-              split4(zj[j][0], zj[j][1], zj[j][2], zj[j][3], vh, vl);
-              *reinterpret_cast<u32x2*>(Xb + plane * XI::PLANE * 2 + off) = vh;
-              if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + plane * XI::PLANE * 2 + off) = vl;
+              restage<XI, TERMS>(Xb, plane, off, zj[j]);
               *(reinterpret_cast<f32x4*>(Zl) + ((size_t)plane * (HP / 4) + (ob >> 2) + 2 * g + h) * PPL + pp) = zj[j];
             }
           }
@@ -285,20 +274,7 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
     }
     __syncthreads();
   }
-  // ---------------- flush ----------------
-  float* red = reinterpret_cast<float*>(ldsb);
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < 3; ++c) red[c * NT + tid] = dbo[c];
-  __syncthreads();
-  if (tid < 3) {
-    float s = 0.f;
-    for (int t = 0; t < NT; ++t) s += red[tid * NT + t];
-    sgacc[sg_bout(HP, L) + tid] = s;
-  }
-  __syncthreads();
-  float* out = a.sg + (size_t)blockIdx.x * SG;
-  for (int i = tid; i < SG; i += NT) out[i] = sgacc[i];
+  flush_sg<HP, NT>(reinterpret_cast<float*>(ldsb), dbo, sgacc, SG, a, tid);
 }
 
 template <int HP, int COLS>
@@ -319,8 +295,7 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const BwdArgs& a, int grid, hipStream_t s) {
-  if (terms == 3) return NS == 4 ? launch_one<HP, 4, 3, COLS>(a, grid, s) : launch_one<HP, 1, 3, COLS>(a, grid, s);
-  return NS == 4 ? launch_one<HP, 4, 1, COLS>(a, grid, s) : launch_one<HP, 1, 1, COLS>(a, grid, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS>(a, grid, s); });
 }
 
 int launch_bwd_bf16(int HP, int NS, int terms, int cols, const BwdArgs& a, int grid, hipStream_t s) {

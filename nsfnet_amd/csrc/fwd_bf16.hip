@@ -10,9 +10,11 @@
 // wave's weight slice (A operand, hi and lo fragments) stays in VGPRs for the layer.
 // Saved activations (S) keep the fp32 layout of layout.h, so fwd / bwd / dW kernels of
 // different precisions interoperate.
+// Everything of the tile program lives here except what wave8_bodies.h holds for the four 8-wave bf16 sweeps: the quad
+// restage, the cross-wave sum of the output layer and the loss flush.
 #include "kernels.h"
 #include "point_stage.h"
-#include "bf16_util.h"
+#include "wave8_bodies.h"
 
 // COLS = 128: tile = 32 points x 4 streams, one workgroup per CU at HP = 256.
 // COLS = 64 : tile = 16 points x 4 streams (two streams per 32-column accumulator tile, exchanged
@@ -23,11 +25,7 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
   constexpr int NW = HP / 32, NT = HP * 2, KS = HP / 16;
-#ifndef PINN_PREK
-#define PINN_PREK 4
-#endif
-  constexpr int PREK = PINN_PREK;   // weight k-steps requested ahead of the epilogue's store burst
-  constexpr int PRE = COLS == 64 ? (KS < 2 ? KS : 2) : (KS < PREK ? KS : PREK);
+  constexpr int PRE = COLS == 64 ? (KS < 2 ? KS : 2) : (KS < 4 ? KS : 4);   // weight k-steps requested ahead of the epilogue's store burst
   constexpr int RING = (PRE + 2 < KS) ? PRE + 2 : KS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   unsigned char* Xb = ldsb;                                   // [2][4][32][RSE] bf16
@@ -104,19 +102,10 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
       auto emit = [&](int g, const f32x4& a0, const f32x4& a1, const f32x4& a2, const f32x4& a3,
                       const f32x4& s0, const f32x4& s1, const f32x4& s2, const f32x4& s3) {
         const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-        u32x2 vh, vl;
-        split4(a0[0], a0[1], a0[2], a0[3], vh, vl);
-        *reinterpret_cast<u32x2*>(Xb + 0 * XI::PLANE * 2 + off) = vh;
-        if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 0 * XI::PLANE * 2 + off) = vl;
-        split4(a1[0], a1[1], a1[2], a1[3], vh, vl);
-        *reinterpret_cast<u32x2*>(Xb + 1 * XI::PLANE * 2 + off) = vh;
-        if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 1 * XI::PLANE * 2 + off) = vl;
-        split4(a2[0], a2[1], a2[2], a2[3], vh, vl);
-        *reinterpret_cast<u32x2*>(Xb + 2 * XI::PLANE * 2 + off) = vh;
-        if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 2 * XI::PLANE * 2 + off) = vl;
-        split4(a3[0], a3[1], a3[2], a3[3], vh, vl);
-        *reinterpret_cast<u32x2*>(Xb + 3 * XI::PLANE * 2 + off) = vh;
-        if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
+        restage<XI, TERMS>(Xb, 0, off, a0);
+        restage<XI, TERMS>(Xb, 1, off, a1);
+        restage<XI, TERMS>(Xb, 2, off, a2);
+        restage<XI, TERMS>(Xb, 3, off, a3);
         if (Sl) {
           // uniform plane bases (scalar registers) + ONE 32-bit lane offset: the stores then take the
           // saddr + voffset form instead of a 64-bit VALU address per plane
@@ -177,10 +166,7 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
 #pragma unroll
             for (int e = 0; e < 4; ++e) t4[e] = fast_tanh(acc[j][4 * g + e]);
             const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-            u32x2 vh, vl;
-            split4(t4[0], t4[1], t4[2], t4[3], vh, vl);
-            *reinterpret_cast<u32x2*>(Xb + plane * XI::PLANE * 2 + off) = vh;
-            if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + plane * XI::PLANE * 2 + off) = vl;
+            restage<XI, TERMS>(Xb, plane, off, t4);
             if (Sl) {
               f32x4* Sg = reinterpret_cast<f32x4*>(Sl) + ((size_t)plane * (HP / 4) + (ob >> 2) + 2 * g + h) * PPL + pp;
               *Sg = t4;
@@ -283,29 +269,14 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
         for (int half = 0; half < NH; ++half) part[(w * 4 + c3) * COLS + 64 * half + lane] = po[c3][half];
     }
     __syncthreads();
-    for (int idx = tid; idx < 3 * COLS; idx += NT) {
-      int c3 = idx / COLS, cc = idx % COLS;
-      float s = (NS == 1 || cc < PPL) ? P[prep_bout(HP, L) + c3] : 0.f;
-      for (int ww = 0; ww < NW; ++ww) s += part[(ww * 4 + c3) * COLS + cc];
-      outv[c3 * COLS + cc] = s;
-    }
+    out_sum<NS, PPL, NW>(part, outv, P + prep_bout(HP, L), tid);
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
     if (NS == 4) residual_point_stage<PPL, COLS>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<COLS, NT>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
-  float* red = reinterpret_cast<float*>(ldsb);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k * NT + tid] = lsum[k];
-  __syncthreads();
-  if (tid < 4) {
-    float s = 0.f;
-    for (int t = 0; t < NT; ++t) s += red[tid * NT + t];
-    a.partials[blockIdx.x * PINN_NLOSS + tid] = s;
-  } else if (tid < PINN_NLOSS) {
-    a.partials[blockIdx.x * PINN_NLOSS + tid] = 0.f;
-  }
+  flush_loss<NT>(reinterpret_cast<float*>(ldsb), lsum, a, tid);
 }
 
 template <int HP, int COLS>
@@ -328,8 +299,7 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
-  if (terms == 3) return NS == 4 ? launch_one<HP, 4, 3, COLS>(a, grid, s) : launch_one<HP, 1, 3, COLS>(a, grid, s);
-  return NS == 4 ? launch_one<HP, 4, 1, COLS>(a, grid, s) : launch_one<HP, 1, 1, COLS>(a, grid, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS>(a, grid, s); });
 }
 
 int launch_fwd_bf16(int HP, int NS, int terms, int cols, const FwdArgs& a, int grid, hipStream_t s) {

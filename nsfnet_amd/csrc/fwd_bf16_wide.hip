@@ -10,9 +10,11 @@
 // wave streams 2 x (hi, lo) weight fragments from L2 (register ring, 2 k-steps ahead) and reads 2 x
 // (hi, lo) B fragments from the LDS image for 12 MFMAs - the same ratio as the 128-column kernel.
 // If HP/32 is odd the last wave owns one block.
+// Everything of the tile program lives here except what wave8_bodies.h holds for the four 8-wave bf16 sweeps: the quad
+// restage, the cross-wave sum of the output layer and the loss flush.
 #include "kernels.h"
 #include "point_stage.h"
-#include "bf16_util.h"
+#include "wave8_bodies.h"
 #include <type_traits>
 
 template <int HP, int NS, int TERMS>
@@ -119,19 +121,10 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
             // restage as bf16 hi/lo (8 bytes at [pp][chunk] + 8h per plane) and spill the saved values
             const int g = gq + 2 * hi;
             const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-            u32x2 vh, vl;
-            split4(a0[0], a0[1], a0[2], a0[3], vh, vl);
-            *reinterpret_cast<u32x2*>(Xb + 0 * XI::PLANE * 2 + off) = vh;
-            if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 0 * XI::PLANE * 2 + off) = vl;
-            split4(a1[0], a1[1], a1[2], a1[3], vh, vl);
-            *reinterpret_cast<u32x2*>(Xb + 1 * XI::PLANE * 2 + off) = vh;
-            if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 1 * XI::PLANE * 2 + off) = vl;
-            split4(a2[0], a2[1], a2[2], a2[3], vh, vl);
-            *reinterpret_cast<u32x2*>(Xb + 2 * XI::PLANE * 2 + off) = vh;
-            if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 2 * XI::PLANE * 2 + off) = vl;
-            split4(a3[0], a3[1], a3[2], a3[3], vh, vl);
-            *reinterpret_cast<u32x2*>(Xb + 3 * XI::PLANE * 2 + off) = vh;
-            if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + 3 * XI::PLANE * 2 + off) = vl;
+            restage<XI, TERMS>(Xb, 0, off, a0);
+            restage<XI, TERMS>(Xb, 1, off, a1);
+            restage<XI, TERMS>(Xb, 2, off, a2);
+            restage<XI, TERMS>(Xb, 3, off, a3);
             if (Sl) {
               const unsigned so = (unsigned)(((ob >> 2) + 2 * g + h) * PPL + pp);
               store_quad(a.spill.quad, Sl, (HP / 4) * PPL, so, s0, s1, s2, s3);
@@ -148,10 +141,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
 #pragma unroll
               for (int e = 0; e < 4; ++e) t4[e] = fast_tanh(acc[m][j][4 * g + e]);
               const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
-              u32x2 vh, vl;
-              split4(t4[0], t4[1], t4[2], t4[3], vh, vl);
-              *reinterpret_cast<u32x2*>(Xb + plane * XI::PLANE * 2 + off) = vh;
-              if (TERMS == 3) *reinterpret_cast<u32x2*>(Xb + XI::HALF * 2 + plane * XI::PLANE * 2 + off) = vl;
+              restage<XI, TERMS>(Xb, plane, off, t4);
               if (Sl) {
                 f32x4* Sg = reinterpret_cast<f32x4*>(Sl) + ((size_t)plane * (HP / 4) + (ob >> 2) + 2 * g + h) * PPL + pp;
                 *Sg = t4;
@@ -267,29 +257,14 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
       for (int c3 = 0; c3 < 3; ++c3) part[(w * 4 + c3) * COLS + lane] = po[c3];
     }
     __syncthreads();
-    for (int idx = tid; idx < 3 * COLS; idx += NT) {
-      int c3 = idx / COLS, cc = idx % COLS;
-      float s = (NS == 1 || cc < PPL) ? P[prep_bout(HP, L) + c3] : 0.f;
-      for (int ww = 0; ww < NWV; ++ww) s += part[(ww * 4 + c3) * COLS + cc];
-      outv[c3 * COLS + cc] = s;
-    }
+    out_sum<NS, PPL, NWV>(part, outv, P + prep_bout(HP, L), tid);
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
     if (NS == 4) residual_point_stage<PPL, COLS>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<COLS, NT>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
-  float* red = reinterpret_cast<float*>(ldsb);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k * NT + tid] = lsum[k];
-  __syncthreads();
-  if (tid < 4) {
-    float s = 0.f;
-    for (int t = 0; t < NT; ++t) s += red[tid * NT + t];
-    a.partials[blockIdx.x * PINN_NLOSS + tid] = s;
-  } else if (tid < PINN_NLOSS) {
-    a.partials[blockIdx.x * PINN_NLOSS + tid] = 0.f;
-  }
+  flush_loss<NT>(reinterpret_cast<float*>(ldsb), lsum, a, tid);
 }
 
 template <int HP>
@@ -312,8 +287,7 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
 
 template <int HP>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
-  if (terms == 3) return NS == 4 ? launch_one<HP, 4, 3>(a, grid, s) : launch_one<HP, 1, 3>(a, grid, s);
-  return NS == 4 ? launch_one<HP, 4, 1>(a, grid, s) : launch_one<HP, 1, 1>(a, grid, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value>(a, grid, s); });
 }
 
 int launch_fwd_bf16_wide(int HP, int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {

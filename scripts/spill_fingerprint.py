@@ -9,7 +9,8 @@ entropy net's gradient.
 
 For comparing two builds of the library on one machine by hand (a refactor of the kernels must leave every line
 equal); the hashes are not a fixture.  The cases cover the four layouts of the S / Z-bar spill (nsfnet_amd/csrc/spill.h)
-with every kernel that writes or reads them.  N = 69 collocation points give an odd tile count and a ragged last tile at
+with every kernel that writes or reads them, and the geometries of the 8-wave bf16 sweeps (fwd_bf16.hip, bwd_bf16.hip
+and their _wide variants).  N = 69 collocation points give an odd tile count and a ragged last tile at
 32 and at 16 points per tile; one case per layout has N = 20001, where the tile index exceeds the grid, so that the
 persistent loops and the dummy partner tile of the paired sweeps run; the value-mode cases carry supervised targets at
 N = 197 (two ragged tiles at 128 points per tile, four at 64)."""
@@ -51,15 +52,30 @@ CASES = [
     case("4x400 (1,1,0)", 4, 400, "bf16x3,bf16x3,fp32"),
     case("3x480 bf16x3", 3, 480, X3),
     case("6x256+4x40 ev bf16x3", 6, 256, X3, ev=True),
+    # the 8-wave bf16 sweeps (wave8_bodies.h) where the cases above do not reach them: 128-column tiles at two workgroups
+    # per CU, 64-column tiles by choice, TERMS = 1, a last wave that owns one block, hidden 512
+    case("4x50 bf16x3", 4, 50, X3),
+    case("4x50 bf16", 4, 50, "bf16"),
+    case("6x128 bf16x3 TILE_COLS=64", 6, 128, X3, {"PINN_TILE_COLS": "64"}),
+    case("6x128 bf16x3 TILE_COLS=128", 6, 128, X3, {"PINN_TILE_COLS": "128"}),
+    case("6x256 bf16 SCHED=0", 6, 256, "bf16", {"PINN_SCHED": "0"}),
+    case("3x288 bf16x3 WSPLIT=0", 3, 288, X3, {"PINN_WSPLIT": "0"}),
+    case("4x400 bf16 WSPLIT=0", 4, 400, "bf16", {"PINN_WSPLIT": "0"}),
+    case("3x512 bf16x3", 3, 512, X3),
     # one per layout where the tile index exceeds the grid
     case("4x50 fp32 S0_SKIP32=0 N=20001", 4, 50, F32, {"PINN_S0_SKIP32": "0"}, n=20001),      # classic
     case("6x256 fp32 N=20001", 6, 256, F32, n=20001),                                          # fp32, layer 0 not stored
     case("4x400 bf16x3 N=20001", 4, 400, X3, n=20001),                                         # 24-bit, classic-sized blocks
     case("6x256 bf16x3 N=20001", 6, 256, X3, n=20001),                                         # 24-bit compact
+    case("6x256 bf16x3 SCHED=0 N=20001", 6, 256, X3, {"PINN_SCHED": "0"}, n=20001),            # 8-wave sweeps, classic
+    case("4x400 bf16x3 WSPLIT=0 N=20001", 4, 400, X3, {"PINN_WSPLIT": "0"}, n=20001),          # 8-wave wide sweeps, 24-bit
     # value-mode plans with targets
     case("4x50 fp32 value N=197", 4, 50, F32, sup=197),
     case("6x256 bf16x3 value N=197", 6, 256, X3, sup=197),
     case("4x400 bf16x3 value N=197", 4, 400, X3, sup=197),
+    case("4x50 bf16x3 value N=197", 4, 50, X3, sup=197),
+    case("6x256 bf16x3 TILE_COLS=64 value N=197", 6, 256, X3, {"PINN_TILE_COLS": "64"}, sup=197),
+    case("3x480 bf16x3 value N=197", 3, 480, X3, sup=197),
 ]
 
 
