@@ -459,6 +459,48 @@ int pinn_rwf_compose(pinn_net_t net, const float* theta, float* params, void* st
 /* gtheta [P + R] = d loss / d theta from theta [P + R] and grads [P] = d loss / d params. */
 int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float* gtheta, void* stream);
 
+/* ---- validation error on the device and the best-weights snapshot ----------------------
+ * The error every training option is judged by - the relative L2 error of (u, v, p) against reference fields - as
+ * device state, so that a captured step can record it at a cadence and keep the weights of its best moment without a
+ * host synchronisation.  After pinn_value_forward has written the prediction planes of the n validation points,
+ * per channel c in (u, v, p) over its valid points (a target that is NaN or not finite masks the point for that
+ * channel, the rule of pinn_value_forward), in fp64 from the fp32 planes, not contracted, every sum in a fixed order
+ * (no float atomics; bit-reproducible):
+ *   D_c = sum (c^ - c)^2,  T_c = sum c^2,  n_c = the valid count;  for p also  A = sum d,  B = sum p,  d = p^ - p
+ *   e_c  = sqrt(D_c / T_c)                                   a fraction, not percent
+ *   e_p0 = sqrt(max(D_p - A^2 / n_p, 0) / (T_p - B^2 / n_p)) the pressure error up to a constant (a cavity fixes the
+ *          pressure only up to one); a difference of sums: its error grows with 1 + mean(d)^2 / var(d)
+ *   metric (launch constant): 0 uv = sqrt((D_u + D_v) / (T_u + T_v)), 1 e_u, 2 e_v, 3 e_p, 4 e_p0
+ * A channel without valid targets gives NaN for its entries and for a metric that depends on it.
+ *
+ * state: PINN_VAL_STATE doubles of device memory:
+ *   [0] n_records  [1] best_metric (+inf at the start)  [2] best_t  [3] stale (validations since the last
+ *   improvement)  [4] nonfinite (validations whose metric was NaN or infinite)  [5] improved (0 / 1, of the last
+ *   validation)  [6] cadence records so far  [7] 0.
+ * The caller starts it as {0, +inf, 0, 0, 0, 0, 0, 0}.  improved is the strict metric < best_metric; a NaN or infinite
+ * metric never improves.
+ * ring: capacity rows of PINN_VAL_RECORD doubles; a validation writes row n_records % capacity:
+ *   [0] t  [1] e_u  [2] e_v  [3] e_p  [4] e_p0  [5] metric  [6] improved  [7] n_p.
+ * t = -1 (the cadence case): the row's t is (state[6] + 1) * every, read from the state, so one captured launch
+ * records the right position on every replay; otherwise t (finite, >= 0) is recorded as given and state[6] stays.
+ * scratch: pinn_val_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (the launch
+ * leaves its workgroup ticket, the double [0], at 0); as doubles [1..11] hold the sums of the last launch:
+ *   D_u T_u n_u  D_v T_v n_v  D_p T_p n_p  A  B;  then block partials.  One scratch serves one stream at a time.
+ * pred3 / tgt3: host arrays of three device pointers, each plane 16-byte aligned with ceil4(n) readable floats
+ * (nothing past n reaches a result); [2] of both NULL: no pressure (metrics 3 and 4 are then refused).
+ * One launch: a grid-stride loop of 16-byte loads, wave reduction by shuffles, per-block partials; the last block to
+ * finish folds them in block order, finishes the record and updates state and ring. */
+#define PINN_VAL_RECORD 8
+#define PINN_VAL_STATE 8
+int64_t pinn_val_scratch_bytes(void);
+int pinn_val_stats(int64_t n, const float* const* pred3, const float* const* tgt3, int metric, double t, int64_t every,
+                   double* scratch, double* state, double* ring, int64_t capacity, void* stream);
+/* dst0[0..n0) = src0[0..n0) and, n1 > 0, dst1[0..n1) = src1[0..n1) when state[5] (improved) is 1; nothing is written
+ * when it is 0.  The condition is read from device memory, so the launch is the same every time (capturable).
+ * n0 >= 1, n1 >= 0; 4-byte aligned fp32 segments.  One launch. */
+int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1, float* dst1, int64_t n1,
+                  const double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,10 @@ SIGNATURES = {
     "pinn_rba_apply": (c_int, [c_int64, c_void_p, c_int64, c_double, c_double, c_double, c_void_p, c_int64, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_rba_fill": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_val_scratch_bytes": (c_int64, []),
+    "pinn_val_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                               c_void_p]),
+    "pinn_val_keep": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "pinn_lr_schedule_value": (c_double, [c_void_p, c_double, c_int64]),
     "pinn_grad_sqnorm_scratch_bytes": (c_int64, []),
     "pinn_grad_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

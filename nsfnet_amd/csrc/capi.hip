@@ -976,4 +976,49 @@ int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float*
   return rc ? hipfail(rc, "pinn_rwf_grad") : 0;
 }
 
+int64_t pinn_val_scratch_bytes(void) { return (int64_t)val_scratch_bytes(); }
+
+static bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+
+int pinn_val_stats(int64_t n, const float* const* pred3, const float* const* tgt3, int metric, double t, int64_t every,
+                   double* scratch, double* state, double* ring, int64_t capacity, void* stream) {
+  static_assert(PINN_VAL_RECORD == VAL_RECORD && PINN_VAL_STATE == VAL_STATE, "validation record / state size mismatch");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_val_stats: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (capacity < 1 || capacity > (int64_t)1 << 30) return fail(-22, "pinn_val_stats: capacity must be 1..2^30 (got %s%ld)", "", (long)capacity);
+  if (every < 1) return fail(-22, "pinn_val_stats: every must be >= 1 (got %s%ld)", "", (long)every);
+  if (metric < 0 || metric > 4) return fail(-22, "pinn_val_stats: metric must be 0..4 (got %s%ld)", "", (long)metric);
+  if (!(t == -1.0 || (t >= 0.0 && std::isfinite(t)))) return fail(-22, "pinn_val_stats: t must be -1 (the cadence) or finite and >= 0%s");
+  if (!pred3 || !tgt3 || !scratch || !state || !ring) return fail(-22, "pinn_val_stats: null argument%s");
+  if (misaligned(scratch, 8) || misaligned(state, 8) || misaligned(ring, 8))
+    return fail(-22, "pinn_val_stats: scratch, state and ring must be 8-byte aligned%s");
+  ValStatsArgs a;
+  for (int c = 0; c < 3; ++c) {
+    a.pred[c] = pred3[c]; a.tgt[c] = tgt3[c];
+    if (c < 2 && (!a.pred[c] || !a.tgt[c])) return fail(-22, "pinn_val_stats: the u and v planes must be given%s");
+    if (misaligned(a.pred[c], 16) || misaligned(a.tgt[c], 16)) return fail(-22, "pinn_val_stats: every plane must be 16-byte aligned%s");
+  }
+  if (!a.pred[2] != !a.tgt[2]) return fail(-22, "pinn_val_stats: the pressure prediction and target come together%s");
+  if (metric >= 3 && !a.pred[2]) return fail(-22, "pinn_val_stats: a pressure metric needs the pressure planes%s");
+  a.n = (long)n; a.capacity = (long)capacity; a.metric = metric; a.t = t; a.every = (double)every;
+  a.scratch = scratch; a.state = state; a.ring = ring;
+  int rc = launch_val_stats(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_val_stats") : 0;
+}
+
+int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1, float* dst1, int64_t n1,
+                  const double* state, void* stream) {
+  if (!src0 || !dst0 || !state) return fail(-22, "pinn_val_keep: null argument%s");
+  if (n0 < 1 || n0 > (int64_t)1 << 30) return fail(-22, "pinn_val_keep: n0 must be 1..2^30 (got %s%ld)", "", (long)n0);
+  if (n1 < 0 || n1 > (int64_t)1 << 30) return fail(-22, "pinn_val_keep: n1 must be 0..2^30 (got %s%ld)", "", (long)n1);
+  if (n1 > 0 && (!src1 || !dst1)) return fail(-22, "pinn_val_keep: the second segment has a length but no buffers%s");
+  if (misaligned(src0, 4) || misaligned(dst0, 4) || misaligned(src1, 4) || misaligned(dst1, 4) || misaligned(state, 8))
+    return fail(-22, "pinn_val_keep: the segments must be 4-byte aligned, state 8-byte%s");
+  ValKeepArgs a;
+  a.src[0] = src0; a.dst[0] = dst0; a.n[0] = (long)n0;
+  a.src[1] = n1 > 0 ? src1 : nullptr; a.dst[1] = n1 > 0 ? dst1 : nullptr; a.n[1] = (long)n1;
+  a.state = state;
+  int rc = launch_val_keep(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_val_keep") : 0;
+}
+
 }  // extern "C"

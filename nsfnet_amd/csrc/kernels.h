@@ -285,3 +285,22 @@ size_t rba_scratch_bytes(long n);
 int launch_rba_stats(long n, const float* fld, long npad, double w4, double* scratch, hipStream_t s);
 int launch_rba_apply(const RbaApplyArgs& a, hipStream_t s);
 int launch_rba_fill(long n, double init, const float* sw, float* lam, float* w, hipStream_t s);
+// validation error on the device and the best-weights snapshot (validate.hip)
+constexpr int VAL_RECORD = 8, VAL_STATE = 8;
+struct ValStatsArgs {
+  const float* pred[3];                    // prediction planes u^, v^, p^ ([2] NULL: no pressure), rows of ceil4(n) floats
+  const float* tgt[3];                     // target planes, same layout (a NaN target masks the point for that channel)
+  long n, capacity;                        // points; rows of the history ring
+  int metric;                              // 0 uv, 1 u, 2 v, 3 p, 4 p0
+  double t, every;                         // t < 0: t = (cadence records + 1) * every, from the state
+  double *scratch, *state, *ring;
+};
+struct ValKeepArgs {
+  const float* src[2];
+  float* dst[2];
+  long n[2];
+  const double* state;
+};
+size_t val_scratch_bytes();
+int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
+int launch_val_keep(const ValKeepArgs& a, hipStream_t s);

@@ -130,6 +130,21 @@ class WeightFactorizationConfig:
     seed: int = 0
 
 
+VALIDATION_METRICS = ("uv", "u", "v", "p", "p0")
+
+
+@dataclass
+class ValidationConfig:
+    """Validation error against the DNS fields on the device, with the best weights kept
+    (PinnEngine.set_validation), off by default.  every: optimizer updates between validations; metric: what
+    `best` means; patience: > 0 ends a stage at a log point after that many validations without improvement."""
+    enabled: bool = False
+    every: int = 1000
+    metric: str = "uv"
+    keep_best: bool = True
+    patience: int = 0
+
+
 SCHEDULERS = ("constant", "multistep", "step", "exponential", "cosine")
 
 
@@ -154,6 +169,7 @@ class TrainingConfig:
     residual_attention: ResidualAttentionConfig = field(default_factory=ResidualAttentionConfig)
     grad_clip: GradClipConfig = field(default_factory=GradClipConfig)
     weight_factorization: WeightFactorizationConfig = field(default_factory=WeightFactorizationConfig)
+    validation: ValidationConfig = field(default_factory=ValidationConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -240,6 +256,10 @@ class ConfigManager:
         wf = c.training.weight_factorization
         if wf.enabled and not (abs(wf.mean) < float("inf") and 0.0 <= wf.std < float("inf") and wf.seed >= 0):
             problems.append("training.weight_factorization: finite mean, finite std >= 0 and seed >= 0 required")
+        va = c.training.validation
+        if va.enabled and (va.every < 1 or va.patience < 0 or va.metric not in VALIDATION_METRICS):
+            problems.append("training.validation: every >= 1, patience >= 0 and metric one of %s required"
+                            % " | ".join(VALIDATION_METRICS))
         for st in c.training.training_stages:
             if st.scheduler not in SCHEDULERS:
                 problems.append("stage %s: scheduler must be one of %s (got %r)" % (st.name, " | ".join(SCHEDULERS),
@@ -299,6 +319,9 @@ class ConfigManager:
         if t.weight_factorization.enabled:
             print("weight fact: mean=%s std=%s seed=%d" % (t.weight_factorization.mean, t.weight_factorization.std,
                                                             t.weight_factorization.seed))
+        if t.validation.enabled:
+            print("validation : every=%d metric=%s keep_best=%s patience=%d"
+                  % (t.validation.every, t.validation.metric, t.validation.keep_best, t.validation.patience))
         for st in t.training_stages:
             if st.scheduler != "constant" or st.warmup_epochs > 0:
                 a = st.schedule_args()

@@ -138,6 +138,13 @@ def main():
         wf = cfg.training.weight_factorization
         if wf.enabled:        # W = diag(exp(s)) V on every layer of both nets; the optimizers act on (V, b, s)
             PINN.set_weight_factorization(mean=wf.mean, std=wf.std, seed=wf.seed)
+        va = cfg.training.validation
+        if va.enabled:
+            if star is None:
+                raise FileNotFoundError("training.validation needs the DNS file %s" % ref)
+            # last: a change of the factorization would drop the best.  Every rank validates the whole grid
+            PINN.set_validation_data(*star, every=va.every, metric=va.metric, keep_best=va.keep_best,
+                                     patience=va.patience)
         run_stages(PINN, cfg.training.training_stages, args.epochs_scale, rank, log, star)
         if rank == 0:
             log.header("training completed")

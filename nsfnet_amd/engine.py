@@ -113,13 +113,7 @@ class DeviceNet:
         self.set_flat(torch.cat(flat))
 
     def state_dict(self):
-        sd, off = {}, 0
-        flat = self.params.detach().cpu()
-        for key, shape in self.keys_and_shapes():
-            n = int(np.prod(shape))
-            sd[key] = flat[off:off + n].reshape(shape).clone()
-            off += n
-        return sd
+        return self.flat_state_dict(self.params)
 
     def set_flat(self, flat):
         flat = torch.as_tensor(flat, dtype=torch.float32).reshape(-1)
@@ -172,6 +166,24 @@ class DeviceNet:
         """params = the effective weights of theta."""
         _lib.check(self.lib.pinn_rwf_compose(self.handle, _ptr(self.theta), _ptr(self.params), _stream()),
                    "pinn_rwf_compose")
+
+    def composed(self, x):
+        """The effective weights (a fresh tensor like params) of x, a vector like the trainable one."""
+        if self.theta is None:
+            return x.clone()
+        out = torch.empty_like(self.params)
+        _lib.check(self.lib.pinn_rwf_compose(self.handle, _ptr(x), _ptr(out), _stream()), "pinn_rwf_compose")
+        return out
+
+    def flat_state_dict(self, flat):
+        """flat (a vector like params) in the checkpoint format of state_dict."""
+        sd, off = {}, 0
+        flat = flat.detach().cpu()
+        for key, shape in self.keys_and_shapes():
+            n = int(np.prod(shape))
+            sd[key] = flat[off:off + n].reshape(shape).clone()
+            off += n
+        return sd
 
     def rwf_grad(self, grads):
         """gtheta = d loss / d theta from the effective gradient; returns it."""
@@ -574,6 +586,41 @@ def rba_fill(init, s, lam, w):
                "pinn_rba_fill")
 
 
+VAL_RECORD = 8           # PINN_VAL_RECORD: [t, e_u, e_v, e_p, e_p0, metric, improved, n_p]
+VAL_STATE = 8            # PINN_VAL_STATE: [n_records, best_metric, best_t, stale, nonfinite, improved, cadence records, 0]
+VAL_METRICS = dict(uv=0, u=1, v=2, p=3, p0=4)
+VAL_ROW = ("t", "e_u", "e_v", "e_p", "e_p0", "metric", "improved", "n_p")
+
+
+def val_scratch(device):
+    """Zeroed device scratch of val_stats."""
+    return torch.zeros(int(_lib.load().pinn_val_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def val_planes(n, device):
+    """fp32 [3, ceil4(n)]: prediction or target planes whose rows start 16-byte aligned."""
+    return torch.zeros(3, (int(n) + 3) // 4 * 4, dtype=torch.float32, device=device)
+
+
+def val_stats(pred, tgt, n, with_p, metric, t, every, scratch, state, ring):
+    """pinn_val_stats: one validation of the prediction planes pred against the target planes tgt (both val_planes;
+    with_p False: no pressure) - a row into ring, state updated; t = -1: the cadence position from the state.  One
+    launch."""
+    rows = 3 if with_p else 2
+    pp = (ctypes.c_void_p * 3)(*[pred[c].data_ptr() if c < rows else 0 for c in range(3)])
+    tp = (ctypes.c_void_p * 3)(*[tgt[c].data_ptr() if c < rows else 0 for c in range(3)])
+    _lib.check(_lib.load().pinn_val_stats(int(n), pp, tp, int(metric), float(t), int(every), _ptr(scratch), _ptr(state),
+                                          _ptr(ring), ring.shape[0], _stream()), "pinn_val_stats")
+
+
+def val_keep(segs, state):
+    """pinn_val_keep: dst = src for the one or two (src, dst) fp32 vector pairs when state's improved word is 1.  One
+    launch."""
+    (s0, d0), (s1, d1) = segs[0], (segs[1] if len(segs) > 1 else (None, None))
+    _lib.check(_lib.load().pinn_val_keep(_ptr(s0), _ptr(d0), s0.numel(), _ptr(s1), _ptr(d1),
+                                         0 if s1 is None else s1.numel(), _ptr(state), _stream()), "pinn_val_keep")
+
+
 OPTIM_RECORD = 6         # PINN_OPTIM_RECORD
 
 
@@ -785,6 +832,18 @@ class _Optim:
         self.cstruct = self.spec.c_struct()
 
 
+class _Validation:
+    """State of the device validation monitor (set_validation): the forward-only value plan over the validation
+    points, whose pred is a view of the prediction planes; tgt (target planes), scratch, state [VAL_STATE] fp64, ring
+    [capacity, VAL_RECORD] fp64 and snap (one snapshot vector per net, of its trainable vector's size).  n counts the
+    optimizer updates since set_validation on the host (the device counts the cadence records itself)."""
+
+    def __init__(self, every, metric, keep_best, capacity, with_p):
+        self.every, self.metric, self.keep_best, self.capacity, self.with_p = every, metric, keep_best, capacity, with_p
+        self.n = 0
+        self.plan = self.pred = self.tgt = self.scratch = self.state = self.ring = self.snap = None
+
+
 # What an evaluation is made for.  Each mode holds what the one before it holds, and more:
 EVAL_ADAM = 0           # an Adam step: a fresh batch, attention and balance updates, the conflict-free combination
 EVAL_FULL_BATCH = 1     # loss_and_grad(full_batch=True): the whole store, the attention weights held
@@ -843,6 +902,7 @@ class PinnEngine:
         self._pool = self._pool_w = self._pool_e = self._pool_scratch = None     # set_resample_pool
         self._opt = None                    # device lr schedule / gradient clipping (set_lr_schedule, set_grad_clipping)
         self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
+        self._val = None                    # device validation monitor (set_validation; None = off)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -1477,9 +1537,11 @@ class PinnEngine:
         out["loss"] = self.alpha_b * loss_b + self.alpha_e * loss_e + self.alpha_s * loss_s
         return out
 
-    def adam_step(self, lr):
+    def adam_step(self, lr, validate=None):
         """Adam on the gradient of the last evaluation.  With a device schedule or clipping on, lr is the schedule's
-        base rate lr0; every trainable net uses the lr_e and the clipping coefficient of the same epoch."""
+        base rate lr0; every trainable net uses the lr_e and the clipping coefficient of the same epoch.  With
+        set_validation on, the update that is due by its cadence is followed by a validation (validate: step()'s
+        decision for a captured sequence; None = by the count)."""
         o = self._opt
         with_e = self.net_e is not None and self.e_trainable
         g, ge = self.grads, self.grads_e
@@ -1499,6 +1561,7 @@ class PinnEngine:
             self.net.adam_step_sched(g, lr, o, advance=True)        # last: it moves the epoch on
         if self._bal is not None:
             self._bal.n += 1
+        self._updated(validate)
 
     def _count_updates(self, d):
         """Move the host mirrors of the update count (what adam_step advances) by d = +1 / -1."""
@@ -1507,6 +1570,8 @@ class PinnEngine:
             self.net_e.adam_t += d
         if self._bal is not None:
             self._bal.n += d
+        if self._val is not None:
+            self._val.n += d
 
     # ---- random weight factorization of the dense layers ----
     def _nets(self):
@@ -1539,6 +1604,7 @@ class PinnEngine:
             self._rwf = None
             for _, net in self._nets():
                 net.set_factorization(None)
+            self._validation_reset()
             return
         given = {}
         if factors is not None:
@@ -1560,6 +1626,7 @@ class PinnEngine:
         for name, net in self._nets():
             net.set_factorization(given[name])
         self._rwf = dict(mean=mean, std=std, seed=seed)
+        self._validation_reset()
 
     def weight_factors(self):
         """dict(net=[s_0, ..., s_L][, net_e=[...]]): the per-layer scale factors s as fp32 device tensors, views of
@@ -1640,6 +1707,174 @@ class PinnEngine:
         return dict(epoch=int(r[0]), lr=r[1], grad_norm=r[2], clip_coef=r[3], clipped=int(r[4]), updates=int(r[5]),
                     next_epoch=int(r[6]), schedule=o.user_spec, max_norm=o.max_norm)
 
+    # ---- validation error on the device and the best weights ----
+    def set_validation(self, x, y, u=None, v=None, p=None, every=1000, metric="uv", keep_best=True, history=4096):
+        """Track the relative L2 error against the reference fields u, v (and p) at the points x, y on the device.
+        After the every-th optimizer update since this call, and every every-th after that (Adam updates of step() and
+        adam_step(), and each lbfgs_step call as one), three things follow the update on the main stream: a value
+        forward of the main net on the validation points, one launch that folds the error sums in fixed-order fp64,
+        writes the record [t, e_u, e_v, e_p, e_p0, metric, improved, n_p] into a history ring of `history` rows and
+        updates the monitor state (best metric, its t, validations since the last improvement, non-finite count), and
+        - keep_best - one launch that copies the trainable vector of every net into a snapshot when that validation
+        improved strictly on the best so far.  Everything is device memory: the captured validating step serves the
+        whole stage, and nothing synchronises.  e_c = ||c^ - c|| / ||c|| as a fraction; e_p0 is the pressure error
+        after removing the mean of p^ - p and of p; metric: 'uv' (u and v together, the default), 'u', 'v', 'p' or
+        'p0'.  A NaN target masks that point for its channel.  Record t is the number of updates since this call, and
+        the record describes the parameters after that update.  Several ranks: every rank validates the whole set it
+        is given; there is no communication (the parameters are identical, so the records are).
+
+        every = 0 or x = None: off (the step launches what it launches without the feature).  A call restarts the
+        state and drops the best; so does a change of the weight factorization."""
+        every, history = int(every), int(history)
+        if every < 0:
+            raise ValueError("validation: every must be >= 0")
+        self._graphs.clear()        # captured steps hold the other monitor's buffers and constants
+        if every == 0 or x is None:
+            self._val = None
+            return
+        if metric not in VAL_METRICS:
+            raise ValueError("validation: metric must be one of %s (got %r)" % (sorted(VAL_METRICS), metric))
+        if u is None or v is None:
+            raise ValueError("validation: the targets u and v must be given")
+        if metric in ("p", "p0") and p is None:
+            raise ValueError("validation: metric %r needs pressure targets" % (metric,))
+        if history < 1:
+            raise ValueError("validation: history must be >= 1")
+        m = _Validation(every, metric, bool(keep_best), history, p is not None)
+        m.plan = ValuePlan(self.net, x, y, with_backward=False)
+        n = m.plan.n
+        m.pred, m.tgt = val_planes(n, self.device), val_planes(n, self.device)
+        m.plan.pred = m.pred[:, :n]         # the forward writes rows that start 16-byte aligned
+        for c, t in enumerate((u, v, p)):
+            if t is None:
+                continue
+            t = torch.as_tensor(np.asarray(t, dtype=np.float32).reshape(-1))
+            if t.numel() != n:
+                raise ValueError("validation: target %d must have one entry per point" % c)
+            m.tgt[c, :n].copy_(t)
+        m.scratch = val_scratch(self.device)
+        m.state = torch.zeros(VAL_STATE, dtype=torch.float64, device=self.device)
+        m.ring = torch.zeros(history, VAL_RECORD, dtype=torch.float64, device=self.device)
+        self._val = m
+        self._validation_reset()
+
+    def _validation_reset(self):
+        """The state at its start, an empty ring and fresh snapshot vectors of the nets' trainable sizes."""
+        m = self._val
+        if m is None:
+            return
+        self._graphs.clear()
+        m.n = 0
+        start = torch.zeros(VAL_STATE, dtype=torch.float64)
+        start[1] = float("inf")
+        m.state.copy_(start)
+        m.ring.zero_()
+        m.snap = [torch.zeros_like(net.trainable) for _, net in self._nets()]
+
+    def _validation_due(self):
+        """True when the next optimizer update is one the cadence validates after."""
+        m = self._val
+        return m is not None and (m.n + 1) % m.every == 0
+
+    def _updated(self, validate=None):
+        """An optimizer update is in place: count it, and validate when the cadence (or the caller) says so."""
+        m = self._val
+        if m is None:
+            return
+        due = self._validation_due() if validate is None else validate
+        m.n += 1
+        if due:
+            self._validate(-1.0)
+
+    def _validate(self, t):
+        m = self._val
+        m.plan.forward(save=False)
+        val_stats(m.pred, m.tgt, m.plan.n, m.with_p, VAL_METRICS[m.metric], t, m.every, m.scratch, m.state, m.ring)
+        if m.keep_best:
+            val_keep([(net.trainable, snap) for (_, net), snap in zip(self._nets(), m.snap)], m.state)
+
+    def _val_on(self):
+        if self._val is None:
+            raise RuntimeError("validation is off: call set_validation() first")
+        return self._val
+
+    def validate(self, t=None):
+        """One validation now, of the current parameters, recorded with the explicit position t (default: the updates
+        counted since set_validation).  It takes part in the best-so-far like any other.  Returns the row as a dict
+        (one host read)."""
+        m = self._val_on()
+        t = float(m.n if t is None else t)
+        if not (math.isfinite(t) and t >= 0.0):
+            raise ValueError("validate: t must be finite and >= 0")
+        self._validate(t)
+        return self.validation_info()["last"]
+
+    def validation_info(self):
+        """The monitor state (one host read), or None when the feature is off: records, best_metric, best_t, stale,
+        nonfinite, last (the newest row as a dict; None before the first), every, metric, points."""
+        m = self._val
+        if m is None:
+            return None
+        st = m.state.cpu().tolist()
+        k = int(st[0])
+        last = None
+        if k > 0:
+            last = dict(zip(VAL_ROW, m.ring[(k - 1) % m.capacity].cpu().tolist()))
+        return dict(records=k, best_metric=st[1], best_t=st[2], stale=int(st[3]), nonfinite=int(st[4]), last=last,
+                    every=m.every, metric=m.metric, points=m.plan.n)
+
+    def validation_history(self):
+        """fp64 numpy array [rows, VAL_RECORD] of the recorded rows in time order (the ring unwrapped: the newest
+        `history` of them); one host read."""
+        m = self._val_on()
+        both = torch.cat([m.state, m.ring.reshape(-1)]).cpu().numpy()
+        k, ring = int(both[0]), both[VAL_STATE:].reshape(m.capacity, VAL_RECORD)
+        if k <= m.capacity:
+            return ring[:k].copy()
+        return np.concatenate([ring[k % m.capacity:], ring[:k % m.capacity]])
+
+    def _has_best(self):
+        m = self._val
+        return m is not None and m.keep_best and math.isfinite(float(m.state[1].item()))
+
+    def best_state_dict(self):
+        """The main net's effective weights at the best validation so far, in the checkpoint format of state_dict();
+        None before the first improvement (or with keep_best off)."""
+        if not self._has_best():
+            return None
+        return self.net.flat_state_dict(self.net.composed(self._val.snap[0]))
+
+    def best_state_dict_e(self):
+        """best_state_dict() of the entropy net (ev flavour)."""
+        if self.net_e is None or not self._has_best():
+            return None
+        return self.net_e.flat_state_dict(self.net_e.composed(self._val.snap[1]))
+
+    def best_factors(self):
+        """The scale factors inside the snapshot, shaped like weight_factors(); None without factorization or best."""
+        if self._rwf is None or not self._has_best():
+            return None
+        out = {}
+        for (name, net), snap in zip(self._nets(), self._val.snap):
+            rows, off = [], net.num_params
+            for r, _ in layer_shapes(net.n_out, net.n_hidden, net.hidden):
+                rows.append(snap[off:off + r].clone())
+                off += r
+            out[name] = rows
+        return out
+
+    def restore_best(self):
+        """Copy the snapshot back into the trainable vector of every net (in place: captured steps stay valid) and
+        rebuild the effective weights.  Adam's moments and the monitor state are left alone.  RuntimeError without a
+        best."""
+        if not self._has_best():
+            raise RuntimeError("restore_best: there is no best snapshot (validation off, keep_best off, or no "
+                               "validation has improved yet)")
+        for (_, net), snap in zip(self._nets(), self._val.snap):
+            net.trainable.copy_(snap)
+            net.update_params()
+        self.lbfgs_reset()
+
     # ---- L-BFGS (DESIGN.md section 7.2) ----
     def lbfgs_reset(self):
         """Forget the L-BFGS history: the next lbfgs_step starts like a fresh torch.optim.LBFGS."""
@@ -1676,6 +1911,7 @@ class PinnEngine:
         finally:
             self.e_trainable = e_trainable
         self.lbfgs_info = info
+        self._updated()     # one call = one update; the accepted point is in place
         return loss
 
     def step(self, lr):
@@ -1689,13 +1925,14 @@ class PinnEngine:
             return
         # with balancing on, a balance step and a plain step are separate graphs (the weights are device state)
         update = self._balance_due()
-        key = self._graph_key(lr, update)
+        validate = self._validation_due()       # a validating step and a plain one are separate graphs, too
+        key = self._graph_key(lr, update, validate)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the
             # supervised-target census happens here), then capture
             self._loss_and_grad(update)
-            self.adam_step(lr)
+            self.adam_step(lr, validate)
             if len(self._graphs) >= 8:
                 self._graphs.clear()
             side = torch.cuda.Stream(device=self.device)
@@ -1704,7 +1941,7 @@ class PinnEngine:
             with torch.cuda.stream(side):
                 with torch.cuda.graph(graph, stream=side):
                     self._loss_and_grad(update)
-                    self.adam_step(lr)
+                    self.adam_step(lr, validate)
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._count_updates(-1)      # the capture itself does not execute
             self._graphs[key] = graph
@@ -1713,7 +1950,7 @@ class PinnEngine:
         self._eval_batch = self._batching_on()
         self._count_updates(1)
 
-    def _graph_key(self, lr, update):
+    def _graph_key(self, lr, update, validate=False):
         """What a captured step depends on besides device memory: the launch constants of the engine and of every
         option that is on (lr is the base rate lr0 under a schedule: the rate of each update is device state)."""
         bt, a, o = self._batch, self._rba, self._opt
@@ -1722,7 +1959,9 @@ class PinnEngine:
                self._bal is not None, update, 0 if bt is None else bt.B,
                (False, 0.0, 0.0) if a is None else (True, a.gamma, a.eta))
         key += () if o is None else (o.spec.key(), o.max_norm)
-        return key + (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
+        key += (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
+        v = self._val
+        return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 
     def _graphs_enabled(self):
         flag = os.environ.get("NSFNET_GRAPH")

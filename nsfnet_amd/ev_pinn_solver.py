@@ -318,6 +318,12 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop%d.pth' % (epoch_id), N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
+            if self._at_log(epoch_id, num_epoch, interval) and self._patience_out():
+                break
+
+    def _at_log(self, epoch_id, num_epoch, interval):
+        """The log cadence without the rank: every rank asks the patience question at the same steps."""
+        return epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1
 
     def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
         """Reference loop :440-487 incl. its schedule: the entropy net trains for exactly one
@@ -348,6 +354,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop%d.pth' % (epoch_id), N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
+            if self._at_log(epoch_id, num_epoch, interval) and self._patience_out():
+                break
         if num_epoch > 0:
             self._publish_terms()
 
@@ -398,6 +406,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             print('  ' + self._optimizer_log())
         if self._confgrad:
             print('  ' + self._confgrad_log())
+        if self._validation:
+            print('  ' + self.validation_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]
@@ -463,6 +473,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         torch.save(self.net.state_dict(), save_results_to + filename)
         torch.save(self.net_1.state_dict(), save_results_to + filename + '_evm')
         self.save_weight_factors(save_results_to + filename)
+        self._save_best(save_results_to + filename)
 
     def neural_net_equations(self, x, y):
         """eq1..eq4 at arbitrary points, forward only, with vis_t = vis_t0 as the reference does

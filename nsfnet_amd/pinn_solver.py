@@ -65,6 +65,8 @@ class SolverBase:
     _lr_schedule = None         # set_lr_schedule: the LrSchedule of every Adam stage without a scheduler= of its own
     _clipping = False
     _lr0 = None                 # the base rate of the running Adam stage while a device schedule is on
+    _validation = False
+    _val_patience = 0           # set_validation_data(patience=k): a stage ends at a log point with stale >= k
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -151,6 +153,67 @@ class SolverBase:
         reference's format - state_dict() is the effective weights - and save() adds the scale factors as a sidecar
         <checkpoint>_rwf, which load() reads back.  mean = None: off."""
         self.engine.set_weight_factorization(mean, std, seed, factors)
+
+    def set_validation_data(self, x, y, u, v, p=None, every=1000, metric="uv", keep_best=True, patience=0,
+                            history=4096):
+        """Reference fields u, v (and p) at the points x, y - the DNS grid the run is judged on: after every `every`
+        optimizer updates the relative L2 error against them is recorded on the device, and with keep_best the weights
+        of the best validation so far are kept there too (PinnEngine.set_validation).  Nothing
+        synchronises: validation_log(), validation_history() and best_state_dict() read when asked.  print_log adds
+        the validation line; save() also writes the best weights (<filename>_best).  patience = k > 0: a training
+        stage ends at a log point when the last k validations brought no improvement - the only place the loops read
+        the monitor.  every = 0 or x = None: off."""
+        if int(patience) < 0:
+            raise ValueError("validation: patience must be >= 0")
+        col = lambda a: None if a is None else _col(a)
+        self.engine.set_validation(col(x), col(y), col(u), col(v), col(p), every=every, metric=metric,
+                                   keep_best=keep_best, history=history)
+        self._validation = self.engine.validation_info() is not None
+        self._val_patience = int(patience) if self._validation else 0
+
+    def validation_log(self):
+        """One line on the validation monitor (one host read)."""
+        i = self.engine.validation_info()
+        if i is None or i["last"] is None:
+            return "validation: no record yet"
+        r = i["last"]
+        return ("validation (t=%d): e_u=%.4e e_v=%.4e e_p=%.4e e_p0=%.4e  best %s=%.4e at t=%d  stale=%d nonfinite=%d "
+                "records=%d" % (r["t"], r["e_u"], r["e_v"], r["e_p"], r["e_p0"], i["metric"], i["best_metric"],
+                                i["best_t"], i["stale"], i["nonfinite"], i["records"]))
+
+    def validation_history(self):
+        """The recorded rows [t, e_u, e_v, e_p, e_p0, metric, improved, n_p] in time order (one host read)."""
+        return self.engine.validation_history()
+
+    def best_state_dict(self):
+        """The main net's weights at the best validation so far (checkpoint format); None before the first."""
+        return self.engine.best_state_dict()
+
+    def load_best(self):
+        """Put the best weights so far back into the nets (PinnEngine.restore_best); RuntimeError without any."""
+        self.engine.restore_best()
+
+    def _save_best(self, path):
+        """Next to the checkpoint at `path`: <path>_best (and _best_evm, and the scale factors as <path>_best_rwf)
+        when a best exists."""
+        sd = self.engine.best_state_dict() if self._validation else None
+        if sd is None:
+            return
+        torch.save(sd, path + '_best')
+        sd_e = self.engine.best_state_dict_e()
+        if sd_e is not None:
+            torch.save(sd_e, path + '_best_evm')
+        f = self.engine.best_factors()
+        if f is not None:
+            torch.save({name: torch.cat([a.detach().reshape(-1) for a in layers]).cpu() for name, layers in f.items()},
+                       path + '_best_rwf')
+
+    def _patience_out(self):
+        """True when the stage should end: patience is set and that many validations brought no improvement (one
+        host read; the loops ask at their log cadence only, on every rank - the records are identical)."""
+        if not self._validation or self._val_patience <= 0:
+            return False
+        return self.engine.validation_info()["stale"] >= self._val_patience
 
     def save_weight_factors(self, path):
         """Write the sidecar of the checkpoint at `path`: {net name: flat fp32 s} as path + '_rwf' (torch.save).  With
@@ -313,6 +376,11 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self.x_f, self.y_f = x.reshape(-1, 1), y.reshape(-1, 1)
         return idx
 
+    def set_validation_data(self, x, y, u, v, every=1000, metric="uv", keep_best=True, patience=0, history=4096):
+        """SolverBase.set_validation_data without pressure targets (the plain flavour's DNS comparison has none)."""
+        super().set_validation_data(x, y, u, v, None, every=every, metric=metric, keep_best=keep_best,
+                                    patience=patience, history=history)
+
     def set_stage(self, stage):
         self.stage = stage
 
@@ -385,6 +453,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop_%d.pth' % epoch_id, N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
+            if log_now and self._patience_out():
+                break
         if num_epoch > 0 and not (log_now or save_now):
             self.fwd_computing_loss_2d(full_batch=True)         # terms and fields of the accepted point
 
@@ -414,6 +484,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop_%d.pth' % epoch_id, N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
+            if log_now and self._patience_out():
+                break
             epoch_id += 1
         self._publish_terms()
 
@@ -428,7 +500,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
                 if self._batching and self.engine.evaluated_batch else ()),
               *(("\n" + self._attention_log(),) if self._attention else ()),
               *(("\n" + self._confgrad_log(),) if self._confgrad else ()),
-              *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()))
+              *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()),
+              *(("\n" + self.validation_log(),) if self._validation else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):
@@ -476,6 +549,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         os.makedirs(save_results_to, exist_ok=True)
         torch.save(self.net.state_dict(), save_results_to + filename)
         self.save_weight_factors(save_results_to + filename)
+        self._save_best(save_results_to + filename)
         save_matlab_to = directory + '/loss/'
         os.makedirs(save_matlab_to, exist_ok=True)
         if getattr(self, "loss_eq1", None) is not None:

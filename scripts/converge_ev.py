@@ -17,6 +17,9 @@ viscosity state restarts from alpha*|e| as at the start of a run).
         [--scheduler cosine --eta-min-factor 0.01 --warmup-epochs 1000]   (device learning-rate schedule of every stage,
                                                   off by default; counts scale with --epochs-scale, each stage starts at 0)
         [--grad-clip 1.0]   (global-norm gradient clipping of the Adam updates, off by default)
+        [--validate-every 1000 --val-metric uv]   (error against the DNS field on the device every that many updates of
+                                                  a stage, the stage's best weights kept: validation.jsonl,
+                                                  net_best.pth / net_best_evm.pth; off by default)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -69,6 +72,10 @@ def main():
     ap.add_argument("--rwf-mean", type=float, default=0.5)
     ap.add_argument("--rwf-std", type=float, default=0.1)
     ap.add_argument("--rwf-seed", type=int, default=0)
+    ap.add_argument("--validate-every", type=int, default=0,
+                    help="> 0: validate against the DNS field on the device every this many updates of a stage and keep "
+                         "the stage's best weights (DESIGN.md 7.9)")
+    ap.add_argument("--val-metric", choices=("uv", "u", "v", "p", "p0"), default="uv", help="what `best` means")
     a = ap.parse_args()
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     from nsfnet_amd.schedule import LrSchedule
@@ -122,6 +129,9 @@ def main():
         n = max(1, int(epochs * a.epochs_scale))
         P.current_stage = "Stage %d" % k
         P.set_alpha_evm(alpha)
+        if a.validate_every > 0:                        # per stage: t counts the stage's updates, the best is the stage's
+            P.set_validation_data(*star, every=a.validate_every, metric=a.val_metric,
+                                  history=max(1, n // a.validate_every))
         t0 = time.time()
         sched = None
         if a.scheduler != "constant" or a.warmup_epochs > 0:
@@ -150,6 +160,17 @@ def main():
                    optimizer=({k_: (v if k_ != "schedule" else (None if v is None else v.key()))
                                for k_, v in P.engine.optimizer_info().items()}
                               if P.engine.optimizer_info() is not None else None))
+        if a.validate_every > 0:
+            info = P.engine.validation_info()
+            rec.update(best_metric=info["best_metric"], best_t=info["best_t"], val_metric=a.val_metric)
+            with open("validation.jsonl", "a") as fh:
+                for row in P.validation_history().tolist():
+                    fh.write(json.dumps(dict(zip(("t", "e_u", "e_v", "e_p", "e_p0", "metric", "improved", "n_p"), row),
+                                             stage=k)) + "\n")
+            best = P.best_state_dict()
+            if best is not None:
+                torch.save(best, "net_best.pth")
+                torch.save(P.engine.best_state_dict_e(), "net_best_evm.pth")
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)

@@ -1,0 +1,383 @@
+"""GPU tests of the device validation monitor: pinn_val_stats and pinn_val_keep against the fp64
+model of tests/val_model.py, the engine with the monitor against a twin without it (observe-only, bitwise), graph replay
+against eager (bitwise), the snapshot with the weight factorization on, and the argument checks of the C ABI."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import val_model as vm  # noqa: E402
+from oracle import autograd_ref as ar  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+# validate.hip has rba.hip's geometry (256 threads x 4 points per block, at most 512 blocks).  1; not a multiple of 4;
+# not a multiple of the block; one block exactly; and more than 512 blocks' worth of points: the grid-stride loop repeats
+# and the fold has two partials per thread
+SIZES = [1, 7, 1003, 1024, 70001, 600013]
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int32 if a.dtype == np.float32 else np.int64)
+
+
+def _data(n, seed, variant):
+    """Random fp32 planes over several decades.  The pressure misfit d = p^ - p has mean 3 std (|mean| <= 10 std, so
+    the cancellation in e_p0's numerator amplifies the summation error by at most 1 + 10^2 = 101), and three quarters
+    of the pressure targets are positive, so neither signed sum cancels."""
+    rng = np.random.RandomState(seed)
+    dec = lambda lo, hi: (rng.randn(n) * 10.0 ** rng.uniform(lo, hi, size=n)).astype(np.float32)
+    tgt = [dec(-3, 1), dec(-3, 1), None]
+    pred = [(tgt[0] + dec(-3, 0)).astype(np.float32), (tgt[1] + dec(-3, 0)).astype(np.float32), None]
+    if variant != "nop":
+        p = np.abs(dec(-3, 1)) * np.where(rng.rand(n) < 0.75, 1.0, -1.0).astype(np.float32)
+        pred[2] = (p.astype(np.float64) + 0.3 + 0.1 * rng.randn(n)).astype(np.float32)
+        if variant == "p_nan10":
+            p[rng.rand(n) < 0.1] = np.nan
+        if variant == "p_allnan":
+            p[:] = np.nan
+        tgt[2] = p.astype(np.float32)
+    return pred, tgt
+
+
+def _planes(rows, n):
+    """Device planes [3, ceil4(n)] of the rows (None: absent), the row padding poisoned with NaN."""
+    from nsfnet_amd import engine as eng
+    t = eng.val_planes(n, DEV)
+    t.fill_(float("nan"))                               # nothing past n may be read into a result
+    for c, r in enumerate(rows):
+        if r is not None:
+            t[c, :n] = torch.tensor(r, device=DEV)
+    return t
+
+
+def _fresh(capacity=4):
+    st = torch.tensor(vm.new_state(), dtype=torch.float64, device=DEV)
+    return st, torch.zeros(capacity, vm.RECORD, dtype=torch.float64, device=DEV)
+
+
+def _close(got, want, rtol, what=""):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert (np.isnan(got) == np.isnan(want)).all(), (what, got, want)
+    ok = ~np.isnan(want)
+    assert (np.abs(got[ok] - want[ok]) <= rtol * np.abs(want[ok])).all(), (what, got, want)
+
+
+# ---------------------------------------------------------------- the kernels
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("variant", ["nop", "p", "p_nan10", "p_allnan"])
+def test_stats_match_the_model(n, variant):
+    from nsfnet_amd import engine as eng
+    pred, tgt = _data(n, n + len(variant), variant)
+    P, T = _planes(pred, n), _planes(tgt, n)
+    with_p = variant != "nop"
+    scratch = eng.val_scratch(DEV)
+    runs = []
+    for _ in range(2):                                  # twice into fresh state on one scratch
+        st, ring = _fresh()
+        eng.val_stats(P, T, n, with_p, vm.METRICS["uv"], -1.0, 5, scratch, st, ring)
+        torch.cuda.synchronize()
+        runs.append((scratch[:16].cpu().numpy(), st.cpu().numpy(), ring.cpu().numpy()))
+    for a, b in zip(*runs):                             # the ticket is 0 again: the same bits
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+    scr, st, ring = runs[0]
+    assert scr[0] == 0.0
+    S = vm.sums(pred, tgt)
+    got = scr[1:12]
+    for k, name in enumerate(vm.SUMS):
+        if name.startswith("n_"):
+            assert got[k] == S[k], (name, got[k], S[k])             # the valid counts are exact
+        else:
+            print("n=%d %s %s rel err %.3e" % (n, variant, name, abs(got[k] - S[k]) / max(abs(S[k]), 1e-300)))
+            assert abs(got[k] - S[k]) <= 1e-12 * abs(S[k]), (name, got[k], S[k])
+    mst, mring = vm.new_state(), np.zeros((4, vm.RECORD))
+    row = vm.record(S, "uv", -1.0, 5, mst, mring)
+    _close(ring[0][[vm.R_EU, vm.R_EV, vm.R_EP, vm.R_METRIC]], row[[vm.R_EU, vm.R_EV, vm.R_EP, vm.R_METRIC]], 1e-12, "errors")
+    # e_p0 is a difference of sums: the data keep its amplification 1 + mean(d)^2 / var(d) <= 101, hence 1e-9
+    _close(ring[0][[vm.R_EP0]], row[[vm.R_EP0]], 1e-9, "e_p0")
+    assert ring[0][vm.R_T] == 5.0 and ring[0][vm.R_NP] == S[8] and ring[0][vm.R_IMPROVED] == 1.0
+    assert st[vm.S_RECORDS] == 1 and st[vm.S_NONFINITE] == 0 and st[vm.S_STALE] == 0 and st[vm.S_BEST_T] == 5.0
+    assert st[vm.S_BEST] == ring[0][vm.R_METRIC]
+    direct = vm.direct_errors(pred, tgt)
+    _close(ring[0][[vm.R_EU, vm.R_EV, vm.R_EP, vm.R_METRIC]], [direct[0], direct[1], direct[2], direct[4]], 1e-9, "direct")
+    if variant in ("nop", "p_allnan"):                  # no valid pressure target: NaN entries, uv unaffected
+        assert np.isnan(ring[0][vm.R_EP]) and np.isnan(ring[0][vm.R_EP0]) and ring[0][vm.R_NP] == 0.0
+        assert np.isfinite(ring[0][vm.R_METRIC])
+    if with_p:                                          # every metric is the entry it names
+        for name, col in (("u", vm.R_EU), ("v", vm.R_EV), ("p", vm.R_EP), ("p0", vm.R_EP0)):
+            st2, ring2 = _fresh()
+            eng.val_stats(P, T, n, True, vm.METRICS[name], -1.0, 5, scratch, st2, ring2)
+            r = ring2.cpu().numpy()[0]
+            np.testing.assert_array_equal(_bits(r[vm.R_METRIC:vm.R_METRIC + 1]), _bits(ring[0][col:col + 1]))
+            assert st2.cpu().numpy()[vm.S_NONFINITE] == (0.0 if np.isfinite(r[vm.R_METRIC]) else 1.0)
+
+
+@pytest.mark.parametrize("n0,n1", [(1, 0), (7, 0), (1027, 0), (1347, 697)])      # (3 x 24 net, 2 x 24 entropy net)
+@pytest.mark.parametrize("shift", [0, 1])               # 1: the segments start off a 16-byte boundary
+def test_keep_copies_exactly_when_improved(n0, n1, shift):
+    from nsfnet_amd import engine as eng
+    rng = np.random.RandomState(n0)
+    src = [torch.tensor(rng.randn(n + shift + 3).astype(np.float32), device=DEV) for n in (n0, n1)]
+    for improved in (0.0, 1.0):
+        dst = [torch.full((n + shift + 3,), -7.5, device=DEV) for n in (n0, n1)]
+        st = torch.tensor(vm.new_state(), dtype=torch.float64, device=DEV)
+        st[vm.S_IMPROVED] = improved
+        segs = [(s[shift:shift + n], d[shift:shift + n]) for s, d, n in zip(src, dst, (n0, n1))]
+        eng.val_keep(segs if n1 else segs[:1], st)
+        torch.cuda.synchronize()
+        for s, d, n in zip(src, dst, (n0, n1)):
+            want = torch.full_like(d, -7.5)
+            if improved:
+                want[shift:shift + n] = s[shift:shift + n]
+            assert torch.equal(d.view(torch.int32), want.view(torch.int32))
+
+
+def test_a_second_segment_of_length_zero_is_accepted():
+    from nsfnet_amd import _lib
+    lib = _lib.load()
+    src, dst = torch.ones(8, device=DEV), torch.zeros(8, device=DEV)
+    st = torch.tensor(vm.new_state(), dtype=torch.float64, device=DEV)
+    st[vm.S_IMPROVED] = 1.0
+    assert lib.pinn_val_keep(src.data_ptr(), dst.data_ptr(), 8, None, None, 0, st.data_ptr(), None) == 0
+    assert lib.pinn_val_keep(src.data_ptr(), dst.data_ptr(), 8, src.data_ptr(), dst.data_ptr(), 0, st.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(src, dst)
+
+
+def test_a_scripted_sequence_follows_the_model():
+    from nsfnet_amd import engine as eng
+    n, every, cap = 1003, 3, 4
+    rng = np.random.RandomState(2)
+    tgt = [rng.randn(n).astype(np.float32), rng.randn(n).astype(np.float32), None]
+    T = _planes(tgt, n)
+    scratch = eng.val_scratch(DEV)
+    st, ring = _fresh(cap)
+    mst, mring = vm.new_state(), np.zeros((cap, vm.RECORD))
+    improved = []
+    for k, m in enumerate([0.5, 0.3, 0.4, float("nan"), 0.3, 0.1]):
+        pred = [(t * np.float32(1.0 + (0.0 if np.isnan(m) else m))).astype(np.float32) for t in tgt[:2]] + [None]
+        if np.isnan(m):
+            pred[1][n // 2] = np.nan
+        eng.val_stats(_planes(pred, n), T, n, False, vm.METRICS["uv"], -1.0, every, scratch, st, ring)
+        row = vm.validate(pred, tgt, "uv", -1.0, every, mst, mring)
+        got = st.cpu().numpy()
+        improved.append(int(got[vm.S_IMPROVED]))
+        assert row[vm.R_T] == every * (k + 1)
+        for w in (vm.S_RECORDS, vm.S_BEST_T, vm.S_STALE, vm.S_NONFINITE, vm.S_IMPROVED, vm.S_CADENCE):
+            assert got[w] == mst[w], (k, w, got, mst)
+        _close(got[[vm.S_BEST]], mst[[vm.S_BEST]], 1e-12)
+        if not np.isnan(m):
+            _close(ring.cpu().numpy()[k % cap][[vm.R_METRIC]], [m], 1e-5)         # the script, not the kernel
+    assert improved == [1, 1, 0, 0, 0, 1]               # the tie does not improve, nor does the NaN
+    got = st.cpu().numpy()
+    assert got[vm.S_RECORDS] == 6 and got[vm.S_NONFINITE] == 1 and got[vm.S_BEST_T] == 18.0
+    hist = vm.history(got, ring.cpu().numpy())
+    np.testing.assert_array_equal(hist[:, vm.R_T], [9.0, 12.0, 15.0, 18.0])      # records 3..6, in order
+    _close(hist, vm.history(mst, mring), 1e-12)
+    pred = [(t * np.float32(1.2)).astype(np.float32) for t in tgt[:2]] + [None]
+    eng.val_stats(_planes(pred, n), T, n, False, vm.METRICS["uv"], 100.5, every, scratch, st, ring)      # on demand
+    vm.validate(pred, tgt, "uv", 100.5, every, mst, mring)
+    got, r = st.cpu().numpy(), ring.cpu().numpy()
+    assert r[6 % cap][vm.R_T] == 100.5 and got[vm.S_RECORDS] == 7 and got[vm.S_CADENCE] == 6
+    assert got[vm.S_STALE] == mst[vm.S_STALE] == 1 and got[vm.S_BEST_T] == 18.0
+
+
+def test_c_abi_refuses_bad_arguments():
+    import ctypes
+    from nsfnet_amd import _lib, engine as eng
+    lib = _lib.load()
+    assert lib.pinn_abi_version() == 3
+    n = 10
+    pred, tgt = _data(n, 0, "p")
+    P, T = _planes(pred, n), _planes(tgt, n)
+    scratch = eng.val_scratch(DEV)
+    st, ring = _fresh()
+    st0, ring0 = st.clone(), ring.clone()
+    arr = lambda t, rows=3, off=0: (ctypes.c_void_p * 3)(*[t[c].data_ptr() + off if c < rows else 0 for c in range(3)])
+    base = dict(n=n, pred=arr(P), tgt=arr(T), metric=0, t=-1.0, every=3, scratch=scratch.data_ptr(), state=st.data_ptr(),
+                ring=ring.data_ptr(), capacity=4)
+
+    def call(**kw):
+        a = dict(base, **kw)
+        return lib.pinn_val_stats(a["n"], a["pred"], a["tgt"], a["metric"], a["t"], a["every"], a["scratch"], a["state"],
+                                  a["ring"], a["capacity"], None)
+
+    assert call(n=0) != 0 and call(n=-3) != 0 and call(capacity=0) != 0 and call(every=0) != 0 and call(every=-1) != 0
+    assert call(pred=None) != 0 and call(tgt=None) != 0 and call(scratch=None) != 0 and call(state=None) != 0
+    assert call(ring=None) != 0
+    assert call(pred=arr(P, off=4)) != 0 and call(tgt=arr(T, off=8)) != 0          # misaligned planes
+    assert call(state=st.data_ptr() + 4) != 0 and call(ring=ring.data_ptr() + 4) != 0
+    assert call(pred=arr(P, rows=1)) != 0                                           # no v plane
+    assert call(pred=arr(P, rows=2)) != 0                                           # a pressure target without prediction
+    assert call(pred=arr(P, rows=2), tgt=arr(T, rows=2), metric=3) != 0             # a pressure metric without pressure
+    assert call(metric=5) != 0 and call(t=-2.0) != 0 and call(t=float("nan")) != 0
+    assert b"pinn_val_stats" in lib.pinn_last_error()
+    src, dst = torch.ones(8, device=DEV), torch.zeros(8, device=DEV)
+    keep = lambda s=src.data_ptr(), d=dst.data_ptr(), n0=8, s1=None, d1=None, n1=0, state=st.data_ptr(): \
+        lib.pinn_val_keep(s, d, n0, s1, d1, n1, state, None)
+    assert keep(s=None) != 0 and keep(d=None) != 0 and keep(state=None) != 0 and keep(n0=0) != 0 and keep(n0=-1) != 0
+    assert keep(n1=-1) != 0 and keep(n1=4) != 0 and keep(s=src.data_ptr() + 2) != 0 and keep(state=st.data_ptr() + 4) != 0
+    torch.cuda.synchronize()
+    assert torch.equal(_as_int(st), _as_int(st0)) and torch.equal(ring, ring0)      # device memory untouched
+    assert float(scratch.abs().sum()) == 0.0 and float(dst.abs().sum()) == 0.0
+    assert call() == 0 and keep() == 0
+    torch.cuda.synchronize()
+    assert float(st[vm.S_RECORDS]) == 1.0 and torch.equal(src, dst)
+
+
+def _as_int(t):
+    return t.view(torch.int64)
+
+
+# ---------------------------------------------------------------- engines
+def _bc(every=16):
+    return tuple(a.reshape(-1)[::every].astype(np.float32) for a in ar.cavity_boundary())
+
+
+def _points(n, seed=5):
+    rng = np.random.RandomState(seed)
+    return (rng.rand(n).astype(np.float32), rng.rand(n).astype(np.float32), (0.5 + rng.rand(n)).astype(np.float32))
+
+
+def _engine(flavour, L, H, prec, seed=5):
+    """test_rba_gpu.py's recipe: 2000 collocation points, the boundary's every 16th point."""
+    from nsfnet_amd import engine as eng
+    x, y, w = _points(2000)
+    ev = dict(flavour="ev", n_hidden_e=2, hidden_e=24, alpha_evm=0.05) if flavour == "ev" else {}
+    E = eng.PinnEngine(DEV, L, H, 2000.0, alpha_b=10.0, alpha_e=1.0, precision=prec, **ev)
+    E.net.set_flat(torch.tensor(ar.flat_params(ar.seeded_net(3, L, H, seed=seed)).numpy().copy()))
+    if flavour == "ev":
+        E.net_e.set_flat(torch.tensor(ar.flat_params(ar.seeded_net(1, 2, 24, seed=seed + 1)).numpy().copy()))
+        E.e_trainable = True                            # both nets move, so both snapshots mean something
+    E.set_collocation(x, y, weights=w if flavour == "ev" else None)
+    E.set_boundary(*_bc())
+    return E
+
+
+def _val_set(n=301):
+    """Smooth synthetic reference fields at n scattered points."""
+    rng = np.random.RandomState(17)
+    x, y = rng.rand(n).astype(np.float32), rng.rand(n).astype(np.float32)
+    u = (np.sin(np.pi * x) * np.cos(np.pi * y)).astype(np.float32)
+    v = (-np.cos(np.pi * x) * np.sin(np.pi * y)).astype(np.float32)
+    p = (0.3 + 0.5 * np.cos(np.pi * x) + x * y).astype(np.float32)
+    return x, y, u, v, p
+
+
+def _state(E):
+    torch.cuda.synchronize()
+    out = [E.net.params, E.net.m, E.net.v]
+    if E.net_e is not None:
+        out += [E.net_e.params, E.net_e.m, E.net_e.v, E.plan_f.vis_t_minus]
+    return [t.cpu().numpy().copy() for t in out]
+
+
+def _trainables(E):
+    return [net.trainable.cpu().numpy().copy() for _, net in E._nets()]
+
+
+SHAPES = [(3, 24, "fp32"), (6, 256, "bf16x3")]
+
+
+def _observe(flavour, L, H, prec, rwf):
+    """Ten eager steps of an engine with the monitor (every = 3) and of its twin without; the twin's predict() planes
+    and trainable vectors after 3, 6 and 9 updates."""
+    x, y, u, v, p = _val_set()
+    E, R = _engine(flavour, L, H, prec), _engine(flavour, L, H, prec)
+    if rwf:
+        E.set_weight_factorization(seed=3); R.set_weight_factorization(seed=3)
+    E.set_validation(x, y, u, v, p, every=3, metric="uv", history=8)
+    seen = {}
+    for k in range(1, 11):
+        E.step(1e-3); R.step(1e-3)
+        if k % 3 == 0:
+            planes = [t.cpu().numpy().copy() for t in R.predict(x, y)]
+            seen[k] = dict(planes=planes, train=_trainables(R), sd=R.net.state_dict())
+    return E, R, seen, (x, y, u, v, p)
+
+
+@pytest.mark.parametrize("flavour", ["nsfnet", "ev"])
+@pytest.mark.parametrize("L,H,prec", SHAPES)
+def test_the_monitor_only_observes_and_is_correct(flavour, L, H, prec, monkeypatch):
+    monkeypatch.setenv("NSFNET_GRAPH", "0")
+    E, R, seen, (x, y, u, v, p) = _observe(flavour, L, H, prec, rwf=False)
+    for a, b in zip(_state(E), _state(R)):              # the twin without the monitor: the same bits
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+    hist = E.validation_history()
+    np.testing.assert_array_equal(hist[:, vm.R_T], [3.0, 6.0, 9.0])
+    mst, mring = vm.new_state(), np.zeros((8, vm.RECORD))
+    for k in (3, 6, 9):
+        vm.validate(seen[k]["planes"], [u, v, p], "uv", -1.0, 3, mst, mring)
+    print("history", hist, "model", vm.history(mst, mring))
+    _close(hist, vm.history(mst, mring), 1e-12)
+    info = E.validation_info()
+    assert info["records"] == 3 and info["nonfinite"] == 0 and info["points"] == 301 and info["every"] == 3
+    assert info["best_t"] == mst[vm.S_BEST_T] and info["stale"] == mst[vm.S_STALE] and info["last"]["t"] == 9.0
+    best = 3 * (1 + int(np.argmin(hist[:, vm.R_METRIC])))
+    assert info["best_t"] == best and info["best_metric"] == hist[:, vm.R_METRIC].min()
+    nets = E._nets()
+    assert len(E._val.snap) == len(nets) == (2 if flavour == "ev" else 1)           # ev: both nets are snapshotted
+    for snap, want in zip(E._val.snap, seen[best]["train"]):
+        np.testing.assert_array_equal(_bits(snap.cpu().numpy()), _bits(want))
+    sd = E.best_state_dict()
+    for key, val in seen[best]["sd"].items():
+        assert torch.equal(sd[key], val)
+    assert (E.best_state_dict_e() is not None) == (flavour == "ev")
+    E.restore_best()
+    for got, want in zip(E.predict(x, y), seen[best]["planes"]):
+        np.testing.assert_array_equal(_bits(got.cpu().numpy()), _bits(want))
+    row = E.validate(t=77)                              # on demand, of the restored weights: the best row again
+    assert row["t"] == 77.0 and row["improved"] == 0.0 and row["metric"] == info["best_metric"]
+
+
+@pytest.mark.parametrize("flavour", ["nsfnet", "ev"])
+@pytest.mark.parametrize("L,H,prec", SHAPES)
+def test_graph_replay_is_bit_identical_to_eager(flavour, L, H, prec, monkeypatch):
+    x, y, u, v, p = _val_set()
+
+    def run(graph):
+        monkeypatch.setenv("NSFNET_GRAPH", "1" if graph else "0")
+        E = _engine(flavour, L, H, prec)
+        E.set_validation(x, y, u, v, p, every=3, metric="uv", history=8)
+        for _ in range(10):
+            E.step(1e-3)
+        out = _state(E)
+        assert len(E._graphs) == (2 if graph else 0)    # one plain, one validating
+        m = E._val
+        assert m.n == 10
+        return out + [m.state.cpu().numpy(), m.ring.cpu().numpy(), E.validation_history()] + \
+            [s.cpu().numpy() for s in m.snap]
+
+    eager, graph = run(False), run(True)
+    for a, b in zip(eager, graph):
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+    np.testing.assert_array_equal(eager[-1 - (2 if flavour == "ev" else 1)][:, vm.R_T], [3.0, 6.0, 9.0])
+
+
+def test_the_snapshot_is_theta_with_the_weight_factorization_on(monkeypatch):
+    monkeypatch.setenv("NSFNET_GRAPH", "0")
+    E, R, seen, _ = _observe("ev", 3, 24, "fp32", rwf=True)
+    for a, b in zip(_state(E), _state(R)):
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+    best = int(E.validation_info()["best_t"])
+    assert E._val.snap[0].numel() == E.net.num_train > E.net.num_params
+    sd = E.best_state_dict()
+    for key, val in seen[best]["sd"].items():           # the composed effective weights, bitwise the twin's
+        assert torch.equal(sd[key], val)
+    fac = E.best_factors()
+    assert sorted(fac) == ["net", "net_e"] and sum(f.numel() for f in fac["net"]) == E.net.rwf_rows
+    E.restore_best()
+    torch.cuda.synchronize()
+    for got, want in zip(_trainables(E), seen[best]["train"]):
+        np.testing.assert_array_equal(_bits(got), _bits(want))
+    E.set_weight_factorization(None)                    # a changed factorization drops the best
+    assert E.best_state_dict() is None and E.validation_info()["records"] == 0
+    with pytest.raises(RuntimeError):
+        E.restore_best()
