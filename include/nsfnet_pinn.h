@@ -404,7 +404,8 @@ double pinn_lr_schedule_value(const pinn_lr_schedule_t* schedule, double lr0, in
  * quads where a vector is not 16-byte aligned - the grouping, and so the result, does not depend on alignment), fp64
  * accumulation, wave reduction by shuffles, per-block partials (at most 256 blocks per vector, vector 0's numbered
  * before vector 1's), and the last block to finish folds them in a fixed order: its thread t adds partials t and
- * t + 256, then a pairwise tree combines the 256 thread sums.  No float atomics: the result is bit-reproducible,
+ * t + 256, then a pairwise tree combines the 256 thread sums (block_fold and strided_tree_fold of
+ * nsfnet_amd/csrc/fixed_fold.h, where every such order is written once).  No float atomics: the result is bit-reproducible,
  * and ranks that hold the same all-reduced gradient get the same value.  A NaN entry gives NaN.
  * scratch: pinn_grad_sqnorm_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (the
  * call leaves its workgroup ticket 0); one scratch serves one stream at a time.  As doubles: [0] the sum, [1] the
@@ -464,8 +465,8 @@ int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float*
  * device state, so that a captured step can record it at a cadence and keep the weights of its best moment without a
  * host synchronisation.  After pinn_value_forward has written the prediction planes of the n validation points,
  * per channel c in (u, v, p) over its valid points (a target that is NaN or not finite masks the point for that
- * channel, the rule of pinn_value_forward), in fp64 from the fp32 planes, not contracted, every sum in a fixed order
- * (no float atomics; bit-reproducible):
+ * channel, the rule of pinn_value_forward), in fp64 from the fp32 planes, one rounding per operation written except
+ * that (c^ - c)^2 enters D_c by one fused multiply-add, every sum in a fixed order (no float atomics; bit-reproducible):
  *   D_c = sum (c^ - c)^2,  T_c = sum c^2,  n_c = the valid count;  for p also  A = sum d,  B = sum p,  d = p^ - p
  *   e_c  = sqrt(D_c / T_c)                                   a fraction, not percent
  *   e_p0 = sqrt(max(D_p - A^2 / n_p, 0) / (T_p - B^2 / n_p)) the pressure error up to a constant (a cavity fixes the

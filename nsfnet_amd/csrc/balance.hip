@@ -17,17 +17,12 @@ namespace {
 constexpr int kBlk = 64;          // parameters per partials block (one per reduce_terms_kernel workgroup)
 constexpr int kUpdThreads = 256;
 
-// NaN-propagating max of non-negative values: a NaN gradient entry must reach lambda_hat (and skip the update)
-__device__ __forceinline__ double nmax(double a, double b) { return (b > a || b != b) ? b : a; }
-
-// max and sum of |v| over the 64 lanes of a wave, in a fixed butterfly order; lane 0 holds the result
+// max (NaN-propagating: a NaN gradient entry must reach lambda_hat and skip the update) and sum of |v| over the 64
+// lanes of a wave; lane 0 holds the result
 __device__ __forceinline__ void wave_abs_stats(float v, double& mx, double& sm) {
-  mx = fabs((double)v); sm = mx;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    mx = nmax(mx, __shfl_down(mx, off, 64));
-    sm = __dadd_rn(sm, __shfl_down(sm, off, 64));
-  }
+  const double a = fabs((double)v);
+  mx = wave_fold<FoldNanMax>(a);
+  sm = wave_fold<FoldSum>(a);
 }
 
 __global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
@@ -95,27 +90,8 @@ __global__ __launch_bounds__(kUpdThreads) void balance_update_kernel(const doubl
                                                                      float* __restrict__ lam, double* record) {
   __shared__ double red[kUpdThreads][6];
   const int tid = threadIdx.x;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (long b = tid; b < nblk; b += kUpdThreads) {      // thread tid: blocks tid, tid + 256, ... in order
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      acc[2 * t] = nmax(acc[2 * t], partials[b * 6 + 2 * t]);
-      acc[2 * t + 1] += partials[b * 6 + 2 * t + 1];
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) red[tid][c] = acc[c];
-  __syncthreads();
-  for (int half = kUpdThreads / 2; half > 0; half >>= 1) {   // fixed pairwise tree: thread i takes i + half
-    if (tid < half) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        red[tid][2 * t] = nmax(red[tid][2 * t], red[tid + half][2 * t]);
-        red[tid][2 * t + 1] += red[tid + half][2 * t + 1];
-      }
-    }
-    __syncthreads();
-  }
+  strided_tree_fold<kUpdThreads, FoldNanMax, FoldSum, FoldNanMax, FoldSum, FoldNanMax, FoldSum>(
+      [&](long b, int c) { return partials[b * 6 + c]; }, nblk, red);
   if (tid != 0) return;
   const double P = (double)n;
   const double max_r = red[0][0];
@@ -148,11 +124,6 @@ __global__ void balance_combine_kernel(float* g, const float* gr, const float* _
   }
 }
 
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
 }  // namespace
 
 long balance_blocks(long n) { return (n + kBlk - 1) / kBlk; }
@@ -160,19 +131,19 @@ long balance_blocks(long n) { return (n + kBlk - 1) / kBlk; }
 int launch_reduce_terms(const TermReduceArgs& a, hipStream_t s) {
   size_t P = flat_total(a.H, a.L, a.n_out);
   hipLaunchKernelGGL(reduce_terms_kernel, dim3((unsigned)((P + 63) / 64)), dim3(512), 0, s, a);
-  return status();
+  return launch_status();
 }
 
 int launch_balance_stats(const float* v0, const float* v1, const float* v2, long n, double* partials, hipStream_t s) {
   hipLaunchKernelGGL(balance_stats_kernel, dim3((unsigned)balance_blocks(n)), dim3(kBlk), 0, s, v0, v1, v2, n, partials);
-  return status();
+  return launch_status();
 }
 
 int launch_balance_update(const double* partials, long n, int terms, double beta, float* lam, double* record,
                           hipStream_t s) {
   hipLaunchKernelGGL(balance_update_kernel, dim3(1), dim3(kUpdThreads), 0, s, partials, balance_blocks(n), n, terms,
                      beta, lam, record);
-  return status();
+  return launch_status();
 }
 
 int launch_balance_combine(float* g, const float* gr, const float* gb, const float* gs, const float* lam, long n,
@@ -180,5 +151,5 @@ int launch_balance_combine(float* g, const float* gr, const float* gb, const flo
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(balance_combine_kernel, dim3(blocks), dim3(256), 0, s, g, gr, gb, gs, lam, n);
-  return status();
+  return launch_status();
 }

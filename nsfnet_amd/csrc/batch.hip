@@ -66,13 +66,11 @@ __global__ __launch_bounds__(kThreads) void batch_scatter_kernel(const long long
 int launch_batch_draw(const BatchDrawArgs& a, hipStream_t s) {
   const int blocks = (int)((a.b + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(batch_draw_kernel, dim3(blocks), dim3(kThreads), 0, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }
 
 int launch_batch_scatter(const long long* idx, long b, long n, const float* src, float* dst, hipStream_t s) {
   const int blocks = (int)((b + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(batch_scatter_kernel, dim3(blocks), dim3(kThreads), 0, s, idx, b, n, src, dst);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }

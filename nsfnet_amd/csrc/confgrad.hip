@@ -42,21 +42,8 @@ __global__ __launch_bounds__(kCoefThreads) void confgrad_coef_kernel(const doubl
 #pragma clang fp contract(off)
   __shared__ double red[kCoefThreads][6];
   const int tid = threadIdx.x;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (long b = tid; b < nblk; b += kCoefThreads) {     // thread tid: blocks tid, tid + 256, ... in order
-#pragma unroll
-    for (int c = 0; c < 6; ++c) acc[c] += partials[b * 6 + c];
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) red[tid][c] = acc[c];
-  __syncthreads();
-  for (int half = kCoefThreads / 2; half > 0; half >>= 1) {  // fixed pairwise tree: thread i takes i + half
-    if (tid < half) {
-#pragma unroll
-      for (int c = 0; c < 6; ++c) red[tid][c] += red[tid + half][c];
-    }
-    __syncthreads();
-  }
+  strided_tree_fold<kCoefThreads, FoldSum, FoldSum, FoldSum, FoldSum, FoldSum, FoldSum>(
+      [&](long b, int c) { return partials[b * 6 + c]; }, nblk, red);
   if (tid != 0) return;
   const double A[3] = {red[0][0], red[0][1], red[0][2]};             // rr bb ss
   const double X[3] = {red[0][3], red[0][4], red[0][5]};             // rb rs bs
@@ -132,22 +119,17 @@ __global__ void confgrad_combine_kernel(float* g, const float* gr, const float* 
   }
 }
 
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
 }  // namespace
 
 int launch_confgrad_gram(const float* v0, const float* v1, const float* v2, long n, double* partials, hipStream_t s) {
   hipLaunchKernelGGL(confgrad_gram_kernel, dim3((unsigned)balance_blocks(n)), dim3(kBlk), 0, s, v0, v1, v2, n, partials);
-  return status();
+  return launch_status();
 }
 
 int launch_confgrad_coef(const double* partials, long n, int nterms, float* coef, double* record, hipStream_t s) {
   hipLaunchKernelGGL(confgrad_coef_kernel, dim3(1), dim3(kCoefThreads), 0, s, partials, balance_blocks(n), nterms, coef,
                      record);
-  return status();
+  return launch_status();
 }
 
 int launch_confgrad_combine(float* g, const float* gr, const float* gb, const float* gs, const float* coef, long n,
@@ -155,5 +137,5 @@ int launch_confgrad_combine(float* g, const float* gr, const float* gb, const fl
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(confgrad_combine_kernel, dim3(blocks), dim3(256), 0, s, g, gr, gb, gs, coef, n);
-  return status();
+  return launch_status();
 }

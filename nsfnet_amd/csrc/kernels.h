@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "fixed_fold.h"
 #include "layout.h"
 #include "spill.h"
 
@@ -161,16 +162,13 @@ struct TermReduceArgs {
 };
 
 // The six dot products of the 64 (r, b, s) a full wave holds, one triple per lane: exact fp64 products of the fp32
-// values, summed in the fixed butterfly order of balance.hip's wave_abs_stats; lane 0 writes out[0..5] = rr bb ss rb rs bs.
+// values, each summed by wave_fold (fixed_fold.h); lane 0 writes out[0..5] = rr bb ss rb rs bs.
 __device__ __forceinline__ void wave_gram(float r, float b, float s, int lane, double* __restrict__ out) {
   const double dr = r, db = b, ds = s;
   double q[6] = {__dmul_rn(dr, dr), __dmul_rn(db, db), __dmul_rn(ds, ds),
                  __dmul_rn(dr, db), __dmul_rn(dr, ds), __dmul_rn(db, ds)};
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) q[c] = __dadd_rn(q[c], __shfl_down(q[c], off, 64));
-  }
+  for (int c = 0; c < 6; ++c) q[c] = wave_fold<FoldSum>(q[c]);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 6; ++c) out[c] = q[c];

@@ -19,6 +19,7 @@
 //   lb_finish      one workgroup: the result block
 // The first call after a reset (t_prev = 0) runs only lb_update (empty history, gamma = 1) and lb_pass_c: d = -g.
 // t_prev < 0 offers a zero step (a line search that accepted t = 0): torch forms s = 0 and rejects the pair.
+#include "fixed_fold.h"
 #include "kernels.h"
 
 #include <cstdint>
@@ -88,21 +89,6 @@ __device__ __forceinline__ double dot4(float4 a, float4 b) {
   return __fma_rn((double)a.w, (double)b.w, s);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-// NaN-propagating max of non-negative values (max|g| must report a NaN, as torch's does)
-__device__ __forceinline__ float nmax(float a, float b) { return (b > a || b != b) ? b : a; }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_down(v, off, 64));
-  return v;
-}
-
 // Pass A.  grid = nb blocks of LB_THREADS; partial column c of block b at partA[c * nb + b]:
 // c = 0..3: y's, y'y, s'g, y'g of the candidate; c = 4 (j + 1) + k: s_j'y, y_j'y, s_j'g, y_j'g of live pair j.
 __global__ __launch_bounds__(LB_THREADS) void lb_pass_a(void* ws, LbLayout L, const float* __restrict__ g,
@@ -155,15 +141,14 @@ __global__ __launch_bounds__(LB_THREADS) void lb_pass_a(void* ws, LbLayout L, co
 #pragma unroll
     for (int q = 0; q < 4 * LB_UNROLL; ++q) {
       if (q < 4 * nj) {
-        const double s = wave_sum(v[q]);
+        const double s = wave_fold<FoldSum>(v[q]);
         if (lane == 0) red[w][q] = s;
       }
     }
     __syncthreads();
     if ((int)threadIdx.x < 4 * nj) {
       const int q = threadIdx.x;
-      double s = red[0][q];
-      for (int i = 1; i < LB_THREADS / 64; ++i) s = __dadd_rn(s, red[i][q]);
+      const double s = ordered_fold<FoldSum>(red[0][q], &red[1][q], LB_THREADS / 64 - 1, 4 * LB_UNROLL);   // wave order
       const long col = (j0 < 0 ? 0 : 4 * (j0 + 1)) + q;
       part[col * L.nb + blockIdx.x] = s;
     }
@@ -178,17 +163,8 @@ __global__ __launch_bounds__(LB_THREADS) void lb_colsum(void* ws, LbLayout L) {
   const long col = blockIdx.x;
   if (col >= 4L * (h->count + 1)) return;
   const double* part = at<double>(ws, L.o_partA) + col * L.nb;
-  const long ch = (L.nb + LB_THREADS - 1) / LB_THREADS;
-  const long lo = threadIdx.x * ch < L.nb ? threadIdx.x * ch : L.nb, hi = lo + ch < L.nb ? lo + ch : L.nb;
-  double s = 0.0;
-  for (long b = lo; b < hi; ++b) s = __dadd_rn(s, part[b]);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < LB_THREADS; ++i) t = __dadd_rn(t, red[i]);
-    at<double>(ws, L.o_col)[col] = t;
-  }
+  const double t = chunk_fold<LB_THREADS, FoldSum>([&](long b) { return part[b]; }, L.nb, red);
+  if (threadIdx.x == 0) at<double>(ws, L.o_col)[col] = t;
 }
 
 // One workgroup: the history update and the dense part.  first != 0: empty history, gamma = 1 (d = -g).
@@ -337,18 +313,18 @@ __global__ __launch_bounds__(LB_THREADS) void lb_pass_c(void* ws, LbLayout L, co
   double gtd = dot4(gv, dv);
   double g1 = __dadd_rn(__dadd_rn((double)fabsf(gv.x), (double)fabsf(gv.y)),
                         __dadd_rn((double)fabsf(gv.z), (double)fabsf(gv.w)));
+  // NaN-propagating: max|d| and max|g| must report a NaN, as torch's do
   float dm = nmax(nmax(fabsf(dv.x), fabsf(dv.y)), nmax(fabsf(dv.z), fabsf(dv.w)));
   float gm = nmax(nmax(fabsf(gv.x), fabsf(gv.y)), nmax(fabsf(gv.z), fabsf(gv.w)));
-  gtd = wave_sum(gtd); g1 = wave_sum(g1); dm = wave_max(dm); gm = wave_max(gm);
+  gtd = wave_fold<FoldSum>(gtd); g1 = wave_fold<FoldSum>(g1); dm = wave_fold<FoldNanMax>(dm); gm = wave_fold<FoldNanMax>(gm);
   if (lane == 0) { redd[w][0] = gtd; redd[w][1] = g1; redf[w][0] = dm; redf[w][1] = gm; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double s0 = redd[0][0], s1 = redd[0][1];
-    float m0 = redf[0][0], m1 = redf[0][1];
-    for (int i = 1; i < LB_THREADS / 64; ++i) {
-      s0 = __dadd_rn(s0, redd[i][0]); s1 = __dadd_rn(s1, redd[i][1]);
-      m0 = nmax(m0, redf[i][0]); m1 = nmax(m1, redf[i][1]);
-    }
+    constexpr int W = LB_THREADS / 64;              // the wave results in wave order
+    const double s0 = ordered_fold<FoldSum>(redd[0][0], &redd[1][0], W - 1, 2);
+    const double s1 = ordered_fold<FoldSum>(redd[0][1], &redd[1][1], W - 1, 2);
+    const float m0 = ordered_fold<FoldNanMax>(redf[0][0], &redf[1][0], W - 1, 2);
+    const float m1 = ordered_fold<FoldNanMax>(redf[0][1], &redf[1][1], W - 1, 2);
     double* part = at<double>(ws, L.o_partC);
     part[0 * L.nb + blockIdx.x] = s0;
     part[1 * L.nb + blockIdx.x] = (double)m0;
@@ -361,27 +337,16 @@ __global__ __launch_bounds__(LB_THREADS) void lb_pass_c(void* ws, LbLayout L, co
 __global__ __launch_bounds__(LB_THREADS) void lb_finish(void* ws, LbLayout L, double* result, int with_state) {
   __shared__ double red[4][LB_THREADS];
   const double* part = at<double>(ws, L.o_partC);
-  const long ch = (L.nb + LB_THREADS - 1) / LB_THREADS;
-  const long lo = threadIdx.x * ch < L.nb ? threadIdx.x * ch : L.nb, hi = lo + ch < L.nb ? lo + ch : L.nb;
+  // chunk_fold of the four columns at once: lane 0 of wave c finishes column c
+  static_assert(LB_THREADS / 64 == 4, "one wave per column");
   for (int c = 0; c < 4; ++c) {
-    const bool mx = c == 1 || c == 3;
-    double s = 0.0;
-    for (long b = lo; b < hi; ++b) {
-      const double v = part[c * L.nb + b];
-      s = mx ? ((v > s || v != v) ? v : s) : __dadd_rn(s, v);
-    }
-    red[c][threadIdx.x] = s;
+    auto load = [&](long b) { return part[c * L.nb + b]; };
+    red[c][threadIdx.x] = (c & 1) ? chunk_partial<LB_THREADS, FoldNanMax>(load, L.nb) : chunk_partial<LB_THREADS, FoldSum>(load, L.nb);
   }
   __syncthreads();
-  if (threadIdx.x < 4) {
-    const int c = threadIdx.x;
-    const bool mx = c == 1 || c == 3;
-    double s = 0.0;
-    for (int i = 0; i < LB_THREADS; ++i) {
-      const double v = red[c][i];
-      s = mx ? ((v > s || v != v) ? v : s) : __dadd_rn(s, v);
-    }
-    result[c] = s;
+  if ((threadIdx.x & 63) == 0) {
+    const int c = threadIdx.x >> 6;
+    result[c] = (c & 1) ? ordered_fold<FoldNanMax>(0.0, red[c], LB_THREADS) : ordered_fold<FoldSum>(0.0, red[c], LB_THREADS);
   }
   if (with_state && threadIdx.x == 0) {
     const LbHead* h = at<LbHead>(ws, 0);
@@ -414,12 +379,12 @@ int launch_lbfgs_direction(void* ws, long n, long m, const float* g, float t_pre
   hipLaunchKernelGGL(lb_update, dim3(1), dim3(LB_THREADS), shm, s, ws, L, first);
   hipLaunchKernelGGL(lb_pass_c, dim3((unsigned)L.nb), dim3(LB_THREADS), 0, s, ws, L, g, d, 1);
   hipLaunchKernelGGL(lb_finish, dim3(1), dim3(LB_THREADS), 0, s, ws, L, result, 1);
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int launch_lbfgs_probe(void* ws, long n, long m, const float* g, const float* d, double* result, hipStream_t s) {
   const LbLayout L = layout(n, m);
   hipLaunchKernelGGL(lb_pass_c, dim3((unsigned)L.nb), dim3(LB_THREADS), 0, s, ws, L, g, const_cast<float*>(d), 0);
   hipLaunchKernelGGL(lb_finish, dim3(1), dim3(LB_THREADS), 0, s, ws, L, result, 0);
-  return (int)hipGetLastError();
+  return launch_status();
 }

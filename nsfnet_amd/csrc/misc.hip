@@ -1,6 +1,7 @@
 // Small bandwidth-bound kernels around the MFMA pipeline: parameter re-layout,
 // fixed-order gradient / loss reductions and the fused Adam update.
 #include "kernels.h"
+#include "optim.h"
 
 // ---------------------------------------------------------------------------
 // flat state_dict-order parameters (NSFnet/net.py:36-46) -> padded, MFMA-fragment
@@ -78,8 +79,7 @@ int launch_prep(const float* params, float* prep, int H, int HP, int L, int n_ou
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(256), 0, s, params, prep, H, HP, L, n_out, prec_fwd, prec_bwd);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }
 
 // ---------------------------------------------------------------------------
@@ -115,8 +115,7 @@ __global__ __launch_bounds__(512) void reduce_kernel(ReduceArgs a) {
 int launch_reduce(const ReduceArgs& a, hipStream_t s) {
   size_t P = flat_total(a.H, a.L, a.n_out);
   hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((P + 63) / 64)), dim3(512), 0, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }
 
 // ---------------------------------------------------------------------------
@@ -140,8 +139,7 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict_
 int launch_loss_sums(const float* partials, int nparts, float* out, hipStream_t s) {
   static_assert(PINN_NLOSS * 32 == 256, "loss_sums_kernel layout");
   hipLaunchKernelGGL(loss_sums_kernel, dim3(1), dim3(256), 0, s, partials, nparts, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }
 
 // ---------------------------------------------------------------------------
@@ -153,14 +151,8 @@ int launch_loss_sums(const float* partials, int nparts, float* out, hipStream_t 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n, float step_size, float b1, float b2, float eps,
                             float bc2_sqrt) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    float mi = m[i] + (gi - m[i]) * (1.f - b1);           // torch: exp_avg.lerp_(grad, 1-beta1)
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;           // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
-    m[i] = mi; v[i] = vi;
-  }
+  adam_update<false>(p, g, m, v, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x,
+                      n, step_size, b1, b2, eps, bc2_sqrt);
 }
 
 // Same update with the step count kept ON THE DEVICE (bias corrections computed in-kernel), so the whole
@@ -168,27 +160,13 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
                                 long long* step_counter) {
-  const double t = (double)(__atomic_load_n(step_counter, __ATOMIC_RELAXED) + 1);
-  const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
-  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
-    m[i] = mi; v[i] = vi;
-  }
+  float step_size, bc2_sqrt;
+  adam_bias_correction(lr, b1, b2, step_counter, step_size, bc2_sqrt);
+  adam_update<false>(p, g, m, v, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x,
+                      n, step_size, b1, b2, eps, bc2_sqrt);
   // the last workgroup to get here has seen every other one read the counter: it advances it
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long* ticket = reinterpret_cast<unsigned long long*>(step_counter + 1);
-    __threadfence();
-    if (atomicAdd(ticket, 1ull) == (unsigned long long)gridDim.x - 1) {
-      *ticket = 0;
-      step_counter[0] = step_counter[0] + 1;
-    }
-  }
+  if (threadIdx.x == 0 && last_ticket(step_counter + 1)) step_counter[0] = step_counter[0] + 1;
 }
 
 int launch_adam_dev(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
@@ -197,8 +175,7 @@ int launch_adam_dev(float* p, const float* g, float* m, float* v, long n, float 
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, step_counter);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }
 
 int launch_adam(float* p, const float* g, float* m, float* v, long n, float step_size, float b1, float b2,
@@ -207,6 +184,5 @@ int launch_adam(float* p, const float* g, float* m, float* v, long n, float step
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_size, b1, b2, eps, bc2_sqrt);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  return launch_status();
 }

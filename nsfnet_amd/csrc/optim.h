@@ -1,5 +1,6 @@
 // Learning-rate schedules and gradient clipping for Adam (optim.hip): the schedule formula,
-// shared by the update kernel and the host query, and the launch entry points.
+// shared by the update kernel and the host query, the one Adam update body of adam_kernel, adam_dev_kernel (misc.hip)
+// and adam_sched_kernel (optim.hip), and the launch entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -27,6 +28,40 @@ __host__ __device__ inline double lr_schedule_value(const pinn_lr_schedule_t& s,
     lr = lr * (s.warmup_start + (1.0 - s.warmup_start) * w);
   }
   return lr;
+}
+
+// g * coef as one rounded fp32 multiply, whatever consumes the product: what the caller's own `grads * coef` gives
+__device__ __forceinline__ float scaled(float g, float coef) {
+#pragma clang fp contract(off)
+  const float r = g * coef;
+  return r;
+}
+
+// Adam's bias corrections for update t + 1, t read from device memory: step_size = lr / (1 - b1^t), sqrt(1 - b2^t)
+__device__ __forceinline__ void adam_bias_correction(float lr, float b1, float b2, const long long* step_counter,
+                                                     float& step_size, float& bc2_sqrt) {
+  const double t = (double)(__atomic_load_n(step_counter, __ATOMIC_RELAXED) + 1);
+  const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
+  step_size = (float)((double)lr / bc1);
+  bc2_sqrt = (float)sqrt(bc2);
+}
+
+// torch.optim.Adam single-tensor semantics (weight_decay = 0, amsgrad = False) on entries first, first + stride, ... < n
+// (the kernel hands its thread's grid-stride range in: blockDim read there is the launch's uniform one); CLIP: the
+// gradient is scaled by coef first.
+//   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)
+template <bool CLIP>
+__device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, long first, long stride, long n, float step_size,
+                                            float b1, float b2, float eps, float bc2_sqrt, float coef = 1.f) {
+  for (long i = first; i < n; i += stride) {
+    float gi = CLIP ? scaled(g[i], coef) : g[i];
+    float mi = m[i] + (gi - m[i]) * (1.f - b1);           // torch: exp_avg.lerp_(grad, 1-beta1)
+    float vi = v[i] * b2 + (1.f - b2) * gi * gi;           // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+    float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] - step_size * (mi / denom);
+    m[i] = mi; v[i] = vi;
+  }
 }
 
 struct AdamSchedArgs {

@@ -1,15 +1,15 @@
 // Learning-rate schedules and global-norm gradient clipping for the Adam stages.  Both live on
 // the device so that a captured training step replays with no host scalar changing between steps:
 //   grad_sqnorm_kernel   the fp64 sum of squares of up to two fp32 vectors (main net, entropy net) into scratch[0]:
-//                        grid-stride loop of 16-byte loads, wave trees, per-block partials (vector 0's blocks numbered
-//                        before vector 1's); the last block to finish folds them in a fixed order: thread t adds
-//                        partials t and t + 256, then a pairwise tree over the threads.  No float atomics.
-//   adam_sched_kernel    adam_dev_kernel (misc.hip) with lr = the fp32 value of lr_e (optim.h) at the epoch counter e
+//                        grid-stride loop of 16-byte loads, block_fold, per-block partials (vector 0's blocks numbered
+//                        before vector 1's); the last block to finish folds them by strided_tree_fold (fixed_fold.h).
+//                        No float atomics.
+//   adam_sched_kernel    adam_dev_kernel (misc.hip; the update body of both is adam_update, optim.h) with lr = the fp32 value of lr_e (optim.h) at the epoch counter e
 //                        read from device memory and, when a squared norm is given, the gradient scaled by the
 //                        clip_grad_norm_ coefficient.  Its last workgroup advances Adam's t, on request e, and
 //                        writes the record.
+#include "fixed_fold.h"
 #include "optim.h"
-#include "xwg_fold.h"
 
 namespace {
 
@@ -29,7 +29,7 @@ __host__ __device__ inline long blocks_of(long n) {
 __global__ __launch_bounds__(kThreads) void grad_sqnorm_kernel(const float* __restrict__ g0, long n0,
                                                                const float* __restrict__ g1, long n1, double* scratch) {
   __shared__ double red[kThreads / 64];
-  __shared__ double tree[kThreads];
+  __shared__ double tree[kThreads][1];
   __shared__ int flag;
   const long nb0 = blocks_of(n0);
   const bool second = (long)blockIdx.x >= nb0;
@@ -51,35 +51,11 @@ __global__ __launch_bounds__(kThreads) void grad_sqnorm_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < kPer; ++j) acc += (double)q[j] * (double)q[j];      // the product is exact in fp64
   }
-  // over the workgroup in a fixed order: wave shuffle tree, then the wave results in wave order
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = red[0];
-    for (int i = 1; i < kThreads / 64; ++i) t += red[i];
-    put(scratch + kPart + blockIdx.x, t);
-  }
+  acc = block_fold<FoldSum, kThreads>(acc, red);
+  if (threadIdx.x == 0) put(scratch + kPart + blockIdx.x, acc);
   if (!last_block(scratch + kTicket, &flag)) return;
-  // thread t adds the partials of blocks t and t + 256 (vector 0's blocks come first in that numbering); then a fixed
-  // pairwise tree over the 256 thread sums (thread i takes i + half)
-  double f = 0.0;
-  for (int k = threadIdx.x; k < (int)gridDim.x; k += kThreads) f += get(scratch + kPart + k);
-  tree[threadIdx.x] = f;
-  __syncthreads();
-  for (int half = kThreads / 2; half > 0; half >>= 1) {
-    if (threadIdx.x < half) tree[threadIdx.x] += tree[threadIdx.x + half];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scratch[0] = tree[0];
-}
-
-// g * coef as one rounded fp32 multiply, whatever consumes the product: what the caller's own `grads * coef` gives
-__device__ __forceinline__ float scaled(float g, float coef) {
-#pragma clang fp contract(off)
-  const float r = g * coef;
-  return r;
+  strided_tree_fold<kThreads, FoldSum>([&](long k, int) { return get(scratch + kPart + k); }, (long)gridDim.x, tree);
+  if (threadIdx.x == 0) scratch[0] = tree[0][0];
 }
 
 template <bool CLIP>
@@ -93,47 +69,24 @@ __global__ void adam_sched_kernel(AdamSchedArgs a) {
     const double c = a.max_norm / (norm + 1e-6);
     coef = (float)(c > 1.0 ? 1.0 : c);              // a NaN norm stays NaN
   }
-  const float b1 = a.b1, b2 = a.b2, eps = a.eps;
-  float* __restrict__ p = a.p;
-  const float* __restrict__ g = a.g;
-  float* __restrict__ m = a.m;
-  float* __restrict__ v = a.v;
-  // from here to the ticket: the body of adam_dev_kernel
-  const double t = (double)(__atomic_load_n(a.step_counter, __ATOMIC_RELAXED) + 1);
-  const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
-  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
-    float gi = CLIP ? scaled(g[i], coef) : g[i];
-    float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
-    m[i] = mi; v[i] = vi;
-  }
+  float step_size, bc2_sqrt;
+  adam_bias_correction(lr, a.b1, a.b2, a.step_counter, step_size, bc2_sqrt);
+  adam_update<CLIP>(a.p, a.g, a.m, a.v, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x,
+                    a.n, step_size, a.b1, a.b2, a.eps, bc2_sqrt, coef);
   // the last workgroup to get here has seen every other one read both counters: it advances them
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long* ticket = reinterpret_cast<unsigned long long*>(a.step_counter + 1);
-    __threadfence();
-    if (atomicAdd(ticket, 1ull) == (unsigned long long)gridDim.x - 1) {
-      *ticket = 0;
-      a.step_counter[0] = a.step_counter[0] + 1;
-      a.record[0] = (double)e;
-      a.record[1] = (double)lr;
-      a.record[2] = norm;
-      a.record[3] = (double)coef;
-      if (a.advance) {
-        a.epoch[0] = e + 1;
-        if (coef < 1.f) a.record[4] += 1.0;
-        a.record[5] += 1.0;
-      }
+  if (threadIdx.x == 0 && last_ticket(a.step_counter + 1)) {
+    a.step_counter[0] = a.step_counter[0] + 1;
+    a.record[0] = (double)e;
+    a.record[1] = (double)lr;
+    a.record[2] = norm;
+    a.record[3] = (double)coef;
+    if (a.advance) {
+      a.epoch[0] = e + 1;
+      if (coef < 1.f) a.record[4] += 1.0;
+      a.record[5] += 1.0;
     }
   }
-}
-
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
 }
 
 }  // namespace
@@ -143,7 +96,7 @@ size_t grad_sqnorm_scratch_bytes() { return (size_t)kScratchDoubles * sizeof(dou
 int launch_grad_sqnorm(const float* g0, long n0, const float* g1, long n1, double* scratch, hipStream_t s) {
   const long blocks = blocks_of(n0) + (n1 > 0 ? blocks_of(n1) : 0);      // <= 2 kMaxBlocksVec partials
   hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, g0, n0, g1, n1, scratch);
-  return status();
+  return launch_status();
 }
 
 int launch_adam_sched(const AdamSchedArgs& a, hipStream_t s) {
@@ -152,5 +105,5 @@ int launch_adam_sched(const AdamSchedArgs& a, hipStream_t s) {
   if (blocks > 2048) blocks = 2048;
   if (a.sq) hipLaunchKernelGGL(adam_sched_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(adam_sched_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-  return status();
+  return launch_status();
 }

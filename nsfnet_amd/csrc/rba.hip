@@ -13,14 +13,14 @@
 // once on store (w from the stored lam).  rmax not finite or 0: nothing is written, the record's skip count goes up
 // by one (the convention of balance_update_kernel).  The weights evaluation k uses are those made after evaluation
 // k - 1: the fused forward + reverse kernel needs w before the residual exists.
-// Three kernels, bandwidth-bound; no float atomics, every sum has a fixed order (bit-reproducible):
-//   rba_stats_kernel   rmax and the unweighted sums of eq1^2..eq4^2: grid-stride loop of 16-byte loads, wave trees,
-//                      per-block partials, the last block to finish folds them in block order
+// Three kernels, bandwidth-bound; no float atomics, every sum has a fixed order (fixed_fold.h; bit-reproducible):
+//   rba_stats_kernel   rmax and the unweighted sums of eq1^2..eq4^2: grid-stride loop of 16-byte loads, block_fold,
+//                      per-block partials, the last block to finish folds them by strided_tree_fold
 //   rba_apply_kernel   the update with rmax read from scratch (a MAX all-reduce of that word may sit in between);
 //                      min / max / sum of the lam values it wrote, folded the same way, go to the record
 //   rba_fill_kernel    lam = init, w = s init^2
-#include "kernels.h"
-#include "xwg_fold.h"
+#include "fixed_fold.h"
+#include "residual_planes.h"
 
 namespace {
 
@@ -33,50 +33,6 @@ constexpr int kTicketStats = 5, kTicketApply = 6;
 constexpr int kPartStats = 8;                      // [kMaxBlocks][5] max, sum eq1^2 .. eq4^2
 constexpr int kPartApply = kPartStats + 5 * kMaxBlocks;   // [kMaxBlocks][4] min, max, sum, count of lam written
 constexpr int kScratchDoubles = kPartApply + 4 * kMaxBlocks;
-
-__device__ __forceinline__ double sq(float v) { return __dmul_rn((double)v, (double)v); }   // exact
-// NaN-propagating max of non-negative values
-__device__ __forceinline__ double nmax(double a, double b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ double e2_of(float e1, float e2, float e3, float e4, double w4) {
-  double s = __dadd_rn(__dadd_rn(sq(e1), sq(e2)), sq(e3));
-  return __dadd_rn(s, __dmul_rn(w4, sq(e4)));       // w4 = 0: e4 is 0 as well (the plane is not read)
-}
-
-// op 0: sum, 1: NaN-propagating max, 2: min, 3: max
-template <int OP>
-__device__ __forceinline__ double comb(double a, double b) {
-  if (OP == 0) return __dadd_rn(a, b);
-  if (OP == 1) return nmax(a, b);
-  if (OP == 2) return b < a ? b : a;
-  return b > a ? b : a;
-}
-// over the workgroup in a fixed order: wave shuffle tree, then the wave results in wave order (valid in thread 0)
-template <int OP>
-__device__ __forceinline__ double block_fold(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = comb<OP>(v, __shfl_down(v, off, 64));
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();                                  // red may still be read from the previous fold
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double t = red[0];
-  if (threadIdx.x == 0)
-    for (int i = 1; i < kThreads / 64; ++i) t = comb<OP>(t, red[i]);
-  return t;
-}
-
-// the four residual values of points base .. base + 3 (base % 4 == 0 and base < n <= npad, npad % 4 == 0: in bounds)
-__device__ __forceinline__ void load_eq(const float* __restrict__ fld, long npad, long base, bool with4, float v[4][4]) {
-  const float4 q1 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ1 * npad + base);
-  const float4 q2 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ2 * npad + base);
-  const float4 q3 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ3 * npad + base);
-  float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (with4) q4 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ4 * npad + base);
-  v[0][0] = q1.x; v[0][1] = q1.y; v[0][2] = q1.z; v[0][3] = q1.w;
-  v[1][0] = q2.x; v[1][1] = q2.y; v[1][2] = q2.z; v[1][3] = q2.w;
-  v[2][0] = q3.x; v[2][1] = q3.y; v[2][2] = q3.z; v[2][3] = q3.w;
-  v[3][0] = q4.x; v[3][1] = q4.y; v[3][2] = q4.z; v[3][3] = q4.w;
-}
 
 __global__ __launch_bounds__(kThreads) void rba_stats_kernel(const float* __restrict__ fld, long npad, long n, double w4,
                                                              double* scratch) {
@@ -95,33 +51,17 @@ __global__ __launch_bounds__(kThreads) void rba_stats_kernel(const float* __rest
       for (int c = 0; c < 4; ++c) acc[1 + c] = __dadd_rn(acc[1 + c], sq(v[c][j]));
     }
   }
-  acc[0] = block_fold<1>(acc[0], red);
+  acc[0] = block_fold<FoldNanMax, kThreads>(acc[0], red);
 #pragma unroll
-  for (int c = 1; c < 5; ++c) acc[c] = block_fold<0>(acc[c], red);
+  for (int c = 1; c < 5; ++c) acc[c] = block_fold<FoldSum, kThreads>(acc[c], red);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int c = 0; c < 5; ++c) put(scratch + kPartStats + (size_t)blockIdx.x * 5 + c, acc[c]);
   }
   if (!last_block(scratch + kTicketStats, &flag)) return;
-  // thread t: blocks t, t + 256, ... in order; then a fixed pairwise tree (thread i takes i + half)
   __shared__ double tree[kThreads][5];
-  double f[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < (int)gridDim.x; b += kThreads) {
-    f[0] = nmax(f[0], get(scratch + kPartStats + (size_t)b * 5));
-#pragma unroll
-    for (int c = 1; c < 5; ++c) f[c] = __dadd_rn(f[c], get(scratch + kPartStats + (size_t)b * 5 + c));
-  }
-#pragma unroll
-  for (int c = 0; c < 5; ++c) tree[threadIdx.x][c] = f[c];
-  __syncthreads();
-  for (int half = kThreads / 2; half > 0; half >>= 1) {
-    if (threadIdx.x < half) {
-      tree[threadIdx.x][0] = nmax(tree[threadIdx.x][0], tree[threadIdx.x + half][0]);
-#pragma unroll
-      for (int c = 1; c < 5; ++c) tree[threadIdx.x][c] = __dadd_rn(tree[threadIdx.x][c], tree[threadIdx.x + half][c]);
-    }
-    __syncthreads();
-  }
+  strided_tree_fold<kThreads, FoldNanMax, FoldSum, FoldSum, FoldSum, FoldSum>(
+      [&](long b, int c) { return get(scratch + kPartStats + (size_t)b * 5 + c); }, (long)gridDim.x, tree);
   if (threadIdx.x != 0) return;
   double mx = tree[0][0];
   if (mx != mx) mx = __longlong_as_double(0x7ff8000000000000LL);     // the positive quiet NaN: integer MAX propagates it
@@ -144,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void rba_apply_kernel(RbaApplyArgs a) {
   }
   const bool with4 = a.w4 != 0.0;
   // the lam values this thread wrote: min, max, sum, count
-  double lo = __longlong_as_double(0x7ff0000000000000LL), hi = -lo, sm = 0.0, cnt = 0.0;
+  double lo = FoldMin::identity(), hi = FoldMax::identity(), sm = 0.0, cnt = 0.0;
   auto upd = [&](float e1, float e2, float e3, float e4, float lam_old, float sw, float& lam_new, float& w_new) {
     const double r = __dsqrt_rn(e2_of(e1, e2, e3, e4, a.w4));
     const double l = __dadd_rn(__dmul_rn(a.gamma, (double)lam_old), __ddiv_rn(__dmul_rn(a.eta, r), rmax));
@@ -179,10 +119,10 @@ __global__ __launch_bounds__(kThreads) void rba_apply_kernel(RbaApplyArgs a) {
       a.w[i] = wn;
     }
   }
-  lo = block_fold<2>(lo, red);
-  hi = block_fold<3>(hi, red);
-  sm = block_fold<0>(sm, red);
-  cnt = block_fold<0>(cnt, red);
+  lo = block_fold<FoldMin, kThreads>(lo, red);
+  hi = block_fold<FoldMax, kThreads>(hi, red);
+  sm = block_fold<FoldSum, kThreads>(sm, red);
+  cnt = block_fold<FoldSum, kThreads>(cnt, red);
   double* part = a.scratch + kPartApply;
   if (threadIdx.x == 0) {
     put(part + (size_t)blockIdx.x * 4, lo); put(part + (size_t)blockIdx.x * 4 + 1, hi);
@@ -190,23 +130,8 @@ __global__ __launch_bounds__(kThreads) void rba_apply_kernel(RbaApplyArgs a) {
   }
   if (!last_block(a.scratch + kTicketApply, &flag)) return;
   __shared__ double tree[kThreads][4];
-  double f[4] = {__longlong_as_double(0x7ff0000000000000LL), -__longlong_as_double(0x7ff0000000000000LL), 0.0, 0.0};
-  for (int b = threadIdx.x; b < (int)gridDim.x; b += kThreads) {
-    f[0] = comb<2>(f[0], get(part + (size_t)b * 4)); f[1] = comb<3>(f[1], get(part + (size_t)b * 4 + 1));
-    f[2] = __dadd_rn(f[2], get(part + (size_t)b * 4 + 2)); f[3] = __dadd_rn(f[3], get(part + (size_t)b * 4 + 3));
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) tree[threadIdx.x][c] = f[c];
-  __syncthreads();
-  for (int half = kThreads / 2; half > 0; half >>= 1) {
-    if (threadIdx.x < half) {
-      double* p = tree[threadIdx.x];
-      const double* q = tree[threadIdx.x + half];
-      p[0] = comb<2>(p[0], q[0]); p[1] = comb<3>(p[1], q[1]);
-      p[2] = __dadd_rn(p[2], q[2]); p[3] = __dadd_rn(p[3], q[3]);
-    }
-    __syncthreads();
-  }
+  strided_tree_fold<kThreads, FoldMin, FoldMax, FoldSum, FoldSum>(
+      [&](long b, int c) { return get(part + (size_t)b * 4 + c); }, (long)gridDim.x, tree);
   if (threadIdx.x != 0) return;
   a.record[0] = rmax;
   for (int c = 1; c < 5; ++c) a.record[c] = a.scratch[c];
@@ -224,11 +149,6 @@ __global__ __launch_bounds__(kThreads) void rba_fill_kernel(long n, double init,
   }
 }
 
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
 }  // namespace
 
 long rba_blocks(long n) {
@@ -240,17 +160,17 @@ size_t rba_scratch_bytes(long) { return (size_t)kScratchDoubles * sizeof(double)
 
 int launch_rba_stats(long n, const float* fld, long npad, double w4, double* scratch, hipStream_t s) {
   hipLaunchKernelGGL(rba_stats_kernel, dim3((unsigned)rba_blocks(n)), dim3(kThreads), 0, s, fld, npad, n, w4, scratch);
-  return status();
+  return launch_status();
 }
 
 int launch_rba_apply(const RbaApplyArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(rba_apply_kernel, dim3((unsigned)rba_blocks(a.n)), dim3(kThreads), 0, s, a);
-  return status();
+  return launch_status();
 }
 
 int launch_rba_fill(long n, double init, const float* sw, float* lam, float* w, hipStream_t s) {
   long blocks = (n + kThreads - 1) / kThreads;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(rba_fill_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, n, init, sw, lam, w);
-  return status();
+  return launch_status();
 }

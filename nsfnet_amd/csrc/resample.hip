@@ -19,7 +19,8 @@
 // anywhere else: P is made non-decreasing by an (exact) running max, each block clamps its o into
 // [o(P_b), o(P_b+1)] and takes an (exact) integer running max.  So every output slot is written by
 // exactly one point, whatever the rounding.
-#include "kernels.h"
+#include "fixed_fold.h"
+#include "residual_planes.h"
 
 namespace {
 
@@ -27,55 +28,25 @@ constexpr int RS_THREADS = 256;
 constexpr int RS_PER = 4;                          // points per thread: one 16-byte load per eq plane
 constexpr int RS_BLOCK = RS_THREADS * RS_PER;
 
-__device__ __forceinline__ double sq(float v) { return __dmul_rn((double)v, (double)v); }   // exact
-
-// a_i from the four residual values (kmode: 0 -> 1, 1 -> sqrt, 2 -> e2, 3 -> pow(e2, k / 2))
-__device__ __forceinline__ double a_of(float e1, float e2, float e3, float e4, double w4, int kmode, double half_k) {
-  double s = __dadd_rn(sq(e1), sq(e2));
-  s = __dadd_rn(s, sq(e3));
-  if (w4 != 0.0) s = __dadd_rn(s, __dmul_rn(w4, sq(e4)));
+// a_i from e2_i (kmode: 0 -> 1, 1 -> sqrt, 2 -> e2, 3 -> pow(e2, k / 2))
+__device__ __forceinline__ double a_of(double s, int kmode, double half_k) {
   if (kmode == 0) return s <= 1.79769313486231570815e308 ? 1.0 : __builtin_nan("");   // a non-finite residual still reaches S
   if (kmode == 1) return __dsqrt_rn(s);
   if (kmode == 2) return s;
   return pow(s, half_k);
 }
 
-// the four a values of this thread's points (0 past n); vector loads of the eq planes (npad % 4 == 0)
+// the four a values of this thread's points (0 past n)
 __device__ __forceinline__ void load_a(const float* __restrict__ fld, long npad, long n, long base, double w4, int kmode,
                                        double half_k, double a[RS_PER]) {
 #pragma unroll
   for (int j = 0; j < RS_PER; ++j) a[j] = 0.0;
-  if (base >= n) return;          // base % 4 == 0 and n <= npad: base + 3 < npad
-  const float4 q1 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ1 * npad + base);
-  const float4 q2 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ2 * npad + base);
-  const float4 q3 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ3 * npad + base);
-  float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (w4 != 0.0) q4 = *reinterpret_cast<const float4*>(fld + (size_t)FLD_EQ4 * npad + base);
-  const float v1[4] = {q1.x, q1.y, q1.z, q1.w}, v2[4] = {q2.x, q2.y, q2.z, q2.w};
-  const float v3[4] = {q3.x, q3.y, q3.z, q3.w}, v4[4] = {q4.x, q4.y, q4.z, q4.w};
+  if (base >= n) return;
+  float v[4][4];
+  load_eq(fld, npad, base, w4 != 0.0, v);
 #pragma unroll
   for (int j = 0; j < RS_PER; ++j)
-    if (base + j < n) a[j] = a_of(v1[j], v2[j], v3[j], v4[j], w4, kmode, half_k);
-}
-
-// wave64 sum, fixed butterfly-free tree (lane 0 holds the result)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-// block sum in a fixed order: wave trees, then the four wave sums in wave order (result valid in thread 0)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  v = wave_sum(v);
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < RS_THREADS / 64; ++i) t = __dadd_rn(t, red[i]);
-  __syncthreads();
-  return t;
+    if (base + j < n) a[j] = a_of(e2_of(v[0][j], v[1][j], v[2][j], v[3][j], w4), kmode, half_k);
 }
 
 // o(C) = min(M, floor(C M / T + U)); 0 for a NaN or a negative value
@@ -95,7 +66,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_partial_kernel(const float* __r
   double s = 0.0;
 #pragma unroll
   for (int j = 0; j < RS_PER; ++j) s = __dadd_rn(s, a[j]);
-  s = block_sum(s, red);
+  s = block_fold<FoldSum, RS_THREADS>(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -106,16 +77,10 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scan_kernel(const double* __res
   __shared__ double red[RS_THREADS];
   __shared__ double sh[2];
   const int t = threadIdx.x;
-  const long ch = (nb + RS_THREADS - 1) / RS_THREADS;
+  const long ch = (nb + RS_THREADS - 1) / RS_THREADS;          // the chunks of chunk_fold
   const long lo = t * ch < nb ? t * ch : nb, hi = lo + ch < nb ? lo + ch : nb;
-  // S: contiguous chunks summed in order, then the chunk sums in thread order
-  double s = 0.0;
-  for (long b = lo; b < hi; ++b) s = __dadd_rn(s, partial[b]);
-  red[t] = s;
-  __syncthreads();
+  const double S = chunk_fold<RS_THREADS, FoldSum>([&](long b) { return partial[b]; }, nb, red);
   if (t == 0) {
-    double S = 0.0;
-    for (int i = 0; i < RS_THREADS; ++i) S = __dadd_rn(S, red[i]);
     const bool zero = S == 0.0;
     st[0] = S;
     st[3] = zero ? 1.0 : 0.0;
@@ -262,20 +227,13 @@ __global__ __launch_bounds__(RG_THREADS) void rs_gather_kernel(const long long* 
     if (dv) dv[j] = sv[p];
   }
   if (!wpart) return;
-  s = block_sum(s, red);
+  s = block_fold<FoldSum, RS_THREADS>(s, red);
   if (threadIdx.x == 0) wpart[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(64) void rs_wsum_kernel(const double* __restrict__ wpart, int nparts, double* __restrict__ w_sum) {
   if (threadIdx.x != 0) return;
-  double s = 0.0;
-  for (int i = 0; i < nparts; ++i) s = __dadd_rn(s, wpart[i]);
-  *w_sum = s;
-}
-
-inline int last_error() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  *w_sum = ordered_fold<FoldSum>(0.0, wpart, nparts);
 }
 
 }  // namespace
@@ -298,13 +256,13 @@ int launch_resample_select(long n, const float* fields, long npad, double w4, do
   const int kmode = k == 0.0 ? 0 : k == 1.0 ? 1 : k == 2.0 ? 2 : 3;
   const double half_k = 0.5 * k;
   hipLaunchKernelGGL(rs_partial_kernel, dim3((unsigned)nb), dim3(RS_THREADS), 0, s, fields, npad, n, w4, kmode, half_k, partial);
-  int rc = last_error();
+  int rc = launch_status();
   if (rc) return rc;
   hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(RS_THREADS), 0, s, partial, nb, n, c, st, P);
-  if ((rc = last_error())) return rc;
+  if ((rc = launch_status())) return rc;
   hipLaunchKernelGGL(rs_emit_kernel, dim3((unsigned)nb), dim3(RS_THREADS), 0, s, fields, npad, n, w4, kmode, half_k, st, P, nb,
                      m, u, out);
-  return last_error();
+  return launch_status();
 }
 
 int launch_resample_gather(const long long* idx, long lo, long hi, long n_pool, const float* sx, const float* sy,
@@ -317,8 +275,8 @@ int launch_resample_gather(const long long* idx, long lo, long hi, long n_pool, 
   double* wpart = w_sum ? reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + rs_off_gather(n_pool)) : nullptr;
   hipLaunchKernelGGL(rs_gather_kernel, dim3((unsigned)blocks), dim3(RG_THREADS), 0, s, idx + lo, cnt, per, n_pool, sx, sy, sw, sv,
                      dx, dy, dw, dv, wpart);
-  int rc = last_error();
+  int rc = launch_status();
   if (rc || !w_sum) return rc;
   hipLaunchKernelGGL(rs_wsum_kernel, dim3(1), dim3(64), 0, s, wpart, (int)blocks, w_sum);
-  return last_error();
+  return launch_status();
 }

@@ -10,6 +10,7 @@
 // ascending, so the accesses of a wave are contiguous.  The row sum of ds is fp64, not contracted, and combined over
 // the lanes by a shuffle-down tree with offsets 32, 16, ..., 1: a fixed order, no atomics and no scratch.
 #include "rwf.h"
+#include "fixed_fold.h"
 #include "layout.h"
 
 namespace {
@@ -86,17 +87,11 @@ __global__ __launch_bounds__(kThreads) void rwf_grad_kernel(RwfNet n, const floa
     acc += (double)theta[row.w + j] * (double)G;      // the product of two fp32 values is exact in fp64
     gtheta[row.w + j] = mul1(g, G);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  acc = wave_fold<FoldSum>(acc);
   if (lane == 0) {
     gtheta[row.b] = grads[row.b];
     gtheta[P + r] = (float)((double)g * acc);
   }
-}
-
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
 }
 
 unsigned blocks_of(const RwfNet& n) { return (unsigned)((rwf_rows(n) + kWaves - 1) / kWaves); }
@@ -105,15 +100,15 @@ unsigned blocks_of(const RwfNet& n) { return (unsigned)((rwf_rows(n) + kWaves - 
 
 int launch_rwf_split(const RwfNet& n, const float* params, const float* s, float* theta, hipStream_t st) {
   hipLaunchKernelGGL(rwf_split_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, st, n, params, s, theta);
-  return status();
+  return launch_status();
 }
 
 int launch_rwf_compose(const RwfNet& n, const float* theta, float* params, hipStream_t st) {
   hipLaunchKernelGGL(rwf_compose_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, st, n, theta, params);
-  return status();
+  return launch_status();
 }
 
 int launch_rwf_grad(const RwfNet& n, const float* theta, const float* grads, float* gtheta, hipStream_t st) {
   hipLaunchKernelGGL(rwf_grad_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, st, n, theta, grads, gtheta);
-  return status();
+  return launch_status();
 }

@@ -5,14 +5,14 @@
 //   e_c  = sqrt(sum (c^ - c)^2 / sum c^2)                                    (a fraction, not percent)
 //   e_p0 = sqrt((sum d^2 - (sum d)^2 / n_p) / (sum p^2 - (sum p)^2 / n_p))   (the pressure up to a constant)
 //   uv   = sqrt((sum (u^ - u)^2 + sum (v^ - v)^2) / (sum u^2 + sum v^2))
-// Everything is fp64 from the fp32 inputs without contraction; no float atomics, every sum has a fixed order
-// (bit-reproducible).  Two kernels, launch-bound:
-//   val_stats_kernel   grid-stride loop of 16-byte loads, wave trees, per-block partials; the last block to finish
-//                      folds them in block order, finishes the record, writes one row of the history ring and
+// Everything is fp64 from the fp32 inputs, one rounding per operation written (d^2 enters its sum by one fma); no float
+// atomics, every sum has a fixed order (fixed_fold.h; bit-reproducible).  Two kernels, launch-bound:
+//   val_stats_kernel   grid-stride loop of 16-byte loads, block_fold, per-block partials; the last block to finish
+//                      folds them by strided_tree_fold, finishes the record, writes one row of the history ring and
 //                      updates the monitor state - all device memory, so one captured launch serves every replay
 //   val_keep_kernel    copies up to two fp32 segments when the state's `improved` word is 1, nothing otherwise
+#include "fixed_fold.h"
 #include "kernels.h"
-#include "xwg_fold.h"
 
 namespace {
 
@@ -30,20 +30,6 @@ constexpr int S_RECORDS = 0, S_BEST = 1, S_BEST_T = 2, S_STALE = 3, S_NONFINITE 
 
 __device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ bool valid_target(float t) { return t == t && fabsf(t) <= 3.0e38f; }
-
-// sums over the workgroup in a fixed order: wave shuffle tree, then the wave results in wave order (valid in thread 0)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off, 64));
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();                                  // red may still be read from the previous fold
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double t = red[0];
-  if (threadIdx.x == 0)
-    for (int i = 1; i < kThreads / 64; ++i) t = __dadd_rn(t, red[i]);
-  return t;
-}
 
 __device__ __forceinline__ void unpack(const float4& q, float v[4]) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
 
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void val_stats_kernel(ValStatsArgs a) {
         if (!valid_target(tg[j])) continue;
         const double t = (double)tg[j];
         const double d = __dsub_rn((double)ph[j], t);
-        acc[3 * c] = __dadd_rn(acc[3 * c], __dmul_rn(d, d));
+        acc[3 * c] = __fma_rn(d, d, acc[3 * c]);      // one rounding: d d is not exact (t t below is)
         acc[3 * c + 1] = __dadd_rn(acc[3 * c + 1], __dmul_rn(t, t));
         acc[3 * c + 2] += 1.0;
         if (c == 2) {
@@ -84,31 +70,16 @@ __global__ __launch_bounds__(kThreads) void val_stats_kernel(ValStatsArgs a) {
     }
   }
 #pragma unroll
-  for (int k = 0; k < kSums - 1; ++k) acc[k] = block_sum(acc[k], red);
+  for (int k = 0; k < kSums - 1; ++k) acc[k] = block_fold<FoldSum, kThreads>(acc[k], red);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kSums - 1; ++k) put(a.scratch + kPart + (size_t)blockIdx.x * kSums + k, acc[k]);
   }
   if (!last_block(a.scratch + kTicket, &flag)) return;
-  // thread t: blocks t, t + 256, ... in order; then a fixed pairwise tree (thread i takes i + half)
   __shared__ double tree[kThreads][kSums];
-  double f[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) f[k] = 0.0;
-  for (int b = threadIdx.x; b < (int)gridDim.x; b += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSums - 1; ++k) f[k] = __dadd_rn(f[k], get(a.scratch + kPart + (size_t)b * kSums + k));
-  }
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) tree[threadIdx.x][k] = f[k];
-  __syncthreads();
-  for (int half = kThreads / 2; half > 0; half >>= 1) {
-    if (threadIdx.x < half) {
-#pragma unroll
-      for (int k = 0; k < kSums - 1; ++k) tree[threadIdx.x][k] = __dadd_rn(tree[threadIdx.x][k], tree[threadIdx.x + half][k]);
-    }
-    __syncthreads();
-  }
+  using S_ = FoldSum;
+  strided_tree_fold<kThreads, S_, S_, S_, S_, S_, S_, S_, S_, S_, S_, S_>(
+      [&](long b, int k) { return get(a.scratch + kPart + (size_t)b * kSums + k); }, (long)gridDim.x, tree);
   if (threadIdx.x != 0) return;
   const double* S = tree[0];
   for (int k = 0; k < kSums - 1; ++k) a.scratch[kOut + k] = S[k];
@@ -170,11 +141,6 @@ __global__ __launch_bounds__(kThreads) void val_keep_kernel(ValKeepArgs a) {
   }
 }
 
-int status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
 }  // namespace
 
 size_t val_scratch_bytes() { return (size_t)kScratchDoubles * sizeof(double); }
@@ -183,7 +149,7 @@ int launch_val_stats(const ValStatsArgs& a, hipStream_t s) {
   long blocks = (a.n + kTile - 1) / kTile;
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
   hipLaunchKernelGGL(val_stats_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
-  return status();
+  return launch_status();
 }
 
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s) {
@@ -191,5 +157,5 @@ int launch_val_keep(const ValKeepArgs& a, hipStream_t s) {
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(val_keep_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
-  return status();
+  return launch_status();
 }

@@ -5,12 +5,15 @@ import math
 
 import numpy as np
 
+import fold_model as fm
+
 BLK = 64
 RECORD = 12
 
 
 def block_partials(vecs, n):
-    """[nblk, 6] partials of three vectors (None = zeros): per 64-entry block max|v_t| (NaN-propagating), sum|v_t|."""
+    """[nblk, 6] partials of three vectors (None = zeros): per 64-entry block max|v_t| (NaN-propagating), sum|v_t|,
+    both in the kernel's order (wave_fold)."""
     nblk = (n + BLK - 1) // BLK
     out = np.zeros((nblk, 6))
     for t, v in enumerate(vecs):
@@ -19,8 +22,8 @@ def block_partials(vecs, n):
         a = np.zeros(nblk * BLK)
         a[:n] = np.abs(np.asarray(v, dtype=np.float64).reshape(-1)[:n])
         a = a.reshape(nblk, BLK)
-        out[:, 2 * t] = np.where(np.isnan(a).any(axis=1), np.nan, a.max(axis=1))
-        out[:, 2 * t + 1] = a.sum(axis=1)
+        out[:, 2 * t] = fm.wave_fold(a, fm.NANMAX)
+        out[:, 2 * t + 1] = fm.wave_fold(a, fm.SUM)
     return out
 
 
@@ -33,9 +36,8 @@ def initial_record(alpha_b, alpha_s):
 def update(partials, n, terms, beta, rec):
     """One balance update from [nblk, 6] partials; returns the new record (rec is not modified)."""
     rec = np.array(rec, dtype=np.float64)
-    p = np.asarray(partials, dtype=np.float64).reshape(-1, 6)
-    mx = [np.nan if np.isnan(p[:, 2 * t]).any() else float(p[:, 2 * t].max()) for t in range(3)]
-    sm = [float(p[:, 2 * t + 1].sum()) for t in range(3)]
+    f = fm.strided_tree_fold(partials, [fm.NANMAX, fm.SUM] * 3)      # the update kernel's order
+    mx, sm = [float(f[2 * t]) for t in range(3)], [float(f[2 * t + 1]) for t in range(3)]
     rec[0], rec[1] = mx[0], sm[0] / n
     for t in (1, 2):
         base = 2 + 3 * (t - 1)

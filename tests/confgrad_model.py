@@ -6,6 +6,8 @@ import math
 
 import numpy as np
 
+import fold_model as fm
+
 BLK = 64
 THREADS = 256
 RECORD = 13
@@ -15,42 +17,21 @@ PAIRS = ((0, 1), (0, 2), (1, 2))          # the terms of the cross entries rb, r
 
 def block_partials(vecs, n):
     """[nblk, 6] partials rr, bb, ss, rb, rs, bs of three vectors (None = zeros) per 64-entry block: exact fp64
-    products of the fp32 entries, summed in the kernel's butterfly order (lane i takes lane i + 32, then 16, ... 1)."""
+    products of the fp32 entries, summed in the kernel's order (wave_fold)."""
     nblk = (n + BLK - 1) // BLK
     v = np.zeros((3, nblk * BLK))
     for t, a in enumerate(vecs):
         if a is not None:
             v[t, :n] = np.asarray(a, dtype=np.float64).reshape(-1)[:n]
     v = v.reshape(3, nblk, BLK)
-    out = np.zeros((nblk, 6))
     cols = [(0, 0), (1, 1), (2, 2)] + list(PAIRS)
     with np.errstate(invalid="ignore", over="ignore"):
-        for c, (i, j) in enumerate(cols):
-            q = v[i] * v[j]
-            off = BLK // 2
-            while off > 0:
-                q = q[:, :off] + q[:, off:2 * off]
-                off //= 2
-            out[:, c] = q[:, 0]
-    return out
+        return np.stack([fm.wave_fold(v[i] * v[j]) for i, j in cols], axis=1)
 
 
 def sum_partials(partials):
-    """The six sums in the coefficient kernel's order: thread i adds blocks i, i + 256, ... in order, then the fixed
-    pairwise tree (thread i takes thread i + half)."""
-    p = np.asarray(partials, dtype=np.float64).reshape(-1, 6)
-    rows = -(-p.shape[0] // THREADS) * THREADS
-    pad = np.zeros((rows, 6))
-    pad[:p.shape[0]] = p
-    acc = np.zeros((THREADS, 6))
-    with np.errstate(invalid="ignore", over="ignore"):
-        for chunk in pad.reshape(-1, THREADS, 6):
-            acc = acc + chunk
-        half = THREADS // 2
-        while half > 0:
-            acc = acc[:half] + acc[half:2 * half]
-            half //= 2
-    return acc[0]
+    """The six sums in the coefficient kernel's order (strided_tree_fold)."""
+    return fm.strided_tree_fold(partials, [fm.SUM] * 6, THREADS)
 
 
 def coefficients(sums, nterms, rec=None):

@@ -422,3 +422,62 @@ def test_confgrad_entry_points_are_declared_and_reject_bad_arguments(lib):
         assert b"pinn_grad_reduce_terms_gram" in lib.pinn_last_error() and b"output" in lib.pinn_last_error()
     finally:
         lib.pinn_net_destroy(h)
+
+
+# ---------------------------------------------------------------- the fold model both statistics models are built on
+def test_fold_model_orders_against_scalar_loops():
+    """tests/fold_model.py against the device orders written out as scalar loops, at sizes with a ragged last wave,
+    block and stride, and against np.sum, from which the fixed order must differ somewhere (or a bitwise test on it
+    would pin nothing)."""
+    from fractions import Fraction
+    import fold_model as fm
+    rng = np.random.RandomState(0)
+    vec = lambda n: rng.randn(n) * 10.0 ** rng.uniform(-4, 1, size=n)
+    v = vec(64)
+    lanes = list(v)
+    for off in (32, 16, 8, 4, 2, 1):
+        lanes = [lanes[i] + lanes[i + off] if i + off < 64 else lanes[i] for i in range(64)]
+    assert fm.wave_fold(v) == lanes[0]
+    p = vec(601)
+    acc = [0.0] * 256
+    for b in range(601):
+        acc[b % 256] += p[b]
+    half = 128
+    while half:
+        acc = [acc[i] + acc[i + half] for i in range(half)]
+        half //= 2
+    assert fm.strided_tree_fold(p[:, None], [fm.SUM])[0] == acc[0]
+    chunks = [0.0] * 256
+    for b in range(601):
+        chunks[b // 3] += p[b]                          # ceil(601 / 256) = 3 per thread
+    tot = 0.0
+    for c in chunks:
+        tot += c
+    assert fm.chunk_fold(p) == tot
+    pm = np.abs(p); pm[77] = np.nan
+    assert np.isnan(fm.strided_tree_fold(pm[:, None], [fm.NANMAX])[0]) and np.isnan(fm.chunk_fold(pm, fm.NANMAX))
+    assert fm.strided_tree_fold(p[:, None], [fm.MIN])[0] == p.min() and fm.strided_tree_fold(p[:, None], [fm.MAX])[0] == p.max()
+    n, nblk = 2 * 2 * 256 * 4 + 5, 2                    # the stride repeats, the last pass is ragged
+    v = vec(n)
+    parts = []
+    for b in range(nblk):
+        th = [0.0] * 256
+        for t in range(256):
+            for base in range((b * 256 + t) * 4, n, nblk * 1024):
+                for j in range(4):
+                    if base + j < n:
+                        th[t] += v[base + j]
+        waves = [fm.wave_fold(np.array(th[w * 64:(w + 1) * 64])) for w in range(4)]
+        parts.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+    np.testing.assert_array_equal(fm.grid_partials(v, nblk), parts)
+    assert fm.grid_fold(v, nblk) == parts[0] + parts[1]
+    assert any(fm.grid_fold(v, min(-(-v.size // 1024), 512)) != np.sum(v) for v in map(vec, (1003, 70001, 330499)))
+    a, b, c = vec(500), vec(500), vec(500)
+    c[:250] = -(a * b)[:250]                            # cancellation: what is left is the product's rounding error
+    want = [float(Fraction(x) * Fraction(y) + Fraction(z)) for x, y, z in zip(a, b, c)]
+    np.testing.assert_array_equal(fm.fma(a, b, c), want)
+    assert (fm.fma(a, b, c) != a * b + c).any()
+    th = np.zeros(256)                                  # one block of 256 threads x 4 entries over 500 products
+    for i in range(500):
+        th[i // 4] = fm.fma(a[i:i + 1], b[i:i + 1], th[i // 4:i // 4 + 1])[0]
+    assert fm.same_bits(fm.grid_partials((a, b), 1), fm.block_fold(th))

@@ -14,6 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import fold_model as fm  # noqa: E402
 import optim_model as om  # noqa: E402
 from nsfnet_amd.schedule import LrSchedule  # noqa: E402
 from oracle import autograd_ref as ar  # noqa: E402
@@ -58,6 +59,25 @@ def test_sqnorm_is_within_the_reordering_bound_and_reproducible(n0, n1):
     print("n=%d+%d rel err %.3e (bound %.3e)" % (n0, n1, rel, n * 2.0 ** -53))
     assert rel <= n * 2.0 ** -53
     assert runs[0].tobytes() == runs[1].tobytes()
+
+
+@pytest.mark.parametrize("n0,n1", [(1, 0), (63, 0), (64, 0), (65, 0), (P_MAIN, 0), (P_MAIN, P_E)])
+def test_sqnorm_equals_the_fold_model_bit_for_bit(n0, n1):
+    """The sum is the folds of csrc/fixed_fold.h in their fixed order: 256 threads x 4 entries per block, at most 256
+    blocks per vector, vector 0's blocks numbered before vector 1's.  Equal to tests/fold_model.py bit for bit."""
+    from nsfnet_amd import engine as eng
+    n = n0 + n1
+    host = _vec(n + 3, seed=n)
+    flat = torch.tensor(host, device=DEV)
+    scratch = eng.grad_sqnorm_scratch(DEV)
+    eng.grad_sqnorm(flat[:n0], flat[n0:n] if n1 else None, scratch)
+    torch.cuda.synchronize()
+    got = scratch[0].item()
+    sq = host[:n].astype(np.float64) ** 2
+    parts = [fm.grid_partials(v, min(-(-v.size // 1024), 256)) for v in (sq[:n0], sq[n0:]) if v.size]
+    want = fm.strided_tree_fold(np.concatenate(parts)[:, None], [fm.SUM])[0]
+    print("n=%d+%d device %r model %r numpy %r" % (n0, n1, got, want, float(np.sum(sq))))
+    assert fm.same_bits(got, want), (got, want)
 
 
 @pytest.mark.parametrize("n0,n1,where", [(65, 0, 64), (P_MAIN, P_E, 1234), (P_MAIN, P_E, P_MAIN + P_E - 1)])

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import batch_model as bm  # noqa: E402
+import fold_model as fm  # noqa: E402
 import rba_model as rm  # noqa: E402
 from oracle import autograd_ref as ar  # noqa: E402
 
@@ -72,6 +73,25 @@ def test_stats_match_the_model(n, w4):
     assert got[5] == 0.0 and got[6] == 0.0
     if w4 == 0.0:
         assert got[4] == 0.0
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("w4", [0.0, 0.1])
+def test_stats_equal_the_fold_model_bit_for_bit(n, w4):
+    """rmax and the four sums are the folds of csrc/fixed_fold.h in their fixed order (256 threads x 4 points per block,
+    at most 512 blocks): equal to tests/fold_model.py bit for bit, not merely close."""
+    from nsfnet_amd import engine as eng
+    plan, eq = _planes(n, seed=n)
+    scratch = eng.rba_scratch(n, DEV)
+    eng.rba_stats(plan, w4, scratch)
+    torch.cuda.synchronize()
+    got = scratch[:5].cpu().numpy()
+    nblk = min(-(-n // 1024), 512)
+    q = eq.astype(np.float64)
+    want = [fm.grid_fold(rm.norms(eq, w4), nblk, fm.NANMAX)]
+    want += [fm.grid_fold(q[k] * q[k], nblk) if k < 3 or w4 != 0.0 else 0.0 for k in range(4)]
+    print("n=%d w4=%s device %r model %r" % (n, w4, got.tolist(), want))
+    assert fm.same_bits(got, want), (got, want)
 
 
 @pytest.mark.parametrize("n", SIZES)

@@ -11,6 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import fold_model as fm  # noqa: E402
 import val_model as vm  # noqa: E402
 from oracle import autograd_ref as ar  # noqa: E402
 
@@ -117,6 +118,34 @@ def test_stats_match_the_model(n, variant):
             r = ring2.cpu().numpy()[0]
             np.testing.assert_array_equal(_bits(r[vm.R_METRIC:vm.R_METRIC + 1]), _bits(ring[0][col:col + 1]))
             assert st2.cpu().numpy()[vm.S_NONFINITE] == (0.0 if np.isfinite(r[vm.R_METRIC]) else 1.0)
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("variant", ["nop", "p", "p_nan10"])
+def test_sums_equal_the_fold_model_bit_for_bit(n, variant):
+    """The eleven sums in scratch[1:12] are the folds of csrc/fixed_fold.h in their fixed order (256 threads x 4 points
+    per block, at most 512 blocks; a masked point adds nothing; d d is taken into its sum by one fma, the other values
+    are exact or plain terms): equal to tests/fold_model.py bit for bit."""
+    from nsfnet_amd import engine as eng
+    pred, tgt = _data(n, n + len(variant), variant)
+    scratch = eng.val_scratch(DEV)
+    st, ring = _fresh()
+    eng.val_stats(_planes(pred, n), _planes(tgt, n), n, variant != "nop", vm.METRICS["uv"], -1.0, 5, scratch, st, ring)
+    torch.cuda.synchronize()
+    got = scratch[1:12].cpu().numpy()
+    nblk = min(-(-n // 1024), 512)
+    want = []
+    for c in range(3):
+        if pred[c] is None:
+            want += [0.0] * 5
+            continue
+        ok = vm.valid(tgt[c])
+        t = np.where(ok, tgt[c], np.float32(0)).astype(np.float64)
+        d = np.where(ok, pred[c].astype(np.float64) - t, 0.0)
+        cols = [(d, d), t * t, ok.astype(np.float64)] + ([d, t] if c == 2 else [])
+        want += [fm.grid_fold(v, nblk) for v in cols]
+    print("n=%d %s device %r model %r" % (n, variant, got.tolist(), want))
+    assert fm.same_bits(got, want), (got, want)
 
 
 @pytest.mark.parametrize("n0,n1", [(1, 0), (7, 0), (1027, 0), (1347, 697)])      # (3 x 24 net, 2 x 24 entropy net)
