@@ -502,6 +502,45 @@ int pinn_val_stats(int64_t n, const float* const* pred3, const float* const* tgt
 int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1, float* dst1, int64_t n1,
                   const double* state, void* stream);
 
+/* ---- hard boundary conditions: the cavity's wall values by an output transform ---------
+ * The no-slip walls and the lid of the lid-driven unit cavity hold by construction instead of by a penalty term: a
+ * constrained plan evaluates
+ *   u = g + D N_u,   v = D N_v,   p = N_p            (N: the net's three outputs)
+ * with D = 0 on the four walls and g the lid profile lifted into the cavity.  The descriptor places the unit cavity in
+ * the net's input coordinates (xi, eta):  X = (xi - x0) inv_len,  Y = (eta - y0) inv_len  (plain NSFnet: x0 = y0 = 0,
+ * inv_len = 1; ev-NSFnet's coordinate map: x0 = y0 = -1, inv_len = 1/2).  Derivatives in X, Y are the scaled
+ * derivatives of the residual calls: a residual call on a constrained plan whose coord_scale * inv_len differs from 1
+ * by more than 1e-6 is refused.
+ *   D   = 16 X(1-X) Y(1-Y)      D_X = 16 (1-2X) Y(1-Y)      D_Y = 16 X(1-X) (1-2Y)      Lap D = -32 [X(1-X) + Y(1-Y)]
+ *   l   = 1 - c cosh(r (X - 1/2))    l' = -r c sinh(r (X - 1/2))    l'' = -r^2 c cosh(r (X - 1/2))
+ *         r = lid_sharpness,  c = 1 / cosh(r / 2) (computed in double, passed to the kernels as a float)
+ *   g   = l Y^m     g_X = l' Y^m     g_Y = l m Y^(m-1)     Lap g = l'' Y^m + l m (m-1) Y^(m-2)
+ *         m = lift_power, 1..8, by repeated multiplication
+ * and for c in (u, v), g = 0 for v:
+ *   c = g + D N     c_X = g_X + D_X N + D N_X   (Y alike)     Lap c = Lap g + Lap D N + 2 (D_X N_X + D_Y N_Y) + D Lap N
+ * Residuals, field planes, loss sums and the lagged viscosity use the constrained u, v: every reader of the field
+ * planes sees the physical field.  The reverse sweep starts from the transpose (a_ the adjoints of c, c_X, c_Y, Lap c):
+ *   N_ = D a + D_X a_X + D_Y a_Y + Lap D a_D     N_X_ = D a_X + 2 D_X a_D     N_Y_ = D a_Y + 2 D_Y a_D     N_D_ = D a_D
+ * then the scale factors; the output-bias gradient sums N_.  Value plans: pred_u = g + D N_u, pred_v = D N_v, and
+ * the output adjoints the forward leaves for pinn_value_backward are coef (pred - tgt) D for u and v.  An out_adj
+ * handed to pinn_value_backward is an adjoint of the NET's outputs, as on any plan.
+ * A constrained plan runs the 8-wave kernel families (fwd / fwd_wide / fwd_bf16 / fwd_bf16_wide and their reverse
+ * sweeps) whatever PINN_SCHED, PINN_WSPLIT and PINN_FUSE say: the role-split and fused sweeps have no constrained
+ * variant.  Only a net with n_out = 3 can be constrained.  The constraint is a compile-time variant of those kernels:
+ * an unconstrained plan runs what it ran before. */
+enum { PINN_HARD_BC_NONE = 0, PINN_HARD_BC_CAVITY = 1 };
+typedef struct {
+  int32_t kind;        /* 0 none, 1 lid-driven unit cavity */
+  int32_t lift_power;  /* m, 1..8 */
+  float x0, y0, inv_len, lid_sharpness;
+} pinn_hard_bc_t;
+/* bc NULL or kind 0: pinn_plan_create.  Refused (pinn_last_error): n_out != 3, an unknown kind, lift_power outside
+ * 1..8, a field that is not finite, inv_len <= 0, |lid_sharpness| > 150 (exp(r / 2) must stay a finite float). */
+int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, const pinn_hard_bc_t* bc,
+                                 pinn_plan_t* out);
+/* What the plan carries (kind 0 and zeros for an unconstrained plan). */
+int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,8 @@ SIGNATURES = {
     "pinn_val_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                c_void_p]),
     "pinn_val_keep": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pinn_plan_create_constrained": (c_int, [c_void_p, c_int64, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
+    "pinn_plan_hard_bc": (c_int, [c_void_p, c_void_p]),
     "pinn_lr_schedule_value": (c_double, [c_void_p, c_double, c_int64]),
     "pinn_grad_sqnorm_scratch_bytes": (c_int64, []),
     "pinn_grad_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -97,6 +99,12 @@ class LrScheduleStruct(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("n_milestones", ctypes.c_int32), ("milestones", c_int64 * 16),
                 ("step_size", c_int64), ("t_max", c_int64), ("warmup_epochs", c_int64),
                 ("gamma", c_double), ("eta_min", c_double), ("warmup_start", c_double)]
+
+
+class HardBcStruct(ctypes.Structure):
+    """pinn_hard_bc_t"""
+    _fields_ = [("kind", ctypes.c_int32), ("lift_power", ctypes.c_int32), ("x0", c_float), ("y0", c_float),
+                ("inv_len", c_float), ("lid_sharpness", c_float)]
 
 
 _lib = None

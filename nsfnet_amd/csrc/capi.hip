@@ -118,6 +118,7 @@ struct pinn_plan_s {
   int stagger;           // $PINN_STAGGER, read once at plan creation
   Role role[ROLE_COUNT];
   Spill spill;           // how the sweeps spill S and Z-bar, and what their readers recompute instead (spill.h)
+  HardBc hbc;            // hard wall conditions (kind 0: none); a constrained plan runs the 8-wave families only
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -215,8 +216,14 @@ static int run_fused(const pinn_plan_s* plan, const FwdArgs& fa, const BwdArgs& 
 
 // Resolves a plan: tiles, one Role per kernel role, the spill format and the workspace layout.  Pure host arithmetic
 // (no HIP call) on the net, the point and stream counts, the compute-unit count and the switches.
-static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw) {
+static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw_in,
+                        const HardBc& hbc = HardBc{}) {
+  // Only the 8-wave families have constrained point stages (point_stage.h): a constrained plan resolves as
+  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, and its spill format follows from that as for any other plan.
+  Switches sw = sw_in;
+  if (hbc.kind) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
+  p->hbc = hbc;
   p->n = n_points; p->streams = streams;
   const bool wide = net.wide != 0;
   const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
@@ -277,6 +284,9 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   if (sw.verbose)
     fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
             (long)n_points, streams, HP, L, net.prec_fwd, net.prec_bwd, net.prec_dw, (int)wide, sf, sb);
+  if (sw.verbose && hbc.kind)
+    fprintf(stderr, "[pinn] plan: hard wall conditions, lid-driven cavity at (%g, %g) x %g, lift power %d, lid sharpness %g\n",
+            (double)hbc.x0, (double)hbc.y0, (double)hbc.inv_len, hbc.m, (double)hbc.r);
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);
@@ -332,6 +342,7 @@ static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.scale = scale;
   a.partials = WS(plan, off_partials);
   a.spill = plan->spill;
+  a.hbc = plan->hbc;
   return a;
 }
 static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -351,6 +362,7 @@ static BwdArgs bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.scale = scale;
   a.sg = WS(plan, off_sg);
   a.spill = plan->spill;
+  a.hbc = plan->hbc;
   return a;
 }
 static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -425,13 +437,13 @@ int pinn_net_prepare(pinn_net_t net, const float* params, float* prep, void* str
   return rc ? hipfail(rc, "pinn_net_prepare") : 0;
 }
 
-int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t* out) {
+static int create_plan(pinn_net_t net, int64_t n_points, int streams, const HardBc& hbc, pinn_plan_t* out) {
   if (!net || !out) return fail(-22, "pinn_plan_create: null argument%s");
   if (streams != 1 && streams != 4) return fail(-22, "pinn_plan_create: streams must be 1 or 4%s");
   if (n_points < 1 || n_points > (int64_t)1 << 30) return fail(-22, "pinn_plan_create: bad point count %s%ld", "", (long)n_points);
   pinn_plan_s* p = new (std::nothrow) pinn_plan_s;
   if (!p) return fail(-12, "pinn_plan_create: out of host memory%s");
-  int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches());
+  int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches(), hbc);
   if (rc) { delete p; return rc; }
   // The dynamic-LDS limit is per-device state of the HIP runtime and idempotent to raise; doing it here, per plan,
   // keeps the launch path free of cached "already configured" flags (no global mutable state; a process may drive
@@ -445,6 +457,32 @@ int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t*
   *out = p;
   return 0;
 }
+int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t* out) {
+  return create_plan(net, n_points, streams, HardBc{}, out);
+}
+int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, const pinn_hard_bc_t* bc, pinn_plan_t* out) {
+  if (!bc || bc->kind == PINN_HARD_BC_NONE) return pinn_plan_create(net, n_points, streams, out);
+  if (!net || !out) return fail(-22, "pinn_plan_create_constrained: null argument%s");
+  if (bc->kind != PINN_HARD_BC_CAVITY) return fail(-22, "pinn_plan_create_constrained: unknown kind %s%ld", "", (long)bc->kind);
+  if (net->n_out != 3) return fail(-22, "pinn_plan_create_constrained: only a (u, v, p) net (n_out = 3) can be constrained%s");
+  if (bc->lift_power < 1 || bc->lift_power > 8)
+    return fail(-22, "pinn_plan_create_constrained: lift_power must be 1..8 (got %s%ld)", "", (long)bc->lift_power);
+  if (!std::isfinite(bc->x0) || !std::isfinite(bc->y0) || !std::isfinite(bc->inv_len) || !std::isfinite(bc->lid_sharpness))
+    return fail(-22, "pinn_plan_create_constrained: x0, y0, inv_len and lid_sharpness must be finite%s");
+  if (!(bc->inv_len > 0.f)) return fail(-22, "pinn_plan_create_constrained: inv_len must be > 0%s");
+  if (std::fabs(bc->lid_sharpness) > 150.f)      // exp(r / 2) must stay a finite float
+    return fail(-22, "pinn_plan_create_constrained: |lid_sharpness| must be <= 150%s");
+  HardBc h;
+  h.kind = bc->kind; h.m = bc->lift_power; h.x0 = bc->x0; h.y0 = bc->y0; h.inv_len = bc->inv_len; h.r = bc->lid_sharpness;
+  h.c = (float)(1.0 / std::cosh(0.5 * (double)bc->lid_sharpness));
+  return create_plan(net, n_points, streams, h, out);
+}
+int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out) {
+  if (!plan || !out) return fail(-22, "pinn_plan_hard_bc: null argument%s");
+  const HardBc& h = plan->hbc;
+  out->kind = h.kind; out->lift_power = h.m; out->x0 = h.x0; out->y0 = h.y0; out->inv_len = h.inv_len; out->lid_sharpness = h.r;
+  return 0;
+}
 int pinn_plan_destroy(pinn_plan_t plan) { delete plan; return 0; }
 int64_t pinn_plan_padded_points(pinn_plan_t plan) { return plan ? plan->npad : -1; }
 const char* pinn_plan_kernel(pinn_plan_t plan, int which) {
@@ -454,6 +492,14 @@ const char* pinn_plan_kernel(pinn_plan_t plan, int which) {
 int64_t pinn_plan_workspace_bytes(pinn_plan_t plan, int with_backward) {
   if (!plan) return -1;
   return (int64_t)(with_backward ? plan->bytes_all : plan->bytes_fwd);
+}
+
+// A constrained plan takes the net's scaled derivatives for derivatives in the unit cavity's X, Y: the coordinate scale of
+// the call must undo the plan's inv_len.
+static int check_hard_bc_scale(const char* what, const pinn_plan_s* plan, float coord_scale) {
+  if (plan->hbc.kind && !(std::fabs((double)coord_scale * (double)plan->hbc.inv_len - 1.0) <= 1e-6))
+    return fail(-22, "%s: coord_scale x inv_len of the plan's hard wall conditions must be 1", what);
+  return 0;
 }
 
 // the loss sums over the partials that a forward (or fused) launch of role `r` left, one row per workgroup
@@ -471,6 +517,7 @@ int pinn_residual_forward(pinn_plan_t plan, void* ws, const float* prep,
   if (!plan || !ws || !prep || !x || !y || !fields) return fail(-22, "pinn_residual_forward: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_residual_forward: plan is not a residual (4-stream) plan%s");
   if (!(Re > 0.f)) return fail(-22, "pinn_residual_forward: Re must be > 0%s");
+  if (int rc = check_hard_bc_scale("pinn_residual_forward", plan, coord_scale)) return rc;
   const FwdArgs a = residual_fwd_args(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,
                                       coord_scale, save, true);
   const Role& r = plan->role[save ? ROLE_FWD_SAVE : ROLE_FWD];
@@ -489,6 +536,7 @@ int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
                                   float Re, float coord_scale, float* ebar_out, int phases, void* stream) {
   if (!plan || !ws || !prep || !x || !y || !fields || !coef_eq4) return fail(-22, "pinn_residual_backward: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_residual_backward: plan is not a residual (4-stream) plan%s");
+  if (int rc = check_hard_bc_scale("pinn_residual_backward", plan, coord_scale)) return rc;
   const BwdArgs a = residual_bwd_args(plan, ws, prep, x, y, e, w, vis_t, fields, coef_eq4, Re, coord_scale, ebar_out);
   int rc = 0;
   if (phases & 1) {

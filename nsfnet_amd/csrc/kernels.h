@@ -43,6 +43,10 @@ static int dispatch_ns_terms(int NS, int terms, F f) {
 // (plane stride = padded point count).
 enum { FLD_U = 0, FLD_V, FLD_UX, FLD_UY, FLD_VX, FLD_VY, FLD_EQ1, FLD_EQ2, FLD_EQ3, FLD_EQ4, FLD_P, FLD_COUNT };
 
+// Hard wall conditions of the lid-driven unit cavity (include/nsfnet_pinn.h pinn_hard_bc_t; point_stage.h): kind 0 = none,
+// m = lift_power, r = lid_sharpness, c = 1 / cosh(r / 2) computed on the host in double.
+struct HardBc { int kind, m; float x0, y0, inv_len, r, c; };
+
 struct FwdArgs {
   const float* x; const float* y;
   int n;            // real points
@@ -67,6 +71,7 @@ struct FwdArgs {
   int stagger;           // start offset unit (x 4096 cycles x (block*5 mod 8)); 0 = off
   int configure;         // 1: do not launch, only raise the kernel's dynamic-LDS limit (pinn_plan_create)
   Spill spill;           // the plan's S / Z-bar format (spill.h)
+  HardBc hbc;            // kind != 0: the 8-wave families launch their constrained instantiation
 };
 
 struct BwdArgs {
@@ -85,6 +90,7 @@ struct BwdArgs {
   float* sg;             // [grid][sg_total]
   int configure;         // see FwdArgs
   Spill spill;           // see FwdArgs
+  HardBc hbc;            // see FwdArgs (residual mode; value mode takes adjoints that carry D already)
 };
 
 struct DwArgs {

@@ -130,6 +130,15 @@ class WeightFactorizationConfig:
     seed: int = 0
 
 
+@dataclass
+class HardBoundaryConfig:
+    """The cavity's wall values by an output transform, u = g + D N_u, v = D N_v (PinnEngine.set_hard_boundary), off by
+    default: `training.hard_boundary: {enabled: true, lift_power: 2}`.  lift_power (1..8) is the exponent of the lid's
+    lift g = l(X) Y^lift_power; its default is a guess, not a measured optimum."""
+    enabled: bool = False
+    lift_power: int = 2
+
+
 VALIDATION_METRICS = ("uv", "u", "v", "p", "p0")
 
 
@@ -170,6 +179,7 @@ class TrainingConfig:
     grad_clip: GradClipConfig = field(default_factory=GradClipConfig)
     weight_factorization: WeightFactorizationConfig = field(default_factory=WeightFactorizationConfig)
     validation: ValidationConfig = field(default_factory=ValidationConfig)
+    hard_boundary: HardBoundaryConfig = field(default_factory=HardBoundaryConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -256,6 +266,9 @@ class ConfigManager:
         wf = c.training.weight_factorization
         if wf.enabled and not (abs(wf.mean) < float("inf") and 0.0 <= wf.std < float("inf") and wf.seed >= 0):
             problems.append("training.weight_factorization: finite mean, finite std >= 0 and seed >= 0 required")
+        hb = c.training.hard_boundary
+        if hb.enabled and not 1 <= hb.lift_power <= 8:
+            problems.append("training.hard_boundary: lift_power in 1..8 required")
         va = c.training.validation
         if va.enabled and (va.every < 1 or va.patience < 0 or va.metric not in VALIDATION_METRICS):
             problems.append("training.validation: every >= 1, patience >= 0 and metric one of %s required"
@@ -319,6 +332,8 @@ class ConfigManager:
         if t.weight_factorization.enabled:
             print("weight fact: mean=%s std=%s seed=%d" % (t.weight_factorization.mean, t.weight_factorization.std,
                                                             t.weight_factorization.seed))
+        if t.hard_boundary.enabled:
+            print("hard walls : lift_power=%d" % t.hard_boundary.lift_power)
         if t.validation.enabled:
             print("validation : every=%d metric=%s keep_best=%s patience=%d"
                   % (t.validation.every, t.validation.metric, t.validation.keep_best, t.validation.patience))

@@ -84,6 +84,10 @@ def main():
                                    sort_training_points=cfg.training.sort_training_points,
                                    sdf_weighting=cfg.training.sdf_weighting,
                                    coord_transform=cfg.training.coordinate_transform)
+        hb = cfg.training.hard_boundary
+        if hb.enabled:        # before any point set: every plan of the main net is then created constrained
+            PINN.set_coordinate_transform(loader.get_coord_scale())
+            PINN.set_hard_boundary_constraints(lift_power=hb.lift_power, dataloader=loader)
         PINN.set_boundary_data(X=loader.loading_boundary_data())
         if distributed:   # every rank must shard the SAME point set: rank 0 samples, the others receive
             pts = [loader.loading_training_data() + (loader.get_sdf_weights(),)] if rank == 0 else [None]

@@ -69,6 +69,7 @@ class DeviceNet:
     update theta (m and v have its size) with gtheta, the gradient rwf_grad makes of the effective one, and rebuild
     params from it (compose) before prepare.  params stays what prepare, state_dict and every plan read."""
     theta = gtheta = None       # the factorization is off
+    hard_bc = None              # _lib.HardBcStruct: every plan of this net is created constrained (PinnEngine.set_hard_boundary)
 
     def __init__(self, n_out, n_hidden, hidden, device, precision=None):
         self.lib = _lib.load()
@@ -251,7 +252,12 @@ class PointPlan:
         if self.y.numel() != self.n or self.n == 0:
             raise ValueError("x and y must be non-empty and of equal length")
         h = ctypes.c_void_p()
-        _lib.check(self.lib.pinn_plan_create(net.handle, self.n, streams, ctypes.byref(h)), "pinn_plan_create")
+        bc = getattr(net, "hard_bc", None)
+        if bc is None:
+            _lib.check(self.lib.pinn_plan_create(net.handle, self.n, streams, ctypes.byref(h)), "pinn_plan_create")
+        else:       # hard wall conditions
+            _lib.check(self.lib.pinn_plan_create_constrained(net.handle, self.n, streams, ctypes.byref(bc), ctypes.byref(h)),
+                       "pinn_plan_create_constrained")
         self.handle = h
         self.npad = int(self.lib.pinn_plan_padded_points(h))
         self.with_backward = with_backward
@@ -260,6 +266,13 @@ class PointPlan:
             raise ValueError("shared workspace too small: %d < %d bytes" % (ws.numel(), nbytes))
         self.ws = ws if ws is not None else torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
         self.sums = torch.zeros(NLOSS, dtype=torch.float32, device=dev)
+
+    def hard_bc(self):
+        """The hard wall conditions the plan carries, as dict(kind, lift_power, x0, y0, inv_len, lid_sharpness); None for
+        an unconstrained plan."""
+        bc = _lib.HardBcStruct()
+        _lib.check(self.lib.pinn_plan_hard_bc(self.handle, ctypes.byref(bc)), "pinn_plan_hard_bc")
+        return None if bc.kind == 0 else {name: getattr(bc, name) for name, _ in bc._fields_}
 
     def kernel_names(self):
         """(forward, reverse sweep, weight-gradient) kernel family names this plan launches (for profiling)."""
@@ -1652,6 +1665,52 @@ class PinnEngine:
                 off += r
             out["layers"][name] = rows
         return out
+
+    # ---- hard wall conditions by an output transform ----
+    def set_hard_boundary(self, enabled=True, lift_power=2, lid_sharpness=10.0, origin=(0.0, 0.0), inv_len=1.0):
+        """enabled: the no-slip walls and the lid of the lid-driven unit cavity hold exactly, by construction:
+        u = g + D N_u, v = D N_v, p = N_p with N the main net's outputs, D = 16 X(1-X) Y(1-Y) zero on the four walls and
+        g = l(X) Y^lift_power the lift of the regularised lid l = 1 - cosh(lid_sharpness (X - 1/2)) / cosh(lid_sharpness / 2)
+        (cavity_data.py's profile at its default 10).  X = (x - origin[0]) inv_len, Y = (y - origin[1]) inv_len place the
+        unit cavity in the net's input coordinates: origin (0, 0) and inv_len 1 without a coordinate map, origin (-1, -1)
+        and inv_len 1/2 with ev-NSFnet's; coord_scale * inv_len must be 1.  lift_power (an integer, 1..8) decides how
+        fast the lid's influence decays into the cavity; the default 2 is a guess, not a measured optimum.
+
+        Every ResidualPlan / ValuePlan of the main net created from here on is constrained (the entropy net's never are):
+        collocation passes and chunks, the batch plan, the resample pool, boundary, supervised, validation and predict.
+        Field planes, losses, predictions and gradients are those of the constrained field.  The boundary term keeps
+        running: its misfit is rounding-size and its gradient exactly zero (D = 0 at wall points), which makes loss_b a
+        live check of the constraint.  A constrained plan runs the 8-wave kernel families; the role-split and fused
+        sweeps have no constrained variant yet.
+
+        Must be called before any point set is attached (ValueError otherwise).  enabled=False: off."""
+        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val)):
+            raise ValueError("hard boundary: call set_hard_boundary before any point set is attached")
+        if not enabled:
+            self.net.hard_bc = None
+            return
+        m = int(lift_power)
+        if m != lift_power or not 1 <= m <= 8:
+            raise ValueError("hard boundary: lift_power must be an integer in 1..8 (got %r)" % (lift_power,))
+        x0, y0 = (float(c) for c in origin)
+        r, il = float(lid_sharpness), float(inv_len)
+        if not all(math.isfinite(c) for c in (x0, y0, r, il)):
+            raise ValueError("hard boundary: origin, inv_len and lid_sharpness must be finite")
+        if not il > 0.0:
+            raise ValueError("hard boundary: inv_len must be > 0 (got %r)" % (inv_len,))
+        if abs(r) > 150.0:
+            raise ValueError("hard boundary: |lid_sharpness| must be <= 150 (got %r)" % (lid_sharpness,))
+        if abs(self.scale * il - 1.0) > 1e-6:
+            raise ValueError("hard boundary: coord_scale * inv_len must be 1 (coord_scale %g, inv_len %g)" % (self.scale, il))
+        self.net.hard_bc = _lib.HardBcStruct(1, m, x0, y0, il, r)
+
+    def hard_boundary_info(self):
+        """dict(lift_power, lid_sharpness, origin=(x0, y0), inv_len) of set_hard_boundary; None when it is off."""
+        bc = self.net.hard_bc
+        if bc is None:
+            return None
+        return dict(lift_power=int(bc.lift_power), lid_sharpness=float(bc.lid_sharpness),
+                    origin=(float(bc.x0), float(bc.y0)), inv_len=float(bc.inv_len))
 
     # ---- device learning-rate schedule and gradient clipping (DESIGN.md section 7.6) ----
     def set_lr_schedule(self, spec=None):

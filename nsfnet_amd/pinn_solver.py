@@ -154,6 +154,38 @@ class SolverBase:
         <checkpoint>_rwf, which load() reads back.  mean = None: off."""
         self.engine.set_weight_factorization(mean, std, seed, factors)
 
+    def set_hard_boundary_constraints(self, enabled=True, lift_power=2, lid_sharpness=10.0, dataloader=None,
+                                      origin=None, inv_len=None):
+        """The cavity's wall values hold exactly, by the output transform u = g + D N_u, v = D N_v
+        (PinnEngine.set_hard_boundary) instead of by the boundary penalty alone.  Call it before
+        set_boundary_data / set_eq_training_data (ValueError once a point set is attached).  Where the unit cavity lies
+        in the net's input coordinates comes from the data loader's coordinate map (dataloader.coord_transform:
+        origin (-1, -1), inv_len 1/2; else origin (0, 0), inv_len 1), without a loader from this solver's coordinate
+        scale, or from origin / inv_len where given.  lift_power's default 2 is a guess, not a measured optimum.  The
+        boundary term keeps running and loss_b becomes a check of the constraint.  save() adds the descriptor as a
+        sidecar <checkpoint>_hardbc, which load() reads back."""
+        if origin is None or inv_len is None:
+            if dataloader is not None:
+                mapped = bool(getattr(dataloader, "coord_transform", False))
+            else:
+                scale = float(getattr(self, "coord_scale", 1.0))
+                if scale not in (1.0, 2.0):
+                    raise ValueError("hard boundary: coordinate scale %g is neither the plain cavity's nor the "
+                                     "[-1, 1] map's; give origin and inv_len" % scale)
+                mapped = scale == 2.0
+            o, il = ((-1.0, -1.0), 0.5) if mapped else ((0.0, 0.0), 1.0)
+            origin = o if origin is None else origin
+            inv_len = il if inv_len is None else inv_len
+        self.engine.set_hard_boundary(enabled, lift_power=lift_power, lid_sharpness=lid_sharpness, origin=origin,
+                                      inv_len=inv_len)
+
+    def save_hard_boundary(self, path):
+        """Write the sidecar of the checkpoint at `path`: the descriptor dict(lift_power, lid_sharpness, origin,
+        inv_len) as path + '_hardbc' (torch.save).  With the constraint off nothing is written."""
+        info = self.engine.hard_boundary_info()
+        if info is not None:
+            torch.save(dict(info, origin=tuple(info["origin"])), path + '_hardbc')
+
     def set_validation_data(self, x, y, u, v, p=None, every=1000, metric="uv", keep_best=True, patience=0,
                             history=4096):
         """Reference fields u, v (and p) at the points x, y - the DNS grid the run is judged on: after every `every`
@@ -227,7 +259,9 @@ class SolverBase:
         """Load a checkpoint written by save(): the main net's state_dict at `path` and, for the ev class, the entropy
         net's at path_evm (default <path>_evm when that file exists).  When the sidecar <path>_rwf is present the
         weight factorization is turned on with its scale factors (the effective weights are the checkpoint's exactly);
-        without it the factorization state of this solver is left as it is."""
+        without it the factorization state of this solver is left as it is.  The sidecar <path>_hardbc turns the hard
+        wall conditions on with its descriptor: the checkpoint's weights are those of the net INSIDE the transform.  An
+        engine that already holds plans must carry the same descriptor (ValueError otherwise)."""
         self.net.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
         net_1 = getattr(self, "net_1", None)
         if net_1 is not None:
@@ -237,6 +271,16 @@ class SolverBase:
                 net_1.load_state_dict(torch.load(path_evm, map_location="cpu", weights_only=True))
         if os.path.exists(path + '_rwf'):
             self.engine.set_weight_factorization(factors=torch.load(path + '_rwf', map_location="cpu", weights_only=True))
+        if os.path.exists(path + '_hardbc'):
+            bc = torch.load(path + '_hardbc', map_location="cpu", weights_only=True)
+            bc = dict(lift_power=int(bc["lift_power"]), lid_sharpness=float(bc["lid_sharpness"]),
+                      origin=tuple(float(c) for c in bc["origin"]), inv_len=float(bc["inv_len"]))
+            if self.engine.hard_boundary_info() != bc:
+                try:
+                    self.engine.set_hard_boundary(True, **bc)
+                except ValueError as err:
+                    raise ValueError("checkpoint %s was trained with hard wall conditions %r, this solver holds %r: %s"
+                                     % (path, bc, self.engine.hard_boundary_info(), err))
 
     def _begin_adam_stage(self, scheduler):
         """Resolve solve_Adam's scheduler= argument.  An LrSchedule, or a torch.optim.lr_scheduler object of type
@@ -549,6 +593,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         os.makedirs(save_results_to, exist_ok=True)
         torch.save(self.net.state_dict(), save_results_to + filename)
         self.save_weight_factors(save_results_to + filename)
+        self.save_hard_boundary(save_results_to + filename)
         self._save_best(save_results_to + filename)
         save_matlab_to = directory + '/loss/'
         os.makedirs(save_matlab_to, exist_ok=True)

@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--rwf-mean", type=float, default=0.5)
     ap.add_argument("--rwf-std", type=float, default=0.1)
     ap.add_argument("--rwf-seed", type=int, default=0)
+    ap.add_argument("--hard-bc", type=int, nargs="?", const=2, default=0, metavar="M",
+                    help="hard wall conditions by the output transform u = g + D N_u, v = D N_v with lift power M "
+                         "(default 2; DESIGN.md 7.10); a resumed slice must be given the same M")
     ap.add_argument("--validate-every", type=int, default=0,
                     help="> 0: validate against the DNS field on the device every this many updates of a stage and keep "
                          "the stage's best weights (DESIGN.md 7.9)")
@@ -94,6 +97,9 @@ def main():
     loader = cavity.EvDataLoader(path="./datasets/", N_f=a.nf, N_b=1000, sort_training_points=False,
                                  sdf_weighting=SimpleNamespace(enabled=True, min_weight=0.2, decay=5.0),
                                  coord_transform=False)
+    if a.hard_bc:                                       # before any point set is attached
+        P.set_coordinate_transform(loader.get_coord_scale())
+        P.set_hard_boundary_constraints(lift_power=a.hard_bc, dataloader=loader)
     P.set_boundary_data(X=loader.loading_boundary_data())
     xf, yf = loader.loading_training_data()
     P.set_coordinate_transform(loader.get_coord_scale())
@@ -177,6 +183,7 @@ def main():
         torch.save(P.net.state_dict(), "net.pth")
         torch.save(P.net_1.state_dict(), "net_evm.pth")
         P.save_weight_factors("net.pth")                 # net.pth_rwf with --rwf, nothing without
+        P.save_hard_boundary("net.pth")                  # net.pth_hardbc with --hard-bc, nothing without
 
 
 if __name__ == "__main__":
