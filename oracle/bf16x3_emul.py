@@ -34,6 +34,10 @@ The keyword options restate what a plan may choose differently (defaults: the al
          kernels' fmaf(w0x, x, fmaf(w0y, y, b0)) (spill_io.h layer0_z: one rounding per fmaf).
   tanh   "libm" | "fast": tanh rounded from fp64, or 1 - 2 / (exp2(z * 2.88539...) + 1) in fp32 as fast_tanh of
          bf16_util.h states it (the bf16 kernels' forward; the fp32 kernels call tanhf).
+  point_map  None, or a pair of callables (forward, transpose) applied in fp32 after the output layer and before the
+         reverse sweep: forward takes the net's output streams (N, 3, 4) - value mode: the predictions (N, n_out) - to
+         the fields the loss is taken of, transpose takes the adjoints of those fields back to the net's outputs.  What
+         the constrained point stages of csrc/point_stage.h do (the hard wall conditions); the caller states the map.
   fault  None, or a deliberate error for the sensitivity controls of tests/test_bf16_fast_mode.py: "trunc" truncates
          GEMM operands to bf16 instead of rounding them; ("stream", s, f) scales a-stream s of every hidden layer's
          forward GEMM input by f.
@@ -158,7 +162,7 @@ def _a_streams(t, zx, zy, zd):
 
 
 def residual_loss_and_grad(flat, x, y, Re, n_hidden, hidden, coef=None, prec="bf16x3", spill="p24", acc="fp32",
-                           tanh="libm", fault=None, spill0="none", out="fp32", layer0="plain"):
+                           tanh="libm", fault=None, spill0="none", out="fp32", layer0="plain", point_map=None):
     """The plain-flavour residual term (unit weights, scale 1) at float32 inputs: eqs, sums and the parameter gradient
     of sum_k coef * sum eq_k^2 / 2 (coef defaults to 2 / N, the engine's alpha_e = 1).  Options: see the module."""
     mm_f, mm_b, mm_d, sp, scale, img = _options(prec, spill, acc, tanh, fault, spill0, out)
@@ -187,6 +191,8 @@ def residual_loss_and_grad(flat, x, y, Re, n_hidden, hidden, coef=None, prec="bf
         else:
             z, zx, zy, zd = img(a[0]) @ W.T + b, img(a[1]) @ W.T, img(a[2]) @ W.T, img(a[3]) @ W.T
     out = np.stack([z, zx, zy, zd], axis=2).astype(F)
+    if point_map is not None:
+        out = np.asarray(point_map[0](out), F)
     nu = F(1.0 / Re)
     u, v = out[:, 0, 0], out[:, 1, 0]
     eq1 = (u * out[:, 0, 1] + v * out[:, 0, 2]) + out[:, 2, 1] - nu * out[:, 0, 3]
@@ -201,6 +207,8 @@ def residual_loss_and_grad(flat, x, y, Re, n_hidden, hidden, coef=None, prec="bf
     adj[:, 1, 1], adj[:, 1, 2] = r2 * u, r2 * v + r3
     adj[:, 2, 1], adj[:, 2, 2] = r1, r2
     adj[:, 0, 3], adj[:, 1, 3] = -nu * r1, -nu * r2
+    if point_map is not None:
+        adj = np.asarray(point_map[1](adj), F)
     # reverse
     grads = [None] * (L + 1)
     Wout = P[-1][0]
@@ -229,7 +237,7 @@ def residual_loss_and_grad(flat, x, y, Re, n_hidden, hidden, coef=None, prec="bf
 
 
 def value_loss_and_grad(flat, x_b, y_b, u_b, v_b, n_hidden, hidden, coef=None, n_out=3, prec="bf16", acc="fp32",
-                        tanh="libm", fault=None, out="image", layer0="plain"):
+                        tanh="libm", fault=None, out="image", layer0="plain", point_map=None):
     """The value-mode (one-stream) boundary term at float32 inputs, after fwdmode_ref.forward1 / backward1 /
     bc_loss_and_grad: predictions (N, n_out), the two sums of squared errors and the parameter gradient of
     coef * (sum (u - u_b)^2 + sum (v - v_b)^2) / 2 (coef defaults to 2 / N).  As in the value branches of fwd_bf16.hip /
@@ -258,9 +266,13 @@ def value_loss_and_grad(flat, x_b, y_b, u_b, v_b, n_hidden, hidden, coef=None, n
             z = mm_f(t * scale[1] if scale is not None else t, W.T) + b
         else:
             pred = (img(t) @ W.T + b).astype(F)
+    if point_map is not None:
+        pred = np.asarray(point_map[0](pred), F)
     du, dv = pred[:, 0] - np.asarray(u_b, F).reshape(-1), pred[:, 1] - np.asarray(v_b, F).reshape(-1)
     adj = np.zeros_like(pred)
     adj[:, 0], adj[:, 1] = c * du, c * dv
+    if point_map is not None:
+        adj = np.asarray(point_map[1](adj), F)
     grads = [None] * (L + 1)
     grads[-1] = ((adj.T @ saved[-1]).astype(F), adj.sum(axis=0))
     g = adj @ P[-1][0]

@@ -5,7 +5,10 @@ Two independent statements of the output transform u = g + D N_u, v = D N_v, p =
     parameter gradient come from autograd through the ansatz (constrained_step);
   * transform_streams / transpose_streams are the closed-form forward-mode map of the four streams (value, d/dX, d/dY,
     Laplacian) and its transpose, operation by operation as the point stages write them, in numpy at any dtype (fp32:
-    the stages' arithmetic up to the compiler's fused multiply-adds and the last place of expf).
+    the stages' arithmetic up to the compiler's fused multiply-adds and the last place of expf);
+  * constrained_fwdmode / constrained_value compose that map with oracle.fwdmode_ref's forward-mode sweeps: the
+    constrained step as the kernels run it, in passes, so that a looping point count costs seconds, and with an
+    optional relative error per Laplacian term for the sensitivity controls of tests/test_hardbc_terms.py.
 """
 import numpy as np
 import torch
@@ -134,23 +137,151 @@ def point_factors(bc, xi, eta, dtype=np.float64):
                 gd=lid2 * pm + lid * (fm * (fm - one)) * pm2)
 
 
-def transform_streams(h, n, nx, ny, nd, lift):
-    """(c, c_X, c_Y, Lap c) of c = lift g + D N from the net's streams (N, N_X, N_Y, Lap N)."""
+# The seven Laplacian-stream terms of the map and its transpose (each enters the loss with weight nu only) and the value
+# mode's D: the keys of `rel`, a dict of relative errors the closed forms below take for the sensitivity controls.
+FORWARD_TERMS = ("lap_g", "lapD_N", "cross", "D_lapN")      # Lap g, Lap D N, 2 (D_X N_X + D_Y N_Y), D Lap N
+TRANSPOSE_TERMS = ("t_lapD", "t_cross", "t_D")              # Lap D a_D, 2 D_X a_D / 2 D_Y a_D, D a_D
+LAPLACIAN_TERMS = FORWARD_TERMS + TRANSPOSE_TERMS
+VALUE_TERM = "v_D"                                          # the D of the value mode's adjoint
+
+
+def _gain(rel, key):
+    return 1.0 + (0.0 if not rel else float(rel.get(key, 0.0)))
+
+
+def transform_streams(h, n, nx, ny, nd, lift, rel=None):
+    """(c, c_X, c_Y, Lap c) of c = lift g + D N from the net's streams (N, N_X, N_Y, Lap N).  rel: relative errors of
+    the Laplacian's terms (FORWARD_TERMS), for the controls."""
     two = h["D"].dtype.type(2.0)
     c = h["D"] * n
     cx = h["Dx"] * n + h["D"] * nx
     cy = h["Dy"] * n + h["D"] * ny
-    cd = h["Dd"] * n + two * (h["Dx"] * nx + h["Dy"] * ny) + h["D"] * nd
+    if not rel:
+        cd = h["Dd"] * n + two * (h["Dx"] * nx + h["Dy"] * ny) + h["D"] * nd
+    else:
+        cd = (_gain(rel, "lapD_N") * (h["Dd"] * n) + _gain(rel, "cross") * (two * (h["Dx"] * nx + h["Dy"] * ny)) +
+              _gain(rel, "D_lapN") * (h["D"] * nd))
     if lift:
-        c, cx, cy, cd = h["g"] + c, h["gx"] + cx, h["gy"] + cy, h["gd"] + cd
+        c, cx, cy, cd = h["g"] + c, h["gx"] + cx, h["gy"] + cy, (h["gd"] if not rel else _gain(rel, "lap_g") * h["gd"]) + cd
     return c, cx, cy, cd
 
 
-def transpose_streams(h, a, ax, ay, ad):
-    """Adjoints of the net's four streams from the adjoints of (c, c_X, c_Y, Lap c)."""
+def transpose_streams(h, a, ax, ay, ad, rel=None):
+    """Adjoints of the net's four streams from the adjoints of (c, c_X, c_Y, Lap c).  rel: relative errors of the
+    terms that carry a_D (TRANSPOSE_TERMS), for the controls."""
     two = h["D"].dtype.type(2.0)
-    return (h["D"] * a + h["Dx"] * ax + h["Dy"] * ay + h["Dd"] * ad, h["D"] * ax + two * h["Dx"] * ad,
-            h["D"] * ay + two * h["Dy"] * ad, h["D"] * ad)
+    if not rel:
+        return (h["D"] * a + h["Dx"] * ax + h["Dy"] * ay + h["Dd"] * ad, h["D"] * ax + two * h["Dx"] * ad,
+                h["D"] * ay + two * h["Dy"] * ad, h["D"] * ad)
+    kd, kc, k0 = _gain(rel, "t_lapD"), _gain(rel, "t_cross"), _gain(rel, "t_D")
+    return (h["D"] * a + h["Dx"] * ax + h["Dy"] * ay + kd * (h["Dd"] * ad), h["D"] * ax + kc * (two * h["Dx"] * ad),
+            h["D"] * ay + kc * (two * h["Dy"] * ad), k0 * (h["D"] * ad))
+
+
+# ---- the constrained step in forward mode: what the kernels run, pass by pass, in fp64 ----
+def _factors64(bc, x, y, factor_dtype):
+    h = point_factors(bc, x, y, dtype=factor_dtype)
+    return {k: np.asarray(v, dtype=np.float64) for k, v in h.items()}
+
+
+def constrained_fwdmode(params, bc, x, y, Re, alpha_e=1.0, vis_t=None, e=None, w=None, scale=1.0, eq4_weight=0.1,
+                        params_e=None, chunk=8192, rel=None, factor_dtype=np.float64):
+    """The residual term of a constrained plan as the sweeps compute it: fr.forward4, the scale factors, the map of
+    the point stage (transform_streams), fr.residuals, the output-adjoint seeds of fr.pde_loss_and_grad, the transpose
+    (transpose_streams), the scale factors again, fr.backward4 - in passes of <= chunk points normalised by the global
+    N, like fr.pde_loss_and_grad_chunked, whose arguments these are (params: fr.unflatten's pairs; params_e: the
+    entropy net, e defaults to its output, grad_e is its gradient).  rel: relative errors per term (LAPLACIAN_TERMS);
+    factor_dtype: the dtype point_factors runs in (fp32: the stage's own factors, pushed through this fp64 model).
+    Returns dict(fields: u, v, p, u_x, u_y, v_x, v_y; eqs; sums; grad[, grad_e])."""
+    from oracle import fwdmode_ref as fr
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    N, s, s2 = x.size, float(scale), float(scale) * float(scale)
+    opt = lambda a, lo, hi: None if a is None else np.asarray(a, dtype=np.float64).reshape(-1)[lo:hi]
+    cw = [1.0, 1.0, 1.0, eq4_weight]
+    sums, grad, grad_e, eqs_all, flds = None, None, None, [], []
+    for lo in range(0, N, int(chunk)):
+        hi = min(N, lo + int(chunk))
+        xs, ys = x[lo:hi], y[lo:hi]
+        ek, saved_e = opt(e, lo, hi), None
+        if params_e is not None:
+            ev, saved_e = fr.forward1(params_e, xs, ys)
+            if ek is None:
+                ek = ev[:, 0]
+        out, saved = fr.forward4(params, xs, ys)
+        h = _factors64(bc, xs.astype(factor_dtype), ys.astype(factor_dtype), factor_dtype)
+        phys = out * np.array([1.0, s, s, s2])                  # derivatives in the cavity's own X, Y
+        con = phys.copy()
+        for c, lift in ((0, True), (1, False)):
+            con[:, c, :] = np.stack(transform_streams(h, *(phys[:, c, k] for k in range(4)), lift=lift, rel=rel), axis=1)
+        vt = opt(vis_t, lo, hi)
+        eqs = fr.residuals(con, Re, vt, ek, 1.0)
+        ww = np.ones(hi - lo) if w is None else opt(w, lo, hi)
+        ps = np.array([float(np.sum(ww * q * q)) for q in eqs])
+        g = [2.0 * alpha_e * cw[k] * ww * eqs[k] / N for k in range(len(eqs))]
+        u, v = con[:, 0, 0], con[:, 1, 0]
+        nu = 1.0 / Re + (0.0 if vt is None else vt)
+        g4 = g[3] if len(eqs) == 4 else np.zeros(hi - lo)
+        r1, r2, r3 = g[0] + g4 * (u - 0.5), g[1] + g4 * (v - 0.5), g[2]
+        adj = np.zeros_like(con)                                # adjoints of the constrained streams (and of p's)
+        adj[:, 0, 0] = r1 * con[:, 0, 1] + r2 * con[:, 1, 1] + (g4 * eqs[0] if len(eqs) == 4 else 0.0)
+        adj[:, 1, 0] = r1 * con[:, 0, 2] + r2 * con[:, 1, 2] + (g4 * eqs[1] if len(eqs) == 4 else 0.0)
+        adj[:, 0, 1], adj[:, 0, 2], adj[:, 0, 3] = r1 * u + r3, r1 * v, -nu * r1
+        adj[:, 1, 1], adj[:, 1, 2], adj[:, 1, 3] = r2 * u, r2 * v + r3, -nu * r2
+        adj[:, 2, 1], adj[:, 2, 2] = r1, r2
+        for c in (0, 1):
+            adj[:, c, :] = np.stack(transpose_streams(h, *(adj[:, c, k] for k in range(4)), rel=rel), axis=1)
+        gk, _ = fr.backward4(params, xs, ys, saved, adj * np.array([1.0, s, s, s2]))
+        sums = ps if sums is None else sums + ps
+        grad = gk if grad is None else grad + gk
+        if params_e is not None:
+            ge = fr.backward1(params_e, xs, ys, saved_e, (-g4).reshape(-1, 1))
+            grad_e = ge if grad_e is None else grad_e + ge
+        eqs_all.append(eqs)
+        flds.append(con)
+    con = np.concatenate(flds)
+    res = dict(sums=[float(q) for q in sums], grad=grad,
+               eqs=[np.concatenate([q[k] for q in eqs_all]) for k in range(len(eqs_all[0]))],
+               fields=dict(u=con[:, 0, 0], v=con[:, 1, 0], p=con[:, 2, 0], u_x=con[:, 0, 1], u_y=con[:, 0, 2],
+                           v_x=con[:, 1, 1], v_y=con[:, 1, 2], u_d=con[:, 0, 3], v_d=con[:, 1, 3], p_x=con[:, 2, 1],
+                           p_y=con[:, 2, 2]))
+    if params_e is not None:
+        res["grad_e"] = grad_e
+    return res
+
+
+def constrained_value(params, bc, x, y, targets=None, coef=None, chunk=8192, rel=None, factor_dtype=np.float64):
+    """Value mode of a constrained plan: fr.forward1, pred_u = g + D N_u, pred_v = D N_v, pred_p = N_p, the squared
+    errors against the finite targets (NaN / inf = masked), the net's output adjoints coef (pred - target) D (p: no D),
+    fr.backward1 - in passes like fr.value_loss_and_grad_chunked, whose arguments and result these are.  rel: the
+    relative error of the adjoint's D (VALUE_TERM)."""
+    from oracle import fwdmode_ref as fr
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    N = x.size
+    tg = [None if t is None else np.asarray(t, dtype=np.float64).reshape(-1) for t in (list(targets or ()) + [None] * 3)[:3]]
+    cf = np.zeros(3) if coef is None else np.asarray(coef, dtype=np.float64).reshape(-1)[:3]
+    sums, grad, preds = np.zeros(4), None, []
+    for lo in range(0, N, int(chunk)):
+        hi = min(N, lo + int(chunk))
+        xs, ys = x[lo:hi], y[lo:hi]
+        net, saved = fr.forward1(params, xs, ys)
+        h = _factors64(bc, xs.astype(factor_dtype), ys.astype(factor_dtype), factor_dtype)
+        pred = np.stack([h["g"] + h["D"] * net[:, 0], h["D"] * net[:, 1], net[:, 2]], axis=1)
+        adj = np.zeros_like(pred)
+        for c in range(3):
+            if tg[c] is None:
+                continue
+            ok = np.isfinite(tg[c][lo:hi])
+            d = np.where(ok, pred[:, c] - np.where(ok, tg[c][lo:hi], 0.0), 0.0)
+            sums[c] += np.sum(d * d)
+            if c == 2:
+                sums[3] += ok.sum()
+            adj[:, c] = cf[c] * d * (_gain(rel, VALUE_TERM) * h["D"] if c < 2 else 1.0)
+        gk = fr.backward1(params, xs, ys, saved, adj)
+        grad = gk if grad is None else grad + gk
+        preds.append(pred)
+    return dict(pred=np.concatenate(preds), sums=[float(q) for q in sums], grad=grad)
 
 
 def special_points(lo=0.0, hi=1.0):

@@ -57,6 +57,10 @@ emulation | bar | format error:
   3x16, the row closest to the emulation 8.7e-9 / 7.3e-8 / 2.3e-7 | 1.8e-4 / 2.6e-5 / 8.8e-5 | 5.7e-3 / 1.7e-3 / 2.7e-3
   value 3x50 .. 3x400, pred/sums/grad <= 1.6e-4 / 3.0e-5 / 8.9e-5 | <= 1.1e-3 / 2.5e-4 / 2.3e-4 | >= 5.3e-3 / 7.5e-4 / 2.1e-3
 No kernel was changed.
+
+The constrained twins of the 8-wave rows (hard wall conditions) are judged the same way at the
+end of the module: 3x50, 3x256 at 128 and 64 columns, 3x400 wide on either spill and four value rows; measured figures
+in DESIGN.md 7.10, "Tests".
 """
 import os
 import sys
@@ -164,9 +168,10 @@ def _emul(c, triple=None, fault=None, **variant):
     return _EMUL[k]
 
 
-def _dist(c, a, b):
-    """Distances of two results of a case in units of the oracle's norms, and the gradient's per block."""
-    ref = _oracle(c)
+def _dist(c, a, b, ref=None):
+    """Distances of two results of a case in units of the oracle's norms (ref: another reference's), and the gradient's
+    per block."""
+    ref = _oracle(c) if ref is None else ref
     blocks = _block_errs(a["grad"], b["grad"], 3, c["L"], c["H"], ref=ref["grad"])
     d = dict(eq=max(float(np.linalg.norm(a["eqs"][k] - b["eqs"][k]) / np.linalg.norm(ref["eqs"][k])) for k in range(3)),
              sums=max(abs(a["sums"][k] - b["sums"][k]) / ref["sums"][k] for k in range(3)), grad=max(blocks),
@@ -418,17 +423,23 @@ def test_the_value_bar_is_four_times_sharper_than_the_format_error(L, H, seed):
 # --------------------------------------------------------------------------------------------------------------------
 # GPU: one engine and one loss_and_grad per row, against the row's emulation at the row's bar
 # --------------------------------------------------------------------------------------------------------------------
-def _engine(monkeypatch, L, H, Re, prec, env, flat, x, y, bc):
+def _engine(monkeypatch, L, H, Re, prec, env, flat, x, y, bc, constrain=False, sup=None):
+    """constrain: hard wall conditions on; sup: a supervised set (x, y, u, v) at alpha_s = ALPHA_B."""
     from nsfnet_amd import engine as eng
     for k in list(os.environ):
         if k.startswith("PINN_") or k == "NSFNET_CHUNK_POINTS":
             monkeypatch.delenv(k, raising=False)
     for k, v in env:
         monkeypatch.setenv(k, v)
-    E = eng.PinnEngine(torch.device("cuda:0"), L, H, Re, alpha_b=ALPHA_B, alpha_e=1.0, precision=prec)
+    E = eng.PinnEngine(torch.device("cuda:0"), L, H, Re, alpha_b=ALPHA_B, alpha_e=1.0, precision=prec,
+                       alpha_s=0.0 if sup is None else ALPHA_B)
+    if constrain:
+        E.set_hard_boundary(True)
     E.net.set_flat(torch.tensor(flat))
     E.set_collocation(x, y)
     E.set_boundary(*bc)
+    if sup is not None:
+        E.set_supervised(*sup)
     return eng, E
 
 
@@ -492,6 +503,255 @@ def test_plain_bf16_value_kernels_vs_their_arithmetic(monkeypatch, L, H, seed):
     d = _value_dist(L, H, seed, got, _value(L, H, seed, "emul"))
     far = _value_dist(L, H, seed, got, _value(L, H, seed, "oracle"))
     print("[bf16 mode] value %dx%d: from the emulation %s | bar %s | format %s | from the oracle %s" % (
+        L, H, " ".join("%s %.2e" % (q, d[q]) for q in VQS), " ".join("%.1e" % (FACTOR * noise[q]) for q in VQS),
+        " ".join("%.1e" % fmt[q] for q in VQS), " ".join("%.1e" % far[q] for q in VQS)))
+    for q in VQS:
+        assert d[q] <= FACTOR * noise[q], (q, d[q], FACTOR * noise[q])
+    for q in ("pred", "sums"):
+        assert far[q] >= fmt[q] - FACTOR * noise[q], (q, far[q], fmt[q])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the constrained twins of the 8-wave rows (hard wall conditions)
+# --------------------------------------------------------------------------------------------------------------------
+# Every TERMS == 1 instantiation of the constrained point stages (half of fwd_bf16's and fwd_bf16_wide's, and the
+# reverse ones), by the method above: the emulation takes the map u = g + D N_u, v = D N_v as a pair of fp32 callables
+# (oracle.bf16x3_emul's point_map; the closed forms of tests/hardbc_model.py at float32), the norms are the fp64
+# model's (hardbc_model.constrained_fwdmode / constrained_value), bar = FACTOR * noise among the emulation's own
+# variants, condition 4 * noise <= format / 4.  A constrained plan runs the 8-wave families whatever the switches say,
+# so the rows are the 8-wave ones: 3x50, 3x256 at 128 and 64 columns, 3x400 wide on either spill, and the value rows -
+# on interior points through the supervised plan, since the boundary plan's gradient is zero under the constraint.
+import hardbc_model as hm  # noqa: E402
+
+HBC = hm.HardBc()
+_EIGHT = {("fwd_bf16_kernel", "bwd_bf16_kernel"), ("fwd_bf16_wide_kernel", "bwd_bf16_wide_kernel")}
+# (L, H, net seed, points seed): the next seeds after NARROW's 3x50, NET_256's and NET_400's at which the conditions hold
+# constrained (the viscous share, 4 * noise <= format / 4, noise of the planes >= 3e-5 and of the gradient >= 1e-5)
+HBC_NETS = {50: (3, 50, 59, 15), 256: (3, 256, 1238, 11), 400: (3, 400, 45, 13)}
+CASES_HBC = [_case(*HBC_NETS[c["H"]], c["row"]) for c in CASES
+             if c["H"] in HBC_NETS and c["row"]["names"][:2] in _EIGHT and c["row"]["triple"][:2] == (B16, B16)]
+# (L, H, net seed): the first seeds from VALUE's on that meet the condition with a noise well above fp32 rounding (pred
+# >= 3e-5, sums >= 4e-6, gradient >= 1e-5: where no variant flips a bf16 rounding the bar would collapse to it)
+VALUE_HBC = [(3, 50, 55), (3, 128, 53), (3, 256, 53), (3, 400, 55)]
+
+
+def _residual_map(x, y):
+    h = hm.point_factors(HBC, x, y, dtype=np.float32)
+
+    def apply(f, kw):
+        def run(q):
+            q = np.array(q, dtype=np.float32)
+            for ch, lift in ((0, True), (1, False)):
+                q[:, ch, :] = np.stack(f(h, *(q[:, ch, k] for k in range(4)), **kw(lift)), axis=1)
+            return q
+        return run
+    return apply(hm.transform_streams, lambda lift: dict(lift=lift)), apply(hm.transpose_streams, lambda lift: {})
+
+
+def _value_map(x, y):
+    h = hm.point_factors(HBC, x, y, dtype=np.float32)
+
+    def forward(pred):
+        pred = np.array(pred, dtype=np.float32)
+        pred[:, 0], pred[:, 1] = h["g"] + h["D"] * pred[:, 0], h["D"] * pred[:, 1]
+        return pred
+
+    def transpose(adj):
+        adj = np.array(adj, dtype=np.float32)
+        adj[:, 0], adj[:, 1] = adj[:, 0] * h["D"], adj[:, 1] * h["D"]
+        return adj
+    return forward, transpose
+
+
+_HBC = {}
+
+
+def _hbc_model(c, Re=None):
+    k = _key(c) + ("model", Re)
+    if k not in _HBC:
+        inp = _inputs(c)
+        P = fr.unflatten(inp["flat"].astype(np.float64), 2, 3, c["L"], c["H"])
+        _HBC[k] = hm.constrained_fwdmode(P, HBC, inp["x"], inp["y"], c["Re"] if Re is None else Re)
+    return _HBC[k]
+
+
+def _hbc_emul(c, triple=None, **variant):
+    row = c["row"]
+    triple = row["triple"] if triple is None else triple
+    opts = dict(_emul_options(row["names"]), **(variant or _default(row["triple"])))
+    k = _key(c) + (triple,) + tuple(sorted(opts.items()))
+    if k not in _HBC:
+        inp = _inputs(c)
+        _HBC[k] = em.residual_loss_and_grad(inp["flat"], inp["x"], inp["y"], c["Re"], c["L"], c["H"], prec=triple,
+                                            point_map=_residual_map(inp["x"], inp["y"]), **opts)
+    return _HBC[k]
+
+
+def _hbc_noise(c):
+    runs = [_hbc_emul(c, **v) for v in VARIANTS]
+    ds = [_dist(c, a, b, _hbc_model(c))[0] for i, a in enumerate(runs) for b in runs[:i]]
+    return {q: max(d[q] for d in ds) for q in QS}
+
+
+def _hbc_format(c):
+    return _dist(c, _hbc_emul(c), _hbc_model(c), _hbc_model(c))[0]
+
+
+def test_the_constrained_table_is_what_the_module_says():
+    assert sorted((c["H"], c["row"]["triple"], c["row"]["env"]) for c in CASES_HBC) == sorted([
+        (50, (B16,) * 3, ()), (256, (B16,) * 3, (("PINN_SCHED", "0"),)), (256, (B16,) * 3, (("PINN_TILE_COLS", "64"),)),
+        (400, (B16,) * 3, (("PINN_WSPLIT", "0"),)), (400, (B16, B16, F32), ())])
+    assert {_emul_options(c["row"]["names"])["spill"] for c in CASES_HBC if c["H"] == 400} == {"p24", "f32"}
+    assert all(_emul_options(c["row"]["names"])["out"] == "image" for c in CASES_HBC)
+
+
+@pytest.mark.parametrize("c", CASES_HBC, ids=_ids(CASES_HBC))
+def test_every_constrained_row_resolves_to_the_names_it_lists(lib, c):
+    from test_hardbc_terms import _constrained_census
+    row = c["row"]
+    got = _constrained_census(lib, (c["H"], c["L"], tuple(CODE[p] for p in row["triple"]), 4, N, dict(row["env"])),
+                              HBC.struct())
+    assert got[1] == 0, got
+    assert tuple(got[5:8]) == row["names"] and got[2] == -(-N // row["tile"]) * row["tile"]
+    # ... with the workspace, hence the spill, of the unconstrained row
+    plain = plan_census.run_case(lib, (c["H"], c["L"], tuple(CODE[p] for p in row["triple"]), 4, N,
+                                       dict(row["env"], PINN_SCHED="0", PINN_WSPLIT="0", PINN_FUSE="0")))
+    assert got[1:] == plain[1:], (got, plain)
+
+
+def test_the_emulations_point_map_is_the_fp64_models_map():
+    """With fp32 products in every role the mapped emulation is the fp64 constrained model to fp32 rounding."""
+    c = CASES_HBC[0]
+    inp, ref = _inputs(c), _hbc_model(c)
+    got = em.residual_loss_and_grad(inp["flat"], inp["x"], inp["y"], c["Re"], c["L"], c["H"], prec=F32, spill="f32",
+                                    point_map=_residual_map(inp["x"], inp["y"]))
+    d, _ = _dist(c, got, ref, ref)
+    assert max(d.values()) <= 1e-5, d
+    plain = em.residual_loss_and_grad(inp["flat"], inp["x"], inp["y"], c["Re"], c["L"], c["H"], prec=F32, spill="f32")
+    assert _dist(c, plain, ref, ref)[0]["eq"] > 0.1       # and the map is not a no-op
+
+
+@pytest.mark.parametrize("c", _nets(CASES_HBC), ids=_ids(_nets(CASES_HBC)))
+def test_the_viscous_term_carries_its_share_constrained(c):
+    r, r0 = _hbc_model(c), _hbc_model(c, 1.0e30)
+    rel_max = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    s = dict(eq1=rel_max(r0["eqs"][0], r["eqs"][0]), eq2=rel_max(r0["eqs"][1], r["eqs"][1]), grad=_rel_l2(r0["grad"], r["grad"]))
+    assert min(s.values()) >= SHARE_MIN, s
+
+
+_NOISE_HBC = _rows_of_nets(CASES_HBC)
+
+
+@pytest.mark.parametrize("c", _NOISE_HBC, ids=_ids(_NOISE_HBC))
+def test_the_constrained_bar_is_four_times_sharper_than_the_format_error(c):
+    """A condition on the inputs, not a measurement: a row that does not meet it gets another seed."""
+    noise, fmt = _hbc_noise(c), _hbc_format(c)
+    print("[bf16 mode] constrained %s noise %s | format %s | bar / format %s" % (
+        c["tag"], " ".join("%s %.1e" % (q, noise[q]) for q in QS), " ".join("%s %.1e" % (q, fmt[q]) for q in QS),
+        " ".join("%s %.3f" % (q, FACTOR * noise[q] / fmt[q]) for q in QS)))
+    for q in _conditioned(c):
+        assert noise[q] > 0.0 and FACTOR * FACTOR * noise[q] <= fmt[q], (q, noise[q], fmt[q])
+
+
+def _supervised():
+    """150 interior points with targets that satisfy the wall conditions themselves, as a measured flow field would:
+    u = g + D a, v = D b with smooth a, b the net does not match, plus noise (test_value_loops' fields)."""
+    rng = np.random.RandomState(23)
+    x, y = (0.02 + 0.96 * rng.rand(N_B)).astype(np.float32), (0.02 + 0.96 * rng.rand(N_B)).astype(np.float32)
+    h = hm.point_factors(HBC, x.astype(np.float64), y.astype(np.float64))
+    a = 0.25 + np.sin(2 * np.pi * x) * np.cos(np.pi * y) + 0.05 * rng.randn(N_B)
+    b = -0.2 + np.cos(3.0 * x) * np.sin(2 * np.pi * y) + 0.05 * rng.randn(N_B)
+    return x, y, (h["g"] + h["D"] * a).astype(np.float32), (h["D"] * b).astype(np.float32)
+
+
+def _hbc_value(L, H, seed, what, **variant):
+    k = (L, H, seed, "value", what) + tuple(sorted(variant.items()))
+    if k not in _HBC:
+        flat, (x, y, u, v) = _net(L, H, seed), _supervised()
+        if what == "model":
+            P = fr.unflatten(flat.astype(np.float64), 2, 3, L, H)
+            c = 2.0 * ALPHA_B / N_B
+            r = hm.constrained_value(P, HBC, x, y, targets=[u, v, None], coef=(c, c, 0.0))
+            _HBC[k] = dict(r, sums=r["sums"][:2])
+        else:
+            _HBC[k] = em.value_loss_and_grad(flat, x, y, u, v, L, H, coef=2.0 * ALPHA_B / N_B, prec=B16,
+                                             point_map=_value_map(x, y), **(variant or _default((B16,) * 3)))
+    return _HBC[k]
+
+
+def _hbc_value_dist(L, H, seed, a, b):
+    ref = _hbc_value(L, H, seed, "model")
+    return dict(pred=max(float(np.linalg.norm(a["pred"][:, k] - b["pred"][:, k]) / np.linalg.norm(ref["pred"][:, k]))
+                         for k in range(3)),
+                sums=max(abs(a["sums"][k] - b["sums"][k]) / ref["sums"][k] for k in range(2)),
+                grad=max(_block_errs(a["grad"], b["grad"], 3, L, H, ref=ref["grad"])))
+
+
+def _hbc_value_noise(L, H, seed):
+    runs = [_hbc_value(L, H, seed, "emul", **v) for v in VARIANTS]
+    ds = [_hbc_value_dist(L, H, seed, a, b) for i, a in enumerate(runs) for b in runs[:i]]
+    return {q: max(d[q] for d in ds) for q in VQS}
+
+
+def _hbc_value_format(L, H, seed):
+    return _hbc_value_dist(L, H, seed, _hbc_value(L, H, seed, "emul"), _hbc_value(L, H, seed, "model"))
+
+
+@pytest.mark.parametrize("L,H,seed", VALUE_HBC, ids=["%dx%d" % v[:2] for v in VALUE_HBC])
+def test_the_constrained_value_bar_is_four_times_sharper_than_the_format_error(L, H, seed):
+    noise, fmt = _hbc_value_noise(L, H, seed), _hbc_value_format(L, H, seed)
+    print("[bf16 mode] constrained value %dx%d noise %s | format %s | bar / format %s" % (
+        L, H, " ".join("%s %.1e" % (q, noise[q]) for q in VQS), " ".join("%s %.1e" % (q, fmt[q]) for q in VQS),
+        " ".join("%s %.3f" % (q, FACTOR * noise[q] / fmt[q]) for q in VQS)))
+    for q in VQS:
+        assert noise[q] > 0.0 and FACTOR * FACTOR * noise[q] <= fmt[q], (q, noise[q], fmt[q])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", CASES_HBC, ids=_ids(CASES_HBC))
+def test_constrained_plain_bf16_kernels_vs_their_arithmetic(monkeypatch, c):
+    row, inp = c["row"], _inputs(c)
+    eng, E = _engine(monkeypatch, c["L"], c["H"], c["Re"], row["prec"], row["env"], inp["flat"], inp["x"], inp["y"],
+                     _boundary(), constrain=True)
+    assert E.plan_f.kernel_names() == row["names"] and E.plan_f.hard_bc() is not None
+    assert E.plan_f.npad == -(-N // row["tile"]) * row["tile"]
+    E.loss_and_grad()
+    got = dict(grad=_alone(eng, E, E.plan_f), sums=list(E.sums.cpu().numpy().astype(np.float64)[:3]),
+               eqs=[E.plan_f.field(k).cpu().numpy().astype(np.float64) for k in ("eq1", "eq2", "eq3")])
+    del E
+    torch.cuda.empty_cache()
+    ref, emu, noise, fmt = _hbc_model(c), _hbc_emul(c), _hbc_noise(c), _hbc_format(c)
+    bar = {q: FACTOR * noise[q] for q in QS}
+    d, blocks = _dist(c, got, emu, ref)
+    far, _ = _dist(c, got, ref, ref)
+    print("[bf16 mode] constrained %s: from the emulation %s | bar %s | format %s | from the model %s" % (
+        c["tag"], " ".join("%s %.2e" % (q, d[q]) for q in QS), " ".join("%.1e" % bar[q] for q in QS),
+        " ".join("%.1e" % fmt[q] for q in QS), " ".join("%.1e" % far[q] for q in QS)))
+    for q in QS:
+        assert d[q] <= bar[q], (q, d[q], bar[q], blocks if q == "grad" else None)
+    for q in ("eq", "sums"):        # the forward role really ran one term (triangle inequality)
+        assert far[q] >= fmt[q] - bar[q], (q, far[q], fmt[q], bar[q])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L,H,seed", VALUE_HBC, ids=["%dx%d" % v[:2] for v in VALUE_HBC])
+def test_constrained_plain_bf16_value_kernels_vs_their_arithmetic(monkeypatch, L, H, seed):
+    rng = np.random.RandomState(5)
+    x, y = rng.rand(N).astype(np.float32), rng.rand(N).astype(np.float32)
+    eng, E = _engine(monkeypatch, L, H, 1.0, B16, (), _net(L, H, seed), x, y, _boundary(), constrain=True,
+                     sup=_supervised())
+    tile = value_tile(H, False)
+    s = E.plan_s
+    assert s.kernel_names() == _value_names(H) and s.npad == -(-N_B // tile) * tile and s.hard_bc() is not None
+    E.loss_and_grad()
+    got = dict(grad=_alone(eng, E, s), sums=list(E.sums.cpu().numpy().astype(np.float64)[16:18]),
+               pred=s.pred.cpu().numpy().astype(np.float64).T[:N_B])
+    del E, s
+    torch.cuda.empty_cache()
+    noise, fmt = _hbc_value_noise(L, H, seed), _hbc_value_format(L, H, seed)
+    d = _hbc_value_dist(L, H, seed, got, _hbc_value(L, H, seed, "emul"))
+    far = _hbc_value_dist(L, H, seed, got, _hbc_value(L, H, seed, "model"))
+    print("[bf16 mode] constrained value %dx%d: from the emulation %s | bar %s | format %s | from the model %s" % (
         L, H, " ".join("%s %.2e" % (q, d[q]) for q in VQS), " ".join("%.1e" % (FACTOR * noise[q]) for q in VQS),
         " ".join("%.1e" % fmt[q] for q in VQS), " ".join("%.1e" % far[q] for q in VQS)))
     for q in VQS:
