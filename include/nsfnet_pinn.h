@@ -524,10 +524,15 @@ int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1,
  * then the scale factors; the output-bias gradient sums N_.  Value plans: pred_u = g + D N_u, pred_v = D N_v, and
  * the output adjoints the forward leaves for pinn_value_backward are coef (pred - tgt) D for u and v.  An out_adj
  * handed to pinn_value_backward is an adjoint of the NET's outputs, as on any plan.
- * A constrained plan runs the 8-wave kernel families (fwd / fwd_wide / fwd_bf16 / fwd_bf16_wide and their reverse
- * sweeps) whatever PINN_SCHED, PINN_WSPLIT and PINN_FUSE say: the role-split and fused sweeps have no constrained
- * variant.  Only a net with n_out = 3 can be constrained.  The constraint is a compile-time variant of those kernels:
- * an unconstrained plan runs what it ran before. */
+ * By default a constrained plan runs the 8-wave kernel families (fwd / fwd_wide / fwd_bf16 / fwd_bf16_wide and their
+ * reverse sweeps) whatever PINN_SCHED, PINN_WSPLIT and PINN_FUSE say.  With PINN_HBC_SPLIT=1 in the environment when
+ * the plan is created it keeps the role-split, wide role-split and fused sweeps those switches give it (fwd_split /
+ * bwd_split / fwdbwd_split at hidden 256, fwd_wsplit / bwd_wsplit at hidden 288 .. 448), which have constrained
+ * variants too; the pipelined schedule has none, so a sweep that would run it (PINN_SCHED=1, one role-split sweep
+ * without the other, an fp32 dW) runs the 8-wave kernel instead.  Forward-only calls (save = 0) and value plans run
+ * the constrained 8-wave kernels either way, and an unconstrained plan never looks at the switch.  Only a net with
+ * n_out = 3 can be constrained.  The constraint is a compile-time variant of those kernels: an unconstrained plan runs
+ * what it ran before. */
 enum { PINN_HARD_BC_NONE = 0, PINN_HARD_BC_CAVITY = 1 };
 typedef struct {
   int32_t kind;        /* 0 none, 1 lid-driven unit cavity */

@@ -32,6 +32,7 @@ struct Switches {
   int s0_skip32;          // $PINN_S0_SKIP32 (default 1; 0 opts out)
   int verbose;            // $PINN_VERBOSE
   int tile_cols;          // $PINN_TILE_COLS = 64 | 128 overrides pick_wide (hidden 128 / 256 only)
+  int hbc_split;          // $PINN_HBC_SPLIT (default 0; 1: a constrained plan may take the role-split / fused sweeps)
 };
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -41,7 +42,7 @@ static Switches read_switches() {
   const int sched = env_int("PINN_SCHED", 2);
   return {env_int("PINN_FWD_SCHED", sched), env_int("PINN_BWD_SCHED", sched), env_int("PINN_WSPLIT", 1),
           env_int("PINN_FUSE", 1), env_int("PINN_STAGGER", 0), env_int("PINN_S0_SKIP32", 1),
-          env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0)};
+          env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0), env_int("PINN_HBC_SPLIT", 0)};
 }
 
 // precision of a kernel family: 0 = fp32-input MFMA (exact fp32), 1 = bf16x3 split, 2 = plain bf16
@@ -118,7 +119,7 @@ struct pinn_plan_s {
   int stagger;           // $PINN_STAGGER, read once at plan creation
   Role role[ROLE_COUNT];
   Spill spill;           // how the sweeps spill S and Z-bar, and what their readers recompute instead (spill.h)
-  HardBc hbc;            // hard wall conditions (kind 0: none); a constrained plan runs the 8-wave families only
+  HardBc hbc;            // hard wall conditions (kind 0: none); resolve_plan says which families a constrained plan runs
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -218,10 +219,15 @@ static int run_fused(const pinn_plan_s* plan, const FwdArgs& fa, const BwdArgs& 
 // (no HIP call) on the net, the point and stream counts, the compute-unit count and the switches.
 static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw_in,
                         const HardBc& hbc = HardBc{}) {
-  // Only the 8-wave families have constrained point stages (point_stage.h): a constrained plan resolves as
-  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, and its spill format follows from that as for any other plan.
+  // The 8-wave, role-split (hidden 256 and wide) and fused families have constrained point stages (point_stage.h); the
+  // pipelined schedule has none.  By default a constrained plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
+  // would.  With $PINN_HBC_SPLIT=1 it keeps what the other switches give it, except that a sweep which would run
+  // the pipelined kernels (PINN_SCHED=1, an incomplete role-split pair, an fp32 dW) runs the 8-wave kernel instead.
+  // Either way the spill format follows from the resolved families as for any other plan, and an unconstrained plan
+  // never looks at the switch.
   Switches sw = sw_in;
-  if (hbc.kind) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
+  const bool hbc_split = hbc.kind && sw.hbc_split != 0;
+  if (hbc.kind && !hbc_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
   p->hbc = hbc;
   p->n = n_points; p->streams = streams;
@@ -270,6 +276,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // one of them alone runs that sweep on schedule 1.
   const bool split_pair = sf == 2 && sb == 2 && net.prec_dw;
   if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
+  if (hbc.kind) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained variant)
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
   const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
@@ -287,6 +294,10 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   if (sw.verbose && hbc.kind)
     fprintf(stderr, "[pinn] plan: hard wall conditions, lid-driven cavity at (%g, %g) x %g, lift power %d, lid sharpness %g\n",
             (double)hbc.x0, (double)hbc.y0, (double)hbc.inv_len, hbc.m, (double)hbc.r);
+  if (sw.verbose && hbc.kind)
+    fprintf(stderr, "[pinn] plan: constrained sweeps: %s (PINN_HBC_SPLIT=%d)\n",
+            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
+            sw.hbc_split);
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);
@@ -569,6 +580,7 @@ int pinn_residual_forward_backward(pinn_plan_t plan, void* ws, const float* prep
                                             ebar_out, stream);
   }
   if (!(Re > 0.f)) return fail(-22, "pinn_residual_forward_backward: Re must be > 0%s");
+  if (int rc = check_hard_bc_scale("pinn_residual_forward_backward", plan, coord_scale)) return rc;
   // the argument blocks of the two launches it replaces (pinn_residual_forward, save = 1 / pinn_residual_backward),
   // except that the fused kernel never staggers its workgroups
   const FwdArgs fa = residual_fwd_args(plan, ws, prep, x, y, e, w, vis_t_minus, vis_t_out, fields, Re, vis_t0, alpha_evm,

@@ -22,7 +22,12 @@
 // every lane of the group for its own column straight from the partials, so neither the forward's output block nor
 // the reverse sweep's output-adjoint block exists; the commit sink of the lanes that own no accumulator slot is the
 // unused fourth output row of the dW_out accumulator.
+//
+// Hard wall conditions (HBC): XB's point stage runs the output map and its transpose of point_stage.h
+// on the lane's column, exactly where residual_point_stage / output_adjoint_stage run them in the two launches; the
+// descriptor rides in the kernel arguments, so the LDS budget is the unconstrained one.
 #include "kernels.h"
+#include "point_stage.h"
 #include "split_phases.h"
 
 template <int HP>
@@ -33,7 +38,7 @@ struct FusedLds {
   static size_t bytes(int L) { return X_BYTES + (PART_F + 6 * HP + (size_t)sg_total(HP, L)) * sizeof(float); }
 };
 
-template <int HP, int TERMS>
+template <int HP, int TERMS, bool HBC = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, BwdArgs a) {
   using G = FusedLds<HP>;
   using SW = SplitWave<HP, TERMS>;
@@ -98,6 +103,12 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     float u = ov[0][0], ux = ov[0][1] * sc, uy = ov[0][2] * sc, ud = ov[0][3] * sc2;
     float v = ov[1][0], vx = ov[1][1] * sc, vy = ov[1][2] * sc, vd = ov[1][3] * sc2;
     float p = ov[2][0], pxx = ov[2][1] * sc, pyy = ov[2][2] * sc;
+    HardBcPoint hb = {};
+    if constexpr (HBC) {                    // hard wall conditions (point_stage.h): a masked or dummy column has D = 0
+      hb = hard_bc_point(fa.hbc, m ? a.x[pt] : 0.f, m ? a.y[pt] : 0.f);
+      hard_bc_apply(hb, true, u, ux, uy, ud);
+      hard_bc_apply(hb, false, v, vx, vy, vd);
+    }
     float vt = 0.f;
     float ev = (fa.e && m) ? fa.e[pt] : 0.f;
     if (fa.vtm && m) {
@@ -125,6 +136,18 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
       }
     }
     // output adjoints (point_stage.h output_adjoint_stage, residual mode) from the values above instead of the field planes
+    HardBcPoint hbt = {};
+    if constexpr (HBC) {
+      // The constrained reverse sweep reads the planes back and computes the point's factors for itself: there 1 - Y
+      // contracts into fma(-inv_len, eta - y0, 1), while above, beside the lift, where Y has other readers, it is
+      // 1 - round(Y).  The transpose takes the reverse sweep's factors, computed again from an opaque copy of the
+      // point, and the planes are opaque too, so that nothing of the map is contracted into the adjoints.
+      float xo = m ? a.x[pt] : 0.f, yo = m ? a.y[pt] : 0.f;
+      asm volatile("" : "+v"(xo), "+v"(yo));
+      asm volatile("" : "+v"(u), "+v"(v), "+v"(ux), "+v"(uy), "+v"(vx), "+v"(vy));
+      asm volatile("" : "+v"(eq1), "+v"(eq2), "+v"(eq3), "+v"(eq4));
+      hbt = hard_bc_point(a.hbc, xo, yo);
+    }
     float ww = m ? (a.w ? a.w[pt] : 1.f) : 0.f;
     float g1 = a.coef_eq[0] * ww * eq1, g2 = a.coef_eq[1] * ww * eq2, g3 = a.coef_eq[2] * ww * eq3;
     float g4 = a.e ? a.coef_eq[3] * ww * eq4 : 0.f;
@@ -133,8 +156,25 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     const float bsc = a.scale, bsc2 = a.scale * a.scale;
     float au = r1 * ux + r2 * vx + g4 * eq1;
     float av = r1 * uy + r2 * vy + g4 * eq2;
-    oc[0][0] = au; oc[0][1] = (r1 * u + r3) * bsc; oc[0][2] = (r1 * v) * bsc; oc[0][3] = -nub * r1 * bsc2;
-    oc[1][0] = av; oc[1][1] = (r2 * u) * bsc; oc[1][2] = (r2 * v + r3) * bsc; oc[1][3] = -nub * r2 * bsc2;
+    if constexpr (HBC) {                    // the adjoints of the constrained fields, pulled back to the net's streams
+      float aux = r1 * u + r3, auy = r1 * v, aud = -nub * r1;
+      float avx = r2 * u, avy = r2 * v + r3, avd = -nub * r2;
+      // The transpose's first sum, D a + D_X a_X + ..., starts with two products, and which of them is rounded by itself
+      // is the compiler's choice by use counts: bwd_split_kernel rounds D_X a_X, this kernel rounded D a.  The reverse
+      // sweep's pairing written out; the other three outputs are hard_bc_transpose's own.
+      float pu = hbt.Dx * aux, pv = hbt.Dx * avx;
+      asm volatile("" : "+v"(pu), "+v"(pv));
+      const float nu0 = fmaf(hbt.Dd, aud, fmaf(hbt.Dy, auy, fmaf(hbt.D, au, pu)));
+      const float nv0 = fmaf(hbt.Dd, avd, fmaf(hbt.Dy, avy, fmaf(hbt.D, av, pv)));
+      hard_bc_transpose(hbt, au, aux, auy, aud);
+      hard_bc_transpose(hbt, av, avx, avy, avd);
+      au = nu0; av = nv0;
+      oc[0][0] = au; oc[0][1] = aux * bsc; oc[0][2] = auy * bsc; oc[0][3] = aud * bsc2;
+      oc[1][0] = av; oc[1][1] = avx * bsc; oc[1][2] = avy * bsc; oc[1][3] = avd * bsc2;
+    } else {
+      oc[0][0] = au; oc[0][1] = (r1 * u + r3) * bsc; oc[0][2] = (r1 * v) * bsc; oc[0][3] = -nub * r1 * bsc2;
+      oc[1][0] = av; oc[1][1] = (r2 * u) * bsc; oc[1][2] = (r2 * v + r3) * bsc; oc[1][3] = -nub * r2 * bsc2;
+    }
     oc[2][0] = 0.f; oc[2][1] = r1 * bsc; oc[2][2] = r2 * bsc; oc[2][3] = 0.f;
     // opaque from here on, as the LDS values of bwd_bf16_split.hip are: the compiler then contracts the epilogue's dot
     // products of them as there (with the zeros and expressions visible it picked other fma pairings: 1-ulp gradients)
@@ -218,15 +258,16 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
 
 size_t fwdbwd_split_lds_bytes(int HP, int L) { (void)HP; return FusedLds<256>::bytes(L); }
 
-template <int HP, int TERMS>
+template <int HP, int TERMS, bool HBC = false>
 static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = FusedLds<HP>::bytes(a.L);
   if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT) || !spill_is(fa.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
+  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS, HBC>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
 }
 
 // residual mode, MSE seeds, role-split plan (HP = 256, SPILL_P24_COMPACT)
 int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(fa, a, grid, s) : launch_one<256, 1, true>(fa, a, grid, s);
   return terms == 3 ? launch_one<256, 3>(fa, a, grid, s) : launch_one<256, 1>(fa, a, grid, s);
 }

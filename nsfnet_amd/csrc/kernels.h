@@ -71,7 +71,7 @@ struct FwdArgs {
   int stagger;           // start offset unit (x 4096 cycles x (block*5 mod 8)); 0 = off
   int configure;         // 1: do not launch, only raise the kernel's dynamic-LDS limit (pinn_plan_create)
   Spill spill;           // the plan's S / Z-bar format (spill.h)
-  HardBc hbc;            // kind != 0: the 8-wave families launch their constrained instantiation
+  HardBc hbc;            // kind != 0: the 8-wave, role-split and fused families launch their constrained instantiation
 };
 
 struct BwdArgs {
