@@ -546,6 +546,58 @@ int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, 
 /* What the plan carries (kind 0 and zeros for an unconstrained plan). */
 int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out);
 
+/* ---- pseudo-time stepping of the residual loss, with device-held anchors ---------------
+ * Every point of a pseudo-time plan carries an anchor (u*, v*, p*): the field at that point when the anchors were last
+ * refreshed.  With the rates sigma = 1 / dtau >= 0 and sigma_p >= 0 (artificial compressibility) the residual term
+ * minimises
+ *   q1 = eq1 + sigma   (u - u*)
+ *   q2 = eq2 + sigma   (v - v*)
+ *   q3 = eq3 + sigma_p (p - p*)
+ *   eq4 = eq1 (u - 1/2) + eq2 (v - 1/2) - e        (ev flavour; on the STEADY eq1, eq2, unchanged)
+ *   loss_e = alpha_e / N  sum_i w_i (q1^2 + q2^2 + q3^2 + 0.1 eq4^2)
+ * eq1..eq3 the steady residuals; on a constrained plan u, v are the constrained fields.  For fixed anchors this is one
+ * backward-Euler step of the pseudo-transient equations; at u = u* it is the steady loss, so the steady solution is a
+ * fixed point.  The reverse sweep starts from (coef_k = coef_eq4[k], q_k rebuilt from the planes and the anchors)
+ *   g_k = coef_k w q_k (k = 1..3)     g4 = coef_4 w eq4
+ *   r1 = g1 + g4 (u - 1/2)     r2 = g2 + g4 (v - 1/2)     r3 = g3
+ *   adj(u) = r1 u_x + r2 v_x + g4 eq1 + sigma g1     adj(v) = r1 u_y + r2 v_y + g4 eq2 + sigma g2
+ *   adj(p value) = sigma_p g3
+ * every other output adjoint and ebar = -g4 as on any residual plan; on a constrained plan adj(u), adj(v) enter the
+ * transpose with the new terms included.  The field planes keep what every reader expects: EQ1..EQ4 the steady
+ * residuals, U, V, P the fields.  Loss sums 0..2 hold sum w q_k^2, slot 3 is unchanged.
+ * The term is a compile-time variant of the 8-wave kernel families (fwd / fwd_wide / fwd_bf16 / fwd_bf16_wide and
+ * their reverse sweeps), with and without hard walls; the role-split, wide role-split, fused and pipelined sweeps have
+ * none: a pseudo-time plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever the environment
+ * (PINN_HBC_SPLIT included) says, and pinn_plan_kernel reports the 8-wave names.  Any other plan runs what it ran
+ * before.
+ * pinn_plan_create_pseudo_time: a residual (4-stream) plan that launches the variant; bc as for
+ * pinn_plan_create_constrained (NULL or kind 0: no hard walls).
+ * pinn_plan_set_pseudo_time: anchor = [3][padded] fp32 on the device (planes u*, v*, p*; padded =
+ * pinn_plan_padded_points), 16-byte aligned; it stays the caller's.  The rates are launch constants of the residual
+ * calls that follow.  Refused: any other plan, a negative or non-finite rate, a NULL or misaligned anchor.  A residual
+ * call on a pseudo-time plan whose anchor is unset is refused (pinn_last_error).
+ * pinn_plan_pseudo_time: the rates the plan carries (0, 0 until set; refused on any other plan). */
+int pinn_plan_create_pseudo_time(pinn_net_t net, int64_t n_points, const pinn_hard_bc_t* bc, pinn_plan_t* out);
+int pinn_plan_set_pseudo_time(pinn_plan_t plan, const float* anchor, float sigma, float sigma_p);
+int pinn_plan_pseudo_time(pinn_plan_t plan, float* sigma, float* sigma_p);
+
+/* One launch per optimiser update: the record of the pseudo-time state and, on its cadence, the anchor refresh.
+ * fields = [PINN_FLD_COUNT][npad] planes of the last evaluation, anchor = [3][npad], both 16-byte aligned, npad >= n and
+ * a multiple of 4; w = [n] weights, 16-byte aligned, or NULL (= 1).  With du = u - u*, dv = v - v*, dp = p - p*, each
+ * in fp64 from the fp32 inputs, sums in a fixed order (no float atomics, bit-reproducible), record =
+ *   [0..2] sum w eq_k^2 (the steady sums)     [3] sum w (du^2 + dv^2)     [4] sum w dp^2
+ *   [5] max(|du|, |dv|), NaN-propagating      [6] updates since the last refresh, after this call     [7] refreshes made
+ * When record[6] + 1 >= every (every >= 1; 0: never), or force != 0, the anchors are overwritten with the current U, V,
+ * P (in whole quads of four points, up to the next multiple of 4 past n), [6] becomes 0 and [7] goes up by one;
+ * otherwise [6] goes up by one.  The condition is read from device memory at kernel entry: one captured launch serves a
+ * whole stage.  record: PINN_PTIME_RECORD doubles of device memory, zero before the first call, 8-byte aligned.
+ * scratch: pinn_ptime_scratch_bytes(n) bytes of device memory, 8-byte aligned, ZERO before the first call (the launch
+ * leaves its ticket word 0 again); -1 for n outside 1..2^30. */
+#define PINN_PTIME_RECORD 8
+int64_t pinn_ptime_scratch_bytes(int64_t n);
+int pinn_ptime_advance(int64_t n, const float* fields, int64_t npad, const float* w, float* anchor, int64_t every,
+                       int force, double* scratch, double* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

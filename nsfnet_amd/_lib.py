@@ -91,6 +91,12 @@ SIGNATURES = {
     "pinn_rwf_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_rwf_compose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_rwf_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_plan_create_pseudo_time": (c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(c_void_p)]),
+    "pinn_plan_set_pseudo_time": (c_int, [c_void_p, c_void_p, c_float, c_float]),
+    "pinn_plan_pseudo_time": (c_int, [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
+    "pinn_ptime_scratch_bytes": (c_int64, [c_int64]),
+    "pinn_ptime_advance": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                   c_void_p]),
 }
 
 

@@ -12,7 +12,7 @@
 #include "point_stage.h"
 #include "reduce_util.h"
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
   constexpr int NT = HP * 2;
   extern __shared__ float lds[];
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     // ---------------- output adjoints per column (point_stage.h) ----------------
     float px[4], py[4];
-    output_adjoint_stage<32, 128, NS, NT, 4, HBC>(a, tile, tid, col, col, npad, oadjL, dbo, px, py);
+    output_adjoint_stage<32, 128, NS, NT, 4, HBC, PT>(a, tile, tid, col, col, npad, oadjL, dbo, px, py);
     __syncthreads();
     // ---------------- adjoint of the last hidden layer's activations (3 -> HP, rank-3) ----------------
     f32x16 acc[4];
@@ -188,15 +188,16 @@ __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
 
 size_t bwd_lds_bytes(int HP, int L) { return ((size_t)HP * 128 + 4 * 128 + sg_total(HP, L)) * sizeof(float); }
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_lds_bytes(HP, a.L);
   if (!spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&bwd_kernel<HP, NS, HBC>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define BWD_CASE(hp)                                                        \
   case hp:                                                                  \
+    if (a.ptime && NS == 4) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
     if (a.hbc.kind && NS == 4) return launch_one<hp, 4, true>(a, grid, s);  \
     return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
 

@@ -10,7 +10,7 @@
 #include "point_stage.h"
 #include "wave8_bodies.h"
 
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false>
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     // ---------------- output adjoints per column (point_stage.h) ----------------
     float px[NTL], py[NTL];
-    output_adjoint_stage<PPL, COLS, NS, NT, NTL, HBC>(a, tile, tid, col, pp, npad, oadjL, dbo, px, py);
+    output_adjoint_stage<PPL, COLS, NS, NT, NTL, HBC, PT>(a, tile, tid, col, pp, npad, oadjL, dbo, px, py);
     __syncthreads();
     // ---------------- adjoint of the last hidden layer's activations (rank-3 update) ----------------
     f32x16 acc[NTL];
@@ -286,15 +286,19 @@ size_t bwd_bf16_lds_bytes(int HP, int L, int cols) {
 #undef LB
 }
 
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false>
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
   if (!spill_is(a.spill, act_block(HP, COLS), IN_CLASSIC)) return -1000;
-  return launch_or_configure(&bwd_bf16_kernel<HP, NS, TERMS, COLS, HBC>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_bf16_kernel<HP, NS, TERMS, COLS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const BwdArgs& a, int grid, hipStream_t s) {
+  if (a.ptime && NS == 4)
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, COLS, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, COLS, false, true>(a, grid, s);
+    });
   if (a.hbc.kind && NS == 4) return dispatch_ns_terms(4, terms, [&](auto, auto t) { return launch_one<HP, 4, decltype(t)::value, COLS, true>(a, grid, s); });
   return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS>(a, grid, s); });
 }

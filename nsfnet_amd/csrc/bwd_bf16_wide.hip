@@ -10,7 +10,7 @@
 #include "wave8_bodies.h"
 #include <type_traits>
 
-template <int HP, int NS, int TERMS, bool HBC = false>
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel(BwdArgs a) {
   constexpr int COLS = 64, PPL = 16, NTL = 2, MT = 2;
   using XI = XImg<HP, PPL>;
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     // ---------------- output adjoints per column (point_stage.h) ----------------
     float px[NTL], py[NTL];
-    output_adjoint_stage<PPL, COLS, NS, NT, NTL, HBC>(a, tile, tid, col, pp, npad, oadjL, dbo, px, py);
+    output_adjoint_stage<PPL, COLS, NS, NT, NTL, HBC, PT>(a, tile, tid, col, pp, npad, oadjL, dbo, px, py);
     __syncthreads();
     // ---------------- adjoint of the last hidden layer's activations (rank-3 update) ----------------
     f32x16 acc[MT][NTL];
@@ -287,15 +287,19 @@ size_t bwd_bf16_wide_lds_bytes(int HP, int L) {
   return XImg<512, 16>::BYTES + ((size_t)4 * 64 + sg_total(HP, L)) * sizeof(float);
 }
 
-template <int HP, int NS, int TERMS, bool HBC = false>
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   size_t lds = bwd_bf16_wide_lds_bytes(HP, a.L);
   if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&bwd_bf16_wide_kernel<HP, NS, TERMS, HBC>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_bf16_wide_kernel<HP, NS, TERMS, HBC, PT>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
 }
 
 template <int HP>
 static int launch_hp(int NS, int terms, const BwdArgs& a, int grid, hipStream_t s) {
+  if (a.ptime && NS == 4)
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, false, true>(a, grid, s);
+    });
   if (a.hbc.kind && NS == 4) return dispatch_ns_terms(4, terms, [&](auto, auto t) { return launch_one<HP, 4, decltype(t)::value, true>(a, grid, s); });
   return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value>(a, grid, s); });
 }

@@ -120,6 +120,9 @@ struct pinn_plan_s {
   Role role[ROLE_COUNT];
   Spill spill;           // how the sweeps spill S and Z-bar, and what their readers recompute instead (spill.h)
   HardBc hbc;            // hard wall conditions (kind 0: none); resolve_plan says which families a constrained plan runs
+  int ptime;             // a pseudo-time plan (pinn_plan_create_pseudo_time): the 8-wave families' pseudo-time variant
+  const float* anchor;   // its anchors [3][npad] (pinn_plan_set_pseudo_time; NULL: unset, residual calls are refused)
+  float sigma, sigma_p;  // its rates
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -218,18 +221,21 @@ static int run_fused(const pinn_plan_s* plan, const FwdArgs& fa, const BwdArgs& 
 // Resolves a plan: tiles, one Role per kernel role, the spill format and the workspace layout.  Pure host arithmetic
 // (no HIP call) on the net, the point and stream counts, the compute-unit count and the switches.
 static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw_in,
-                        const HardBc& hbc = HardBc{}) {
+                        const HardBc& hbc = HardBc{}, bool ptime = false) {
   // The 8-wave, role-split (hidden 256 and wide) and fused families have constrained point stages (point_stage.h); the
   // pipelined schedule has none.  By default a constrained plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
   // would.  With $PINN_HBC_SPLIT=1 it keeps what the other switches give it, except that a sweep which would run
   // the pipelined kernels (PINN_SCHED=1, an incomplete role-split pair, an fp32 dW) runs the 8-wave kernel instead.
   // Either way the spill format follows from the resolved families as for any other plan, and an unconstrained plan
   // never looks at the switch.
+  // The pseudo-time term has a variant in the 8-wave families only: a pseudo-time plan, constrained or not, resolves as
+  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever the switches (PINN_HBC_SPLIT included) say.
   Switches sw = sw_in;
-  const bool hbc_split = hbc.kind && sw.hbc_split != 0;
-  if (hbc.kind && !hbc_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
+  const bool hbc_split = hbc.kind && sw.hbc_split != 0 && !ptime;
+  if ((hbc.kind && !hbc_split) || ptime) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
   p->hbc = hbc;
+  p->ptime = ptime; p->anchor = nullptr; p->sigma = p->sigma_p = 0.f;
   p->n = n_points; p->streams = streams;
   const bool wide = net.wide != 0;
   const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
@@ -288,6 +294,8 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   const bool fuse = sf == 2 && sb == 2 && split_pair && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
                     fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
   p->stagger = sw.stagger;
+  if (sw.verbose && ptime)
+    fprintf(stderr, "[pinn] plan: pseudo-time stepping: 8-wave kernels (the role-split, fused and pipelined sweeps have no variant)\n");
   if (sw.verbose)
     fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
             (long)n_points, streams, HP, L, net.prec_fwd, net.prec_bwd, net.prec_dw, (int)wide, sf, sb);
@@ -354,6 +362,9 @@ static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.partials = WS(plan, off_partials);
   a.spill = plan->spill;
   a.hbc = plan->hbc;
+  if (plan->streams == 4) {     // (these share their bytes with the value-mode fields)
+    a.ptime = plan->ptime; a.anchor = plan->anchor; a.sigma = plan->sigma; a.sigma_p = plan->sigma_p;
+  }
   return a;
 }
 static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -374,6 +385,7 @@ static BwdArgs bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.sg = WS(plan, off_sg);
   a.spill = plan->spill;
   a.hbc = plan->hbc;
+  a.ptime = plan->ptime; a.anchor = plan->anchor; a.sigma = plan->sigma; a.sigma_p = plan->sigma_p;
   return a;
 }
 static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,
@@ -448,13 +460,13 @@ int pinn_net_prepare(pinn_net_t net, const float* params, float* prep, void* str
   return rc ? hipfail(rc, "pinn_net_prepare") : 0;
 }
 
-static int create_plan(pinn_net_t net, int64_t n_points, int streams, const HardBc& hbc, pinn_plan_t* out) {
+static int create_plan(pinn_net_t net, int64_t n_points, int streams, const HardBc& hbc, pinn_plan_t* out, bool ptime = false) {
   if (!net || !out) return fail(-22, "pinn_plan_create: null argument%s");
   if (streams != 1 && streams != 4) return fail(-22, "pinn_plan_create: streams must be 1 or 4%s");
   if (n_points < 1 || n_points > (int64_t)1 << 30) return fail(-22, "pinn_plan_create: bad point count %s%ld", "", (long)n_points);
   pinn_plan_s* p = new (std::nothrow) pinn_plan_s;
   if (!p) return fail(-12, "pinn_plan_create: out of host memory%s");
-  int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches(), hbc);
+  int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches(), hbc, ptime);
   if (rc) { delete p; return rc; }
   // The dynamic-LDS limit is per-device state of the HIP runtime and idempotent to raise; doing it here, per plan,
   // keeps the launch path free of cached "already configured" flags (no global mutable state; a process may drive
@@ -471,9 +483,8 @@ static int create_plan(pinn_net_t net, int64_t n_points, int streams, const Hard
 int pinn_plan_create(pinn_net_t net, int64_t n_points, int streams, pinn_plan_t* out) {
   return create_plan(net, n_points, streams, HardBc{}, out);
 }
-int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, const pinn_hard_bc_t* bc, pinn_plan_t* out) {
-  if (!bc || bc->kind == PINN_HARD_BC_NONE) return pinn_plan_create(net, n_points, streams, out);
-  if (!net || !out) return fail(-22, "pinn_plan_create_constrained: null argument%s");
+// the checked descriptor of pinn_plan_create_constrained / pinn_plan_create_pseudo_time (bc given, kind != 0)
+static int hard_bc_of(pinn_net_t net, const pinn_hard_bc_t* bc, HardBc* h_out) {
   if (bc->kind != PINN_HARD_BC_CAVITY) return fail(-22, "pinn_plan_create_constrained: unknown kind %s%ld", "", (long)bc->kind);
   if (net->n_out != 3) return fail(-22, "pinn_plan_create_constrained: only a (u, v, p) net (n_out = 3) can be constrained%s");
   if (bc->lift_power < 1 || bc->lift_power > 8)
@@ -486,7 +497,39 @@ int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, 
   HardBc h;
   h.kind = bc->kind; h.m = bc->lift_power; h.x0 = bc->x0; h.y0 = bc->y0; h.inv_len = bc->inv_len; h.r = bc->lid_sharpness;
   h.c = (float)(1.0 / std::cosh(0.5 * (double)bc->lid_sharpness));
+  *h_out = h;
+  return 0;
+}
+int pinn_plan_create_constrained(pinn_net_t net, int64_t n_points, int streams, const pinn_hard_bc_t* bc, pinn_plan_t* out) {
+  if (!bc || bc->kind == PINN_HARD_BC_NONE) return pinn_plan_create(net, n_points, streams, out);
+  if (!net || !out) return fail(-22, "pinn_plan_create_constrained: null argument%s");
+  HardBc h;
+  if (int rc = hard_bc_of(net, bc, &h)) return rc;
   return create_plan(net, n_points, streams, h, out);
+}
+int pinn_plan_create_pseudo_time(pinn_net_t net, int64_t n_points, const pinn_hard_bc_t* bc, pinn_plan_t* out) {
+  if (!net || !out) return fail(-22, "pinn_plan_create_pseudo_time: null argument%s");
+  if (net->n_out != 3) return fail(-22, "pinn_plan_create_pseudo_time: only a (u, v, p) net (n_out = 3) has a pseudo-time term%s");
+  HardBc h{};
+  if (bc && bc->kind != PINN_HARD_BC_NONE)
+    if (int rc = hard_bc_of(net, bc, &h)) return rc;
+  return create_plan(net, n_points, 4, h, out, true);
+}
+int pinn_plan_set_pseudo_time(pinn_plan_t plan, const float* anchor, float sigma, float sigma_p) {
+  if (!plan) return fail(-22, "pinn_plan_set_pseudo_time: null plan%s");
+  if (!plan->ptime) return fail(-22, "pinn_plan_set_pseudo_time: not a pseudo-time plan (pinn_plan_create_pseudo_time)%s");
+  if (!std::isfinite(sigma) || !std::isfinite(sigma_p) || sigma < 0.f || sigma_p < 0.f)
+    return fail(-22, "pinn_plan_set_pseudo_time: sigma and sigma_p must be finite and >= 0%s");
+  if (!anchor) return fail(-22, "pinn_plan_set_pseudo_time: null anchor%s");
+  if (reinterpret_cast<uintptr_t>(anchor) % 16 != 0) return fail(-22, "pinn_plan_set_pseudo_time: anchor must be 16-byte aligned%s");
+  plan->anchor = anchor; plan->sigma = sigma; plan->sigma_p = sigma_p;
+  return 0;
+}
+int pinn_plan_pseudo_time(pinn_plan_t plan, float* sigma, float* sigma_p) {
+  if (!plan || !sigma || !sigma_p) return fail(-22, "pinn_plan_pseudo_time: null argument%s");
+  if (!plan->ptime) return fail(-22, "pinn_plan_pseudo_time: not a pseudo-time plan (pinn_plan_create_pseudo_time)%s");
+  *sigma = plan->sigma; *sigma_p = plan->sigma_p;
+  return 0;
 }
 int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out) {
   if (!plan || !out) return fail(-22, "pinn_plan_hard_bc: null argument%s");
@@ -508,6 +551,8 @@ int64_t pinn_plan_workspace_bytes(pinn_plan_t plan, int with_backward) {
 // A constrained plan takes the net's scaled derivatives for derivatives in the unit cavity's X, Y: the coordinate scale of
 // the call must undo the plan's inv_len.
 static int check_hard_bc_scale(const char* what, const pinn_plan_s* plan, float coord_scale) {
+  if (plan->ptime && !plan->anchor)     // (every residual call comes through here)
+    return fail(-22, "%s: the plan's pseudo-time anchors are unset (pinn_plan_set_pseudo_time)", what);
   if (plan->hbc.kind && !(std::fabs((double)coord_scale * (double)plan->hbc.inv_len - 1.0) <= 1e-6))
     return fail(-22, "%s: coord_scale x inv_len of the plan's hard wall conditions must be 1", what);
   return 0;
@@ -1034,6 +1079,29 @@ int pinn_rwf_grad(pinn_net_t net, const float* theta, const float* grads, float*
     return fail(-22, "pinn_rwf_grad: gtheta must not overlap theta or grads%s");
   int rc = launch_rwf_grad(n, theta, grads, gtheta, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_rwf_grad") : 0;
+}
+
+int64_t pinn_ptime_scratch_bytes(int64_t n) {
+  return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)ptime_scratch_bytes((long)n);
+}
+
+int pinn_ptime_advance(int64_t n, const float* fields, int64_t npad, const float* w, float* anchor, int64_t every,
+                       int force, double* scratch, double* record, void* stream) {
+  static_assert(PINN_PTIME_RECORD == PTIME_RECORD, "pseudo-time record size mismatch");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_ptime_advance: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (!fields || !anchor || !scratch || !record) return fail(-22, "pinn_ptime_advance: null argument%s");
+  if (npad < n || npad % 4 != 0) return fail(-22, "pinn_ptime_advance: npad must be >= n and a multiple of 4%s");
+  if (every < 0) return fail(-22, "pinn_ptime_advance: every must be >= 0 (got %s%ld)", "", (long)every);
+  if (reinterpret_cast<uintptr_t>(fields) % 16 != 0 || reinterpret_cast<uintptr_t>(anchor) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(w) % 16 != 0)
+    return fail(-22, "pinn_ptime_advance: fields, anchor and w must be 16-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(scratch) % 8 != 0 || reinterpret_cast<uintptr_t>(record) % 8 != 0)
+    return fail(-22, "pinn_ptime_advance: scratch and record must be 8-byte aligned%s");
+  PtimeArgs a;
+  a.n = (long)n; a.npad = (long)npad; a.fld = fields; a.w = w; a.anchor = anchor;
+  a.every = (double)every; a.force = force != 0; a.scratch = scratch; a.record = record;
+  int rc = launch_ptime_advance(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_ptime_advance") : 0;
 }
 
 int64_t pinn_val_scratch_bytes(void) { return (int64_t)val_scratch_bytes(); }

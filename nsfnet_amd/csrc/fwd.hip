@@ -16,7 +16,7 @@
 #include "spill_io.h"
 #include "point_stage.h"
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
   constexpr int NW = HP / 32;
   constexpr int NT = HP * 2;
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
     }
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
-    if (NS == 4) residual_point_stage<32, 128, HBC>(a, outv, tile, tid, npad, lsum);
+    if (NS == 4) residual_point_stage<32, 128, HBC, PT>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<128, NT, HBC>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
@@ -172,15 +172,16 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
 
 size_t fwd_lds_bytes(int HP) { return ((size_t)HP * 128 + (size_t)(HP / 32) * 4 * 128 + 4 * 128) * sizeof(float); }
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_lds_bytes(HP);
   if (a.S && !spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_kernel<HP, NS, HBC>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define FWD_CASE(hp)                                                        \
   case hp:                                                                  \
+    if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
     if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
     return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
 

@@ -20,7 +20,7 @@
 // COLS = 64 : tile = 16 points x 4 streams (two streams per 32-column accumulator tile, exchanged
 //             with v_permlane16_swap before the lane-local epilogue); half the LDS and <= 128 VGPRs,
 //             so two workgroups share a CU and cover each other's epilogue / spill / MFMA phases.
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false>
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd_bf16_kernel(FwdArgs a) {
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
     out_sum<NS, PPL, NW>(part, outv, P + prep_bout(HP, L), tid);
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
-    if (NS == 4) residual_point_stage<PPL, COLS, HBC>(a, outv, tile, tid, npad, lsum);
+    if (NS == 4) residual_point_stage<PPL, COLS, HBC, PT>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<COLS, NT, HBC>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
@@ -290,15 +290,19 @@ size_t fwd_bf16_lds_bytes(int HP, int L, int cols) {
 #undef LB
 }
 
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false>
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
   if (a.S && !spill_is(a.spill, act_block(HP, COLS), IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS, HBC>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
+  if (NS == 4 && a.ptime)
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, COLS, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, COLS, false, true>(a, grid, s);
+    });
   if (a.hbc.kind) return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS, true>(a, grid, s); });
   return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS>(a, grid, s); });
 }

@@ -17,7 +17,7 @@
 #include "wave8_bodies.h"
 #include <type_traits>
 
-template <int HP, int NS, int TERMS, bool HBC = false>
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel(FwdArgs a) {
   constexpr int COLS = 64, PPL = 16, NTL = 2, MT = 2;
   using XI = XImg<HP, PPL>;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
     out_sum<NS, PPL, NWV>(part, outv, P + prep_bout(HP, L), tid);
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
-    if (NS == 4) residual_point_stage<PPL, COLS, HBC>(a, outv, tile, tid, npad, lsum);
+    if (NS == 4) residual_point_stage<PPL, COLS, HBC, PT>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<COLS, NT, HBC>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
@@ -278,15 +278,19 @@ size_t fwd_bf16_wide_lds_bytes(int HP, int L) {
 }
 int fwd_bf16_wide_threads(int HP) { return ((HP / 32 + 1) / 2) * 64; }
 
-template <int HP, int NS, int TERMS, bool HBC = false>
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP>(a.L);
   if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_bf16_wide_kernel<HP, NS, TERMS, HBC>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_bf16_wide_kernel<HP, NS, TERMS, HBC, PT>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
 }
 
 template <int HP>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
+  if (NS == 4 && a.ptime)
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, false, true>(a, grid, s);
+    });
   if (a.hbc.kind) return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, true>(a, grid, s); });
   return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value>(a, grid, s); });
 }

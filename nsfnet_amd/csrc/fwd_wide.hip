@@ -12,7 +12,7 @@
 #include "spill_io.h"
 #include "point_stage.h"
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
   constexpr int NW = HP / 32, NT = HP * 2, COLS = 64, PPL = 16, NQ = HP / 8;
   constexpr int PRE = 4, RING = 8;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
     }
     __syncthreads();
     // ---------------- per-point stage (point_stage.h) ----------------
-    if (NS == 4) residual_point_stage<PPL, COLS, HBC>(a, outv, tile, tid, npad, lsum);
+    if (NS == 4) residual_point_stage<PPL, COLS, HBC, PT>(a, outv, tile, tid, npad, lsum);
     else value_point_stage<COLS, NT, HBC>(a, outv, tile, tid, npad, lsum);
     __syncthreads();
   }
@@ -183,15 +183,16 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
 
 size_t fwd_wide_lds_bytes(int HP) { return ((size_t)HP * 64 + (size_t)(HP / 32) * 4 * 64 + 4 * 64) * sizeof(float); }
 
-template <int HP, int NS, bool HBC = false>
+template <int HP, int NS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_wide_lds_bytes(HP);
   if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_wide_kernel<HP, NS, HBC>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_wide_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define FWD_CASE(hp)                                                        \
   case hp:                                                                  \
+    if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
     if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
     return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
 

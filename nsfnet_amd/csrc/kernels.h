@@ -62,11 +62,22 @@ struct FwdArgs {
   float* vtm;       // vis_t_minus state (in/out) or null
   float* vis_used;  // artificial viscosity used this step (out) or null
   float inv_re, vis_t0, alpha_evm, scale;
-  // value mode (1 stream)
-  float* pred[3];        // optional prediction planes
-  const float* tgt[3];   // optional targets (NaN target = masked)
-  float* oadj;           // [4][npad] output adjoints (written when non-null)
-  float coef[3];         // oadj_c = coef[c] * (pred_c - tgt_c)
+  union {
+    struct {               // value mode (1 stream)
+      float* pred[3];        // optional prediction planes
+      const float* tgt[3];   // optional targets (NaN target = masked)
+      float* oadj;           // [4][npad] output adjoints (written when non-null)
+      float coef[3];         // oadj_c = coef[c] * (pred_c - tgt_c)
+    };
+    // Pseudo-time stepping (residual mode, 8-wave families; point_stage.h), in the bytes residual mode leaves unused:
+    // the block keeps its size and every other member its offset, so the kernels that do not read these are
+    // compiled as before.  The launchers read ptime in residual mode only (NS == 4).
+    struct {
+      const float* anchor;   // [3][npad] anchors u*, v*, p*
+      float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation
+      int ptime;             // != 0: launch the pseudo-time variant
+    };
+  };
   float* partials;       // [grid][PINN_NLOSS]
   int stagger;           // start offset unit (x 4096 cycles x (block*5 mod 8)); 0 = off
   int configure;         // 1: do not launch, only raise the kernel's dynamic-LDS limit (pinn_plan_create)
@@ -91,6 +102,10 @@ struct BwdArgs {
   int configure;         // see FwdArgs
   Spill spill;           // see FwdArgs
   HardBc hbc;            // see FwdArgs (residual mode; value mode takes adjoints that carry D already)
+  // pseudo-time stepping (residual mode, 8-wave families; point_stage.h): ptime != 0 launches the variant
+  int ptime;
+  const float* anchor;   // [3][npad] anchors u*, v*, p*
+  float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation
 };
 
 struct DwArgs {
@@ -305,6 +320,18 @@ struct ValKeepArgs {
   long n[2];
   const double* state;
 };
+// pseudo-time stepping: the per-update record and anchor refresh (ptime.hip)
+constexpr int PTIME_RECORD = 8;
+struct PtimeArgs {
+  long n, npad;                            // points; plane stride of fld and of anchor
+  const float* fld;                        // [FLD_COUNT][npad] field planes of the last evaluation
+  const float* w;                          // [n] weights (NULL: 1)
+  float* anchor;                           // [3][npad] u*, v*, p*
+  double every; int force;                 // refresh when record[6] + 1 >= every, or when force != 0
+  double *scratch, *record;
+};
+size_t ptime_scratch_bytes(long n);
+int launch_ptime_advance(const PtimeArgs& a, hipStream_t s);
 size_t val_scratch_bytes();
 int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s);

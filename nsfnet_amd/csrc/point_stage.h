@@ -47,7 +47,10 @@ __device__ __forceinline__ void hard_bc_transpose(const HardBcPoint& h, float& a
 
 // Residual mode: NS-residual assembly, lagged artificial viscosity, field planes, loss partial sums.
 // Replaces NSFnet/pinn_solver.py:132-163,212-222 and ev-NSFnet/pinn_solver.py:290-342,372-428.
-template <int PPL, int COLS, bool HBC = false>
+// PT = true (pseudo-time stepping, include/nsfnet_pinn.h "Pseudo-time stepping"): the loss sums 0..2 take the residuals
+// q1 = eq1 + sigma (u - u*), q2 = eq2 + sigma (v - v*), q3 = eq3 + sigma_p (p - p*) against the anchor planes
+// a.anchor = [3][npad]; the field planes keep the steady eq1..eq4, and eq4 is built on the steady eq1, eq2.
+template <int PPL, int COLS, bool HBC = false, bool PT = false>
 __device__ __forceinline__ void residual_point_stage(const FwdArgs& a, const float* outv, int tile, int tid, int npad,
                                                      float (&lsum)[4]) {
   if (tid >= PPL) return;
@@ -84,6 +87,12 @@ __device__ __forceinline__ void residual_point_stage(const FwdArgs& a, const flo
   f[FLD_P * (size_t)npad] = p;
   if (m) {
     float ww = a.w ? a.w[pt] : 1.f;
+    if constexpr (PT) {                   // (the planes above hold the steady residuals)
+      const float* an = a.anchor + pt;
+      eq1 += a.sigma * (u - an[0]);
+      eq2 += a.sigma * (v - an[(size_t)npad]);
+      eq3 += a.sigma_p * (p - an[2 * (size_t)npad]);
+    }
     lsum[0] += ww * eq1 * eq1; lsum[1] += ww * eq2 * eq2;
     lsum[2] += ww * eq3 * eq3; lsum[3] += ww * eq4 * eq4;
   }
@@ -135,7 +144,9 @@ __device__ __forceinline__ void value_point_stage(const FwdArgs& a, const float*
 // p_x, p_y) - what loss.backward() (NSFnet/pinn_solver.py:252, ev-NSFnet/pinn_solver.py:469) propagates into the
 // output layer; value mode copies the adjoints the value forward wrote.  px[j] / py[j]: point of column
 // 32 j + col (value mode) or of column pp (residual mode, j = 0).
-template <int PPL, int COLS, int NS, int NT, int NJ, bool HBC = false>
+// PT = true (residual mode only): the seeds of the pseudo-time residuals q_k, rebuilt from the planes and the anchors;
+// the field values take sigma g1, sigma g2 and - the one non-zero value adjoint of the pressure - sigma_p g3.
+template <int PPL, int COLS, int NS, int NT, int NJ, bool HBC = false, bool PT = false>
 __device__ __forceinline__ void output_adjoint_stage(const BwdArgs& a, int tile, int tid, int col, int pp, int npad,
                                                      float* oadjL, float (&dbo)[3], float (&px)[NJ], float (&py)[NJ]) {
   if (NS == 4) {
@@ -152,13 +163,24 @@ __device__ __forceinline__ void output_adjoint_stage(const BwdArgs& a, int tile,
       float eq1 = f[FLD_EQ1 * (size_t)npad], eq2 = f[FLD_EQ2 * (size_t)npad];
       float eq3 = f[FLD_EQ3 * (size_t)npad], eq4 = f[FLD_EQ4 * (size_t)npad];
       float ww = m ? (a.w ? a.w[pt] : 1.f) : 0.f;
-      float g1 = a.coef_eq[0] * ww * eq1, g2 = a.coef_eq[1] * ww * eq2, g3 = a.coef_eq[2] * ww * eq3;
+      float q1 = eq1, q2 = eq2, q3 = eq3;
+      if constexpr (PT) {
+        if (m) {
+          const float* an = a.anchor + pt;
+          q1 += a.sigma * (u - an[0]);
+          q2 += a.sigma * (v - an[(size_t)npad]);
+          q3 += a.sigma_p * (f[FLD_P * (size_t)npad] - an[2 * (size_t)npad]);
+        }
+      }
+      float g1 = a.coef_eq[0] * ww * q1, g2 = a.coef_eq[1] * ww * q2, g3 = a.coef_eq[2] * ww * q3;
       float g4 = a.e ? a.coef_eq[3] * ww * eq4 : 0.f;
       float r1 = g1 + g4 * (u - 0.5f), r2 = g2 + g4 * (v - 0.5f), r3 = g3;
       float nu = a.inv_re + ((a.vis_used && m) ? a.vis_used[pt] : 0.f);
       const float sc = a.scale, sc2 = a.scale * a.scale;
       float au = r1 * ux + r2 * vx + g4 * eq1;
       float av = r1 * uy + r2 * vy + g4 * eq2;
+      float ap = 0.f;
+      if constexpr (PT) { au += a.sigma * g1; av += a.sigma * g2; ap = a.sigma_p * g3; }
       if constexpr (HBC) {                  // the planes hold the constrained fields: their adjoints, pulled back to the net's
         const HardBcPoint hb = hard_bc_point(a.hbc, m ? a.x[pt] : 0.f, m ? a.y[pt] : 0.f);
         float aux = r1 * u + r3, auy = r1 * v, aud = -nu * r1;
@@ -183,12 +205,13 @@ __device__ __forceinline__ void output_adjoint_stage(const BwdArgs& a, int tile,
         oadjL[1 * COLS + 2 * PPL + tid] = (r2 * v + r3) * sc;
         oadjL[1 * COLS + 3 * PPL + tid] = -nu * r2 * sc2;
       }
-      oadjL[2 * COLS + 0 * PPL + tid] = 0.f;
+      oadjL[2 * COLS + 0 * PPL + tid] = ap;
       oadjL[2 * COLS + 1 * PPL + tid] = r1 * sc;
       oadjL[2 * COLS + 2 * PPL + tid] = r2 * sc;
       oadjL[2 * COLS + 3 * PPL + tid] = 0.f;
       if (a.ebar && m) a.ebar[pt] = -g4;
       dbo[0] += au; dbo[1] += av;
+      if constexpr (PT) dbo[2] += ap;
     }
   } else {
 #pragma unroll

@@ -139,6 +139,19 @@ class HardBoundaryConfig:
     lift_power: int = 2
 
 
+@dataclass
+class PseudoTimeConfig:
+    """Pseudo-time stepping of the equation loss with device-held anchors (PinnEngine.set_pseudo_time), off by default:
+    `training.pseudo_time: {enabled: true, dtau: 0.5, every: 100}`.  dtau: the pseudo-time step of the momentum
+    equations; every: optimiser updates between anchor refreshes; pressure_dtau: that of the continuity equation
+    (artificial compressibility), 0 = none.  None of them has a measured default.  Not together with resampling or
+    batching."""
+    enabled: bool = False
+    dtau: float = 1.0
+    every: int = 100
+    pressure_dtau: float = 0.0
+
+
 VALIDATION_METRICS = ("uv", "u", "v", "p", "p0")
 
 
@@ -180,6 +193,7 @@ class TrainingConfig:
     weight_factorization: WeightFactorizationConfig = field(default_factory=WeightFactorizationConfig)
     validation: ValidationConfig = field(default_factory=ValidationConfig)
     hard_boundary: HardBoundaryConfig = field(default_factory=HardBoundaryConfig)
+    pseudo_time: PseudoTimeConfig = field(default_factory=PseudoTimeConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -269,6 +283,11 @@ class ConfigManager:
         hb = c.training.hard_boundary
         if hb.enabled and not 1 <= hb.lift_power <= 8:
             problems.append("training.hard_boundary: lift_power in 1..8 required")
+        pt = c.training.pseudo_time
+        if pt.enabled and not (0.0 < pt.dtau < float("inf") and pt.every >= 1 and 0.0 <= pt.pressure_dtau < float("inf")):
+            problems.append("training.pseudo_time: finite dtau > 0, every >= 1 and finite pressure_dtau >= 0 required")
+        if pt.enabled and (c.training.resampling.enabled or c.training.batching.enabled):
+            problems.append("training.pseudo_time does not go together with training.resampling or training.batching")
         va = c.training.validation
         if va.enabled and (va.every < 1 or va.patience < 0 or va.metric not in VALIDATION_METRICS):
             problems.append("training.validation: every >= 1, patience >= 0 and metric one of %s required"
@@ -334,6 +353,9 @@ class ConfigManager:
                                                             t.weight_factorization.seed))
         if t.hard_boundary.enabled:
             print("hard walls : lift_power=%d" % t.hard_boundary.lift_power)
+        if t.pseudo_time.enabled:
+            print("pseudo-time: dtau=%s every=%d pressure_dtau=%s" % (t.pseudo_time.dtau, t.pseudo_time.every,
+                                                                      t.pseudo_time.pressure_dtau or None))
         if t.validation.enabled:
             print("validation : every=%d metric=%s keep_best=%s patience=%d"
                   % (t.validation.every, t.validation.metric, t.validation.keep_best, t.validation.patience))

@@ -88,6 +88,9 @@ def main():
         if hb.enabled:        # before any point set: every plan of the main net is then created constrained
             PINN.set_coordinate_transform(loader.get_coord_scale())
             PINN.set_hard_boundary_constraints(lift_power=hb.lift_power, dataloader=loader)
+        pt = cfg.training.pseudo_time
+        if pt.enabled:        # before the collocation set: its plan is then created with the pseudo-time term
+            PINN.set_pseudo_time_stepping(pt.dtau, pt.every, pressure_dtau=pt.pressure_dtau or None)
         PINN.set_boundary_data(X=loader.loading_boundary_data())
         if distributed:   # every rank must shard the SAME point set: rank 0 samples, the others receive
             pts = [loader.loading_training_data() + (loader.get_sdf_weights(),)] if rank == 0 else [None]

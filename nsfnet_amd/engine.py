@@ -243,7 +243,7 @@ class DeviceNet:
 class PointPlan:
     """A fixed set of points evaluated by one DeviceNet (residual or value mode)."""
 
-    def __init__(self, net, x, y, streams, with_backward=True, ws=None):
+    def __init__(self, net, x, y, streams, with_backward=True, ws=None, pseudo_time=False):
         self.lib, self.net, self.streams = net.lib, net, streams
         dev = net.device
         self.x = torch.as_tensor(np.asarray(x, dtype=np.float32).reshape(-1)).to(dev).contiguous()
@@ -253,7 +253,10 @@ class PointPlan:
             raise ValueError("x and y must be non-empty and of equal length")
         h = ctypes.c_void_p()
         bc = getattr(net, "hard_bc", None)
-        if bc is None:
+        if pseudo_time:     # pseudo-time stepping, with or without hard walls
+            _lib.check(self.lib.pinn_plan_create_pseudo_time(net.handle, self.n, None if bc is None else ctypes.byref(bc),
+                                                             ctypes.byref(h)), "pinn_plan_create_pseudo_time")
+        elif bc is None:
             _lib.check(self.lib.pinn_plan_create(net.handle, self.n, streams, ctypes.byref(h)), "pinn_plan_create")
         else:       # hard wall conditions
             _lib.check(self.lib.pinn_plan_create_constrained(net.handle, self.n, streams, ctypes.byref(bc), ctypes.byref(h)),
@@ -288,9 +291,10 @@ class PointPlan:
 
 
 class ResidualPlan(PointPlan):
-    def __init__(self, net, x, y, weights=None, with_backward=True, ws=None):
-        super().__init__(net, x, y, 4, with_backward, ws)
+    def __init__(self, net, x, y, weights=None, with_backward=True, ws=None, pseudo_time=False):
+        super().__init__(net, x, y, 4, with_backward, ws, pseudo_time)
         dev = net.device
+        self.anchor = None          # [3, npad] anchors u*, v*, p* of a pseudo-time plan (set_pseudo_time)
         self.fields = torch.zeros(FLD_COUNT, self.npad, dtype=torch.float32, device=dev)
         self.w = None if weights is None else torch.as_tensor(
             np.asarray(weights, dtype=np.float32).reshape(-1)).to(dev).contiguous()
@@ -335,6 +339,19 @@ class ResidualPlan(PointPlan):
 
     def field(self, name):
         return self.fields[FLD[name], :self.n]
+
+    def set_pseudo_time(self, sigma, sigma_p):
+        """Hand the anchors (allocated as zeros at the first call) and the rates to a pseudo-time plan."""
+        if self.anchor is None:
+            self.anchor = torch.zeros(3, self.npad, dtype=torch.float32, device=self.net.device)
+        _lib.check(self.lib.pinn_plan_set_pseudo_time(self.handle, _ptr(self.anchor), float(sigma), float(sigma_p)),
+                   "pinn_plan_set_pseudo_time")
+
+    def pseudo_time(self):
+        """(sigma, sigma_p) the plan carries."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _lib.check(self.lib.pinn_plan_pseudo_time(self.handle, ctypes.byref(a), ctypes.byref(b)), "pinn_plan_pseudo_time")
+        return float(a.value), float(b.value)
 
 
 class ChunkedResidual:
@@ -599,6 +616,25 @@ def rba_fill(init, s, lam, w):
                "pinn_rba_fill")
 
 
+PTIME_RECORD = 8         # PINN_PTIME_RECORD: [sum w eq1^2, eq2^2, eq3^2, sum w (du^2 + dv^2), sum w dp^2, max|du|,|dv|, since, refreshes]
+
+
+def ptime_scratch(n, device):
+    """Zeroed device scratch of ptime_advance for n points (the launch leaves its ticket word 0 again)."""
+    nbytes = int(_lib.load().pinn_ptime_scratch_bytes(int(n)))
+    if nbytes < 0:
+        raise ValueError("bad point count %d" % n)
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def ptime_advance(plan, every, force, scratch, record):
+    """pinn_ptime_advance over the planes the last evaluation of the pseudo-time ResidualPlan `plan` left: the record,
+    and the anchor refresh on its cadence (or forced).  One launch."""
+    _lib.check(_lib.load().pinn_ptime_advance(plan.n, _ptr(plan.fields), plan.npad, _ptr(plan.w), _ptr(plan.anchor),
+                                              int(every), 1 if force else 0, _ptr(scratch), _ptr(record), _stream()),
+               "pinn_ptime_advance")
+
+
 VAL_RECORD = 8           # PINN_VAL_RECORD: [t, e_u, e_v, e_p, e_p0, metric, improved, n_p]
 VAL_STATE = 8            # PINN_VAL_STATE: [n_records, best_metric, best_t, stale, nonfinite, improved, cadence records, 0]
 VAL_METRICS = dict(uv=0, u=1, v=2, p=3, p0=4)
@@ -826,6 +862,17 @@ class _Attention:
         self.n_eval = 0
 
 
+class _PseudoTime:
+    """State of the pseudo-time stepping (PinnEngine.set_pseudo_time): the launch constants here, anchors on the
+    collocation plan, scratch and record in device memory."""
+
+    def __init__(self, dtau, every, pressure_dtau):
+        self.dtau, self.pressure_dtau, self.every = dtau, pressure_dtau, every
+        self.sigma = 1.0 / dtau
+        self.sigma_p = 0.0 if pressure_dtau is None else 1.0 / pressure_dtau
+        self.scratch = self.record = None
+
+
 class _Optim:
     """State of the device learning-rate schedule and gradient clipping (set_lr_schedule / set_grad_clipping): the
     schedule (an LrSchedule; constant while only clipping is on) with its C struct, max_norm (0 = no clipping) and the
@@ -916,6 +963,7 @@ class PinnEngine:
         self._opt = None                    # device lr schedule / gradient clipping (set_lr_schedule, set_grad_clipping)
         self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
         self._val = None                    # device validation monitor (set_validation; None = off)
+        self._pt = None                     # pseudo-time stepping (set_pseudo_time; None = off)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -964,12 +1012,14 @@ class PinnEngine:
             raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points" % (bt.B, n))
         if self._rba is not None and chunk_points and n > int(chunk_points):
             raise ValueError("residual attention needs a resident store: chunk_points=%d with it on" % int(chunk_points))
+        if self._pt is not None and chunk_points and n > int(chunk_points):
+            raise ValueError("pseudo-time stepping needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         self._graphs.clear()      # captured steps hold the old plan's pointers
         self.lbfgs_reset()
         if chunk_points and n > int(chunk_points):
             self.plan_f = ChunkedResidual(self.net, x, y, weights, chunk_points)
         else:
-            self.plan_f = ResidualPlan(self.net, x, y, weights)
+            self.plan_f = ResidualPlan(self.net, x, y, weights, **({} if self._pt is None else dict(pseudo_time=True)))
         self.n_f_global = int(n_global if n_global is not None else self.plan_f.n)
         if self.net_e is not None:
             self.plan_e = ValuePlan(self.net_e, x, y)
@@ -979,6 +1029,8 @@ class PinnEngine:
             self._attach_attention()        # the new set starts at lam = init; its weights are the new s
         if bt is not None:
             self._make_batch_plans(bt)      # the store may have gained or lost its weights; the draw counter carries on
+        if self._pt is not None:
+            self._attach_pseudo_time()      # the new set starts anchored at the field of the current weights
 
     # ---- residual-based attention weights on the collocation points ----
     def set_residual_attention(self, eta=0.0, gamma=0.999, init=1.0):
@@ -1099,6 +1151,9 @@ class PinnEngine:
         B, seed = int(batch_points), int(seed)
         if B < 0:
             raise ValueError("mini-batching: batch_points must be >= 0")
+        if B > 0 and self._pt is not None:
+            raise ValueError("mini-batching is not available with pseudo-time stepping: the anchors live with the "
+                             "evaluated plan (store-level anchors and a gather are a follow-up)")
         if B > 0:
             if self.plan_f is None:
                 raise RuntimeError("set_batching() needs set_collocation() first")
@@ -1231,6 +1286,8 @@ class PinnEngine:
         vis_t_minus of a new point is alpha_evm |e|, what init_vis_t gives it.  Stream-ordered after the last step; one
         8-byte host read.  Returns the int64 pool indices (ascending, may repeat)."""
         f, pool = self.plan_f, self._pool
+        if self._pt is not None:
+            raise ValueError("resample() is not available with pseudo-time stepping: new points invalidate the anchors")
         if pool is None or f is None:
             raise RuntimeError("resample() needs set_collocation() and set_resample_pool() first")
         rba = self._rba              # on: the gather and the renormalisation work on the static weights s
@@ -1386,7 +1443,8 @@ class PinnEngine:
             raise ValueError("loss mode must be 'MSE' or 'L2' (got %r)" % (mode,))
         l2 = mode == "L2"
         for state, needs in ((self._bal, "loss balancing needs"), (self._cfg, "conflict-free gradients need"),
-                             (self._batch, "mini-batching needs"), (self._rba, "residual attention needs")):
+                             (self._batch, "mini-batching needs"), (self._rba, "residual attention needs"),
+                             (self._pt, "pseudo-time stepping needs")):
             if l2 and state is not None:
                 raise ValueError("%s the MSE loss (loss mode %r)" % (needs, mode))
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
@@ -1525,7 +1583,12 @@ class PinnEngine:
         """Device tensors (no sync): dict of loss_eq1..4, loss_e, loss_b, loss_s, loss of the sums of the last
         evaluation, in the loss mode it ran with.  The equation terms carry the per-point weights the evaluation
         used - with residual attention on, the effective weights s lam^2: they are what Adam minimises
-        (attention_info() has the unweighted ones)."""
+        (attention_info() has the unweighted ones).  With pseudo-time stepping on, loss_e (and loss_eq1..3) is the
+        minimised term, of the residuals q_k; loss_e_steady is the same sum over the steady residuals and drift is
+        (sum w ((u-u*)^2 + (v-v*)^2) + sum w (p-p*)^2) / N, both from the record the advance after the last update left,
+        in the normalisation of loss_e.  The record is per rank - nothing new is all-reduced - so with several ranks
+        these two are THIS rank's share of the global mean; before the first update they are those of the attached
+        weights: the steady term, and a drift of 0."""
         s = self.sums
         if mode == "L2":      # NSFnet/pinn_solver.py:202-204, 214-217
             eq = torch.sqrt(s[S_EQ:S_EQ + 4])
@@ -1542,6 +1605,11 @@ class PinnEngine:
             n_p = self._n_p_valid_global()
             loss_s = (s[S_SUP] + s[S_SUP + 1]) / self.n_s_global + (s[S_SUP + 2] / n_p if n_p > 0 else 0.0)
         out["loss_s"] = loss_s
+        if self._pt is not None:        # this rank's record of the last update (nothing new is all-reduced)
+            r = self._pt.record
+            out["loss_e_steady"] = (r[0] + r[1] + r[2]) / self.n_f_global + (
+                self.eq4_weight * eq[3].double() if self.net_e is not None else 0.0)
+            out["drift"] = (r[3] + r[4]) / self.n_f_global
         if self._bal is not None:
             lam = self._bal.lam
             out["loss"] = lam[0] * loss_b + self.alpha_e * loss_e + lam[1] * loss_s
@@ -1712,6 +1780,93 @@ class PinnEngine:
         return dict(lift_power=int(bc.lift_power), lid_sharpness=float(bc.lid_sharpness),
                     origin=(float(bc.x0), float(bc.y0)), inv_len=float(bc.inv_len))
 
+    # ---- pseudo-time stepping of the residual loss ----
+    def set_pseudo_time(self, dtau=None, every=0, pressure_dtau=None):
+        """dtau > 0 and every >= 1: pseudo-time stepping of the collocation term.  Every local collocation point carries
+        an anchor (u*, v*, p*) in device memory, the field there when the anchors were last refreshed, and the
+        residuals the term minimises become, with sigma = 1 / dtau and sigma_p = 1 / pressure_dtau (0 when None:
+        no artificial compressibility),
+            q1 = eq1 + sigma (u - u*),  q2 = eq2 + sigma (v - v*),  q3 = eq3 + sigma_p (p - p*),
+            loss_e = alpha_e / N sum_i w_i (q1^2 + q2^2 + q3^2 + eq4_weight eq4^2)
+        with eq4 (ev flavour) on the steady eq1, eq2 as before.  For fixed anchors that is one backward-Euler step of
+        the pseudo-transient equations; at u = u* it is the steady loss, so the steady solution is a fixed point.  The
+        field planes keep the steady residuals and the fields: resampling pools, residual attention, validation,
+        logging and the eq*_pred views read what they read without the feature.  With hard walls u, v are the
+        constrained fields.
+
+        After every optimiser update (an Adam step, or one lbfgs_step call; line-search evaluations never count) one
+        launch records, from the planes of the evaluation that update used, the steady sums, the drift
+        sum w ((u - u*)^2 + (v - v*)^2), sum w (p - p*)^2 and max(|u - u*|, |v - v*|), and on every `every`-th update
+        overwrites the anchors with those planes' U, V, P - the field one update old, the lag vis_t_minus has.  The
+        cadence is device state: the launch is part of the captured step.  The first anchor is the field of the
+        weights when set_collocation attaches the points; reset_pseudo_time() re-anchors at the current weights.
+        Anchors are not part of a checkpoint.
+
+        The collocation plan runs the 8-wave kernel families (as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would): the
+        role-split, fused and pipelined sweeps have no pseudo-time variant yet.  dtau, every and pressure_dtau have
+        no measured defaults: any value is a guess until the convergence runs exist.
+
+        Must be called before set_collocation (ValueError otherwise).  dtau None or every 0: off.  Refused with
+        ValueError: mini-batching, resample(), a chunked collocation set and the loss mode 'L2'."""
+        if self.plan_f is not None:
+            raise ValueError("pseudo-time stepping: call set_pseudo_time before set_collocation")
+        if dtau is None or not every:
+            if pressure_dtau is not None and dtau is None:
+                raise ValueError("pseudo-time stepping: pressure_dtau needs dtau")
+            self._pt = None
+            return
+        ev = int(every)
+        if ev != every or ev < 1:
+            raise ValueError("pseudo-time stepping: every must be an integer >= 0 (got %r)" % (every,))
+        for name, v in (("dtau", dtau), ("pressure_dtau", pressure_dtau)):
+            if v is not None and not (math.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError("pseudo-time stepping: %s must be finite and > 0 (got %r)" % (name, v))
+        if self._batch is not None:
+            raise ValueError("pseudo-time stepping is not available with mini-batching: the anchors live with the "
+                             "evaluated plan (store-level anchors and a gather are a follow-up)")
+        self._pt = _PseudoTime(float(dtau), ev, None if pressure_dtau is None else float(pressure_dtau))
+
+    def _attach_pseudo_time(self):
+        """Scratch and record for the new collocation plan, and its first anchors."""
+        pt, f = self._pt, self.plan_f
+        pt.scratch = ptime_scratch(f.n, self.device)
+        pt.record = torch.zeros(PTIME_RECORD, dtype=torch.float64, device=self.device)
+        self.reset_pseudo_time()
+        pt.record[3:6].zero_()      # (the forced advance measured the drift from the zero-initialised planes)
+
+    def reset_pseudo_time(self):
+        """Re-anchor at the current weights: one forward of the collocation plan with the rates at 0 (the fields do not
+        depend on the entropy net or the lagged viscosity: neither is read or advanced), then a forced advance.  The
+        record's refresh count goes up by one, its update count restarts at 0."""
+        pt, f = self._pt, self.plan_f
+        if pt is None or f is None:
+            raise RuntimeError("pseudo-time stepping is off, or no collocation set is attached")
+        f.set_pseudo_time(0.0, 0.0)
+        vtm, f.vis_t_minus = f.vis_t_minus, None
+        try:
+            f.forward(self.Re, scale=self.scale, save=False)
+        finally:
+            f.vis_t_minus = vtm
+        ptime_advance(f, pt.every, True, pt.scratch, pt.record)
+        f.set_pseudo_time(pt.sigma, pt.sigma_p)
+
+    def pseudo_time_info(self):
+        """dict(dtau, pressure_dtau, sigma, sigma_p, every, kernels, and - one host read of this rank's record -
+        steady_sums (sum w eq_k^2, k = 1..3), drift_uv, drift_p (sum w (u-u*)^2 + (v-v*)^2, sum w (p-p*)^2), max_drift,
+        since_refresh, refreshes); None when it is off.  The record entries are None before a collocation set is
+        attached."""
+        pt = self._pt
+        if pt is None:
+            return None
+        out = dict(dtau=pt.dtau, pressure_dtau=pt.pressure_dtau, sigma=pt.sigma, sigma_p=pt.sigma_p, every=pt.every,
+                   kernels=None if self.plan_f is None else self.plan_f.kernel_names() + ("ptime_advance_kernel",),
+                   steady_sums=None, drift_uv=None, drift_p=None, max_drift=None, since_refresh=None, refreshes=None)
+        if pt.record is not None:
+            r = pt.record.cpu().numpy()
+            out.update(steady_sums=tuple(float(v) for v in r[:3]), drift_uv=float(r[3]), drift_p=float(r[4]),
+                       max_drift=float(r[5]), since_refresh=int(r[6]), refreshes=int(r[7]))
+        return out
+
     # ---- device learning-rate schedule and gradient clipping (DESIGN.md section 7.6) ----
     def set_lr_schedule(self, spec=None):
         """spec = an LrSchedule: the Adam updates of step() and adam_step(lr) use the rate lr_e = spec.value(lr, e) of a
@@ -1837,6 +1992,8 @@ class PinnEngine:
 
     def _updated(self, validate=None):
         """An optimizer update is in place: count it, and validate when the cadence (or the caller) says so."""
+        if self._pt is not None:
+            ptime_advance(self.plan_f, self._pt.every, False, self._pt.scratch, self._pt.record)
         m = self._val
         if m is None:
             return
@@ -2019,6 +2176,7 @@ class PinnEngine:
                (False, 0.0, 0.0) if a is None else (True, a.gamma, a.eta))
         key += () if o is None else (o.spec.key(), o.max_norm)
         key += (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
+        key += () if self._pt is None else (("ptime", self._pt.sigma, self._pt.sigma_p, self._pt.every),)
         v = self._val
         return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 

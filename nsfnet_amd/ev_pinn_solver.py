@@ -399,6 +399,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
                 self.engine.batch_info()["batch_points"], self.x_f.shape[0]))
         if self._attention:
             print('  ' + self._attention_log())
+        if self._pseudo_time:
+            print('  ' + self._pseudo_time_log())
         if self.supervision_total_points > 0 and self.alpha_s != 0.0:
             print('  supervision: loss=%.3e alpha=%.3g samples_total=%d local=%d' % (
                 float(self.loss_s), self.alpha_s, self.supervision_total_points, self.supervision_point_count))

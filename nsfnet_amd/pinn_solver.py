@@ -67,6 +67,7 @@ class SolverBase:
     _lr0 = None                 # the base rate of the running Adam stage while a device schedule is on
     _validation = False
     _val_patience = 0           # set_validation_data(patience=k): a stage ends at a log point with stale >= k
+    _pseudo_time = False
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -128,6 +129,29 @@ class SolverBase:
         a = self.engine.attention_info()
         return "attention lam: min=%.3e mean=%.3e max=%.3e  unweighted loss_e=%.3e" % (
             a["lam_min"], a["lam_mean"], a["lam_max"], a["loss_e"])
+
+    def set_pseudo_time_stepping(self, dtau=None, every=0, pressure_dtau=None):
+        """dtau > 0 and every >= 1: pseudo-time stepping of the equation loss (PinnEngine.set_pseudo_time; DESIGN.md
+        section 7.11).  Every collocation point of this rank carries an anchor (u*, v*, p*) on the device, the
+        momentum residuals gain (u - u*) / dtau and (v - v*) / dtau, the continuity residual (p - p*) / pressure_dtau
+        (None: nothing), and after every `every` optimiser updates (Adam steps, L-BFGS calls) the anchors are refreshed
+        from the current field.  Call it before set_eq_training_data (ValueError afterwards).  The loss terms published
+        and logged are those the optimiser minimises; print_log adds the steady equation loss and the drift.  The
+        anchors are not saved: load() re-anchors at the loaded weights.  Not together with mini-batching, resampling or
+        chunked passes.  dtau, every and pressure_dtau have no measured defaults.  dtau None or every 0: off."""
+        self.engine.set_pseudo_time(dtau, every, pressure_dtau)
+        self._pseudo_time = self.engine.pseudo_time_info() is not None
+
+    def _pseudo_time_log(self):
+        """The print_log suffix of the pseudo-time stepping (one host read, at log points only): this rank's record of
+        the last update."""
+        i = self.engine.pseudo_time_info()
+        if i["steady_sums"] is None:
+            return "pseudo-time: no collocation set yet"
+        n = max(self.engine.n_f_global, 1)
+        return ("pseudo-time (dtau=%g every=%d): steady loss_e(eq1..3)=%.3e drift_uv=%.3e drift_p=%.3e max|du|=%.3e "
+                "since refresh=%d refreshes=%d" % (i["dtau"], i["every"], sum(i["steady_sums"]) / n, i["drift_uv"] / n,
+                                                   i["drift_p"] / n, i["max_drift"], i["since_refresh"], i["refreshes"]))
 
     def set_lr_schedule(self, spec=None):
         """spec = an nsfnet_amd.schedule.LrSchedule: every Adam stage (train / solve_Adam) that is not given a
@@ -281,6 +305,8 @@ class SolverBase:
                 except ValueError as err:
                     raise ValueError("checkpoint %s was trained with hard wall conditions %r, this solver holds %r: %s"
                                      % (path, bc, self.engine.hard_boundary_info(), err))
+        if self._pseudo_time and self.engine.plan_f is not None:       # anchors are not checkpointed
+            self.engine.reset_pseudo_time()
 
     def _begin_adam_stage(self, scheduler):
         """Resolve solve_Adam's scheduler= argument.  An LrSchedule, or a torch.optim.lr_scheduler object of type
@@ -543,6 +569,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("(losses of the last batch of %d points)" % self.engine.batch_info()["batch_points"],)
                 if self._batching and self.engine.evaluated_batch else ()),
               *(("\n" + self._attention_log(),) if self._attention else ()),
+              *(("\n" + self._pseudo_time_log(),) if self._pseudo_time else ()),
               *(("\n" + self._confgrad_log(),) if self._confgrad else ()),
               *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()),
               *(("\n" + self.validation_log(),) if self._validation else ()))

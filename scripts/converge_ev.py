@@ -75,6 +75,11 @@ def main():
     ap.add_argument("--hard-bc", type=int, nargs="?", const=2, default=0, metavar="M",
                     help="hard wall conditions by the output transform u = g + D N_u, v = D N_v with lift power M "
                          "(default 2; DESIGN.md 7.10); a resumed slice must be given the same M")
+    ap.add_argument("--pseudo-time", type=float, nargs=2, default=None, metavar=("DTAU", "EVERY"),
+                    help="pseudo-time stepping of the equation loss: step DTAU, anchors refreshed every EVERY updates "
+                         "(DESIGN.md 7.11); not with --resample-every or --batch-points")
+    ap.add_argument("--pressure-dtau", type=float, default=0.0,
+                    help="with --pseudo-time: the pseudo-time step of the continuity equation (0: none)")
     ap.add_argument("--validate-every", type=int, default=0,
                     help="> 0: validate against the DNS field on the device every this many updates of a stage and keep "
                          "the stage's best weights (DESIGN.md 7.9)")
@@ -100,6 +105,8 @@ def main():
     if a.hard_bc:                                       # before any point set is attached
         P.set_coordinate_transform(loader.get_coord_scale())
         P.set_hard_boundary_constraints(lift_power=a.hard_bc, dataloader=loader)
+    if a.pseudo_time is not None:                       # before the collocation set is attached
+        P.set_pseudo_time_stepping(a.pseudo_time[0], int(a.pseudo_time[1]), pressure_dtau=a.pressure_dtau or None)
     P.set_boundary_data(X=loader.loading_boundary_data())
     xf, yf = loader.loading_training_data()
     P.set_coordinate_transform(loader.get_coord_scale())
