@@ -566,10 +566,16 @@ int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out);
  * transpose with the new terms included.  The field planes keep what every reader expects: EQ1..EQ4 the steady
  * residuals, U, V, P the fields.  Loss sums 0..2 hold sum w q_k^2, slot 3 is unchanged.
  * The term is a compile-time variant of the 8-wave kernel families (fwd / fwd_wide / fwd_bf16 / fwd_bf16_wide and
- * their reverse sweeps), with and without hard walls; the role-split, wide role-split, fused and pipelined sweeps have
- * none: a pseudo-time plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever the environment
- * (PINN_HBC_SPLIT included) says, and pinn_plan_kernel reports the 8-wave names.  Any other plan runs what it ran
- * before.
+ * their reverse sweeps), of the role-split sweeps (fwd_split / bwd_split / fwdbwd_split at hidden 256, fwd_wsplit /
+ * bwd_wsplit at hidden 288 .. 448), with and without hard walls; the pipelined sweeps have none.  By default a
+ * pseudo-time plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever the environment says, and
+ * pinn_plan_kernel reports the 8-wave names.  With PINN_PTIME_SPLIT=1 in the environment when the plan is created it
+ * keeps the role-split, wide role-split and fused sweeps that PINN_SCHED, PINN_FWD_SCHED, PINN_BWD_SCHED, PINN_WSPLIT
+ * and PINN_FUSE give a plain plan - the same names, workspace bytes and padded points - except that a sweep which would
+ * run the pipelined kernels (PINN_SCHED=1, one role-split sweep without the other, an fp32 dW) runs the 8-wave kernel
+ * instead; the fused kernel computes bit for bit what the two launches compute.  Forward-only calls (save = 0) run the
+ * 8-wave variant either way.  A pseudo-time plan never looks at PINN_HBC_SPLIT (with walls, PINN_PTIME_SPLIT alone
+ * decides), and no other plan looks at PINN_PTIME_SPLIT: any other plan runs what it ran before.
  * pinn_plan_create_pseudo_time: a residual (4-stream) plan that launches the variant; bc as for
  * pinn_plan_create_constrained (NULL or kind 0: no hard walls).
  * pinn_plan_set_pseudo_time: anchor = [3][padded] fp32 on the device (planes u*, v*, p*; padded =

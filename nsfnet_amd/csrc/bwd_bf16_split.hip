@@ -25,7 +25,7 @@ struct SplitBwdLds {
   static size_t bytes(int L) { return X_BYTES + (OADJ_F + DUMMY_F + 6 * HP + (size_t)sg_total(HP, L)) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
   using G = SplitBwdLds<HP>;
   using SW = SplitWave<HP, TERMS>;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
     const int col = lane0 & 31;
     if (tile < a.ntiles) {
       float pxa[1], pya[1];
-      output_adjoint_stage<PPL, COLS, 4, GT, 1, HBC>(a, tile, gtid, col, col, npad, oadjG, dbo, pxa, pya);
+      output_adjoint_stage<PPL, COLS, 4, GT, 1, HBC, PT>(a, tile, gtid, col, col, npad, oadjG, dbo, pxa, pya);
       px = pxa[0]; py = pya[0];
     } else {
       for (int i = gtid; i < 3 * COLS; i += GT) oadjG[i] = 0.f;
@@ -113,16 +113,20 @@ __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
 
 size_t bwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitBwdLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitBwdLds<HP>::bytes(a.L);
   if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&bwd_split_kernel<HP, TERMS, HBC>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 
 // residual mode, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_bwd_split(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (a.ptime) {
+    if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(a, grid, s) : launch_one<256, 1, true, true>(a, grid, s);
+    return terms == 3 ? launch_one<256, 3, false, true>(a, grid, s) : launch_one<256, 1, false, true>(a, grid, s);
+  }
   if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(a, grid, s) : launch_one<256, 1, true>(a, grid, s);
   return terms == 3 ? launch_one<256, 3>(a, grid, s) : launch_one<256, 1>(a, grid, s);
 }

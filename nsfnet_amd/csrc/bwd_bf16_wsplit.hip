@@ -12,7 +12,7 @@
 #include "point_stage.h"
 #include "wsplit_phases.h"
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
   using SW = WSplitWave<HP, TERMS>;
   constexpr int GT = 256, MQ = SW::MQ, PPL = SW::PPL, COLS = SW::COLS;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
     const int col = lane0 & 31;
     if (tile < a.ntiles) {
       float pxa[1], pya[1];
-      output_adjoint_stage<PPL, COLS, 4, GT, 1, HBC>(a, tile, gtid, col, col & 15, npad, oadjG, dbo, pxa, pya);
+      output_adjoint_stage<PPL, COLS, 4, GT, 1, HBC, PT>(a, tile, gtid, col, col & 15, npad, oadjG, dbo, pxa, pya);
       px = pxa[0]; py = pya[0];
     } else {
       for (int i = gtid; i < 3 * COLS; i += GT) oadjG[i] = 0.f;
@@ -93,17 +93,21 @@ size_t bwd_wsplit_lds_bytes(int HP, int L) {
   return wsplit_width(HP, (size_t)1 << 30, [&](auto hp) { return WSplitWave<decltype(hp)::value, 3>::bwd_bytes(L); });
 }
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::bwd_bytes(a.L);
   if (!spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
-  return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS, HBC>, dim3(grid), dim3(512), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, 24-bit spill, L >= 2 hidden layers (the caller checks)
 int launch_bwd_wsplit(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
   return wsplit_width(HP, -1000, [&](auto hp) {
     constexpr int H = decltype(hp)::value;
+    if (a.ptime) {
+      if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true, true>(a, grid, s) : launch_one<H, 1, true, true>(a, grid, s);
+      return terms == 3 ? launch_one<H, 3, false, true>(a, grid, s) : launch_one<H, 1, false, true>(a, grid, s);
+    }
     if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true>(a, grid, s) : launch_one<H, 1, true>(a, grid, s);
     return terms == 3 ? launch_one<H, 3>(a, grid, s) : launch_one<H, 1>(a, grid, s);
   });

@@ -33,6 +33,7 @@ struct Switches {
   int verbose;            // $PINN_VERBOSE
   int tile_cols;          // $PINN_TILE_COLS = 64 | 128 overrides pick_wide (hidden 128 / 256 only)
   int hbc_split;          // $PINN_HBC_SPLIT (default 0; 1: a constrained plan may take the role-split / fused sweeps)
+  int ptime_split;        // $PINN_PTIME_SPLIT (default 0; 1: a pseudo-time plan may take the role-split / fused sweeps)
 };
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -42,7 +43,8 @@ static Switches read_switches() {
   const int sched = env_int("PINN_SCHED", 2);
   return {env_int("PINN_FWD_SCHED", sched), env_int("PINN_BWD_SCHED", sched), env_int("PINN_WSPLIT", 1),
           env_int("PINN_FUSE", 1), env_int("PINN_STAGGER", 0), env_int("PINN_S0_SKIP32", 1),
-          env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0), env_int("PINN_HBC_SPLIT", 0)};
+          env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0), env_int("PINN_HBC_SPLIT", 0),
+          env_int("PINN_PTIME_SPLIT", 0)};
 }
 
 // precision of a kernel family: 0 = fp32-input MFMA (exact fp32), 1 = bf16x3 split, 2 = plain bf16
@@ -120,7 +122,7 @@ struct pinn_plan_s {
   Role role[ROLE_COUNT];
   Spill spill;           // how the sweeps spill S and Z-bar, and what their readers recompute instead (spill.h)
   HardBc hbc;            // hard wall conditions (kind 0: none); resolve_plan says which families a constrained plan runs
-  int ptime;             // a pseudo-time plan (pinn_plan_create_pseudo_time): the 8-wave families' pseudo-time variant
+  int ptime;             // a pseudo-time plan (pinn_plan_create_pseudo_time); resolve_plan says which families it runs
   const float* anchor;   // its anchors [3][npad] (pinn_plan_set_pseudo_time; NULL: unset, residual calls are refused)
   float sigma, sigma_p;  // its rates
   // workspace offsets in bytes
@@ -228,11 +230,13 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // the pipelined kernels (PINN_SCHED=1, an incomplete role-split pair, an fp32 dW) runs the 8-wave kernel instead.
   // Either way the spill format follows from the resolved families as for any other plan, and an unconstrained plan
   // never looks at the switch.
-  // The pseudo-time term has a variant in the 8-wave families only: a pseudo-time plan, constrained or not, resolves as
-  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever the switches (PINN_HBC_SPLIT included) say.
+  // The pseudo-time term has a variant in the same families, with and without walls, and none in the pipelined
+  // schedule.  By default a pseudo-time plan, constrained or not, resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
+  // would; $PINN_PTIME_SPLIT=1 is to it what $PINN_HBC_SPLIT=1 is to a constrained plan.  A pseudo-time plan never
+  // looks at PINN_HBC_SPLIT, and no other plan looks at PINN_PTIME_SPLIT.
   Switches sw = sw_in;
-  const bool hbc_split = hbc.kind && sw.hbc_split != 0 && !ptime;
-  if ((hbc.kind && !hbc_split) || ptime) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
+  const bool keep_split = ptime ? sw.ptime_split != 0 : hbc.kind && sw.hbc_split != 0;
+  if ((hbc.kind || ptime) && !keep_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
   p->hbc = hbc;
   p->ptime = ptime; p->anchor = nullptr; p->sigma = p->sigma_p = 0.f;
@@ -282,7 +286,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // one of them alone runs that sweep on schedule 1.
   const bool split_pair = sf == 2 && sb == 2 && net.prec_dw;
   if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
-  if (hbc.kind) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained variant)
+  if (hbc.kind || ptime) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained or pseudo-time variant)
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
   const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
@@ -294,8 +298,6 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   const bool fuse = sf == 2 && sb == 2 && split_pair && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
                     fwdbwd_split_lds_bytes(HP, L) <= PINN_LDS_MAX;
   p->stagger = sw.stagger;
-  if (sw.verbose && ptime)
-    fprintf(stderr, "[pinn] plan: pseudo-time stepping: 8-wave kernels (the role-split, fused and pipelined sweeps have no variant)\n");
   if (sw.verbose)
     fprintf(stderr, "[pinn] plan: %ld pts, %d streams, HP %d, L %d, prec %d/%d/%d, wide %d, schedule fwd %d bwd %d\n",
             (long)n_points, streams, HP, L, net.prec_fwd, net.prec_bwd, net.prec_dw, (int)wide, sf, sb);
@@ -306,6 +308,10 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
     fprintf(stderr, "[pinn] plan: constrained sweeps: %s (PINN_HBC_SPLIT=%d)\n",
             fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
             sw.hbc_split);
+  if (sw.verbose && ptime)
+    fprintf(stderr, "[pinn] plan: pseudo-time sweeps: %s (PINN_PTIME_SPLIT=%d)\n",
+            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
+            sw.ptime_split);
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);

@@ -40,7 +40,7 @@ struct SplitLds {
   static size_t bytes(int L) { return X_BYTES + (PART_F + OUTV_F + (size_t)L * HP + 6 * HP) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
   using G = SplitLds<HP>;
   using SW = SplitWave<HP, TERMS>;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
         outvG[c3 * COLS + cc] = s;
       }
     }
-    if (ptile >= 0 && ptile < a.ntiles && q == 1) residual_point_stage<PPL, COLS, HBC>(a, outvG, ptile, gtid, npad, lsum);
+    if (ptile >= 0 && ptile < a.ntiles && q == 1) residual_point_stage<PPL, COLS, HBC, PT>(a, outvG, ptile, gtid, npad, lsum);
   };
   auto bias = [&](int l) {      // bias rows from LDS
     return [=](int, int, int o, int) { return *reinterpret_cast<const f32x4*>(biasL + (size_t)l * HP + o); };
@@ -124,16 +124,20 @@ __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
 
 size_t fwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitLds<HP>::bytes(a.L);
   if (a.S && !spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&fwd_split_kernel<HP, TERMS, HBC>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_fwd_split(int HP, int terms, const FwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (a.ptime) {
+    if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(a, grid, s) : launch_one<256, 1, true, true>(a, grid, s);
+    return terms == 3 ? launch_one<256, 3, false, true>(a, grid, s) : launch_one<256, 1, false, true>(a, grid, s);
+  }
   if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(a, grid, s) : launch_one<256, 1, true>(a, grid, s);
   return terms == 3 ? launch_one<256, 3>(a, grid, s) : launch_one<256, 1>(a, grid, s);
 }

@@ -28,7 +28,7 @@
 #include "point_stage.h"
 #include "wsplit_phases.h"
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
   using SW = WSplitWave<HP, TERMS>;
   constexpr int GT = 256, MQ = SW::MQ, PPL = SW::PPL, COLS = SW::COLS;
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
         outvG[c3 * COLS + cc] = s;
       }
     }
-    if (ptile >= 0 && ptile < a.ntiles && q == 1) residual_point_stage<PPL, COLS, HBC>(a, outvG, ptile, gtid, npad, lsum);
+    if (ptile >= 0 && ptile < a.ntiles && q == 1) residual_point_stage<PPL, COLS, HBC, PT>(a, outvG, ptile, gtid, npad, lsum);
   };
   auto S_of = [&](int tile, int l) { return a.S + spill_off<act_block(HP, COLS), 0>(a.spill, tile, l, L); };
   auto none = [](auto&&...) {};      // no kernel work in this hook
@@ -107,17 +107,21 @@ size_t fwd_wsplit_lds_bytes(int HP) {
   return wsplit_width(HP, (size_t)1 << 30, [](auto hp) { return WSplitWave<decltype(hp)::value, 3>::fwd_bytes(); });
 }
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::fwd_bytes();
   if (a.S && !spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
-  return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS, HBC>, dim3(grid), dim3(512), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations in the 24-bit format, L >= 2 hidden layers (the caller checks)
 int launch_fwd_wsplit(int HP, int terms, const FwdArgs& a, int grid, hipStream_t s) {
   return wsplit_width(HP, -1000, [&](auto hp) {
     constexpr int H = decltype(hp)::value;
+    if (a.ptime) {
+      if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true, true>(a, grid, s) : launch_one<H, 1, true, true>(a, grid, s);
+      return terms == 3 ? launch_one<H, 3, false, true>(a, grid, s) : launch_one<H, 1, false, true>(a, grid, s);
+    }
     if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true>(a, grid, s) : launch_one<H, 1, true>(a, grid, s);
     return terms == 3 ? launch_one<H, 3>(a, grid, s) : launch_one<H, 1>(a, grid, s);
   });

@@ -26,6 +26,11 @@
 // Hard wall conditions (HBC): XB's point stage runs the output map and its transpose of point_stage.h
 // on the lane's column, exactly where residual_point_stage / output_adjoint_stage run them in the two launches; the
 // descriptor rides in the kernel arguments, so the LDS budget is the unconstrained one.
+//
+// Pseudo-time stepping (PT): every lane reads the three anchor values of its column from global memory
+// (no LDS is left for them).  As the two launches do, XB builds the residuals q_k twice: for the loss sums from the
+// registers of the forward, and for the seeds from opaque copies of the values the reverse sweep would read back from
+// the planes.  The planes keep the steady residuals.
 #include "kernels.h"
 #include "point_stage.h"
 #include "split_phases.h"
@@ -38,7 +43,7 @@ struct FusedLds {
   static size_t bytes(int L) { return X_BYTES + (PART_F + 6 * HP + (size_t)sg_total(HP, L)) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, BwdArgs a) {
   using G = FusedLds<HP>;
   using SW = SplitWave<HP, TERMS>;
@@ -103,6 +108,10 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     float u = ov[0][0], ux = ov[0][1] * sc, uy = ov[0][2] * sc, ud = ov[0][3] * sc2;
     float v = ov[1][0], vx = ov[1][1] * sc, vy = ov[1][2] * sc, vd = ov[1][3] * sc2;
     float p = ov[2][0], pxx = ov[2][1] * sc, pyy = ov[2][2] * sc;
+    float an0 = 0.f, an1 = 0.f, an2 = 0.f;  // the column's anchors u*, v*, p*
+    if constexpr (PT) {
+      if (m) { an0 = fa.anchor[pt]; an1 = fa.anchor[(size_t)npad + pt]; an2 = fa.anchor[2 * (size_t)npad + pt]; }
+    }
     HardBcPoint hb = {};
     if constexpr (HBC) {                    // hard wall conditions (point_stage.h): a masked or dummy column has D = 0
       hb = hard_bc_point(fa.hbc, m ? a.x[pt] : 0.f, m ? a.y[pt] : 0.f);
@@ -131,8 +140,15 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
       f[FLD_P * (size_t)npad] = p;
       if (m) {
         float ww = fa.w ? fa.w[pt] : 1.f;
-        lsum[0] += ww * eq1 * eq1; lsum[1] += ww * eq2 * eq2;
-        lsum[2] += ww * eq3 * eq3; lsum[3] += ww * eq4 * eq4;
+        if constexpr (PT) {                 // (the planes above hold the steady residuals)
+          const float q1 = eq1 + fa.sigma * (u - an0), q2 = eq2 + fa.sigma * (v - an1);
+          const float q3 = eq3 + fa.sigma_p * (p - an2);
+          lsum[0] += ww * q1 * q1; lsum[1] += ww * q2 * q2;
+          lsum[2] += ww * q3 * q3; lsum[3] += ww * eq4 * eq4;
+        } else {
+          lsum[0] += ww * eq1 * eq1; lsum[1] += ww * eq2 * eq2;
+          lsum[2] += ww * eq3 * eq3; lsum[3] += ww * eq4 * eq4;
+        }
       }
     }
     // output adjoints (point_stage.h output_adjoint_stage, residual mode) from the values above instead of the field planes
@@ -149,13 +165,38 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
       hbt = hard_bc_point(a.hbc, xo, yo);
     }
     float ww = m ? (a.w ? a.w[pt] : 1.f) : 0.f;
-    float g1 = a.coef_eq[0] * ww * eq1, g2 = a.coef_eq[1] * ww * eq2, g3 = a.coef_eq[2] * ww * eq3;
+    float q1 = eq1, q2 = eq2, q3 = eq3;
+    if constexpr (PT) {
+      // The reverse sweep rebuilds q_k from the planes and the anchors: opaque copies, so that nothing of the forward's
+      // expressions above is shared with or contracted into the seeds.
+      asm volatile("" : "+v"(u), "+v"(v), "+v"(ux), "+v"(uy), "+v"(vx), "+v"(vy));
+      asm volatile("" : "+v"(eq1), "+v"(eq2), "+v"(eq3), "+v"(eq4), "+v"(p));
+      asm volatile("" : "+v"(an0), "+v"(an1), "+v"(an2));
+      q1 = eq1; q2 = eq2; q3 = eq3;
+      if (m) {
+        q1 += a.sigma * (u - an0);
+        q2 += a.sigma * (v - an1);
+        q3 += a.sigma_p * (p - an2);
+      }
+    }
+    float g1 = a.coef_eq[0] * ww * q1, g2 = a.coef_eq[1] * ww * q2, g3 = a.coef_eq[2] * ww * q3;
     float g4 = a.e ? a.coef_eq[3] * ww * eq4 : 0.f;
     float r1 = g1 + g4 * (u - 0.5f), r2 = g2 + g4 * (v - 0.5f), r3 = g3;
     float nub = a.inv_re + ((a.vis_used && m) ? vt : 0.f);
     const float bsc = a.scale, bsc2 = a.scale * a.scale;
     float au = r1 * ux + r2 * vx + g4 * eq1;
     float av = r1 * uy + r2 * vy + g4 * eq2;
+    float ap = 0.f;
+    if constexpr (PT) {
+      // r1 u_x + r2 v_x starts with two products, and which of them is rounded by itself is the compiler's choice:
+      // bwd_split_kernel rounds r1 u_x, this kernel rounded r2 v_x (1-ulp gradients).  The reverse sweep's pairing
+      // written out, with the pseudo-time term last as there.
+      float pu = r1 * ux, pv = r1 * uy;
+      asm volatile("" : "+v"(pu), "+v"(pv));
+      au = fmaf(a.sigma, g1, fmaf(g4, eq1, fmaf(r2, vx, pu)));
+      av = fmaf(a.sigma, g2, fmaf(g4, eq2, fmaf(r2, vy, pv)));
+      ap = a.sigma_p * g3;
+    }
     if constexpr (HBC) {                    // the adjoints of the constrained fields, pulled back to the net's streams
       float aux = r1 * u + r3, auy = r1 * v, aud = -nub * r1;
       float avx = r2 * u, avy = r2 * v + r3, avd = -nub * r2;
@@ -175,7 +216,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
       oc[0][0] = au; oc[0][1] = (r1 * u + r3) * bsc; oc[0][2] = (r1 * v) * bsc; oc[0][3] = -nub * r1 * bsc2;
       oc[1][0] = av; oc[1][1] = (r2 * u) * bsc; oc[1][2] = (r2 * v + r3) * bsc; oc[1][3] = -nub * r2 * bsc2;
     }
-    oc[2][0] = 0.f; oc[2][1] = r1 * bsc; oc[2][2] = r2 * bsc; oc[2][3] = 0.f;
+    oc[2][0] = ap; oc[2][1] = r1 * bsc; oc[2][2] = r2 * bsc; oc[2][3] = 0.f;
     // opaque from here on, as the LDS values of bwd_bf16_split.hip are: the compiler then contracts the epilogue's dot
     // products of them as there (with the zeros and expressions visible it picked other fma pairings: 1-ulp gradients)
 #pragma unroll
@@ -185,6 +226,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     if (owner) {
       if (a.ebar && m) a.ebar[pt] = -g4;
       dbo[0] += au; dbo[1] += av;
+      if constexpr (PT) dbo[2] += ap;
     }
   };
 
@@ -258,16 +300,20 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
 
 size_t fwdbwd_split_lds_bytes(int HP, int L) { (void)HP; return FusedLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false>
 static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = FusedLds<HP>::bytes(a.L);
   if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT) || !spill_is(fa.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS, HBC>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
+  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
 }
 
 // residual mode, MSE seeds, role-split plan (HP = 256, SPILL_P24_COMPACT)
 int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (fa.ptime) {
+    if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(fa, a, grid, s) : launch_one<256, 1, true, true>(fa, a, grid, s);
+    return terms == 3 ? launch_one<256, 3, false, true>(fa, a, grid, s) : launch_one<256, 1, false, true>(fa, a, grid, s);
+  }
   if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(fa, a, grid, s) : launch_one<256, 1, true>(fa, a, grid, s);
   return terms == 3 ? launch_one<256, 3>(fa, a, grid, s) : launch_one<256, 1>(fa, a, grid, s);
 }

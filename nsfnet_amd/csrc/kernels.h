@@ -69,7 +69,7 @@ struct FwdArgs {
       float* oadj;           // [4][npad] output adjoints (written when non-null)
       float coef[3];         // oadj_c = coef[c] * (pred_c - tgt_c)
     };
-    // Pseudo-time stepping (residual mode, 8-wave families; point_stage.h), in the bytes residual mode leaves unused:
+    // Pseudo-time stepping (residual mode; 8-wave, role-split and fused families; point_stage.h), in the bytes residual mode leaves unused:
     // the block keeps its size and every other member its offset, so the kernels that do not read these are
     // compiled as before.  The launchers read ptime in residual mode only (NS == 4).
     struct {
@@ -102,7 +102,7 @@ struct BwdArgs {
   int configure;         // see FwdArgs
   Spill spill;           // see FwdArgs
   HardBc hbc;            // see FwdArgs (residual mode; value mode takes adjoints that carry D already)
-  // pseudo-time stepping (residual mode, 8-wave families; point_stage.h): ptime != 0 launches the variant
+  // pseudo-time stepping (residual mode; 8-wave, role-split and fused families; point_stage.h): ptime != 0 launches the variant
   int ptime;
   const float* anchor;   // [3][npad] anchors u*, v*, p*
   float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation

@@ -1802,9 +1802,12 @@ class PinnEngine:
         weights when set_collocation attaches the points; reset_pseudo_time() re-anchors at the current weights.
         Anchors are not part of a checkpoint.
 
-        The collocation plan runs the 8-wave kernel families (as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would): the
-        role-split, fused and pipelined sweeps have no pseudo-time variant yet.  dtau, every and pressure_dtau have
-        no measured defaults: any value is a guess until the convergence runs exist.
+        By default the collocation plan runs the 8-wave kernel families (as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
+        would).  With PINN_PTIME_SPLIT=1 in the environment when set_collocation creates the plan it keeps the
+        role-split, wide role-split and fused sweeps the other switches choose, in their pseudo-time variants; the
+        pipelined schedule has none, and a sweep that would run it runs the 8-wave kernel (pseudo_time_info()["kernels"]
+        names what the plan launches).  dtau, every and pressure_dtau have no measured defaults: any value is a guess
+        until the convergence runs exist.
 
         Must be called before set_collocation (ValueError otherwise).  dtau None or every 0: off.  Refused with
         ValueError: mini-batching, resample(), a chunked collocation set and the loss mode 'L2'."""

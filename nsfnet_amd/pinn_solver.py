@@ -138,7 +138,9 @@ class SolverBase:
         from the current field.  Call it before set_eq_training_data (ValueError afterwards).  The loss terms published
         and logged are those the optimiser minimises; print_log adds the steady equation loss and the drift.  The
         anchors are not saved: load() re-anchors at the loaded weights.  Not together with mini-batching, resampling or
-        chunked passes.  dtau, every and pressure_dtau have no measured defaults.  dtau None or every 0: off."""
+        chunked passes.  By default the collocation plan runs the 8-wave kernel families; PINN_PTIME_SPLIT=1 in the
+        environment when the data are attached keeps the role-split, wide role-split and fused sweeps, in their
+        pseudo-time variants.  dtau, every and pressure_dtau have no measured defaults.  dtau None or every 0: off."""
         self.engine.set_pseudo_time(dtau, every, pressure_dtau)
         self._pseudo_time = self.engine.pseudo_time_info() is not None
 
