@@ -24,14 +24,23 @@ FLD_U, FLD_V, FLD_EQ1, FLD_EQ2, FLD_EQ3, FLD_P, FLD_COUNT = 0, 1, 6, 7, 8, 10, 1
 RECORD = 8
 R_STEADY, R_DRIFT_UV, R_DRIFT_P, R_MAX, R_SINCE, R_REFRESHES = 0, 3, 4, 5, 6, 7
 THREADS, PER, MAX_BLOCKS = 256, 4, 512
+# the places the pseudo-time term is written out in a point stage, each a separate place to go wrong (residual_term's
+# `errors`): the drift sigma_k (c_k - c_k*) as it enters the loss sums (fwd_q*), as the reverse sweep rebuilds it for
+# g_k (bwd_q*), the value seeds sigma g1, sigma g2, sigma_p g3 (seed_*), and eq4 built on q1, q2 (eq4_on_q, boolean)
+FORWARD_TERMS = ("fwd_q1", "fwd_q2", "fwd_q3")
+REVERSE_TERMS = ("bwd_q1", "bwd_q2", "bwd_q3")
+SEED_TERMS = ("seed_u", "seed_v", "seed_p")
+TERMS = FORWARD_TERMS + REVERSE_TERMS + SEED_TERMS + ("eq4_on_q",)
 
 
 def residual_term(params, x, y, Re, anchor, sigma, sigma_p, alpha_e=1.0, vis_t=None, e=None, w=None, scale=1.0,
-                  eq4_weight=0.1, bc=None, params_e=None, chunk=8192):
+                  eq4_weight=0.1, bc=None, params_e=None, chunk=8192, errors=None):
     """The pseudo-time residual term and its gradient.  params: fr.unflatten's pairs; anchor [3, N] (u*, v*, p*); bc: a
     hardbc_model.HardBc (u, v are then the constrained fields) or None; params_e: the entropy net (e defaults to its
     output and grad_e is its gradient); the other arguments as fr.pde_loss_and_grad.  In passes of <= chunk points, each
-    normalised by the global N.  Returns dict(fields: u, v, p, u_x, u_y, v_x, v_y; eqs: the steady eq1..eq3[, eq4];
+    normalised by the global N.  errors: {term of TERMS: factor} - that term alone is multiplied by the factor (0 drops
+    it, 1 + 2^-8 is one dropped bf16 term), or eq4_on_q=True: eq4 and its seeds on q1, q2, the mistake the header warns
+    of; None changes no bit of any result.  q is always the exact one.  Returns dict(fields: u, v, p, u_x, u_y, v_x, v_y; eqs: the steady eq1..eq3[, eq4];
     q: q1..q3; sums: sum w q_k^2 (k = 1..3)[, sum w eq4^2]; steady_sums: sum w eq_k^2 (k = 1..3); loss_e; grad[,
     grad_e])."""
     x = np.asarray(x, dtype=np.float64).reshape(-1)
@@ -42,6 +51,10 @@ def residual_term(params, x, y, Re, anchor, sigma, sigma_p, alpha_e=1.0, vis_t=N
     opt = lambda a, lo, hi: None if a is None else np.asarray(a, dtype=np.float64).reshape(-1)[lo:hi]
     cw = [1.0, 1.0, 1.0, eq4_weight]
     rates = (float(sigma), float(sigma), float(sigma_p))
+    er = {} if errors is None else dict(errors)
+    assert set(er) <= set(TERMS), sorted(set(er) - set(TERMS))
+    fac = lambda t: float(er.get(t, 1.0))
+    on_q = bool(er.get("eq4_on_q", False))
     sums, steady, grad, grad_e, eqs_all, q_all, flds = None, None, None, None, [], [], []
     for lo in range(0, N, int(chunk)):
         hi = min(N, lo + int(chunk))
@@ -61,20 +74,31 @@ def residual_term(params, x, y, Re, anchor, sigma, sigma_p, alpha_e=1.0, vis_t=N
         vt = opt(vis_t, lo, hi)
         eqs = fr.residuals(con, Re, vt, ek, 1.0)
         ww = np.ones(hi - lo) if w is None else opt(w, lo, hi)
-        q = [eqs[k] + rates[k] * (con[:, k, 0] - anchor[k, lo:hi]) for k in range(3)]
+        drift = [rates[k] * (con[:, k, 0] - anchor[k, lo:hi]) for k in range(3)]
+        q = [eqs[k] + drift[k] for k in range(3)]
+        u, v = con[:, 0, 0], con[:, 1, 0]
+        if on_q and len(eqs) == 4:
+            eqs[3] = q[0] * (u - 0.5) + q[1] * (v - 0.5) - np.asarray(ek).reshape(-1)
         mins = q + eqs[3:]                                      # what the loss squares
+        mins_b = mins                                           # ... and what the reverse sweep rebuilds for g_k
+        if er:
+            mins = [eqs[k] + fac(FORWARD_TERMS[k]) * drift[k] for k in range(3)] + eqs[3:]
+            mins_b = [eqs[k] + fac(REVERSE_TERMS[k]) * drift[k] for k in range(3)] + eqs[3:]
         ps = np.array([float(np.sum(ww * r * r)) for r in mins])
         st = np.array([float(np.sum(ww * r * r)) for r in eqs[:3]])
-        g = [2.0 * alpha_e * cw[k] * ww * mins[k] / N for k in range(len(mins))]
-        u, v = con[:, 0, 0], con[:, 1, 0]
+        g = [2.0 * alpha_e * cw[k] * ww * mins_b[k] / N for k in range(len(mins_b))]
         nu = 1.0 / Re + (0.0 if vt is None else vt)
         ev_on = len(eqs) == 4
         g4 = g[3] if ev_on else np.zeros(hi - lo)
         r1, r2, r3 = g[0] + g4 * (u - 0.5), g[1] + g4 * (v - 0.5), g[2]
         adj = np.zeros_like(con)
-        adj[:, 0, 0] = r1 * con[:, 0, 1] + r2 * con[:, 1, 1] + (g4 * eqs[0] if ev_on else 0.0) + rates[0] * g[0]
-        adj[:, 1, 0] = r1 * con[:, 0, 2] + r2 * con[:, 1, 2] + (g4 * eqs[1] if ev_on else 0.0) + rates[1] * g[1]
-        adj[:, 2, 0] = rates[2] * g[2]
+        e1, e2, s1, s2g = (q[0], q[1], r1, r2) if on_q else (eqs[0], eqs[1], g[0], g[1])
+        seed = [rates[0] * s1, rates[1] * s2g, rates[2] * g[2]]
+        if er:
+            seed = [fac(SEED_TERMS[k]) * seed[k] for k in range(3)]
+        adj[:, 0, 0] = r1 * con[:, 0, 1] + r2 * con[:, 1, 1] + (g4 * e1 if ev_on else 0.0) + seed[0]
+        adj[:, 1, 0] = r1 * con[:, 0, 2] + r2 * con[:, 1, 2] + (g4 * e2 if ev_on else 0.0) + seed[1]
+        adj[:, 2, 0] = seed[2]
         adj[:, 0, 1], adj[:, 0, 2], adj[:, 0, 3] = r1 * u + r3, r1 * v, -nu * r1
         adj[:, 1, 1], adj[:, 1, 2], adj[:, 1, 3] = r2 * u, r2 * v + r3, -nu * r2
         adj[:, 2, 1], adj[:, 2, 2] = r1, r2

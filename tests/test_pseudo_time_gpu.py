@@ -4,7 +4,7 @@ independently seeded net and rates at 1x and 10x the balanced ones (ptime_model.
 steady residuals and the pseudo-time terms carry weight.  Bars, those of tests/test_hardbc_gpu.py:
                                    fp32     bf16x3
   steady planes, max-abs / max|ref|  2e-5     5e-4       (fields, derivatives, eq1..eq4; unscaled)
-  loss, relative                     1e-5     1e-4       x max(1, A)
+  loss, relative                     1e-5     1e-4       x max(1, A)      (and each of the sums w q_k^2 alone)
   gradient, relative L2              1e-4     1e-4       x max(1, A)
 A = max_k (max|eq_k| + sigma_k max|c_k|) / max|q_k| (ptime_model.amplification) is the first-order growth of q's error
 from the cancellation in eq + sigma (c - c*); the test asserts A <= 8 on the model alone.  Then: zero rates equal the
@@ -189,6 +189,7 @@ def test_loss_and_gradient_match_the_fp64_model(L, H, N, prec, extra, kernels, m
     sums = E.sums.cpu().numpy().astype(np.float64)
     for k in range(3):
         print("sum w q%d^2: relative error %.3e" % (k + 1, abs(sums[k] - r["sums"][k]) / r["sums"][k]))
+        assert abs(sums[k] - r["sums"][k]) < bar["loss"] * grow * r["sums"][k], k
     lt = E.loss_terms()
     loss, want = float(lt["loss"]), c.loss_v + r["loss_e"]
     print("loss %.9e (model %.9e): relative error %.3e, bar %.3e" % (loss, want, abs(loss - want) / want, bar["loss"] * grow))

@@ -4,8 +4,8 @@ fwd_wsplit / bwd_wsplit (hidden 288 .. 448), with and without hard walls.
 
 They run the point-stage expressions of point_stage.h that the 8-wave pseudo-time kernels run, so the method and the
 bars are those of tests/test_pseudo_time_gpu.py, imported from it (_problem, _engine, BARS) - no bar here is new:
-bf16x3 steady planes 5e-4 unscaled, loss 1e-4 and gradient 1e-4 each times max(1, A), with A <= 8 and "the pseudo-time
-terms carry weight" asserted on the fp64 model alone.  Anchors: the fields of an independently seeded net; rates: 1x
+bf16x3 steady planes 5e-4 unscaled, loss (and each sum w q_k^2 alone) 1e-4 and gradient 1e-4 each times max(1, A),
+with A <= 8 and "the pseudo-time terms carry weight" asserted on the fp64 model alone.  Anchors: the fields of an independently seeded net; rates: 1x
 and 10x ptime_model.balanced_rates.  One row departs: 2x400 with walls runs at 1x and 2x, because at 10x the MODEL has
 A = 15.4 (3x: 10.4, 2x: 7.2; the same at every point count tried from 37 to 200, and 11.0 at 3x400, 9.3 at 3x330):
 with the lid's lift max|u| is 1 while q1 stays small, so the cancellation measure grows with the rate.  The bound
@@ -152,6 +152,7 @@ def test_loss_and_gradient_match_the_fp64_model(monkeypatch, capfd, L, H, N, ext
     sums = E.sums.cpu().numpy().astype(np.float64)
     for k in range(3):
         print("sum w q%d^2: relative error %.3e" % (k + 1, abs(sums[k] - r["sums"][k]) / r["sums"][k]))
+        assert abs(sums[k] - r["sums"][k]) < bar["loss"] * grow * r["sums"][k], k
     lt = E.loss_terms()
     loss, want = float(lt["loss"]), c.loss_v + r["loss_e"]
     print("loss %.9e (model %.9e): relative error %.3e, bar %.3e" % (loss, want, abs(loss - want) / want, bar["loss"] * grow))
