@@ -604,6 +604,34 @@ int64_t pinn_ptime_scratch_bytes(int64_t n);
 int pinn_ptime_advance(int64_t n, const float* fields, int64_t npad, const float* w, float* anchor, int64_t every,
                        int force, double* scratch, double* record, void* stream);
 
+/* ---- training-state snapshots: many device buffers <-> one staging buffer, with digests ----
+ * A snapshot is a list of segments (any number; a launch takes up to 64, more take several launches).  In the staging
+ * buffer segment k starts at align256(end of the segment stored before it) and the padding behind a segment is zero,
+ * so two snapshots of one state are the same bytes.  Every segment size is a multiple of 4 (others are refused).
+ * The digest of a segment reads its bytes as little-endian 32-bit words w_0 .. w_{n-1}:
+ *   A = sum w_i mod 2^64      B = sum (i + 1) w_i mod 2^64
+ * - modular integer sums, independent of order and grid.  float32 [1..8] gives (8648654848, 39057358848).
+ * pinn_state_layout: host only; offsets_out[k] for the sizes bytes[k] (a segment that is not stored is given size 0
+ *   here), returns the total size, -1 on a bad size.
+ * pinn_state_digest_host: host only; the digest of host memory into out2 = (A, B) - what verifies a file before
+ *   anything is uploaded.
+ * pinn_state_pack: copies the device buffers src[k] (bytes[k] each, 4-byte aligned) to dst + offsets[k], zeroes the
+ *   padding behind each (up to the next multiple of 256 or the end of dst) and writes the digests (A, B) of segment k to digests_out[2 k], [2 k + 1] (device memory).
+ *   offsets[k] = -1: digest only - src[k] is read and digested, nothing is stored.  The offsets must ascend, be multiples
+ *   of 256 and stay inside dst_bytes (all checked before anything is launched); dst 16-byte aligned.
+ * pinn_state_unpack: the reverse scatter from src + offsets[k] into the live buffers dst[k]; the digests are those of
+ *   what it wrote.  offsets[k] = -1: dst[k] is digested as it stands, nothing is written.
+ * Accesses are 16 bytes wide where both pointers of a segment are 16-byte aligned, 4 bytes otherwise.
+ * scratch: pinn_state_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (a launch
+ * leaves its ticket word 0 again); calls that share it must be ordered on one stream. */
+int64_t pinn_state_scratch_bytes(void);
+int64_t pinn_state_layout(int nseg, const int64_t* bytes, int64_t* offsets_out);
+int pinn_state_digest_host(const void* ptr, int64_t bytes, uint64_t* out2);
+int pinn_state_pack(int nseg, const void* const* src, const int64_t* bytes, const int64_t* offsets, void* dst, int64_t dst_bytes,
+                    uint64_t* digests_out, void* scratch, void* stream);
+int pinn_state_unpack(int nseg, const void* src, int64_t src_bytes, const int64_t* bytes, const int64_t* offsets, void* const* dst,
+                      uint64_t* digests_out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

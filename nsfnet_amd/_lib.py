@@ -97,6 +97,13 @@ SIGNATURES = {
     "pinn_ptime_scratch_bytes": (c_int64, [c_int64]),
     "pinn_ptime_advance": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                    c_void_p]),
+    "pinn_state_scratch_bytes": (c_int64, []),
+    "pinn_state_layout": (c_int64, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "pinn_state_digest_host": (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_uint64)]),
+    "pinn_state_pack": (c_int, [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p,
+                                c_int64, c_void_p, c_void_p, c_void_p]),
+    "pinn_state_unpack": (c_int, [c_int, c_void_p, c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                                  ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -1155,4 +1155,89 @@ int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1,
   return rc ? hipfail(rc, "pinn_val_keep") : 0;
 }
 
+
+// ---- training-state snapshots (state.hip) ----
+int64_t pinn_state_scratch_bytes(void) { return (int64_t)state_scratch_bytes(); }
+
+int64_t pinn_state_layout(int nseg, const int64_t* bytes, int64_t* offsets_out) {
+  if (nseg < 0 || (nseg > 0 && (!bytes || !offsets_out))) { fail(-22, "pinn_state_layout: bad argument%s"); return -1; }
+  int64_t end = 0;
+  for (int k = 0; k < nseg; ++k) {
+    if (bytes[k] < 0 || bytes[k] % 4 != 0 || bytes[k] > (int64_t)1 << 46) {
+      fail(-22, "pinn_state_layout: a segment size must be a multiple of 4 in 0..2^46 (got %s%ld)", "", (long)bytes[k]);
+      return -1;
+    }
+    offsets_out[k] = end = (end + 255) / 256 * 256;
+    end += bytes[k];
+  }
+  return end;
+}
+
+int pinn_state_digest_host(const void* ptr, int64_t bytes, uint64_t* out2) {
+  if (bytes < 0 || bytes % 4 != 0) return fail(-22, "pinn_state_digest_host: the size must be a multiple of 4 and >= 0 (got %s%ld)", "", (long)bytes);
+  if ((bytes > 0 && !ptr) || !out2) return fail(-22, "pinn_state_digest_host: null argument%s");
+  unsigned long long d[2];
+  state_digest_host(ptr, (unsigned long long)bytes, d);
+  out2[0] = d[0]; out2[1] = d[1];
+  return 0;
+}
+
+// pack (live != NULL table of sources) or unpack (table of destinations): checks, then one launch per STATE_MAX_SEG segments
+static int state_copy(const char* what, bool pack, int nseg, void* const* live, const int64_t* bytes, const int64_t* offsets,
+                      void* staging, int64_t staging_bytes, uint64_t* digests, void* scratch, void* stream) {
+  if (nseg < 1 || nseg > 1 << 16) return fail(-22, "%s: nseg must be 1..65536 (got %ld)", what, (long)nseg);
+  if (!live || !bytes || !offsets || !digests || !scratch) return fail(-22, "%s: null argument", what);
+  if (misaligned(digests, 8) || misaligned(scratch, 8)) return fail(-22, "%s: digests_out and scratch must be 8-byte aligned", what);
+  if (misaligned(staging, 16)) return fail(-22, "%s: the staging buffer must be 16-byte aligned", what);
+  int64_t end = 0;
+  for (int k = 0; k < nseg; ++k) {
+    if (bytes[k] < 0 || bytes[k] % 4 != 0 || bytes[k] > (int64_t)1 << 46)
+      return fail(-22, "%s: a segment size must be a multiple of 4 in 0..2^46 (got %ld)", what, (long)bytes[k]);
+    if (bytes[k] > 0 && (!live[k] || misaligned(live[k], 4)))
+      return fail(-22, "%s: segment %ld has bytes but no buffer, or one that is not 4-byte aligned", what, (long)k);
+    if (offsets[k] == -1 || bytes[k] == 0) continue;            // digest only, or empty: nothing in the staging buffer
+    if (offsets[k] < end || offsets[k] % 256 != 0 || !staging || offsets[k] + bytes[k] > staging_bytes)
+      return fail(-22, "%s: the offset of segment %ld is not a multiple of 256, overlaps the segment before it or runs past the staging buffer",
+                  what, (long)k);
+    end = offsets[k] + bytes[k];
+  }
+  for (int k0 = 0; k0 < nseg; k0 += STATE_MAX_SEG) {
+    StateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nseg = nseg - k0 < STATE_MAX_SEG ? nseg - k0 : STATE_MAX_SEG;
+    a.digests = reinterpret_cast<unsigned long long*>(digests) + 2 * (size_t)k0;
+    a.scratch = static_cast<double*>(scratch);
+    for (int j = 0; j < a.nseg; ++j) {
+      const int k = k0 + j;
+      char* st = offsets[k] == -1 || bytes[k] == 0 ? nullptr : static_cast<char*>(staging) + offsets[k];
+      StateSeg& s = a.seg[j];
+      s.bytes = (unsigned long long)bytes[k];
+      s.chunk0 = a.nchunks;
+      a.nchunks += state_chunks(s.bytes);
+      if (st) {                                                  // the padding stops at the buffer's end (the last segment)
+        const int64_t e = offsets[k] + bytes[k], lim = (e + 255) / 256 * 256;
+        s.pad = (unsigned long long)((lim < staging_bytes ? lim : staging_bytes) - e);
+      }
+      if (pack) { s.rd = live[k]; s.wr = st; }                   // st NULL: the source is digested, nothing is stored
+      else if (st) { s.rd = st; s.wr = live[k]; }
+      else { s.rd = live[k]; s.wr = nullptr; }                   // the live buffer is digested, nothing is written
+    }
+    int rc = launch_state_copy(a, pack, (hipStream_t)stream);
+    if (rc) return hipfail(rc, what);
+  }
+  return 0;
+}
+
+int pinn_state_pack(int nseg, const void* const* src, const int64_t* bytes, const int64_t* offsets, void* dst, int64_t dst_bytes,
+                    uint64_t* digests_out, void* scratch, void* stream) {
+  return state_copy("pinn_state_pack", true, nseg, const_cast<void* const*>(src), bytes, offsets, dst, dst_bytes, digests_out,
+                    scratch, stream);
+}
+
+int pinn_state_unpack(int nseg, const void* src, int64_t src_bytes, const int64_t* bytes, const int64_t* offsets, void* const* dst,
+                      uint64_t* digests_out, void* scratch, void* stream) {
+  return state_copy("pinn_state_unpack", false, nseg, dst, bytes, offsets, const_cast<void*>(src), src_bytes, digests_out, scratch,
+                    stream);
+}
+
 }  // extern "C"

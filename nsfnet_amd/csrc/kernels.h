@@ -335,3 +335,23 @@ int launch_ptime_advance(const PtimeArgs& a, hipStream_t s);
 size_t val_scratch_bytes();
 int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s);
+// training-state snapshots: gather / scatter of many buffers with per-segment digests (state.hip)
+constexpr int STATE_MAX_SEG = 64;
+struct StateSeg {
+  const void* rd;                          // what the segment's bytes are read from
+  void* wr;                                // where they go (NULL: digest only, nothing is written)
+  unsigned long long bytes;                // a multiple of 4
+  unsigned long long chunk0;               // index of the segment's first chunk among all chunks of the launch
+  unsigned long long pad;                  // pack: bytes to zero behind the segment (up to the next multiple of 256, or the buffer's end)
+};
+struct StateArgs {
+  StateSeg seg[STATE_MAX_SEG];
+  int nseg;
+  unsigned long long nchunks;              // of all segments
+  unsigned long long* digests;             // [nseg][2] (A, B)
+  double* scratch;
+};
+size_t state_scratch_bytes();
+unsigned long long state_chunks(unsigned long long bytes);
+void state_digest_host(const void* p, unsigned long long bytes, unsigned long long out[2]);
+int launch_state_copy(const StateArgs& a, bool pad, hipStream_t s);

@@ -167,6 +167,18 @@ class ValidationConfig:
     patience: int = 0
 
 
+@dataclass
+class CheckpointConfig:
+    """Training-state snapshots that resume bit for bit (solver.set_checkpointing), off by default: path of the file
+    (one per rank) and the optimizer updates between two non-blocking snapshots."""
+    path: str = ""
+    every: int = 0
+
+    @property
+    def enabled(self):
+        return bool(self.path) and self.every > 0
+
+
 SCHEDULERS = ("constant", "multistep", "step", "exponential", "cosine")
 
 
@@ -194,6 +206,7 @@ class TrainingConfig:
     validation: ValidationConfig = field(default_factory=ValidationConfig)
     hard_boundary: HardBoundaryConfig = field(default_factory=HardBoundaryConfig)
     pseudo_time: PseudoTimeConfig = field(default_factory=PseudoTimeConfig)
+    checkpoint: CheckpointConfig = field(default_factory=CheckpointConfig)
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -292,6 +305,9 @@ class ConfigManager:
         if va.enabled and (va.every < 1 or va.patience < 0 or va.metric not in VALIDATION_METRICS):
             problems.append("training.validation: every >= 1, patience >= 0 and metric one of %s required"
                             % " | ".join(VALIDATION_METRICS))
+        ck = c.training.checkpoint
+        if ck.every < 0 or (ck.every > 0 and not ck.path):
+            problems.append("training.checkpoint: every >= 0, and a path when every > 0, required")
         for st in c.training.training_stages:
             if st.scheduler not in SCHEDULERS:
                 problems.append("stage %s: scheduler must be one of %s (got %r)" % (st.name, " | ".join(SCHEDULERS),
@@ -359,6 +375,8 @@ class ConfigManager:
         if t.validation.enabled:
             print("validation : every=%d metric=%s keep_best=%s patience=%d"
                   % (t.validation.every, t.validation.metric, t.validation.keep_best, t.validation.patience))
+        if t.checkpoint.enabled:
+            print("checkpoint : path=%s every=%d" % (t.checkpoint.path, t.checkpoint.every))
         for st in t.training_stages:
             if st.scheduler != "constant" or st.warmup_epochs > 0:
                 a = st.schedule_args()

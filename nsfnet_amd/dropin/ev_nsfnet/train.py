@@ -30,26 +30,40 @@ def setup_distributed():
     return True
 
 
-def run_stages(PINN, stages, epochs_scale, rank, log, star=None):
+def run_stages(PINN, stages, epochs_scale, rank, log, star=None, resume=None):
     """The staged schedule: per stage alpha_evm, then `epochs` (scaled) L-BFGS iterations or Adam updates at `lr`; an
-    Adam stage with a scheduler or a warm-up runs under that device schedule, every count scaled like the epochs."""
+    Adam stage with a scheduler or a warm-up runs under that device schedule, every count scaled like the epochs.
+    resume: the `extra` of a loaded training state - the stages before its current_stage are skipped and that stage is
+    entered at its next_epoch."""
+    names = [st.name for st in stages]
+    if resume is not None and resume.get("current_stage") not in names:
+        raise ValueError("--resume: the state was saved in stage %r, the configuration has %s"
+                         % (resume.get("current_stage"), names))
     for st in stages:
+        start = 0
+        if resume is not None:
+            if st.name != resume["current_stage"]:
+                continue
+            start, resume = int(resume.get("next_epoch") or 0), None
         if rank == 0:
             log.stage(st.name, st.alpha, st.epochs, st.lr)
         PINN.current_stage = st.name
         PINN.set_alpha_evm(st.alpha)
         epochs = max(1, int(st.epochs * epochs_scale))
+        if start >= epochs:         # the state was saved after the stage's last epoch
+            continue
         if st.optimizer == "lbfgs":     # one epoch = one L-BFGS iteration of the main net, lr = step scale
             # max_eval: room for the line search (torch's default for max_iter = 1 is one evaluation)
             opt = torch.optim.LBFGS(PINN.net.parameters(), lr=st.lr, max_iter=1, max_eval=25,
                                     history_size=st.history_size,
                                     line_search_fn=None if st.line_search == "none" else st.line_search)
-            PINN.train(num_epoch=epochs, lr=st.lr, optimizer=opt)
+            PINN.train(num_epoch=epochs, lr=st.lr, optimizer=opt, start_epoch=start)
             PINN.set_optimizers(AdamHandle(st.lr))      # a later adam stage runs Adam again
         elif st.scheduler != "constant" or st.warmup_epochs > 0:    # lr is the base rate, the stage starts at epoch 0
-            PINN.train(num_epoch=epochs, lr=st.lr, scheduler=LrSchedule(**st.schedule_args(epochs_scale)))
+            PINN.train(num_epoch=epochs, lr=st.lr, scheduler=LrSchedule(**st.schedule_args(epochs_scale)),
+                       start_epoch=start)
         else:
-            PINN.train(num_epoch=epochs, lr=st.lr)
+            PINN.train(num_epoch=epochs, lr=st.lr, start_epoch=start)
         if rank == 0 and star is not None:
             PINN.evaluate(*star)
 
@@ -60,6 +74,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--epochs-scale", type=float, default=1.0)
     ap.add_argument("--data", default=None, help="DNS .mat (X_ref,Y_ref,U_ref,V_ref,P_ref)")
+    ap.add_argument("--resume", default=None, metavar="FILE",
+                    help="training state of training.checkpoint / save_training_state: continue its stage bit for bit")
     args = ap.parse_args()
     mgr = ConfigManager.from_file(args.config) if os.path.exists(args.config) else ConfigManager()
     cfg = mgr.config
@@ -152,7 +168,13 @@ def main():
             # last: a change of the factorization would drop the best.  Every rank validates the whole grid
             PINN.set_validation_data(*star, every=va.every, metric=va.metric, keep_best=va.keep_best,
                                      patience=va.patience)
-        run_stages(PINN, cfg.training.training_stages, args.epochs_scale, rank, log, star)
+        ck = cfg.training.checkpoint
+        if ck.enabled:
+            PINN.set_checkpointing(ck.path, ck.every)
+        resume = None
+        if args.resume:       # after every option and point set is attached: the state is unpacked into their tensors
+            resume = PINN.load_training_state(args.resume)
+        run_stages(PINN, cfg.training.training_stages, args.epochs_scale, rank, log, star, resume)
         if rank == 0:
             log.header("training completed")
     finally:

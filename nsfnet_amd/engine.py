@@ -10,8 +10,11 @@ loss (BC MSE + PDE residual MSE [+ supervised MSE]) -> d loss/d theta -> Adam.
 """
 import contextlib
 import ctypes
+import json
 import math
 import os
+import threading
+import time
 
 import numpy as np
 import torch
@@ -19,6 +22,8 @@ import torch
 from . import _lib
 from . import lbfgs as _lbfgs
 from . import schedule as _schedule
+from . import state_file as _state_file
+from .state_file import StateFileError
 
 NLOSS = 8
 FLD = dict(u=0, v=1, u_x=2, u_y=3, v_x=4, v_y=5, eq1=6, eq2=7, eq3=8, eq4=9, p=10)
@@ -684,6 +689,51 @@ def grad_sqnorm(g0, g1, scratch):
                                             _ptr(scratch), _stream()), "pinn_grad_sqnorm")
 
 
+def state_scratch(device):
+    """Zeroed device scratch of state_pack / state_unpack."""
+    return torch.zeros(int(_lib.load().pinn_state_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def _state_tables(tensors, offsets):
+    n = len(tensors)
+    for t in tensors:
+        if not t.is_contiguous():
+            raise ValueError("training state: a segment must be a contiguous tensor")
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() if t.numel() else 0 for t in tensors])
+    nbytes = (ctypes.c_int64 * n)(*[t.numel() * t.element_size() for t in tensors])
+    return n, ptrs, nbytes, (ctypes.c_int64 * n)(*[int(o) for o in offsets])
+
+
+def state_pack(srcs, offsets, staging, digests, scratch):
+    """pinn_state_pack: the device tensors srcs[k] into the uint8 staging buffer at offsets[k] (-1: digest only, nothing
+    stored; staging may then be None), padding zeroed, the digests (A, B) into the int64 device tensor digests [n, 2]
+    (the bits of the unsigned words).  One launch per 64 segments."""
+    n, ptrs, nbytes, offs = _state_tables(srcs, offsets)
+    _lib.check(_lib.load().pinn_state_pack(n, ptrs, nbytes, offs, _ptr(staging), 0 if staging is None else staging.numel(),
+                                           _ptr(digests), _ptr(scratch), _stream()), "pinn_state_pack")
+
+
+def state_unpack(staging, offsets, dsts, digests, scratch):
+    """pinn_state_unpack: the reverse scatter, from staging at offsets[k] into the live tensors dsts[k] in place (-1:
+    dsts[k] is digested as it stands); digests as in state_pack, of what was written."""
+    n, ptrs, nbytes, offs = _state_tables(dsts, offsets)
+    _lib.check(_lib.load().pinn_state_unpack(n, _ptr(staging), 0 if staging is None else staging.numel(), nbytes, offs, ptrs,
+                                             _ptr(digests), _ptr(scratch), _stream()), "pinn_state_unpack")
+
+
+class _Snapshot:
+    """What save_training_state keeps between calls: the staging buffer (allocated once per segment layout), its pinned
+    host copy, the digests, the scratch, the side stream with its events, and the one snapshot in flight."""
+
+    def __init__(self):
+        self.sig = None                 # (name, bytes, stored) of every segment the buffers were sized for
+        self.offsets, self.total = [], 0
+        self.staging = self.host = self.digests = self.digests_host = self.scratch = None
+        self.stream = self.ev = None
+        self.thread, self.error = None, None
+        self.info = None
+
+
 class LbfgsHistory:
     """Device state of the L-BFGS direction (csrc/lbfgs.hip): the workspace with history_size + 1 (s, y) slots,
     g_prev, R and Y'Y, plus the direction d, the line search's x0 and the two result blocks."""
@@ -909,6 +959,7 @@ EVAL_ADAM = 0           # an Adam step: a fresh batch, attention and balance upd
 EVAL_FULL_BATCH = 1     # loss_and_grad(full_batch=True): the whole store, the attention weights held
 EVAL_LBFGS = 2          # the L-BFGS objective: also the loss weights held, and its own gradient (the plain sum)
 _SAME_MODE = contextlib.nullcontext()       # (an evaluation that asks for nothing: no generator on the step's path)
+_RESTORED = object()    # the L-BFGS owner after load_training_state: whoever calls lbfgs_step next adopts the state
 
 
 class PinnEngine:
@@ -964,6 +1015,7 @@ class PinnEngine:
         self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
         self._val = None                    # device validation monitor (set_validation; None = off)
         self._pt = None                     # pseudo-time stepping (set_pseudo_time; None = off)
+        self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -1047,7 +1099,8 @@ class PinnEngine:
         batch's and only the drawn points change.  Evaluations of lbfgs_step and with full_batch=True do not update:
         the L-BFGS objective uses the current weights throughout.  resample() renormalises s and restarts lam at
         init.  loss_terms() keeps returning the WEIGHTED terms Adam minimises; attention_info() has the unweighted
-        ones.  lam is not part of a checkpoint: a restored run restarts it at init.
+        ones.  lam is not part of a save() checkpoint: a run restored from one restarts it at init (a training state,
+        save_training_state, carries it).
 
         eta = 0: off (plan_f.w is s again and every path launches what it launches without the feature).  A call
         restarts lam at init; so does set_collocation.  Refused: a chunked store, gamma outside (0, 1], eta < 0,
@@ -1800,7 +1853,7 @@ class PinnEngine:
         overwrites the anchors with those planes' U, V, P - the field one update old, the lag vis_t_minus has.  The
         cadence is device state: the launch is part of the captured step.  The first anchor is the field of the
         weights when set_collocation attaches the points; reset_pseudo_time() re-anchors at the current weights.
-        Anchors are not part of a checkpoint.
+        Anchors are not part of a save() checkpoint (a training state, save_training_state, carries them).
 
         By default the collocation plan runs the 8-wave kernel families (as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
         would).  With PINN_PTIME_SPLIT=1 in the environment when set_collocation creates the plan it keeps the
@@ -2114,6 +2167,8 @@ class PinnEngine:
         if self._lbfgs is None or self._lbfgs.history_size != int(history_size):
             self._lbfgs = LbfgsHistory(self.net.num_train, int(history_size), self.device)
             self.lbfgs_reset()
+        if self._lbfgs_owner is _RESTORED:      # load_training_state: the restored state is this owner's from here on
+            self._lbfgs_owner = owner
         if owner is not self._lbfgs_owner:
             self.lbfgs_reset()
             self._lbfgs_owner = owner
@@ -2186,6 +2241,285 @@ class PinnEngine:
     def _graphs_enabled(self):
         flag = os.environ.get("NSFNET_GRAPH")
         return flag is not None and flag not in ("0", "", "false", "False") and self.device.type == "cuda"
+
+    # ---- training-state snapshots that resume bit for bit (DESIGN.md section 7.12) ----
+    def _state_segments(self, lbfgs=None):
+        """[(name, tensor, stored)]: everything in device memory that a step reads and an earlier step wrote, in the
+        file's fixed order - per net (net, net_e) trainable, m, v, adam_t; per collocation pass x, y, w (the static
+        weights), vis_t_minus; plan_e x, y; opt epoch, rec; bal lam, rec; cfg coef, rec; batch counter, idx; rba lam, w,
+        rec; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
+        (stored False), the sets a resume must attach again unchanged: boundary, supervised, validation, resample pool."""
+        segs = []
+
+        def add(name, t, stored=True):
+            if t is not None:
+                segs.append((name, t, stored))
+
+        for name, net in self._nets():
+            for key, t in (("trainable", net.trainable), ("m", net.m), ("v", net.v), ("adam_t", net.adam_t_dev)):
+                add("%s.%s" % (name, key), t)
+        if self.plan_f is not None:
+            for i, (_, p) in enumerate(_passes(self.plan_f)):
+                add("colloc.%d.x" % i, p.x)
+                add("colloc.%d.y" % i, p.y)
+                add("colloc.%d.w" % i, self._rba.s if self._rba is not None else p.w)
+                add("colloc.%d.vis_t_minus" % i, p.vis_t_minus)
+        if self.plan_e is not None:
+            add("plan_e.x", self.plan_e.x)
+            add("plan_e.y", self.plan_e.y)
+        for name, obj, keys in (("opt", self._opt, ("epoch", "rec")), ("bal", self._bal, ("lam", "rec")),
+                                ("cfg", self._cfg, ("coef", "rec")), ("batch", self._batch, ("counter", "idx")),
+                                ("rba", self._rba, ("lam", "w", "rec")), ("val", self._val, ("state", "ring"))):
+            if obj is not None:
+                for key in keys:
+                    add("%s.%s" % (name, key), getattr(obj, key))
+        if self._pt is not None and self.plan_f is not None:
+            add("ptime.anchor", self.plan_f.anchor)
+            add("ptime.record", self._pt.record)
+        if self._val is not None:
+            for i, t in enumerate(self._val.snap):
+                add("val.snap.%d" % i, t)
+        lbfgs = lbfgs if lbfgs is not None else self._lbfgs     # (a load hands in the workspace it is about to adopt)
+        if lbfgs is not None:
+            for key in ("ws", "d", "x0"):
+                add("lbfgs.%s" % key, getattr(lbfgs, key))
+        for name, plan in (("boundary", self.plan_b), ("supervised", self.plan_s),
+                           ("val", None if self._val is None else self._val.plan), ("pool", self._pool)):
+            if plan is not None:
+                add("%s.x" % name, plan.x, False)
+                add("%s.y" % name, plan.y, False)
+                for c, t in enumerate(getattr(plan, "targets", ())):
+                    add("%s.target%d" % (name, c), t, False)
+        if self._val is not None:
+            add("val.tgt", self._val.tgt, False)
+        add("pool.w", self._pool_w, False)
+        return segs
+
+    def _state_fingerprint(self):
+        """The structure a file must share with the engine that loads it."""
+        shape = lambda net: None if net is None else [net.n_out, net.n_hidden, net.hidden]
+        count = lambda plan, g: None if plan is None else [plan.n, int(g)]
+        v, f = self._val, self.plan_f
+        return dict(
+            flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
+            points_colloc=count(f, self.n_f_global), points_boundary=count(self.plan_b, self.n_b_global),
+            points_supervised=[0 if self.plan_s is None else self.plan_s.n, int(self.n_s_global)],
+            points_val=None if v is None else v.plan.n, points_pool=None if self._pool is None else self._pool.n,
+            points_colloc_passes=None if f is None else [[int(a), int(b)] for (a, b), _ in _passes(f)],
+            colloc_weights=f is not None and self._static_w() is not None,
+            schedule_or_clipping=self._opt is not None, balancing=self._bal is not None, confgrad=self._cfg is not None,
+            batch_points=0 if self._batch is None else self._batch.B, attention=self._rba is not None,
+            validation=None if v is None else dict(capacity=v.capacity, metric=v.metric, with_p=v.with_p,
+                                                   keep_best=v.keep_best),
+            lbfgs_history=None if self._lbfgs is None else self._lbfgs.history_size, rwf=self._rwf is not None,
+            hard_bc=None if self.hard_boundary_info() is None else
+            {k: list(x) if isinstance(x, tuple) else x for k, x in self.hard_boundary_info().items()},
+            pseudo_time=self._pt is not None, world_size=self.world_size, rank=self._rank())
+
+    def _state_info(self):
+        """What a file records beside the structure; load_training_state reports the keys that differ."""
+        o, a, b, bt, v, pt = self._opt, self._rba, self._bal, self._batch, self._val, self._pt
+        kernels = getattr(self.plan_f, "kernel_names", None)
+        return dict(
+            precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
+            kernels=None if kernels is None else list(kernels()), Re=self.Re, alpha_b=self.alpha_b, alpha_e=self.alpha_e,
+            alpha_s=self.alpha_s, alpha_evm=self.alpha_evm, scale=self.scale, vis_t0=self.vis_t0, eq4_weight=self._w4(),
+            pseudo_time=None if pt is None else [pt.sigma, pt.sigma_p, pt.every],
+            attention=None if a is None else [a.eta, a.gamma, a.init],
+            balancing=None if b is None else [b.every, b.beta], batch_seed=None if bt is None else bt.seed,
+            validation_every=None if v is None else v.every,
+            schedule=None if o is None else repr(o.spec.key()), max_norm=None if o is None else o.max_norm)
+
+    def _state_host(self):
+        """The host mirrors of the device state."""
+        ls = self._lbfgs_state
+        return dict(adam_t=[net.adam_t for _, net in self._nets()], e_trainable=bool(self.e_trainable),
+                    resample_calls=self._resample_calls,
+                    bal=None if self._bal is None else [self._bal.n, self._bal.done],
+                    rba_n_eval=None if self._rba is None else self._rba.n_eval,
+                    val_n=None if self._val is None else self._val.n,
+                    lbfgs=None if self._lbfgs is None else [ls.n_iter, ls.func_evals, ls.t, ls.prev_loss])
+
+    def _state_path(self, path):
+        return path if self.world_size == 1 else path + ".rank%d" % self._rank()
+
+    def _state_join(self):
+        """Wait for the snapshot in flight, if any; an error of its writer is raised here."""
+        sn = self._snap
+        if sn is None or sn.thread is None:
+            return
+        sn.thread.join()
+        sn.thread = None
+        err, sn.error = sn.error, None
+        if err is not None:
+            raise err
+
+    def __del__(self):
+        try:
+            self._state_join()
+        except Exception:
+            pass
+
+    def save_training_state(self, path, extra=None, wait=True):
+        """Write everything a later step reads that an earlier step wrote (_state_segments, and the host mirrors) to
+        `path` (several ranks: path + '.rank%d', every rank its own file, no collective), so that a fresh process that
+        builds the same engine, attaches the same data and options and calls load_training_state continues bit for bit.
+        One launch (per 64 segments) on the current stream packs the state into a staging buffer that is allocated
+        once; a side stream then copies it to pinned host memory, so the stream the steps run on waits for the pack
+        alone.  wait=False: a host thread waits for that copy, writes path + '.tmp' and renames it over path - a job
+        killed meanwhile leaves the previous file whole - and the call returns at once; the file then holds the state
+        of the moment of the call, whatever steps follow.  At most one snapshot is in flight: the next call, wait=True
+        and the engine's teardown join it.  extra: a JSON-able dict kept in the header (the solvers' loop position)."""
+        self._state_join()
+        segs = self._state_segments()
+        cuda = self.device.type == "cuda"
+        sn = self._snap = self._snap or _Snapshot()
+        sig = [(name, t.numel() * t.element_size(), stored) for name, t, stored in segs]
+        if sig != sn.sig:
+            offs, sn.total = _state_file.layout([b if stored else 0 for _, b, stored in sig])
+            sn.offsets = [o if stored else -1 for o, (_, _, stored) in zip(offs, sig)]
+            sn.staging = torch.zeros(max(sn.total, 256), dtype=torch.uint8, device=self.device)
+            sn.digests = torch.zeros(len(segs), 2, dtype=torch.int64, device=self.device)
+            sn.host = torch.zeros(max(sn.total, 256), dtype=torch.uint8, pin_memory=cuda)
+            sn.digests_host = torch.zeros(len(segs), 2, dtype=torch.int64, pin_memory=cuda)
+            sn.scratch = sn.scratch if sn.scratch is not None else state_scratch(self.device)
+            sn.sig = sig
+        header = dict(fingerprint=self._state_fingerprint(), info=self._state_info(), host=self._state_host(),
+                      extra={} if extra is None else extra,
+                      segments=[dict(name=name, dtype=str(t.dtype).replace("torch.", ""), shape=list(t.shape), bytes=b,
+                                     offset=o) for (name, t, _), (_, b, _), o in zip(segs, sig, sn.offsets)])
+        path = self._state_path(path)
+        t0 = time.perf_counter()
+        if cuda:
+            if sn.stream is None:
+                sn.stream = torch.cuda.Stream(device=self.device)
+                sn.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] + [torch.cuda.Event()]
+            main = torch.cuda.current_stream(self.device)
+            sn.ev[0].record(main)
+            state_pack([t for _, t, _ in segs], sn.offsets, sn.staging, sn.digests, sn.scratch)
+            sn.ev[1].record(main)
+            with torch.cuda.stream(sn.stream):
+                sn.stream.wait_event(sn.ev[1])
+                sn.host.copy_(sn.staging, non_blocking=True)
+                sn.digests_host.copy_(sn.digests, non_blocking=True)
+                sn.ev[2].record(sn.stream)
+        else:
+            state_pack([t for _, t, _ in segs], sn.offsets, sn.staging, sn.digests, sn.scratch)
+            sn.host.copy_(sn.staging)
+            sn.digests_host.copy_(sn.digests)
+
+        def finish():
+            if cuda:
+                sn.ev[2].synchronize()
+            dig = sn.digests_host.numpy().view(np.uint64)
+            for seg, d in zip(header["segments"], dig):
+                seg["digest"] = [int(d[0]), int(d[1])]
+            _state_file.write(path, header, sn.host.numpy()[:sn.total])
+            sn.info = dict(path=path, bytes=sn.total, segments=[name for name, _, _ in segs],
+                           stream_ms=sn.ev[0].elapsed_time(sn.ev[1]) if cuda else None,
+                           wall_s=time.perf_counter() - t0)
+
+        if wait:
+            finish()
+            return
+
+        def run():
+            try:
+                finish()
+            except BaseException as e:      # raised by the call that joins
+                sn.error = e
+
+        sn.thread = threading.Thread(target=run, name="nsfnet-state-writer")
+        sn.thread.start()
+
+    def training_state_info(self):
+        """dict(path, bytes, segments, stream_ms, wall_s) of the last finished snapshot (stream_ms: the pack, between two
+        events on the stream of the steps; wall_s: from the call to the renamed file); None before the first.  Joins
+        the snapshot in flight."""
+        self._state_join()
+        return None if self._snap is None else self._snap.info
+
+    def load_training_state(self, path, strict=True):
+        """Continue from a file of save_training_state.  The engine must be built as the saving one was, with the same
+        point sets and options attached (the file's fingerprint: a difference raises ValueError naming the first key that
+        differs - another world size, rank or point count, an option on here and off there).  Every stored segment is
+        verified against its digest on the host before anything is uploaded: a short or damaged file raises
+        StateFileError and the engine is untouched.  strict: the boundary, supervised, validation and pool sets, which
+        are not stored, must digest to what the file recorded (ValueError); strict=False skips only that.  Then one
+        host-to-device copy and an unpack IN PLACE into the existing tensors - captured hipGraphs stay valid -, `prep`
+        of every net rebuilt (compose under the weight factorization, then prepare), the host mirrors restored and the
+        digests the unpack wrote compared with the header's.  An L-BFGS history in the file is adopted by the next
+        lbfgs_step, whatever `owner` it is given.  loss_terms() and the field planes are not state: after a load they
+        are those of the NEXT evaluation.  (With the factorization on, `params` comes back as compose(theta), which is
+        what every update leaves; only a file saved before the first update could differ from the saving engine in
+        the rounding of that product.)  Returns dict(extra=the caller's dict, changed=[info keys that differ])."""
+        self._state_join()
+        header, payload = _state_file.read(self._state_path(path))
+        fp_file, fp = header["fingerprint"], self._state_fingerprint()
+        adopt = fp_file.get("lbfgs_history") if self._lbfgs is None else None
+        if adopt is not None:
+            fp["lbfgs_history"] = adopt                 # the workspace is made below, once nothing can refuse any more
+        if fp_file.get("lbfgs_history") is None:
+            fp["lbfgs_history"] = None                  # nothing to restore: the engine's own history restarts
+        fp, fp_file = json.loads(json.dumps(fp)), dict(fp_file)
+        for key in sorted(set(fp) | set(fp_file)):
+            if fp.get(key) != fp_file.get(key):
+                raise ValueError("training state %s: fingerprint key %r differs: the file has %r, this engine %r"
+                                 % (path, key, fp_file.get(key), fp.get(key)))
+        made = None
+        if adopt is not None:
+            made = LbfgsHistory(self.net.num_train, int(adopt), self.device)
+        segs = self._state_segments(lbfgs=made)
+        if fp_file.get("lbfgs_history") is None:
+            segs = [s for s in segs if not s[0].startswith("lbfgs.")]
+        mine = [(name, t.numel() * t.element_size(), stored) for name, t, stored in segs]
+        theirs = [(s["name"], s["bytes"], s["offset"] >= 0) for s in header["segments"]]
+        if mine != theirs:
+            bad = next((a, b) for a, b in zip(mine + [None], theirs + [None]) if a != b)
+            raise ValueError("training state %s: the segments differ: this engine has %r, the file %r" % ((path,) + bad))
+        sn = self._snap = self._snap or _Snapshot()
+        if sn.scratch is None:
+            sn.scratch = state_scratch(self.device)
+        digests = torch.zeros(len(segs), 2, dtype=torch.int64, device=self.device)
+        want = [[int(v) for v in s["digest"]] for s in header["segments"]]
+        got = lambda: [[int(v) for v in row] for row in digests.cpu().numpy().view(np.uint64)]
+        loose = [k for k, (_, _, stored) in enumerate(segs) if not stored]
+        if strict and loose:                            # before anything is written
+            state_pack([segs[k][1] for k in loose], [-1] * len(loose), None, digests[:len(loose)], sn.scratch)
+            for k, d in zip(loose, got()):
+                if d != want[k]:
+                    raise ValueError("training state %s: %r is not what the saving run had attached (digest %s, the file "
+                                     "has %s)" % (path, segs[k][0], d, want[k]))
+        staging = torch.from_numpy(payload).to(self.device) if payload.size else None
+        offsets = [s["offset"] for s in header["segments"]]
+        if made is not None:
+            self._lbfgs = made
+        state_unpack(staging, offsets, [t for _, t, _ in segs], digests, sn.scratch)
+        for _, net in self._nets():
+            net.update_params()
+        host = header["host"]
+        for (_, net), t in zip(self._nets(), host["adam_t"]):
+            net.adam_t = int(t)
+        self.e_trainable, self._resample_calls = bool(host["e_trainable"]), int(host["resample_calls"])
+        if self._bal is not None:
+            self._bal.n, self._bal.done = (int(v) for v in host["bal"])
+        if self._rba is not None:
+            self._rba.n_eval = int(host["rba_n_eval"])
+        if self._val is not None:
+            self._val.n = int(host["val_n"])
+        self.lbfgs_reset()
+        if host["lbfgs"] is not None:
+            ls = self._lbfgs_state
+            ls.n_iter, ls.func_evals, ls.t, ls.prev_loss = host["lbfgs"]
+            self._lbfgs_owner = _RESTORED
+        self._eval_batch = False
+        for k, d in enumerate(got()):
+            if (strict or segs[k][2]) and d != want[k]:
+                raise StateFileError("training state %s: segment %r arrived with digest %s, the file has %s"
+                                     % (path, segs[k][0], d, want[k]))
+        info = json.loads(json.dumps(self._state_info()))
+        changed = sorted(k for k in set(info) | set(header["info"]) if info.get(k) != header["info"].get(k))
+        return dict(extra=header["extra"], changed=changed)
 
     # ---- inference (evaluate / test / predict) ----
     def predict(self, x, y, with_e=False):

@@ -30,6 +30,7 @@ from .pinn_solver import AdamHandle, SolverBase, _col, default_device, is_lbfgs,
 class PysicsInformedNeuralNetwork(SolverBase):
     tb_writer = None
     global_step = 0
+    freeze_period = 10000       # the entropy net trains for one step in every freeze_period (reference :459-462)
 
     def __init__(self,
                  opt=None,
@@ -283,28 +284,32 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self._publish_terms()
         return self.loss, [self.loss_e, self.loss_b]
 
-    def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None):
+    def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None, start_epoch=0, stop_epoch=None):
+        """start_epoch = k > 0 (after load_training_state): the stage's loop runs epochs k .. num_epoch - 1 and does
+        none of its stage-start resets (the schedule position, freeze_evm_net(0)); the freeze schedule, resampling,
+        logging and saving keep keying on epoch_id."""
         if is_lbfgs(optimizer):
             self.opt = optimizer
         if self.opt is not None:
             self.opt.param_groups[0]['lr'] = lr
         if is_lbfgs(self.opt):          # before solve_Adam's freeze schedule would replace self.opt
-            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
-        return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
+            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler, start_epoch, stop_epoch)
+        return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler, start_epoch, stop_epoch)
 
-    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None):
+    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None, start_epoch=0, stop_epoch=None):
         """One epoch = one torch.optim.LBFGS.step(closure) of self.opt's knobs on the main net (PinnEngine.lbfgs_step):
         the entropy net stays frozen and the 10 000-step unfreeze schedule does not run; Adam's state is untouched.
         Logging, checkpoints and resampling keep solve_Adam's per-epoch cadence (a resample resets the history)."""
-        self._last_log_time, self._last_log_epoch = time.time(), 0
+        self._last_log_time, self._last_log_epoch = time.time(), int(start_epoch)
         if not hasattr(self, 'log_interval'):
             self.log_interval = 100
-        for epoch_id in range(num_epoch):
+        for epoch_id in range(int(start_epoch), self._end_epoch(num_epoch, stop_epoch)):
             self._maybe_resample(epoch_id)
             self.global_step += 1
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
             if scheduler is not None and not isinstance(scheduler, _schedule.LrSchedule):
                 scheduler.step()
+            self._maybe_checkpoint(epoch_id, num_epoch, stop_epoch)
             interval = self.log_interval if self.log_interval > 0 else 100
             log_now = self.rank == 0 and (epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1)
             save_now = self.rank == 0 and (epoch_id == 0 or epoch_id % 10000 == 0)
@@ -325,17 +330,18 @@ class PysicsInformedNeuralNetwork(SolverBase):
         """The log cadence without the rank: every rank asks the patience question at the same steps."""
         return epoch_id == 0 or (epoch_id + 1) % interval == 0 or epoch_id == num_epoch - 1
 
-    def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
+    def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None, start_epoch=0, stop_epoch=None):
         """Reference loop :440-487 incl. its schedule: the entropy net trains for exactly one
         step in every 10 000 and Adam is re-created (moments reset) at every stage start and at
         steps k*10000 and k*10000+1."""
-        self._last_log_time, self._last_log_epoch = time.time(), 0
+        self._last_log_time, self._last_log_epoch = time.time(), int(start_epoch)
         if not hasattr(self, 'log_interval'):
             self.log_interval = 100
-        scheduler = self._begin_adam_stage(scheduler)
-        self.freeze_evm_net(0)
+        scheduler = self._begin_adam_stage(scheduler, resume=start_epoch > 0)
+        if not start_epoch:
+            self.freeze_evm_net(0)
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
-        for epoch_id in range(num_epoch):
+        for epoch_id in range(int(start_epoch), self._end_epoch(num_epoch, stop_epoch)):
             self._maybe_resample(epoch_id)
             self.global_step += 1
             self._apply_freeze_schedule(epoch_id)
@@ -349,6 +355,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
                 self.engine.adam_step(self._adam_lr())
             if scheduler:
                 scheduler.step()
+            self._maybe_checkpoint(epoch_id, num_epoch, stop_epoch)
             if log_now:
                 self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
             if save_now:
@@ -356,14 +363,14 @@ class PysicsInformedNeuralNetwork(SolverBase):
                           N_f=self.N_f)
             if self._at_log(epoch_id, num_epoch, interval) and self._patience_out():
                 break
-        if num_epoch > 0:
+        if num_epoch > start_epoch:
             self._publish_terms()
 
     def _apply_freeze_schedule(self, epoch_id):
         """:459-462 - unfreeze at k*10000 (k >= 1), re-freeze one step later."""
-        if epoch_id != 0 and epoch_id % 10000 == 0:
+        if epoch_id != 0 and epoch_id % self.freeze_period == 0:
             self.defreeze_evm_net(epoch_id)
-        if (epoch_id - 1) % 10000 == 0:
+        if (epoch_id - 1) % self.freeze_period == 0:
             self.freeze_evm_net(epoch_id)
 
     def freeze_evm_net(self, epoch_id):

@@ -281,6 +281,62 @@ class SolverBase:
             torch.save({name: torch.cat([a.detach().reshape(-1) for a in layers]).cpu() for name, layers in f.items()},
                        path + '_rwf')
 
+    # ---- training-state checkpoints that resume bit for bit ----
+    _ckpt_path, _ckpt_every = None, 0
+
+    def set_checkpointing(self, path=None, every=0):
+        """path and every > 0: after the update of every epoch with (epoch_id + 1) % every == 0, and after the last
+        epoch of a train() call, write a non-blocking training-state snapshot to `path` whose `next_epoch` is
+        epoch_id + 1 (save_training_state).  Off by default; path None or every 0: off."""
+        every = int(every)
+        if every < 0:
+            raise ValueError("checkpointing: every must be >= 0")
+        self._ckpt_path, self._ckpt_every = (path, every) if path and every else (None, 0)
+
+    @staticmethod
+    def _end_epoch(num_epoch, stop_epoch):
+        """Where this call's loop ends: num_epoch, or stop_epoch when train() is told to cut the stage there."""
+        return num_epoch if stop_epoch is None else min(num_epoch, int(stop_epoch))
+
+    def _maybe_checkpoint(self, epoch_id, num_epoch, stop_epoch=None):
+        last = epoch_id == self._end_epoch(num_epoch, stop_epoch) - 1
+        if self._ckpt_path is not None and ((epoch_id + 1) % self._ckpt_every == 0 or last):
+            self.save_training_state(self._ckpt_path, wait=False, next_epoch=epoch_id + 1, num_epoch=num_epoch)
+
+    def save_training_state(self, path, wait=True, next_epoch=None, num_epoch=None):
+        """PinnEngine.save_training_state with the loop position as `extra`: next_epoch and num_epoch (what
+        train(start_epoch=...) continues from), stage / current_stage, global_step, the optimizer handle's lr, the
+        running stage's base rate and alpha_evm."""
+        opt = getattr(self, "opt", None)
+        lr = None if opt is None or is_lbfgs(opt) else float(opt.param_groups[0]['lr'])
+        extra = dict(next_epoch=next_epoch, num_epoch=num_epoch, stage=getattr(self, "stage", None),
+                     current_stage=getattr(self, "current_stage", None), global_step=getattr(self, "global_step", None),
+                     lr=lr, lr0=self._lr0, alpha_evm=getattr(self, "alpha_evm", None))
+        self.engine.save_training_state(path, extra=extra, wait=wait)
+
+    def load_training_state(self, path, strict=True):
+        """PinnEngine.load_training_state, after every option and point set is attached as in the saving run.  Applies
+        global_step, the handle's lr, the stage's base rate, alpha_evm and stage / current_stage from the file's `extra`
+        and returns it: train(..., start_epoch=extra['next_epoch']) then continues the stage where it was cut."""
+        fp = _eng._state_file.read_header(self.engine._state_path(path))["fingerprint"]
+        if fp.get("schedule_or_clipping") and self.engine._opt is None:
+            # the cut stage ran under a schedule given to its train() call: the device position needs its tensors now,
+            # train(scheduler=..., start_epoch=k) installs the schedule itself and keeps the position
+            self.engine.set_lr_schedule(_schedule.LrSchedule())
+        extra = self.engine.load_training_state(path, strict=strict)["extra"]
+        if extra.get("global_step") is not None:
+            self.global_step = int(extra["global_step"])
+        opt = getattr(self, "opt", None)
+        if extra.get("lr") is not None and opt is not None and not is_lbfgs(opt):
+            opt.param_groups[0]['lr'] = extra["lr"]
+        self._lr0 = extra.get("lr0")
+        if extra.get("alpha_evm") is not None and hasattr(self, "set_alpha_evm"):
+            self.set_alpha_evm(extra["alpha_evm"])
+        for key in ("stage", "current_stage"):
+            if extra.get(key) is not None and hasattr(self, key):
+                setattr(self, key, extra[key])
+        return extra
+
     def load(self, path, path_evm=None):
         """Load a checkpoint written by save(): the main net's state_dict at `path` and, for the ev class, the entropy
         net's at path_evm (default <path>_evm when that file exists).  When the sidecar <path>_rwf is present the
@@ -310,8 +366,9 @@ class SolverBase:
         if self._pseudo_time and self.engine.plan_f is not None:       # anchors are not checkpointed
             self.engine.reset_pseudo_time()
 
-    def _begin_adam_stage(self, scheduler):
-        """Resolve solve_Adam's scheduler= argument.  An LrSchedule, or a torch.optim.lr_scheduler object of type
+    def _begin_adam_stage(self, scheduler, resume=False):
+        """Resolve solve_Adam's scheduler= argument.  resume (train(start_epoch > 0)): the schedule object is installed
+        but the device position is left where load_training_state put it.  An LrSchedule, or a torch.optim.lr_scheduler object of type
         MultiStepLR, StepLR, ExponentialLR or CosineAnnealingLR (translated once, from its own attributes), becomes
         the device schedule of this stage: an LrSchedule starts at e = 0 with the stage's rate as lr0, a torch object
         at e = its last_epoch with its base_lrs[0].  Returns the object whose step() the loop still calls - the torch
@@ -327,6 +384,13 @@ class SolverBase:
             else:
                 spec = None         # a host schedule the device does not know: the old path
         o = self.engine._opt
+        if resume:
+            if spec != (o.user_spec if o is not None else None):
+                e0 = 0 if o is None else int(o.epoch.item())
+                self.engine.set_lr_schedule(spec)
+                self.engine.reset_lr_schedule(e0)
+            self._lr0 = lr0 if spec is not None else None
+            return stepper
         if spec is not (o.user_spec if o is not None else None):
             self.engine.set_lr_schedule(spec)
         self.engine.reset_lr_schedule(e0)
@@ -495,26 +559,30 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self._publish_terms(loss_mode)
         return self.loss, [self.loss_e, self.loss_b]
 
-    def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None):
+    def train(self, num_epoch=1, lr=1e-4, optimizer=None, scheduler=None, batchsize=None, start_epoch=0, stop_epoch=None):
+        """start_epoch = k > 0 (after load_training_state): the stage's loop runs epochs k .. num_epoch - 1 and does
+        none of its stage-start resets; the per-epoch cadences keep keying on epoch_id.  stop_epoch: cut the stage
+        there (the loop ends before that epoch; with set_checkpointing on, the last epoch run writes a snapshot)."""
         if is_lbfgs(optimizer):
             self.opt = optimizer
         self.opt.param_groups[0]['lr'] = lr
         if is_lbfgs(self.opt):
-            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
-        return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler)
+            return self.solve_LBFGS(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler, start_epoch, stop_epoch)
+        return self.solve_Adam(self.fwd_computing_loss_2d, num_epoch, batchsize, scheduler, start_epoch, stop_epoch)
 
-    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None):
+    def solve_LBFGS(self, loss_func, num_epoch=1, batchsize=None, scheduler=None, start_epoch=0, stop_epoch=None):
         """One epoch = one torch.optim.LBFGS.step(closure) of self.opt's knobs on the device (PinnEngine.lbfgs_step);
         logging, checkpoints and resampling keep solve_Adam's per-epoch cadence (a resample resets the history)."""
         print('--------')
         print(num_epoch)
         print('--------')
         log_now = save_now = False
-        for epoch_id in range(num_epoch):
+        for epoch_id in range(int(start_epoch), self._end_epoch(num_epoch, stop_epoch)):
             self._maybe_resample(epoch_id)
             self.engine.lbfgs_step(owner=self.opt, **lbfgs_knobs(self.opt))   # a new LBFGS object starts fresh
             if scheduler is not None and not isinstance(scheduler, _schedule.LrSchedule):
                 scheduler.step()
+            self._maybe_checkpoint(epoch_id, num_epoch, stop_epoch)
             log_now = self.log_every and epoch_id % self.log_every == 0
             save_now = self.save_every and epoch_id % self.save_every == 0
             if log_now or save_now:
@@ -530,16 +598,16 @@ class PysicsInformedNeuralNetwork(SolverBase):
         if num_epoch > 0 and not (log_now or save_now):
             self.fwd_computing_loss_2d(full_batch=True)         # terms and fields of the accepted point
 
-    def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None):
+    def solve_Adam(self, loss_func, num_epoch=1000, batchsize=None, scheduler=None, start_epoch=0, stop_epoch=None):
         """The reference loop (solver :240-278): loss -> backward -> Adam step; log every 1000,
         checkpoint every 10000 (incl. step 0).  Adam moments persist across calls."""
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
-        scheduler = self._begin_adam_stage(scheduler)
-        epoch_id = 0
+        scheduler = self._begin_adam_stage(scheduler, resume=start_epoch > 0)
+        epoch_id, end_epoch = int(start_epoch), self._end_epoch(num_epoch, stop_epoch)
         print('--------')
         print(num_epoch)
         print('--------')
-        while epoch_id < num_epoch:
+        while epoch_id < end_epoch:
             self._maybe_resample(epoch_id)
             lr = self._adam_lr()
             log_now = self.log_every and epoch_id % self.log_every == 0
@@ -551,6 +619,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
                 self.engine.adam_step(lr)
             if scheduler:
                 scheduler.step()
+            self._maybe_checkpoint(epoch_id, num_epoch, stop_epoch)
             if log_now:
                 self.print_log(self.loss, [self.loss_e, self.loss_b], epoch_id, num_epoch)
             if save_now:

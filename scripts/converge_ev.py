@@ -7,19 +7,28 @@ state_dicts + a JSON line per stage; the next call resumes from them (the refere
 every stage start, so a stage boundary is an exact resume point for the optimiser; the lagged
 viscosity state restarts from alpha*|e| as at the start of a run).
 
+With --state FILE a slice may end anywhere: the run writes a training-state snapshot to FILE
+every --state-every updates and where --max-steps cuts it, and a call that finds FILE continues from it bit for
+bit, in the middle of its stage, with the state of every option below - the balanced weights, the draw counter,
+the attention multipliers, the lagged viscosity, the schedule position, the validation ring and best weights, the
+pseudo-time anchors, a resampled collocation set.  The call must be given the same options as the one that wrote FILE.
+
     python scripts/converge_ev.py --re 3000 --dns tests/golden/dns/cavity_Re3000_256_Uniform.mat \
         --out gpurun_out/conv_ev --first 1 --last 2 [--resume DIR] [--epochs-scale 0.5]
         [--resample-every 5000 --pool 1000000 --rs-k 1 --rs-c 1]   (residual-based resampling, off by default)
-        [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call)
+        [--balance-every 100 --balance-beta 0.1]   (adaptive boundary weight, off by default; restarts per call unless --state carries it)
         [--confgrad]   (conflict-free combination of the per-term gradients, off by default; stateless)
-        [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call)
-        [--rba-eta 0.01 --rba-gamma 0.999]   (residual-based attention weights, off by default; lam restarts per call)
+        [--batch-points 12000 --batch-seed 0]   (stochastic mini-batching, off by default; the draw counter restarts per call unless --state carries it)
+        [--rba-eta 0.01 --rba-gamma 0.999]   (residual-based attention weights, off by default; lam restarts per call unless --state carries it)
         [--scheduler cosine --eta-min-factor 0.01 --warmup-epochs 1000]   (device learning-rate schedule of every stage,
                                                   off by default; counts scale with --epochs-scale, each stage starts at 0)
         [--grad-clip 1.0]   (global-norm gradient clipping of the Adam updates, off by default)
         [--validate-every 1000 --val-metric uv]   (error against the DNS field on the device every that many updates of
                                                   a stage, the stage's best weights kept: validation.jsonl,
                                                   net_best.pth / net_best_evm.pth; off by default)
+        [--state FILE --state-every 50000 --max-steps 400000]   (training-state snapshots: continue from FILE when it
+                                                  exists, write it every that many updates, end the call after that many
+                                                  updates, anywhere in a stage)
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -84,7 +93,12 @@ def main():
                     help="> 0: validate against the DNS field on the device every this many updates of a stage and keep "
                          "the stage's best weights (DESIGN.md 7.9)")
     ap.add_argument("--val-metric", choices=("uv", "u", "v", "p", "p0"), default="uv", help="what `best` means")
+    ap.add_argument("--state", default=None, metavar="FILE",
+                    help="training-state file (DESIGN.md 7.12): continue from it when it exists, and write it")
+    ap.add_argument("--state-every", type=int, default=0, help="updates between two non-blocking snapshots (0: only where the call ends)")
+    ap.add_argument("--max-steps", type=int, default=0, help="> 0: end this call after that many updates, anywhere in a stage")
     a = ap.parse_args()
+    state = None if a.state is None else os.path.abspath(a.state)
     from nsfnet_amd import ev_pinn_solver as es, cavity_data as cavity
     from nsfnet_amd.schedule import LrSchedule
     os.makedirs(a.out, exist_ok=True)
@@ -137,7 +151,13 @@ def main():
             P.set_weight_factorization(mean=a.rwf_mean, std=a.rwf_std, seed=a.rwf_seed)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
-    for k in range(a.first, a.last + 1):
+    first, start, left = a.first, 0, a.max_steps if a.max_steps > 0 else None
+    if state is not None:
+        P.set_checkpointing(state, a.state_every if a.state_every > 0 else 1 << 62)
+    resumed = state is not None and os.path.exists(P.engine._state_path(state))
+    if resumed:       # the stage the file was cut in, entered at its next epoch
+        first = int(es._eng._state_file.read_header(P.engine._state_path(state))["extra"]["current_stage"].split()[-1])
+    for k in range(first, a.last + 1):
         alpha, epochs, lr = STAGES[k - 1]
         n = max(1, int(epochs * a.epochs_scale))
         P.current_stage = "Stage %d" % k
@@ -145,6 +165,12 @@ def main():
         if a.validate_every > 0:                        # per stage: t counts the stage's updates, the best is the stage's
             P.set_validation_data(*star, every=a.validate_every, metric=a.val_metric,
                                   history=max(1, n // a.validate_every))
+        if resumed:   # every option is attached as in the call that wrote the file
+            start, resumed = int(P.load_training_state(state)["next_epoch"]), False
+            if start >= n:
+                start = 0
+                continue
+        stop = None if left is None else start + left
         t0 = time.time()
         sched = None
         if a.scheduler != "constant" or a.warmup_epochs > 0:
@@ -152,11 +178,18 @@ def main():
             sched = LrSchedule(a.scheduler, milestones=[c(m, 0) for m in a.milestones], gamma=a.gamma,
                                step_size=c(a.step_size, 1), t_max=n, eta_min=a.eta_min_factor * lr,
                                warmup_epochs=c(a.warmup_epochs, 0), warmup_start=a.warmup_start)
-        P.train(num_epoch=n, lr=lr, scheduler=sched)
+        P.train(num_epoch=n, lr=lr, scheduler=sched, start_epoch=start, stop_epoch=stop)
         torch.cuda.synchronize()
+        if stop is not None and stop < n:               # the call's budget ends inside the stage: the snapshot is written
+            P.engine.training_state_info()
+            print("SLICE", json.dumps(dict(stage=k, next_epoch=stop, steps=n, state=state)), flush=True)
+            return
+        if left is not None:
+            left -= n - start
+        ran, start = n - start, 0
         dt = time.time() - t0
         eu, ev = P.evaluate(*star)[:2]
-        rec = dict(stage=k, alpha_evm=alpha, lr=lr, steps=n, seconds=round(dt, 1), ms_per_step=round(1e3 * dt / n, 4),
+        rec = dict(stage=k, alpha_evm=alpha, lr=lr, steps=n, seconds=round(dt, 1), ms_per_step=round(1e3 * dt / ran, 4),
                    loss=float(P.loss), loss_b=float(P.loss_b), loss_e=float(P.loss_e),
                    err_u=float(eu), err_v=float(ev), Re=a.re, net="%dx%d+4x40" % (a.layers, a.hidden), N_f=a.nf,
                    precision=os.environ.get("NSFNET_PRECISION", "fp32"),
@@ -191,6 +224,8 @@ def main():
         torch.save(P.net_1.state_dict(), "net_evm.pth")
         P.save_weight_factors("net.pth")                 # net.pth_rwf with --rwf, nothing without
         P.save_hard_boundary("net.pth")                  # net.pth_hardbc with --hard-bc, nothing without
+        if left is not None and left <= 0:               # the call's budget ended with the stage
+            return
 
 
 if __name__ == "__main__":
