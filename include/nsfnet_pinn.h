@@ -50,6 +50,30 @@ int pinn_net_destroy(pinn_net_t net);
  * product), 2 = plain bf16 operands (fast mode, does NOT meet the 1e-4 loss-parity bar).
  * All three modes exist for every supported width (hidden <= 512).  Call before pinn_net_prepare / pinn_plan_create. */
 int pinn_net_set_precision(pinn_net_t net, int prec_fwd, int prec_bwd, int prec_dw);
+/* ---- frozen Fourier-feature first layer (opt-in) ---------------
+ * The random-Fourier-feature embedding gamma(x) = [cos(2 pi B x), sin(2 pi B x)], B of shape (hidden / 2) x 2, followed
+ * by a tanh MLP, is this net with two changes: layer 0 uses sin instead of tanh, and layer 0 is frozen.  Rows 2k and
+ * 2k + 1 of W0 both hold 2 pi B_k, their biases are pi / 2 (the cosine) and 0 (the sine); the caller writes them into
+ * the flat parameters, whose keys and shapes do not change.  With kind = PINN_FIRST_LAYER_SINE, for the coordinates
+ * the net is fed:
+ *     z   = fmaf(w0x, x, fmaf(w0y, y, b0))                                  (as before)
+ *     a   = sin z     a_x = cos z * w0x     a_y = cos z * w0y     a_D = -sin z * (w0x^2 + w0y^2)
+ * (value mode: a alone); layers 1 .. L-1 and the output layer are exactly what they are with tanh.  fp32 mode uses the
+ * accurate sinf / cosf, the bf16 modes the hardware sine and cosine after an explicit range reduction.
+ * Layer 0 is not trained: its 3 * hidden gradient entries - the first 3 * hidden of the flat vector - are +0.0 bit for
+ * bit in every vector that pinn_grad_reduce, pinn_grad_reduce_terms and pinn_grad_reduce_terms_gram write (the
+ * statistics and Gram partials see the zeros), whether or not the call accumulates.
+ * The kind belongs to the net: every plan over it (residual, value) sees the same function.  A plan keeps the kind
+ * its net had when it was created; after a change every launch on such a plan, and every gradient assembly from it,
+ * is refused by name - create the plan again.
+ * Plans of such a net run the 8-wave kernel families whatever PINN_SCHED / PINN_WSPLIT / PINN_FUSE say, and store
+ * layer 0 (its a-streams) whatever PINN_S0_SKIP32 says; pinn_plan_kernel names the kernels as before.
+ * Refused (-22, pinn_last_error names the reason): an odd hidden width; fewer than 2 hidden layers (the output
+ * layer's gradient is formed from the last hidden layer by the tanh rule); pinn_plan_create_constrained with walls
+ * and pinn_plan_create_pseudo_time over such a net. */
+enum { PINN_FIRST_LAYER_TANH = 0, PINN_FIRST_LAYER_SINE = 1 };
+int pinn_net_set_first_layer(pinn_net_t net, int kind);
+int pinn_net_first_layer(pinn_net_t net);      /* the kind; -1 for a null net */
 int64_t pinn_net_num_params(pinn_net_t net);
 int64_t pinn_net_prep_floats(pinn_net_t net);
 /* Re-layout the flat parameters into padded MFMA-fragment order; call after every

@@ -36,11 +36,12 @@ __global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
   const bool live = p < P;
   const ReduceLoc loc = live ? reduce_locate(p, H, HP, L, a.n_out) : ReduceLoc{-1, -1, 0};
   const size_t SG = sg_total(HP, L);
+  const bool frozen = p < (size_t)a.frozen;      // (a frozen first layer: +0.0 in every vector, and in the statistics)
   int k = 0;
   for (int t = 0; t < 3; ++t) {
     double s = 0.0;
     for (int j = 0; j < a.nsrc[t]; ++j, ++k)
-      if (live) s = reduce_source_add(s, a.src[k], loc, HP, SG, w);
+      if (live && !frozen) s = reduce_source_add(s, a.src[k], loc, HP, SG, w);
     part[t][w][lane] = s;
   }
   __syncthreads();
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(512) void reduce_terms_kernel(TermReduceArgs a) {
       double s = part[t][0][lane];
 #pragma unroll
       for (int i = 1; i < 8; ++i) s += part[t][i][lane];
-      v = (a.acc_mask >> t) & 1 ? a.out[t][p] + (float)s : (float)s;
+      v = frozen ? 0.f : (a.acc_mask >> t) & 1 ? a.out[t][p] + (float)s : (float)s;
       a.out[t][p] = v;
     }
     if (a.partials) {

@@ -39,6 +39,20 @@ __device__ __forceinline__ float fast_tanh(float z) {
 }
 struct TanhFast { __device__ __forceinline__ float operator()(float z) const { return fast_tanh(z); } };
 
+// sine and cosine for the bf16 modes (the frozen sine first layer, spill_io.h layer0_sine): v_sin_f32 / v_cos_f32 take
+// their argument in revolutions and are specified on [-256, 256] only, so the range is reduced explicitly: k = the
+// nearest whole number of revolutions, f = z / 2 pi - k in [-1/2, 1/2] from ONE fused product (the rounding of the
+// large product z / 2 pi never reaches f) plus the low part of 1 / 2 pi, which matters once |z| is tens of radians.
+// Four VALU and two transcendental instructions; absolute error about 1e-6, below the bf16x3 operand rounding.
+__device__ __forceinline__ void fast_sincos(float z, float& s, float& c) {
+  constexpr float INV2PI_HI = 0.159154937f, INV2PI_LO = 6.42063824e-9f;     // 1 / 2 pi = hi + lo
+  const float k = rintf(z * INV2PI_HI);
+  const float f = fmaf(z, INV2PI_LO, fmaf(z, INV2PI_HI, -k));
+  s = __builtin_amdgcn_sinf(f);
+  c = __builtin_amdgcn_cosf(f);
+}
+struct SinCosFast { __device__ __forceinline__ void operator()(float z, float& s, float& c) const { fast_sincos(z, s, c); } };
+
 __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <atomic>
 #include <new>
 
 #include "../../include/nsfnet_pinn.h"
@@ -48,11 +49,19 @@ static Switches read_switches() {
 }
 
 // precision of a kernel family: 0 = fp32-input MFMA (exact fp32), 1 = bf16x3 split, 2 = plain bf16
+// What a net shares with the plans created over it (each plan keeps a copy of pinn_net_s): the first-layer kind as it
+// is NOW, so that a launch can refuse a plan whose copy predates a change.  Reference counted: it outlives whichever of
+// the net and its plans is destroyed first.
+struct NetShared { std::atomic<int> refs, first_layer; };
+static void shared_release(NetShared* s) { if (s && s->refs.fetch_sub(1) == 1) delete s; }
 struct pinn_net_s {
   int n_out, L, H, HP;
   int wide;   // 64-column tile kernels (always for HP > 256; pick_wide for HP 128/256)
   int prec_fwd, prec_bwd, prec_dw;
+  int first_layer;      // PINN_FIRST_LAYER_TANH | PINN_FIRST_LAYER_SINE (pinn_net_set_first_layer); a plan's copy: at its creation
+  NetShared* shared;
 };
+static bool is_ff(const pinn_net_s& n) { return n.first_layer == PINN_FIRST_LAYER_SINE; }
 static int terms_of(int prec) { return prec == 1 ? 3 : 1; }
 // 64-column-tile kernels: always for HP > 256; for HP == 256 in fp32 mode they are also the faster
 // choice (two workgroups per CU overlap each other's epilogue and MFMA phases).
@@ -234,9 +243,16 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // schedule.  By default a pseudo-time plan, constrained or not, resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
   // would; $PINN_PTIME_SPLIT=1 is to it what $PINN_HBC_SPLIT=1 is to a constrained plan.  A pseudo-time plan never
   // looks at PINN_HBC_SPLIT, and no other plan looks at PINN_PTIME_SPLIT.
+  // A net with the frozen sine first layer has its variant in the 8-wave families only, and none with walls or
+  // pseudo-time: its plans resolve as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever those switches say, and
+  // store layer 0 (SPILL_CLASSIC in every precision): what is stored there is the layer's a-streams, which no reader
+  // recomputes.
   Switches sw = sw_in;
-  const bool keep_split = ptime ? sw.ptime_split != 0 : hbc.kind && sw.hbc_split != 0;
-  if ((hbc.kind || ptime) && !keep_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
+  const bool ff = is_ff(net);
+  if (ff && (hbc.kind || ptime))
+    return fail(-22, "pinn_plan_create: a net with the frozen sine first layer has no %s variant", hbc.kind ? "hard-wall (constrained)" : "pseudo-time");
+  const bool keep_split = !ff && (ptime ? sw.ptime_split != 0 : hbc.kind && sw.hbc_split != 0);
+  if ((hbc.kind || ptime || ff) && !keep_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
   p->hbc = hbc;
   p->ptime = ptime; p->anchor = nullptr; p->sigma = p->sigma_p = 0.f;
@@ -288,7 +304,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
   if (hbc.kind || ptime) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained or pseudo-time variant)
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
-  const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
+  const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw && !ff;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
   // K region must fit twice in the 512-element image rows); $PINN_WSPLIT=0 keeps the 8-wave kernels.
   const bool wsplit = s24w && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
@@ -312,6 +328,8 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
     fprintf(stderr, "[pinn] plan: pseudo-time sweeps: %s (PINN_PTIME_SPLIT=%d)\n",
             fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
             sw.ptime_split);
+  if (sw.verbose && ff)
+    fprintf(stderr, "[pinn] plan: frozen sine first layer: 8-wave kernels, layer 0 stored (PINN_SCHED, PINN_WSPLIT, PINN_FUSE and PINN_S0_SKIP32 are not consulted)\n");
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);
@@ -339,7 +357,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // of 8.9 GB each at 6x256 / 360 000 points).  Every other plan keeps [tile][L][HP x columns] blocks: an fp32 residual
   // plan without layer 0 in them ($PINN_S0_SKIP32=0 opts out), a wide all-bf16 residual plan in the 24-bit format.
   const size_t ablk = act_block(HP, wide ? 64 : PINN_TILE_COLS);
-  const bool skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0;
+  const bool skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0 && !ff;
   p->spill = spill_make(split_pair ? SPILL_P24_COMPACT : s24w ? SPILL_P24_WIDE : skip32 ? SPILL_SKIP0 : SPILL_CLASSIC, ablk);
   for (int r = 0; r < ROLE_COUNT; ++r)
     if (ROLE_SPILL_COL[r] >= 0 && p->role[r].family && (r != ROLE_DW || p->groups) &&
@@ -368,6 +386,7 @@ static FwdArgs fwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.partials = WS(plan, off_partials);
   a.spill = plan->spill;
   a.hbc = plan->hbc;
+  a.ff = is_ff(plan->net);
   if (plan->streams == 4) {     // (these share their bytes with the value-mode fields)
     a.ptime = plan->ptime; a.anchor = plan->anchor; a.sigma = plan->sigma; a.sigma_p = plan->sigma_p;
   }
@@ -411,6 +430,7 @@ static DwArgs dw_args(const pinn_plan_s* plan, void* ws, const float* prep, cons
   d.slabs = WS(plan, off_slabs);
   d.x = x; d.y = y; d.prep = prep; d.n = (int)plan->n;
   d.spill = plan->spill;
+  d.ff = plan->streams == 4 && is_ff(plan->net);
   return d;
 }
 
@@ -443,9 +463,27 @@ int pinn_net_create(int n_out, int n_hidden_layers, int hidden, pinn_net_t* out)
   n->n_out = n_out; n->L = n_hidden_layers; n->H = hidden; n->HP = (hidden + 31) / 32 * 32;
   n->prec_fwd = n->prec_bwd = n->prec_dw = 0;
   n->wide = pick_wide(n);
+  n->first_layer = PINN_FIRST_LAYER_TANH;
+  n->shared = new (std::nothrow) NetShared;
+  if (!n->shared) { delete n; return fail(-12, "pinn_net_create: out of host memory%s"); }
+  n->shared->refs = 1; n->shared->first_layer = PINN_FIRST_LAYER_TANH;
   *out = n;
   return 0;
 }
+int pinn_net_set_first_layer(pinn_net_t net, int kind) {
+  if (!net) return fail(-22, "pinn_net_set_first_layer: null net%s");
+  if (kind != PINN_FIRST_LAYER_TANH && kind != PINN_FIRST_LAYER_SINE)
+    return fail(-22, "pinn_net_set_first_layer: kind must be 0 (tanh) or 1 (frozen sine), got %s%ld", "", (long)kind);
+  if (kind == PINN_FIRST_LAYER_SINE) {
+    if (net->H % 2) return fail(-22, "pinn_net_set_first_layer: the frozen sine layer pairs a cosine with a sine row: the hidden width must be even (got %s%ld)", "", (long)net->H);
+    if (net->L < 2)
+      return fail(-22, "pinn_net_set_first_layer: the frozen sine layer needs at least 2 hidden layers (the output layer's gradient is formed from the last hidden layer by the tanh rule)%s");
+  }
+  net->first_layer = kind;
+  net->shared->first_layer = kind;
+  return 0;
+}
+int pinn_net_first_layer(pinn_net_t net) { return net ? net->first_layer : -1; }
 int pinn_net_set_precision(pinn_net_t net, int prec_fwd, int prec_bwd, int prec_dw) {
   if (!net) return fail(-22, "pinn_net_set_precision: null net%s");
   if (prec_fwd < 0 || prec_fwd > 2 || prec_bwd < 0 || prec_bwd > 2 || prec_dw < 0 || prec_dw > 2)
@@ -455,7 +493,11 @@ int pinn_net_set_precision(pinn_net_t net, int prec_fwd, int prec_bwd, int prec_
   net->wide = pick_wide(net);
   return 0;
 }
-int pinn_net_destroy(pinn_net_t net) { delete net; return 0; }
+int pinn_net_destroy(pinn_net_t net) {
+  if (net) shared_release(net->shared);
+  delete net;
+  return 0;
+}
 int64_t pinn_net_num_params(pinn_net_t net) { return net ? (int64_t)flat_total(net->H, net->L, net->n_out) : -1; }
 int64_t pinn_net_prep_floats(pinn_net_t net) { return net ? (int64_t)prep_total(net->HP, net->L) : -1; }
 
@@ -474,6 +516,7 @@ static int create_plan(pinn_net_t net, int64_t n_points, int streams, const Hard
   if (!p) return fail(-12, "pinn_plan_create: out of host memory%s");
   int rc = resolve_plan(p, *net, (long)n_points, streams, num_cus(), read_switches(), hbc, ptime);
   if (rc) { delete p; return rc; }
+  p->net.shared->refs.fetch_add(1);
   // The dynamic-LDS limit is per-device state of the HIP runtime and idempotent to raise; doing it here, per plan,
   // keeps the launch path free of cached "already configured" flags (no global mutable state; a process may drive
   // several devices and threads).
@@ -481,7 +524,7 @@ static int create_plan(pinn_net_t net, int64_t n_points, int streams, const Hard
   if (hipGetDeviceCount(&ndev) != hipSuccess) { ndev = 0; (void)hipGetLastError(); }
   if (ndev > 0) {     // (a host without a device can still size workspaces; it cannot launch anyway)
     rc = configure_plan(p);
-    if (rc) { delete p; return hipfail(rc, "pinn_plan_create(kernel attributes)"); }
+    if (rc) { shared_release(p->net.shared); delete p; return hipfail(rc, "pinn_plan_create(kernel attributes)"); }
   }
   *out = p;
   return 0;
@@ -543,7 +586,11 @@ int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out) {
   out->kind = h.kind; out->lift_power = h.m; out->x0 = h.x0; out->y0 = h.y0; out->inv_len = h.inv_len; out->lid_sharpness = h.r;
   return 0;
 }
-int pinn_plan_destroy(pinn_plan_t plan) { delete plan; return 0; }
+int pinn_plan_destroy(pinn_plan_t plan) {
+  if (plan) shared_release(plan->net.shared);
+  delete plan;
+  return 0;
+}
 int64_t pinn_plan_padded_points(pinn_plan_t plan) { return plan ? plan->npad : -1; }
 const char* pinn_plan_kernel(pinn_plan_t plan, int which) {
   if (!plan || which < 0 || which > 2) return nullptr;
@@ -556,7 +603,15 @@ int64_t pinn_plan_workspace_bytes(pinn_plan_t plan, int with_backward) {
 
 // A constrained plan takes the net's scaled derivatives for derivatives in the unit cavity's X, Y: the coordinate scale of
 // the call must undo the plan's inv_len.
+// A plan sees the first layer its net had when it was created; after pinn_net_set_first_layer changed the kind it
+// would compute another function than the net's other plans, so every launch refuses it.
+static int check_first_layer(const char* what, const pinn_plan_s* plan) {
+  if (plan->net.shared->first_layer.load() != plan->net.first_layer)
+    return fail(-22, "%s: the plan was created before the net's first-layer kind changed (pinn_net_set_first_layer): create it again", what);
+  return 0;
+}
 static int check_hard_bc_scale(const char* what, const pinn_plan_s* plan, float coord_scale) {
+  if (int rc = check_first_layer(what, plan)) return rc;
   if (plan->ptime && !plan->anchor)     // (every residual call comes through here)
     return fail(-22, "%s: the plan's pseudo-time anchors are unset (pinn_plan_set_pseudo_time)", what);
   if (plan->hbc.kind && !(std::fabs((double)coord_scale * (double)plan->hbc.inv_len - 1.0) <= 1e-6))
@@ -652,6 +707,7 @@ int pinn_value_forward(pinn_plan_t plan, void* ws, const float* prep,
                        int save, float* loss_sums, void* stream) {
   if (!plan || !ws || !prep || !x || !y) return fail(-22, "pinn_value_forward: null argument%s");
   if (plan->streams != 1) return fail(-22, "pinn_value_forward: plan is not a value (1-stream) plan%s");
+  if (int rc = check_first_layer("pinn_value_forward", plan)) return rc;
   FwdArgs a = fwd_args(plan, ws, prep, x, y, save, 1.f);
   for (int c = 0; c < 3; ++c) {
     a.pred[c] = (pred3 && c < a.n_out) ? pred3[c] : nullptr;
@@ -669,6 +725,7 @@ int pinn_value_backward(pinn_plan_t plan, void* ws, const float* prep,
                         const float* x, const float* y, const float* out_adj, void* stream) {
   if (!plan || !ws || !prep || !x || !y) return fail(-22, "pinn_value_backward: null argument%s");
   if (plan->streams != 1) return fail(-22, "pinn_value_backward: plan is not a value (1-stream) plan%s");
+  if (int rc = check_first_layer("pinn_value_backward", plan)) return rc;
   BwdArgs a = bwd_args(plan, ws, prep, x, y, 1.f);
   a.oadj = out_adj ? out_adj : WS(plan, off_oadj);
   int rc = run_bwd(plan, a, (hipStream_t)stream);
@@ -686,6 +743,8 @@ static int reduce_sources(const char* who, const pinn_net_s* net, int nsrc, cons
     if (!p || !ws) return fail(-22, "%s: null plan/workspace", who);
     if (p->net.H != net->H || p->net.L != net->L || p->net.n_out != net->n_out)  // (precision may differ)
       return fail(-22, "%s: plan belongs to a different net", who);
+    if (p->net.first_layer != net->first_layer)
+      return fail(-22, "%s: the plan was created before the net's first-layer kind changed (pinn_net_set_first_layer): create it again", who);
     src[k].slabs = WS(p, off_slabs); src[k].groups = p->groups;
     src[k].sg = WS(p, off_sg); src[k].nwg = p->role[ROLE_BWD].grid;
   }
@@ -700,6 +759,7 @@ int pinn_grad_reduce(pinn_net_t net, int nsrc, const pinn_plan_t* plans, void* c
   memset(&r, 0, sizeof(r));
   r.nsrc = nsrc; r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
   r.grads = grads; r.accumulate = accumulate;
+  r.frozen = is_ff(*net) ? 3 * net->H : 0;
   if (int rc = reduce_sources("pinn_grad_reduce", net, nsrc, plans, wss, r.src)) return rc;
   int rc = launch_reduce(r, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_grad_reduce") : 0;
@@ -818,6 +878,7 @@ static int reduce_terms(const char* what, pinn_net_t net, const int* nsrc3, cons
   if (!plans || !wss) return fail(-22, "%s: null argument", what);
   r.H = net->H; r.HP = net->HP; r.L = net->L; r.n_out = net->n_out;
   r.acc_mask = accumulate_mask & 7; r.partials = partials; r.gram = gram;
+  r.frozen = is_ff(*net) ? 3 * net->H : 0;
   if (int rc = reduce_sources(what, net, total, plans, wss, r.src)) return rc;
   int rc = launch_reduce_terms(r, (hipStream_t)stream);
   return rc ? hipfail(rc, what) : 0;

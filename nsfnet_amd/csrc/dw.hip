@@ -24,8 +24,10 @@ template <> struct DwCfg<6> { static constexpr int TM = 2, TN = 3; };
 template <> struct DwCfg<7> { static constexpr int TM = 1, TN = 7; };
 template <> struct DwCfg<8> { static constexpr int TM = 4, TN = 2; };
 
-template <int HP, int NS>
-__global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
+// A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
+// the A operand is taken straight from it, no chain rule.  A template parameter chosen per workgroup (dw_kernel).
+template <int HP, int NS, bool A0>
+__device__ __forceinline__ void dw_body(const DwArgs& a) {
   constexpr int T = HP / 32;
   constexpr int TM = DwCfg<T>::TM, TN = DwCfg<T>::TN;
   constexpr int WN = T / TN;          // waves along N; waves along M = T / TM; WM*WN == T
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
         float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         a0[e] = t; a1[e] = d1 * zx; a2[e] = d1 * zy; a3[e] = d2 * (zx * zx + zy * zy) + d1 * 0.f;
       }
-    } else if (NS == 4) {
+    } else if (NS == 4 && !A0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = sr[0][e], zx = sr[1][e], zy = sr[2][e], zd = sr[3][e];
@@ -143,18 +145,26 @@ __global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
       }
 }
 
+// FF: the layer-1 workgroups (blockIdx.y == 0) of a plan over a frozen sine first layer run the A0 body
+template <int HP, int NS, bool FF = false>
+__global__ __launch_bounds__(HP * 2) void dw_kernel(DwArgs a) {
+  if (FF && blockIdx.y == 0) dw_body<HP, NS, true>(a);
+  else dw_body<HP, NS, false>(a);
+}
+
 size_t dw_lds_bytes(int HP) { return (size_t)2 * 2 * 32 * (HP + 4) * sizeof(float); }
 int dw_threads(int HP) { return HP * 2; }
 
-template <int HP, int NS>
+template <int HP, int NS, bool FF = false>
 static int launch_one(const DwArgs& a, hipStream_t s) {
   size_t lds = dw_lds_bytes(HP);
-  if (!spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&dw_kernel<HP, NS>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
+  if (!spill_is(a.spill, act_block(HP), NS == 4 && !FF ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
+  return launch_or_configure(&dw_kernel<HP, NS, FF>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define DW_CASE(hp)                                                         \
   case hp:                                                                  \
+    if (NS == 4 && a.ff) return launch_one<hp, 4, true>(a, s);             \
     return NS == 4 ? launch_one<hp, 4>(a, s) : launch_one<hp, 1>(a, s);
 
 int launch_dw(int HP, int NS, const DwArgs& a, hipStream_t s) {

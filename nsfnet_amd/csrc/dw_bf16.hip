@@ -42,12 +42,15 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 // are in the 24-bit format (Spill::quad).  Template parameters, not run-time flags: the steady-state loop must stay one
 // basic block (see below).  The fp32 format with an unstored layer 0 has no reader here: no plan pairs SPILL_SKIP0 with
 // a bf16 dW kernel, and the launcher refuses it.
-template <int HP, int NS, int TERMS, int PPL, bool REC, bool P24>
+// A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
+// the A operand is taken straight from it, no chain rule.  Chosen per workgroup like REC.
+template <int HP, int NS, int TERMS, int PPL, bool REC, bool P24, bool A0 = false>
 __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
   constexpr int CPT = PPL / 8;                 // 32-column chunks per tile
   constexpr size_t ABLK = act_block(HP, 4 * PPL);
   using DI = DwImg<HP>;
   static_assert(P24 || !REC, "no fp32-format reader that recomputes layer 0");
+  static_assert(!A0 || (!REC && !P24 && NS == 4), "a stored sine layer: SPILL_CLASSIC, residual mode");
   constexpr int T = HP / 32;
   constexpr int TM = DwCfgB<T>::TM, TN = DwCfgB<T>::TN;
   constexpr int WN = T / TN;
@@ -131,7 +134,7 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
         const float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * (zx * zx + zy * zy);
       }
-    } else if (NS == 4) {
+    } else if (NS == 4 && !A0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = sr[0][e], zx = sr[1][e], zy = sr[2][e], zd = sr[3][e];
@@ -278,10 +281,16 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
 }
 
 // P24: 24-bit format; REC0: layer 0 is not stored, so the layer-1 workgroups recompute it
-template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0>
+// FF: the plan's net has the frozen sine first layer, so the layer-1 workgroups run the A0 body
+template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0, bool FF = false>
 __global__ __launch_bounds__(HP * 2) void dw_bf16_kernel(DwArgs a) {
-  if (REC0 && blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, REC0, P24>(a);
-  else dw_bf16_body<HP, NS, TERMS, PPL, false, P24>(a);
+  if constexpr (FF) {
+    if (blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, false, false, true>(a);
+    else dw_bf16_body<HP, NS, TERMS, PPL, false, false>(a);
+  } else {
+    if (REC0 && blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, REC0, P24>(a);
+    else dw_bf16_body<HP, NS, TERMS, PPL, false, P24>(a);
+  }
 }
 
 template <int HP>
@@ -295,10 +304,10 @@ size_t dw_bf16_lds_bytes(int HP) {
   }
 }
 
-template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0>
+template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0, bool FF = false>
 static int launch_fmt(const DwArgs& a, hipStream_t s) {
   size_t lds = lds_bytes_t<HP>();
-  return launch_or_configure(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24, REC0>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&dw_bf16_kernel<HP, NS, TERMS, PPL, P24, REC0, FF>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
 }
 // The two formats this kernel reads: SPILL_CLASSIC, and - where the role-split pair runs, hidden 256 at 128-column
 // tiles in residual mode - SPILL_P24_COMPACT.  The 24-bit reader follows the quad field, the recompute the layer-0 field.
@@ -307,6 +316,9 @@ static int launch_one(const DwArgs& a, hipStream_t s) {
   constexpr bool CAN_COMPACT = HP == 256 && NS == 4 && PPL == 32;
   if (!spill_is(a.spill, act_block(HP, 4 * PPL), CAN_COMPACT ? IN_CLASSIC | IN_P24_COMPACT : IN_CLASSIC)) return -1000;
   const bool p24 = a.spill.quad == SPILL_QUAD_P24, rec0 = a.spill.skip0 != 0;
+  if constexpr (NS == 4) {
+    if (a.ff) return p24 || rec0 ? -1000 : launch_fmt<HP, 4, TERMS, PPL, false, false, true>(a, s);
+  }
   if constexpr (CAN_COMPACT) {
     if (p24 && rec0) return launch_fmt<HP, NS, TERMS, PPL, true, true>(a, s);
   }

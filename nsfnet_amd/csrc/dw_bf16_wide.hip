@@ -23,8 +23,10 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 
 // P24: S / Z-bar in the 24-bit three-plane spill format (Spill::quad; residual mode only) - a template parameter, the
 // steady-state loop must stay one basic block
-template <int NS, int TERMS, bool P24>
-__global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
+// A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
+// the A operand is taken straight from it.  A template parameter chosen per workgroup (dw_bf16_wide_kernel).
+template <int NS, int TERMS, bool P24, bool A0>
+__device__ __forceinline__ void dw_bf16_wide_body(const DwArgs& a, int HP) {
   constexpr int TM = 4, TN = 2, WN = 4, PPL = 16, CPT = PPL / 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, i32 = lane & 31, h = lane >> 5;
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
       for (int s = 0; s < 4; ++s) { zr[s] = unpack24_plane(zp, s); sr[s] = unpack24_plane(sp, s); }
     }
     f32x4 av[4];
-    if (NS == 4) {
+    if (NS == 4 && !A0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = sr[0][e], zx = sr[1][e], zy = sr[2][e], zd = sr[3][e];
@@ -185,13 +187,24 @@ __global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
     }
 }
 
+// FF: the layer-1 workgroups (blockIdx.y == 0) of a plan over a frozen sine first layer run the A0 body
+template <int NS, int TERMS, bool P24, bool FF = false>
+__global__ __launch_bounds__(512) void dw_bf16_wide_kernel(DwArgs a, int HP) {
+  if (FF && blockIdx.y == 0) dw_bf16_wide_body<NS, TERMS, P24, true>(a, HP);
+  else dw_bf16_wide_body<NS, TERMS, P24, false>(a, HP);
+}
+
 size_t dw_bf16_wide_lds_bytes() { return DI::BYTES; }
 
 template <int NS, int TERMS, bool P24 = false>
 static int launch_one(int HP, const DwArgs& a, hipStream_t s) {
-  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
+  const bool ff = NS == 4 && a.ff;
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 && !ff ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
   if (!P24 && NS == 4 && a.spill.quad == SPILL_QUAD_P24) return launch_one<NS, TERMS, NS == 4>(HP, a, s);
   const int nblk = (HP / 32 + 7) / 8;
+  if constexpr (NS == 4 && !P24) {
+    if (ff) return launch_or_configure(&dw_bf16_wide_kernel<4, TERMS, false, true>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
+  }
   return launch_or_configure(&dw_bf16_wide_kernel<NS, TERMS, P24>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
 }
 

@@ -5,8 +5,10 @@
 #include "kernels.h"
 #include "spill_io.h"
 
-template <int NS>
-__global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
+// A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
+// the A operand is taken straight from it.  A template parameter chosen per workgroup (dw_wide_kernel).
+template <int NS, bool A0>
+__device__ __forceinline__ void dw_wide_body(const DwArgs& a, int HP) {
   constexpr int TM = 4, TN = 2, WN = 4, LDW = 260, CH = 32, PPL = 16;
   extern __shared__ float lds[];
   float* Zs = lds;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
         float d1 = 1.f - t * t, d2 = -2.f * t * d1;
         a0[e] = t; a1[e] = d1 * zx; a2[e] = d1 * zy; a3[e] = d2 * (zx * zx + zy * zy);
       }
-    } else if (NS == 4) {
+    } else if (NS == 4 && !A0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = sr[0][e], zx = sr[1][e], zy = sr[2][e], zd = sr[3][e];
@@ -130,14 +132,23 @@ __global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
     }
 }
 
+// FF: the layer-1 workgroups (blockIdx.y == 0) of a plan over a frozen sine first layer run the A0 body
+template <int NS, bool FF = false>
+__global__ __launch_bounds__(512) void dw_wide_kernel(DwArgs a, int HP) {
+  if (FF && blockIdx.y == 0) dw_wide_body<NS, true>(a, HP);
+  else dw_wide_body<NS, false>(a, HP);
+}
+
 size_t dw_wide_lds_bytes() { return (size_t)2 * 2 * 32 * 260 * sizeof(float); }
 
 int launch_dw_wide(int HP, int NS, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
   const int T = HP / 32, nblk = (T + 7) / 8;
   size_t lds = dw_wide_lds_bytes();
-  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
+  const bool ff = NS == 4 && a.ff;
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 && !ff ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
   dim3 grid(a.groups, a.L - 1, nblk * nblk);
+  if (ff) return launch_or_configure(&dw_wide_kernel<4, true>, grid, dim3(512), lds, s, a.configure, a, HP);
   if (a.configure) {   // raises the limit of both stream counts' kernels, whichever the plan has
     int rc = launch_or_configure(&dw_wide_kernel<4>, grid, dim3(512), lds, s, 1, a, HP);
     return rc ? rc : launch_or_configure(&dw_wide_kernel<1>, grid, dim3(512), lds, s, 1, a, HP);

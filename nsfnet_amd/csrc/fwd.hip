@@ -16,7 +16,9 @@
 #include "spill_io.h"
 #include "point_stage.h"
 
-template <int HP, int NS, bool HBC = false, bool PT = false>
+// FF: the first layer is the frozen sine layer (spill_io.h layer0_sine): for l == 0 the epilogue applies its map in place
+// of the tanh chain rule and saves the a-streams; layers >= 1 run the code below unchanged.
+template <int HP, int NS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
   constexpr int NW = HP / 32;
   constexpr int NT = HP * 2;
@@ -73,7 +75,19 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
           const int r = 4 * g + e;
           const int o = ob + 8 * g + 4 * h + e;
           float* Xo = X + o * 128 + col;
-          if (NS == 4) {
+          if (FF && l == 0) {      // (uniform)
+            if (NS == 4) {
+              float a0, a1, a2, a3;
+              layer0_sine(acc[0][r], acc[1][r], acc[2][r], SinCosLibm(), a0, a1, a2, a3);
+              Xo[0] = a0; Xo[32] = a1; Xo[64] = a2; Xo[96] = a3;
+              s0[e] = a0; s1[e] = a1; s2[e] = a2; s3[e] = a3;
+            } else {
+              float t0 = layer0_sine_value(acc[0][r], SinCosLibm()), t1 = layer0_sine_value(acc[1][r], SinCosLibm());
+              float t2 = layer0_sine_value(acc[2][r], SinCosLibm()), t3 = layer0_sine_value(acc[3][r], SinCosLibm());
+              Xo[0] = t0; Xo[32] = t1; Xo[64] = t2; Xo[96] = t3;
+              s0[e] = t0; s1[e] = t1; s2[e] = t2; s3[e] = t3;
+            }
+          } else if (NS == 4) {
             float t = tanhf(acc[0][r]);
             float zx = acc[1][r], zy = acc[2][r], zd = acc[3][r];
             float d1 = 1.f - t * t;
@@ -172,15 +186,16 @@ __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
 
 size_t fwd_lds_bytes(int HP) { return ((size_t)HP * 128 + (size_t)(HP / 32) * 4 * 128 + 4 * 128) * sizeof(float); }
 
-template <int HP, int NS, bool HBC = false, bool PT = false>
+template <int HP, int NS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_lds_bytes(HP);
-  if (a.S && !spill_is(a.spill, act_block(HP), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  if (a.S && !spill_is(a.spill, act_block(HP), NS == 4 && !FF ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
+  return launch_or_configure(&fwd_kernel<HP, NS, HBC, PT, FF>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define FWD_CASE(hp)                                                        \
   case hp:                                                                  \
+    if (a.ff) return a.hbc.kind || (NS == 4 && a.ptime) ? -1000 : NS == 4 ? launch_one<hp, 4, false, false, true>(a, grid, s) : launch_one<hp, 1, false, false, true>(a, grid, s); \
     if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
     if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
     return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);

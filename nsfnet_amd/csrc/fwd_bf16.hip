@@ -20,7 +20,8 @@
 // COLS = 64 : tile = 16 points x 4 streams (two streams per 32-column accumulator tile, exchanged
 //             with v_permlane16_swap before the lane-local epilogue); half the LDS and <= 128 VGPRs,
 //             so two workgroups share a CU and cover each other's epilogue / spill / MFMA phases.
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
+// FF: the frozen sine first layer (fwd.hip, spill_io.h layer0_sine), on the hardware sine / cosine (SinCosFast)
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd_bf16_kernel(FwdArgs a) {
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
@@ -117,6 +118,15 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
       };
       auto chain = [&](float z, float zx, float zy, float zd, int e, f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3,
                        f32x4& s0, f32x4& s1, f32x4& s2, f32x4& s3) {
+        if constexpr (FF) {      // (discarded without FF: the lambda does not even capture l there)
+          if (l == 0) {          // (uniform; z-streams of layer 0: zx = w0x, zy = w0y)
+            float f0, f1, f2, f3;
+            layer0_sine(z, zx, zy, SinCosFast(), f0, f1, f2, f3);
+            a0[e] = f0; a1[e] = f1; a2[e] = f2; a3[e] = f3;
+            s0[e] = f0; s1[e] = f1; s2[e] = f2; s3[e] = f3;
+            return;
+          }
+        }
         float t = fast_tanh(z);
         float d1 = 1.f - t * t;
         float d2 = -2.f * t * d1;
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd
           for (int g = 0; g < 4; ++g) {
             f32x4 t4;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t4[e] = fast_tanh(acc[j][4 * g + e]);
+            for (int e = 0; e < 4; ++e) t4[e] = FF && l == 0 ? layer0_sine_value(acc[j][4 * g + e], SinCosFast()) : fast_tanh(acc[j][4 * g + e]);
             const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
             restage<XI, TERMS>(Xb, plane, off, t4);
             if (Sl) {
@@ -290,15 +300,19 @@ size_t fwd_bf16_lds_bytes(int HP, int L, int cols) {
 #undef LB
 }
 
-template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
+template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP, COLS>(a.L);
   if (a.S && !spill_is(a.spill, act_block(HP, COLS), IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_bf16_kernel<HP, NS, TERMS, COLS, HBC, PT, FF>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
+  if (a.ff) {
+    if (a.hbc.kind || (NS == 4 && a.ptime)) return -1000;
+    return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS, false, false, true>(a, grid, s); });
+  }
   if (NS == 4 && a.ptime)
     return dispatch_ns_terms(4, terms, [&](auto, auto t) {
       return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, COLS, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, COLS, false, true>(a, grid, s);

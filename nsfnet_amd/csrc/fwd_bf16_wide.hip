@@ -17,7 +17,8 @@
 #include "wave8_bodies.h"
 #include <type_traits>
 
-template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
+// FF: the frozen sine first layer (fwd.hip, spill_io.h layer0_sine), on the hardware sine / cosine (SinCosFast)
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel(FwdArgs a) {
   constexpr int COLS = 64, PPL = 16, NTL = 2, MT = 2;
   using XI = XImg<HP, PPL>;
@@ -112,6 +113,13 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
             for (int e = 0; e < 4; ++e) {
               const int q = 4 * gq + e;
               float z = acc[m][0][q], zx = acc[m][0][q + 8], zy = acc[m][1][q], zd = acc[m][1][q + 8];
+              if (FF && l == 0) {      // (uniform; z-streams of layer 0: zx = w0x, zy = w0y)
+                float f0, f1, f2, f3;
+                layer0_sine(z, zx, zy, SinCosFast(), f0, f1, f2, f3);
+                a0[e] = f0; a1[e] = f1; a2[e] = f2; a3[e] = f3;
+                s0[e] = f0; s1[e] = f1; s2[e] = f2; s3[e] = f3;
+                continue;
+              }
               float t = fast_tanh(z);
               float d1 = 1.f - t * t;
               float d2 = -2.f * t * d1;
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
             for (int g = 0; g < 4; ++g) {
               f32x4 t4;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) t4[e] = fast_tanh(acc[m][j][4 * g + e]);
+              for (int e = 0; e < 4; ++e) t4[e] = FF && l == 0 ? layer0_sine_value(acc[m][j][4 * g + e], SinCosFast()) : fast_tanh(acc[m][j][4 * g + e]);
               const int off = XI::chunk_off(pp, (ob >> 3) + g) + 8 * h;
               restage<XI, TERMS>(Xb, plane, off, t4);
               if (Sl) {
@@ -278,15 +286,19 @@ size_t fwd_bf16_wide_lds_bytes(int HP, int L) {
 }
 int fwd_bf16_wide_threads(int HP) { return ((HP / 32 + 1) / 2) * 64; }
 
-template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int NS, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = lds_bytes_t<HP>(a.L);
-  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_bf16_wide_kernel<HP, NS, TERMS, HBC, PT>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
+  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 && !FF ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
+  return launch_or_configure(&fwd_bf16_wide_kernel<HP, NS, TERMS, HBC, PT, FF>, dim3(grid), dim3(((HP / 32 + 1) / 2) * 64), lds, s, a.configure, a);
 }
 
 template <int HP>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
+  if (a.ff) {
+    if (a.hbc.kind || (NS == 4 && a.ptime)) return -1000;
+    return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, false, false, true>(a, grid, s); });
+  }
   if (NS == 4 && a.ptime)
     return dispatch_ns_terms(4, terms, [&](auto, auto t) {
       return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, false, true>(a, grid, s);

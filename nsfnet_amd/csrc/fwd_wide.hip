@@ -12,7 +12,8 @@
 #include "spill_io.h"
 #include "point_stage.h"
 
-template <int HP, int NS, bool HBC = false, bool PT = false>
+// FF: the frozen sine first layer (fwd.hip, spill_io.h layer0_sine)
+template <int HP, int NS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
   constexpr int NW = HP / 32, NT = HP * 2, COLS = 64, PPL = 16, NQ = HP / 8;
   constexpr int PRE = 4, RING = 8;
@@ -83,11 +84,18 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
           for (int e = 0; e < 4; ++e) {
             const int q = 4 * gq + e;
             const int o = ob + 8 * g + 4 * h + e;
+            float* Xo = X + o * COLS + pp;
+            if (FF && l == 0) {      // (uniform)
+              float a0, a1, a2, a3;
+              layer0_sine(acc[0][q], acc[0][q + 8], acc[1][q], SinCosLibm(), a0, a1, a2, a3);
+              Xo[0] = a0; Xo[16] = a1; Xo[32] = a2; Xo[48] = a3;
+              s0[e] = a0; s1[e] = a1; s2[e] = a2; s3[e] = a3;
+              continue;
+            }
             float t = tanhf(acc[0][q]);
             float zx = acc[0][q + 8], zy = acc[1][q], zd = acc[1][q + 8];
             float d1 = 1.f - t * t;
             float d2 = -2.f * t * d1;
-            float* Xo = X + o * COLS + pp;
             Xo[0] = t; Xo[16] = d1 * zx; Xo[32] = d1 * zy;
             Xo[48] = d2 * (zx * zx + zy * zy) + d1 * zd;
             s0[e] = t; s1[e] = zx; s2[e] = zy; s3[e] = zd;
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int o = ob + 8 * g + 4 * h + e;
-              float t = tanhf(acc[j][4 * g + e]);
+              float t = FF && l == 0 ? layer0_sine_value(acc[j][4 * g + e], SinCosLibm()) : tanhf(acc[j][4 * g + e]);
               X[o * COLS + 32 * j + c] = t;
               s[e] = t;
             }
@@ -183,15 +191,16 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
 
 size_t fwd_wide_lds_bytes(int HP) { return ((size_t)HP * 64 + (size_t)(HP / 32) * 4 * 64 + 4 * 64) * sizeof(float); }
 
-template <int HP, int NS, bool HBC = false, bool PT = false>
+template <int HP, int NS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   size_t lds = fwd_wide_lds_bytes(HP);
-  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
-  return launch_or_configure(&fwd_wide_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
+  if (a.S && !spill_is(a.spill, act_block(HP, 64), NS == 4 && !FF ? IN_CLASSIC | IN_SKIP0 : IN_CLASSIC)) return -1000;
+  return launch_or_configure(&fwd_wide_kernel<HP, NS, HBC, PT, FF>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
 #define FWD_CASE(hp)                                                        \
   case hp:                                                                  \
+    if (a.ff) return a.hbc.kind || (NS == 4 && a.ptime) ? -1000 : NS == 4 ? launch_one<hp, 4, false, false, true>(a, grid, s) : launch_one<hp, 1, false, false, true>(a, grid, s); \
     if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
     if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
     return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);

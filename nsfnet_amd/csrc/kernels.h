@@ -83,6 +83,8 @@ struct FwdArgs {
   int configure;         // 1: do not launch, only raise the kernel's dynamic-LDS limit (pinn_plan_create)
   Spill spill;           // the plan's S / Z-bar format (spill.h)
   HardBc hbc;            // kind != 0: the 8-wave, role-split and fused families launch their constrained instantiation
+  int ff;                // != 0: the net's first layer is the frozen sine layer (spill_io.h layer0_sine); the 8-wave families
+                         // launch their FF instantiation, which saves layer 0's a-streams.  Never with hbc.kind or ptime.
 };
 
 struct BwdArgs {
@@ -117,6 +119,8 @@ struct DwArgs {
   // points, the prepared parameters (w0x | w0y | b0 lead them) and n
   const float* x; const float* y; const float* prep; int n;
   Spill spill;           // see FwdArgs
+  int ff;                // != 0 (residual mode): layer 0's stored quad holds its a-streams; the layer-1 workgroups run the
+                         // instantiation that takes the A operand straight from it (see FwdArgs)
 };
 
 struct ReduceSrc { const float* slabs; int groups; const float* sg; int nwg; };
@@ -124,6 +128,8 @@ struct ReduceArgs {
   ReduceSrc src[4]; int nsrc;
   int H, HP, L, n_out;
   float* grads; int accumulate;
+  int frozen;            // the first `frozen` flat parameters are not trained (a frozen sine first layer: 3 H): their entries
+                         // are written as +0.0 whatever the sources hold and whether or not the call accumulates
 };
 
 // Where flat parameter p (state_dict order) finds its partials: a row of the dW slabs of layer `layer` (>= 1) at
@@ -180,6 +186,7 @@ struct TermReduceArgs {
   float* out[3]; int acc_mask;
   double* partials;
   double* gram;
+  int frozen;            // see ReduceArgs; partials and gram see the zeros
 };
 
 // The six dot products of the 64 (r, b, s) a full wave holds, one triple per lane: exact fp64 products of the fp32

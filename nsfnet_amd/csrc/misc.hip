@@ -97,8 +97,9 @@ __global__ __launch_bounds__(512) void reduce_kernel(ReduceArgs a) {
   const size_t p = blockIdx.x * (size_t)64 + lane;
   const bool live = p < P;
   const ReduceLoc loc = live ? reduce_locate(p, H, HP, L, a.n_out) : ReduceLoc{-1, -1, 0};
+  const bool frozen = p < (size_t)a.frozen;      // (a frozen first layer: its partials are finite and discarded)
   double s = 0.0;
-  if (live) {
+  if (live && !frozen) {
     const size_t SG = sg_total(HP, L);
     for (int k = 0; k < a.nsrc; ++k) s = reduce_source_add(s, a.src[k], loc, HP, SG, w);
   }
@@ -108,7 +109,8 @@ __global__ __launch_bounds__(512) void reduce_kernel(ReduceArgs a) {
     double t = part[0][lane];
 #pragma unroll
     for (int i = 1; i < 8; ++i) t += part[i][lane];
-    if (a.accumulate) a.grads[p] += (float)t; else a.grads[p] = (float)t;
+    if (frozen) a.grads[p] = 0.f;
+    else if (a.accumulate) a.grads[p] += (float)t; else a.grads[p] = (float)t;
   }
 }
 

@@ -19,6 +19,9 @@
 //   SPILL_P24_COMPACT  p24   3/4 ablk  1      1      fwd_bf16_split, bwd_bf16_split, bwd_bf16_split, fwdbwd_bf16_split,
 //                                                    fwdbwd_bf16_split               dw_bf16: all recompute layer 0
 //
+// A plan over a net with the frozen sine first layer (kernels.h FwdArgs::ff) is SPILL_CLASSIC in every precision, and what
+// its layer-0 block of S holds is that layer's a-streams (a, a_x, a_y, a_D) themselves: dW's layer-1 workgroups take
+// their A operand straight from it, and nothing recomputes a sine layer.
 // Z-bar of layer 0 is never stored in any layout (dW_0 is accumulated by the reverse sweep itself); with first == 0 its
 // slot exists and stays unused.
 #pragma once

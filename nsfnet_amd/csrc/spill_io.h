@@ -55,6 +55,27 @@ __device__ __forceinline__ void layer0_saved(const f32x4& wx, const f32x4& wy, c
   s1 = wx; s2 = wy; s3 = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// ---- layer 0, frozen sine (the Fourier-feature first layer; include/nsfnet_pinn.h) -------------------
+// The single statement of the layer: from its pre-activation z (layer0_z) and its weights, the four a-streams
+//   a = sin z,  a_x = cos z * w0x,  a_y = cos z * w0y,  a_D = -sin z * (w0x^2 + w0y^2)
+// with the sine / cosine pair of the caller's precision mode (SinCosLibm here, SinCosFast in bf16_util.h).  Every forward
+// kernel's FF instantiation calls this for l == 0; the quad it returns is also what an FF plan SAVES for layer 0 (the
+// a-streams themselves, not (t, z_x, z_y, z_D)), so the layer-1 dW workgroups read their A operand straight from it.
+struct SinCosLibm { __device__ __forceinline__ void operator()(float z, float& s, float& c) const { s = sinf(z); c = cosf(z); } };
+template <class SinCos>
+__device__ __forceinline__ void layer0_sine(float z, float wx, float wy, SinCos sc, float& a, float& ax, float& ay, float& ad) {
+  float s, c;
+  sc(z, s, c);
+  a = s; ax = c * wx; ay = c * wy; ad = -s * fmaf(wx, wx, wy * wy);
+}
+// value mode: only a
+template <class SinCos>
+__device__ __forceinline__ float layer0_sine_value(float z, SinCos sc) {
+  float s, c;
+  sc(z, s, c);
+  return s;
+}
+
 // ---- SPILL_QUAD_P24: the 24-bit format ------------------------------------------------------------------------------
 // The bf16x3 operand split consumes 16 significant bits of a value (bf16 hi + bf16 lo); the spilled activations and
 // z-adjoints are read back only to be split (MFMA operands) or to enter chain-rule products whose other factors are

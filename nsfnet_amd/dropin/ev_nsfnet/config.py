@@ -2,7 +2,7 @@
 (config.py:9-178: cfg.physics / cfg.network / cfg.training{.sdf_weighting,.training_stages} /
 cfg.supervision, ConfigManager.from_file / print_config / validate_config)."""
 from dataclasses import dataclass, field, fields, is_dataclass
-from typing import List
+from typing import List, Optional
 
 import yaml
 
@@ -16,11 +16,20 @@ class PhysicsConfig:
 
 
 @dataclass
+class FourierFeaturesConfig:
+    """Random Fourier features as the main net's first layer, frozen (PinnEngine.set_fourier_features):
+    `network.fourier_features: {sigma: 1.0, seed: 0}`.  Absent (the default): off.  sigma's default is a guess."""
+    sigma: float = 1.0
+    seed: int = 0
+
+
+@dataclass
 class NetworkConfig:
     layers: int = 6
     layers_1: int = 4
     hidden_size: int = 80
     hidden_size_1: int = 40
+    fourier_features: Optional[FourierFeaturesConfig] = None      # absent = off
 
 
 @dataclass
@@ -240,6 +249,9 @@ def _fill(obj, data):
                                              warmup_epochs=int(s.get("warmup_epochs", 0)),
                                              warmup_start=float(s.get("warmup_start", 0.0)))
                                for s in (val or [])])
+        elif key == "fourier_features":          # absent, null or false: off
+            if val is not None and val is not False:
+                setattr(obj, key, _fill(FourierFeaturesConfig(), val))
         elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
             if val is not None and val is not False:
                 cur.enabled = True
@@ -293,6 +305,12 @@ class ConfigManager:
         wf = c.training.weight_factorization
         if wf.enabled and not (abs(wf.mean) < float("inf") and 0.0 <= wf.std < float("inf") and wf.seed >= 0):
             problems.append("training.weight_factorization: finite mean, finite std >= 0 and seed >= 0 required")
+        ff = c.network.fourier_features
+        if ff is not None and not (0.0 < ff.sigma < float("inf") and ff.seed >= 0 and c.network.hidden_size % 2 == 0 and
+                                   c.network.layers >= 2):
+            problems.append("network.fourier_features: finite sigma > 0, seed >= 0, an even hidden_size and layers >= 2 required")
+        if ff is not None and (c.training.hard_boundary.enabled or c.training.pseudo_time.enabled):
+            problems.append("network.fourier_features does not go together with training.hard_boundary or training.pseudo_time")
         hb = c.training.hard_boundary
         if hb.enabled and not 1 <= hb.lift_power <= 8:
             problems.append("training.hard_boundary: lift_power in 1..8 required")
@@ -346,6 +364,8 @@ class ConfigManager:
               % (c.physics.Re, c.physics.alpha_evm, c.physics.bc_weight, c.physics.eq_weight))
         print("network    : %dx%d (u,v,p) + %dx%d (e)"
               % (c.network.layers, c.network.hidden_size, c.network.layers_1, c.network.hidden_size_1))
+        if c.network.fourier_features is not None:
+            print("fourier    : sigma=%s seed=%d (first layer frozen)" % (c.network.fourier_features.sigma, c.network.fourier_features.seed))
         t = c.training
         print("training   : N_f=%d log_interval=%d sort=%s sdf=%s coord_transform=%s stages=%d"
               % (t.N_f, t.log_interval, t.sort_training_points, t.sdf_weighting.enabled, t.coordinate_transform,

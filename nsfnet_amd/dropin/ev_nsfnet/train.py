@@ -100,6 +100,9 @@ def main():
                                    sort_training_points=cfg.training.sort_training_points,
                                    sdf_weighting=cfg.training.sdf_weighting,
                                    coord_transform=cfg.training.coordinate_transform)
+        ff = cfg.network.fourier_features
+        if ff is not None:    # before any point set: every plan of the main net then sees the frozen sine first layer
+            PINN.set_fourier_features(sigma=ff.sigma, seed=ff.seed)
         hb = cfg.training.hard_boundary
         if hb.enabled:        # before any point set: every plan of the main net is then created constrained
             PINN.set_coordinate_transform(loader.get_coord_scale())

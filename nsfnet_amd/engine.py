@@ -50,6 +50,17 @@ def layer_shapes(n_out, n_hidden, hidden):
     return [(widths[i + 1], widths[i]) for i in range(len(widths) - 1)]
 
 
+def fourier_first_layer(B):
+    """(W0 fp32 [hidden, 2], b0 fp32 [hidden]) of the Fourier-feature embedding with frequencies B (fp64 [hidden / 2, 2];
+    DESIGN.md section 7.13): rows 2k and 2k + 1 of W0 are fp32(2 pi B_k), the biases fp32(pi / 2) and 0, so that
+    sin(W0 x + b0) is [cos(2 pi B_k x), sin(2 pi B_k x)] interleaved."""
+    B = torch.as_tensor(B, dtype=torch.float64)
+    w0 = (2.0 * math.pi * B).to(torch.float32).repeat_interleave(2, dim=0)
+    b0 = torch.zeros(2 * B.shape[0], dtype=torch.float32)
+    b0[0::2] = float(np.float32(math.pi / 2.0))
+    return w0, b0
+
+
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2}
 
 
@@ -75,6 +86,7 @@ class DeviceNet:
     params from it (compose) before prepare.  params stays what prepare, state_dict and every plan read."""
     theta = gtheta = None       # the factorization is off
     hard_bc = None              # _lib.HardBcStruct: every plan of this net is created constrained (PinnEngine.set_hard_boundary)
+    first_layer = 0             # 0 tanh | 1 frozen sine (set_first_layer; PinnEngine.set_fourier_features)
 
     def __init__(self, n_out, n_hidden, hidden, device, precision=None):
         self.lib = _lib.load()
@@ -100,6 +112,13 @@ class DeviceNet:
                 self.handle = None
         except Exception:
             pass
+
+    def set_first_layer(self, kind):
+        """The kind of layer 0: 0 tanh, 1 the frozen sine layer of a Fourier-feature
+        embedding.  It belongs to the net: every plan created from here on sees it, and the library refuses plans
+        created before a change.  The weights are the caller's to set (PinnEngine.set_fourier_features does both)."""
+        _lib.check(self.lib.pinn_net_set_first_layer(self.handle, int(kind)), "pinn_net_set_first_layer")
+        self.first_layer = int(self.lib.pinn_net_first_layer(self.handle))
 
     # ---- state_dict interop (checkpoint format of the reference) ----
     def keys_and_shapes(self):
@@ -1015,6 +1034,7 @@ class PinnEngine:
         self._rwf = None                    # random weight factorization (set_weight_factorization; None = off)
         self._val = None                    # device validation monitor (set_validation; None = off)
         self._pt = None                     # pseudo-time stepping (set_pseudo_time; None = off)
+        self._ff = None                     # frozen Fourier-feature first layer (set_fourier_features; None = off)
         self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
 
     # ---- what the evaluations are made for ----
@@ -1787,6 +1807,68 @@ class PinnEngine:
             out["layers"][name] = rows
         return out
 
+    # ---- frozen Fourier-feature first layer ----
+    def set_fourier_features(self, sigma=1.0, seed=0, frequencies=None):
+        """Random Fourier features (Tancik et al. 2020; Wang, Wang & Perdikaris 2021) as the main net's first layer:
+        gamma(x) = [cos(2 pi B x), sin(2 pi B x)] with B of shape (hidden / 2, 2), followed by the tanh layers 1 .. L-1.
+        That is this net with layer 0 on sin instead of tanh and frozen: rows 2k and 2k + 1 of W0 are both
+        fp32(2 pi B_k), their biases fp32(pi / 2) (the cosine) and 0 (the sine).  The call writes them into the flat
+        parameters - state_dict keeps its keys and shapes, every other layer the values it had - and sets the net's
+        first-layer kind, so every plan of the main net (collocation passes, batch, pool, boundary, supervised,
+        validation, predict) evaluates the same function.  The entropy net of the ev flavour keeps tanh.
+
+        B ~ Normal(0, sigma^2), drawn in fp64 from a torch.Generator of its own seeded with `seed`: the global
+        generators are not consumed and every rank draws the same B.  frequencies: the B to use instead of a draw.
+        sigma's default 1.0 is a guess; no value has been compared in training.
+
+        Layer 0 is not trained: its 3 * hidden entries lead every gradient vector as +0.0 (grads, the term vectors of
+        balancing and ConFIG, the L-BFGS gradient), so Adam, clipping and L-BFGS leave it where it is.  The plans run
+        the 8-wave kernel families.  Needs an even hidden width and at least 2 hidden layers; not available together
+        with hard walls or pseudo-time.  Must be called before any point set is attached (ValueError otherwise).
+        sigma = None without frequencies: off (layer 0 is tanh again and trainable; its weights stay as they are)."""
+        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val)):
+            raise ValueError("fourier features: call set_fourier_features before any point set is attached")
+        net = self.net
+        if sigma is None and frequencies is None:
+            net.set_first_layer(0)
+            self._ff = None
+            return
+        if net.hard_bc is not None or self._pt is not None:
+            raise ValueError("fourier features: not available together with hard walls or pseudo-time")
+        H = net.hidden
+        if H % 2:
+            raise ValueError("fourier features: the hidden width must be even (got %d)" % H)
+        if net.n_hidden < 2:
+            raise ValueError("fourier features: at least 2 hidden layers are needed (got %d)" % net.n_hidden)
+        if frequencies is not None:
+            B = torch.as_tensor(np.asarray(frequencies, dtype=np.float64))
+            if tuple(B.shape) != (H // 2, 2):
+                raise ValueError("fourier features: frequencies must have shape (%d, 2), got %s" % (H // 2, tuple(B.shape)))
+            sigma = seed = None
+        else:
+            sigma, seed = float(sigma), int(seed)
+            if not (math.isfinite(sigma) and sigma > 0.0):
+                raise ValueError("fourier features: sigma must be finite and > 0 (got %r)" % (sigma,))
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(seed)
+            B = sigma * torch.randn(H // 2, 2, generator=gen, dtype=torch.float64)
+        if not bool(torch.isfinite(B).all()):
+            raise ValueError("fourier features: frequencies must be finite")
+        w0, b0 = fourier_first_layer(B)
+        flat = net.params.detach().cpu().clone()
+        flat[:2 * H] = w0.reshape(-1)
+        flat[2 * H:3 * H] = b0
+        net.set_first_layer(1)
+        net.set_flat(flat)
+        self._ff = dict(sigma=sigma, seed=seed, frequencies=B.clone())
+
+    def fourier_info(self):
+        """dict(kind="sine", sigma, seed, frequencies=B as an fp64 (hidden / 2, 2) tensor) of set_fourier_features (sigma
+        and seed None where B was given); None when the option is off."""
+        if self._ff is None:
+            return None
+        return dict(kind="sine", sigma=self._ff["sigma"], seed=self._ff["seed"], frequencies=self._ff["frequencies"].clone())
+
     # ---- hard wall conditions by an output transform (DESIGN.md section 7.10) ----
     def set_hard_boundary(self, enabled=True, lift_power=2, lid_sharpness=10.0, origin=(0.0, 0.0), inv_len=1.0):
         """enabled: the no-slip walls and the lid of the lid-driven unit cavity hold exactly, by construction:
@@ -1810,6 +1892,8 @@ class PinnEngine:
         if not enabled:
             self.net.hard_bc = None
             return
+        if self.net.first_layer:
+            raise ValueError("hard boundary: not available together with fourier features")
         m = int(lift_power)
         if m != lift_power or not 1 <= m <= 8:
             raise ValueError("hard boundary: lift_power must be an integer in 1..8 (got %r)" % (lift_power,))
@@ -2314,7 +2398,8 @@ class PinnEngine:
             lbfgs_history=None if self._lbfgs is None else self._lbfgs.history_size, rwf=self._rwf is not None,
             hard_bc=None if self.hard_boundary_info() is None else
             {k: list(x) if isinstance(x, tuple) else x for k, x in self.hard_boundary_info().items()},
-            pseudo_time=self._pt is not None, world_size=self.world_size, rank=self._rank())
+            pseudo_time=self._pt is not None, world_size=self.world_size, rank=self._rank(),
+            first_layer="sine" if self.net.first_layer else None)
 
     def _state_info(self):
         """What a file records beside the structure; load_training_state reports the keys that differ."""

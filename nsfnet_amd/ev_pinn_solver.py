@@ -483,6 +483,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         torch.save(self.net_1.state_dict(), save_results_to + filename + '_evm')
         self.save_weight_factors(save_results_to + filename)
         self.save_hard_boundary(save_results_to + filename)
+        self.save_fourier_features(save_results_to + filename)
         self._save_best(save_results_to + filename)
 
     def neural_net_equations(self, x, y):

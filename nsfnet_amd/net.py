@@ -40,6 +40,12 @@ class FCNet:
         self.dev_net = _eng.DeviceNet(num_outs, num_layers, hidden_size, dev)
         self.dev_net.set_flat(init)
 
+    @property
+    def first_layer(self):
+        """The kind of layer 0: "tanh", or "sine" for the frozen Fourier-feature layer (PinnEngine.set_fourier_features;
+        DESIGN.md section 7.13).  forward evaluates whichever the net has: its value plan belongs to the same net."""
+        return "sine" if self.dev_net.first_layer else "tanh"
+
     # ---- torch.nn.Module-like surface used by the reference scripts ----
     def state_dict(self):
         return OrderedDict(self.dev_net.state_dict())

@@ -6,6 +6,7 @@ per-step work (``fwd_computing_loss_2d`` + ``loss.backward()`` + ``opt.step()``,
 pinn_solver.py:197-278) is executed by the HIP pipeline through nsfnet_amd.engine.
 There is no torch-autograd or CPU fallback.
 """
+import math
 import os
 
 import numpy as np
@@ -205,6 +206,21 @@ class SolverBase:
         self.engine.set_hard_boundary(enabled, lift_power=lift_power, lid_sharpness=lid_sharpness, origin=origin,
                                       inv_len=inv_len)
 
+    def set_fourier_features(self, sigma=1.0, seed=0, frequencies=None):
+        """Random Fourier features as the main net's first layer, frozen (PinnEngine.set_fourier_features; DESIGN.md
+        section 7.13): B ~ Normal(0, sigma^2) from a generator of its own seeded with `seed`, or the given
+        `frequencies`.  Call it before set_boundary_data / set_eq_training_data (ValueError once a point set is
+        attached).  Checkpoints keep the reference's format - layer 0's weights hold B - and save() adds the sidecar
+        <checkpoint>_fourier (kind, sigma, seed), which load() reads back.  sigma's default 1.0 is a guess."""
+        self.engine.set_fourier_features(sigma, seed, frequencies)
+
+    def save_fourier_features(self, path):
+        """Write the sidecar of the checkpoint at `path`: dict(kind, sigma, seed) as path + '_fourier' (torch.save).  With
+        the option off nothing is written."""
+        info = self.engine.fourier_info()
+        if info is not None:
+            torch.save(dict(kind=info["kind"], sigma=info["sigma"], seed=info["seed"]), path + '_fourier')
+
     def save_hard_boundary(self, path):
         """Write the sidecar of the checkpoint at `path`: the descriptor dict(lift_power, lid_sharpness, origin,
         inv_len) as path + '_hardbc' (torch.save).  With the constraint off nothing is written."""
@@ -363,6 +379,20 @@ class SolverBase:
                 except ValueError as err:
                     raise ValueError("checkpoint %s was trained with hard wall conditions %r, this solver holds %r: %s"
                                      % (path, bc, self.engine.hard_boundary_info(), err))
+        if os.path.exists(path + '_fourier'):
+            ff = torch.load(path + '_fourier', map_location="cpu", weights_only=True)
+            if ff.get("kind") != "sine":
+                raise ValueError("checkpoint %s: unknown first-layer kind %r in its _fourier sidecar" % (path, ff.get("kind")))
+            if self.engine.fourier_info() is None:
+                # the checkpoint's layer 0 holds 2 pi B in its even rows: taken up as the frequencies, which rewrites
+                # layer 0 with the values it has
+                w0 = self.net.state_dict()["layers.layer_0.weight"].to(torch.float64)
+                try:
+                    self.engine.set_fourier_features(frequencies=w0[0::2] / (2.0 * math.pi))
+                except ValueError as err:
+                    raise ValueError("checkpoint %s was trained with a Fourier-feature first layer: %s" % (path, err))
+                self.net.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))      # (bit for bit)
+                self.engine._ff.update(sigma=ff.get("sigma"), seed=ff.get("seed"))
         if self._pseudo_time and self.engine.plan_f is not None:       # anchors are not checkpointed
             self.engine.reset_pseudo_time()
 
@@ -692,6 +722,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         torch.save(self.net.state_dict(), save_results_to + filename)
         self.save_weight_factors(save_results_to + filename)
         self.save_hard_boundary(save_results_to + filename)
+        self.save_fourier_features(save_results_to + filename)
         self._save_best(save_results_to + filename)
         save_matlab_to = directory + '/loss/'
         os.makedirs(save_matlab_to, exist_ok=True)

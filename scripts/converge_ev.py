@@ -84,6 +84,10 @@ def main():
     ap.add_argument("--hard-bc", type=int, nargs="?", const=2, default=0, metavar="M",
                     help="hard wall conditions by the output transform u = g + D N_u, v = D N_v with lift power M "
                          "(default 2; DESIGN.md 7.10); a resumed slice must be given the same M")
+    ap.add_argument("--fourier", type=float, default=0.0, metavar="SIGMA",
+                    help="> 0: random Fourier features of scale SIGMA as the main net's first layer, frozen (DESIGN.md "
+                         "7.13); not with --hard-bc or --pseudo-time; a resumed slice must be given the same SIGMA")
+    ap.add_argument("--fourier-seed", type=int, default=0)
     ap.add_argument("--pseudo-time", type=float, nargs=2, default=None, metavar=("DTAU", "EVERY"),
                     help="pseudo-time stepping of the equation loss: step DTAU, anchors refreshed every EVERY updates "
                          "(DESIGN.md 7.11); not with --resample-every or --batch-points")
@@ -116,6 +120,8 @@ def main():
     loader = cavity.EvDataLoader(path="./datasets/", N_f=a.nf, N_b=1000, sort_training_points=False,
                                  sdf_weighting=SimpleNamespace(enabled=True, min_weight=0.2, decay=5.0),
                                  coord_transform=False)
+    if a.fourier > 0:                                   # before any point set is attached (the same seed redraws the same B)
+        P.set_fourier_features(sigma=a.fourier, seed=a.fourier_seed)
     if a.hard_bc:                                       # before any point set is attached
         P.set_coordinate_transform(loader.get_coord_scale())
         P.set_hard_boundary_constraints(lift_power=a.hard_bc, dataloader=loader)
