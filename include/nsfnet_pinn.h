@@ -66,8 +66,17 @@ int pinn_net_set_precision(pinn_net_t net, int prec_fwd, int prec_bwd, int prec_
  * The kind belongs to the net: every plan over it (residual, value) sees the same function.  A plan keeps the kind
  * its net had when it was created; after a change every launch on such a plan, and every gradient assembly from it,
  * is refused by name - create the plan again.
- * Plans of such a net run the 8-wave kernel families whatever PINN_SCHED / PINN_WSPLIT / PINN_FUSE say, and store
- * layer 0 (its a-streams) whatever PINN_S0_SKIP32 says; pinn_plan_kernel names the kernels as before.
+ * By default plans of such a net run the 8-wave kernel families whatever PINN_SCHED / PINN_WSPLIT / PINN_FUSE say, and
+ * store layer 0 (its a-streams) whatever PINN_S0_SKIP32 says; pinn_plan_kernel names the kernels as before.  With
+ * PINN_FF_SPLIT=1 in the environment when a residual (4-stream) plan is created it keeps the role-split (hidden 256),
+ * fused and wide role-split (hidden 288 .. 448) sweeps that PINN_SCHED, PINN_FWD_SCHED, PINN_BWD_SCHED, PINN_WSPLIT and
+ * PINN_FUSE give a tanh net's plan - the same names, workspace bytes and padded points - in variants whose forward forms
+ * layer 0 by the lines above and whose reverse sweep, the layer being frozen, ends at layer 1.  Only whole plans: where
+ * either sweep would run the pipelined schedule or an 8-wave kernel (PINN_SCHED=1, one role-split sweep without the
+ * other, an fp32 dW, PINN_WSPLIT=0, hidden 480 or 512, LDS) the plan is exactly the default one.  The fused kernel
+ * computes bit for bit what the two launches compute.  Forward-only calls (save = 0), value plans and the fp32 mode run
+ * the 8-wave variant either way.  No other plan looks at PINN_FF_SPLIT, and such a plan never looks at PINN_HBC_SPLIT or
+ * PINN_PTIME_SPLIT.
  * Refused (-22, pinn_last_error names the reason): an odd hidden width; fewer than 2 hidden layers (the output
  * layer's gradient is formed from the last hidden layer by the tanh rule); pinn_plan_create_constrained with walls
  * and pinn_plan_create_pseudo_time over such a net. */

@@ -12,6 +12,19 @@
 // HBM; layer 0's are recomputed from the point instead - the role-split forward does not spill them), turns the a-stream adjoints (accumulators of G_{l+1}; for l = L-1 the rank-3 update W_out^T o-bar) into z-bar,
 // column-sums the skinny gradients into the LDS accumulator, splits z-bar into bf16 hi/lo, spills it.
 // G_l = W_l^T z-bar_l (MFMA only).  One shared z-bar image, four K regions, 32 parked registers: fwd_bf16_split.hip.
+//
+// FF (the frozen sine first layer): layer 0 is not trained, so nothing of it is needed - not
+// G_1 = W_1^T z-bar_1, not E_0 (its adjoint, dW_0, db_0).  The per-tile program ends at E_1:
+//
+//     group 0:  E_{L-1}(A)  G_{L-1}(A)  ...  G_2(A)  E_1(A) | E_{L-1}(A') ...
+//     group 1:              E_{L-1}(B)  ...          G_2(B)   E_1(B) | ...
+//
+// Two phases fewer per tile, so the groups stay in opposite roles across the tile boundary.  What made the boundary
+// safe before is that E_0 touches no image: it may meet the other group's image-writing E_{L-1} of the next tile.  The
+// last E_1 takes exactly that place, so it must touch no image either: it runs with park = false (split_phases.h) -
+// z-bar_1 goes to its spill block, which dW reads, and nowhere else.  It also carries E_0's hook, the next tile's
+// output adjoints in quarter 3.  For L = 2 the one phase per tile is the seed phase E_1 itself, unparked.  The layer-0
+// entries of the skinny-gradient accumulator (db_0, dW_0) stay at the zeros they are initialised with.
 #include "kernels.h"
 #include "point_stage.h"
 #include "split_phases.h"
@@ -25,10 +38,10 @@ struct SplitBwdLds {
   static size_t bytes(int L) { return X_BYTES + (OADJ_F + DUMMY_F + 6 * HP + (size_t)sg_total(HP, L)) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
   using G = SplitBwdLds<HP>;
-  using SW = SplitWave<HP, TERMS>;
+  using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   float* const oadjL = reinterpret_cast<float*>(ldsb + G::X_BYTES);         // [2][4][128]
@@ -84,14 +97,29 @@ __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
   for (int pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
     const int tile = 2 * pair + grp;
     const int next_tile = pair + (int)gridDim.x < npairs ? 2 * (pair + (int)gridDim.x) + grp : -1;
-    sw.template bphase<0, false>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, sgacc, dummy + wave * 64, oadj, none);
-    for (int l = L - 1; l >= 2; --l) {
-      sw.template mphase<true, true>(l, S_of(tile, l - 1));
-      sw.template bphase<1, false>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, dummy + wave * 64, oadj, none);
+    if constexpr (FF) {      // the program that ends at E_1 (see the head of the file); L = 2: the seed phase is the last
+      const bool more = L > 2;
+      sw.template bphase<0, false>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, sgacc, dummy + wave * 64, oadj,
+                                   [&](int q) { if (!more && q == 3 && next_tile >= 0) seeds(next_tile, pxN, pyN); }, more);
+      if (more) {
+        for (int l = L - 1; l >= 3; --l) {
+          sw.template mphase<true, true>(l, S_of(tile, l - 1));
+          sw.template bphase<1, false>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, dummy + wave * 64, oadj, none);
+        }
+        sw.template mphase<true, true>(2, S_of(tile, 1));
+        sw.template bphase<1, false>(1, L, S_of(tile, 1), Z_of(tile, 1), px, py, sgacc, dummy + wave * 64, oadj,
+                                     [&](int q) { if (q == 3 && next_tile >= 0) seeds(next_tile, pxN, pyN); }, false);
+      }
+    } else {
+      sw.template bphase<0, false>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, sgacc, dummy + wave * 64, oadj, none);
+      for (int l = L - 1; l >= 2; --l) {
+        sw.template mphase<true, true>(l, S_of(tile, l - 1));
+        sw.template bphase<1, false>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, dummy + wave * 64, oadj, none);
+      }
+      sw.template mphase<true, false>(1, nullptr);
+      sw.template bphase<2, false>(0, L, S_of(tile, 0), Z_of(tile, 0), px, py, sgacc, dummy + wave * 64, oadj,
+                                   [&](int q) { if (q == 3 && next_tile >= 0) seeds(next_tile, pxN, pyN); });
     }
-    sw.template mphase<true, false>(1, nullptr);
-    sw.template bphase<2, false>(0, L, S_of(tile, 0), Z_of(tile, 0), px, py, sgacc, dummy + wave * 64, oadj,
-                                 [&](int q) { if (q == 3 && next_tile >= 0) seeds(next_tile, pxN, pyN); });
     px = pxN; py = pyN;
   }
   if (grp == 0) SW::idle();
@@ -113,16 +141,20 @@ __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
 
 size_t bwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitBwdLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitBwdLds<HP>::bytes(a.L);
   if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&bwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_split_kernel<HP, TERMS, HBC, PT, FF>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 
 // residual mode, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_bwd_split(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
+    if (a.ptime || a.hbc.kind || a.L < 2) return -1000;
+    return terms == 3 ? launch_one<256, 3, false, false, true>(a, grid, s) : launch_one<256, 1, false, false, true>(a, grid, s);
+  }
   if (a.ptime) {
     if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(a, grid, s) : launch_one<256, 1, true, true>(a, grid, s);
     return terms == 3 ? launch_one<256, 3, false, true>(a, grid, s) : launch_one<256, 1, false, true>(a, grid, s);

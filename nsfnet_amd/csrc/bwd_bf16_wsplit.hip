@@ -8,13 +8,18 @@
 //
 //     group 0:  E_{L-1}(A)  G_{L-1}(A)  E_{L-2}(A)  ...  G_1(A)  E_0(A) | E_{L-1}(A') ...
 //     group 1:              E_{L-1}(B)  G_{L-1}(B)  ...          G_1(B)   E_0(B) | ...
+//
+// FF (the frozen sine first layer): the program ends at E_1, run with park = false, exactly as in
+// bwd_bf16_split.hip - see there for why the two groups stay in opposite roles and why that phase must touch no image
+// (here that includes the group's own copy of the last region: nothing reads it after E_1).  S of layer 0, which holds
+// the a-streams in an FF plan, is not read by this kernel.
 #include "kernels.h"
 #include "point_stage.h"
 #include "wsplit_phases.h"
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
-  using SW = WSplitWave<HP, TERMS>;
+  using SW = WSplitWave<HP, TERMS, FF>;
   constexpr int GT = 256, MQ = SW::MQ, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   float* const oadjL = reinterpret_cast<float*>(ldsb + SW::XI::BYTES);       // [2][4][64]
@@ -62,14 +67,28 @@ __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
   for (int pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
     const int tile = 2 * pair + grp;
     const int next_tile = pair + (int)gridDim.x < npairs ? 2 * (pair + (int)gridDim.x) + grp : -1;
-    sw.template bphase<0>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, oadjG, sgacc, dummy + wave * 64, none);
-    for (int l = L - 1; l >= 2; --l) {
-      sw.template mphase<true, true>(l, S_of(tile, l - 1));
-      sw.template bphase<1>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, oadjG, sgacc, dummy + wave * 64, none);
+    auto hook = [&](int q) { if (q == MQ - 1 && next_tile >= 0) seeds(next_tile, pxN, pyN); };
+    if constexpr (FF) {      // the program that ends at E_1 (see the head of the file)
+      const bool more = L > 2;      // (L = 2: the first phase is the last)
+      sw.template bphase<0>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, oadjG, sgacc, dummy + wave * 64,
+                            [&](int q) { if (!more) hook(q); }, more);
+      if (more) {
+        for (int l = L - 1; l >= 3; --l) {
+          sw.template mphase<true, true>(l, S_of(tile, l - 1));
+          sw.template bphase<1>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, oadjG, sgacc, dummy + wave * 64, none);
+        }
+        sw.template mphase<true, true>(2, S_of(tile, 1));
+        sw.template bphase<1>(1, L, S_of(tile, 1), Z_of(tile, 1), px, py, oadjG, sgacc, dummy + wave * 64, hook, false);
+      }
+    } else {
+      sw.template bphase<0>(L - 1, L, S_of(tile, L - 1), Z_of(tile, L - 1), px, py, oadjG, sgacc, dummy + wave * 64, none);
+      for (int l = L - 1; l >= 2; --l) {
+        sw.template mphase<true, true>(l, S_of(tile, l - 1));
+        sw.template bphase<1>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, oadjG, sgacc, dummy + wave * 64, none);
+      }
+      sw.template mphase<true, false>(1, nullptr);
+      sw.template bphase<2>(0, L, S_of(tile, 0), Z_of(tile, 0), px, py, oadjG, sgacc, dummy + wave * 64, hook);
     }
-    sw.template mphase<true, false>(1, nullptr);
-    sw.template bphase<2>(0, L, S_of(tile, 0), Z_of(tile, 0), px, py, oadjG, sgacc, dummy + wave * 64,
-                          [&](int q) { if (q == MQ - 1 && next_tile >= 0) seeds(next_tile, pxN, pyN); });
     px = pxN; py = pyN;
   }
   if (grp == 0) SW::idle();
@@ -93,17 +112,21 @@ size_t bwd_wsplit_lds_bytes(int HP, int L) {
   return wsplit_width(HP, (size_t)1 << 30, [&](auto hp) { return WSplitWave<decltype(hp)::value, 3>::bwd_bytes(L); });
 }
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::bwd_bytes(a.L);
   if (!spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
-  return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(512), lds, s, a.configure, a);
+  return launch_or_configure(&bwd_wsplit_kernel<HP, TERMS, HBC, PT, FF>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, 24-bit spill, L >= 2 hidden layers (the caller checks)
 int launch_bwd_wsplit(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
   return wsplit_width(HP, -1000, [&](auto hp) {
     constexpr int H = decltype(hp)::value;
+    if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
+      if (a.ptime || a.hbc.kind || a.L < 2) return -1000;
+      return terms == 3 ? launch_one<H, 3, false, false, true>(a, grid, s) : launch_one<H, 1, false, false, true>(a, grid, s);
+    }
     if (a.ptime) {
       if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true, true>(a, grid, s) : launch_one<H, 1, true, true>(a, grid, s);
       return terms == 3 ? launch_one<H, 3, false, true>(a, grid, s) : launch_one<H, 1, false, true>(a, grid, s);

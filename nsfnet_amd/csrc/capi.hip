@@ -35,6 +35,7 @@ struct Switches {
   int tile_cols;          // $PINN_TILE_COLS = 64 | 128 overrides pick_wide (hidden 128 / 256 only)
   int hbc_split;          // $PINN_HBC_SPLIT (default 0; 1: a constrained plan may take the role-split / fused sweeps)
   int ptime_split;        // $PINN_PTIME_SPLIT (default 0; 1: a pseudo-time plan may take the role-split / fused sweeps)
+  int ff_split;           // $PINN_FF_SPLIT (default 0; 1: a plan over a frozen sine first layer may take the role-split / fused sweeps)
 };
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -45,7 +46,7 @@ static Switches read_switches() {
   return {env_int("PINN_FWD_SCHED", sched), env_int("PINN_BWD_SCHED", sched), env_int("PINN_WSPLIT", 1),
           env_int("PINN_FUSE", 1), env_int("PINN_STAGGER", 0), env_int("PINN_S0_SKIP32", 1),
           env_int("PINN_VERBOSE", 0), env_int("PINN_TILE_COLS", 0), env_int("PINN_HBC_SPLIT", 0),
-          env_int("PINN_PTIME_SPLIT", 0)};
+          env_int("PINN_PTIME_SPLIT", 0), env_int("PINN_FF_SPLIT", 0)};
 }
 
 // precision of a kernel family: 0 = fp32-input MFMA (exact fp32), 1 = bf16x3 split, 2 = plain bf16
@@ -243,15 +244,20 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // schedule.  By default a pseudo-time plan, constrained or not, resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
   // would; $PINN_PTIME_SPLIT=1 is to it what $PINN_HBC_SPLIT=1 is to a constrained plan.  A pseudo-time plan never
   // looks at PINN_HBC_SPLIT, and no other plan looks at PINN_PTIME_SPLIT.
-  // A net with the frozen sine first layer has its variant in the 8-wave families only, and none with walls or
-  // pseudo-time: its plans resolve as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever those switches say, and
-  // store layer 0 (SPILL_CLASSIC in every precision): what is stored there is the layer's a-streams, which no reader
-  // recomputes.
+  // A net with the frozen sine first layer has no variant with walls or pseudo-time.  By default its plans resolve as
+  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever those switches say, and store layer 0 (SPILL_CLASSIC in every
+  // precision): what is stored there is the layer's a-streams, which no reader recomputes.  With $PINN_FF_SPLIT=1 a
+  // residual plan keeps the role-split sweeps the other switches give it, but only where BOTH sweeps land in the same
+  // role-split family - the complete hidden-256 pair with the bf16 dW (fused where that holds), or the wide pair.  If
+  // either sweep would run the pipelined schedule or an 8-wave kernel, the whole plan is the default one: no mixed
+  // layouts.  The layout follows from the families: the compact one recomputes layer 0 (layer0_sine), the wide one keeps
+  // the a-streams in layer 0's slot, in the 24-bit format.  Such a plan never looks at PINN_HBC_SPLIT or
+  // PINN_PTIME_SPLIT, and no other plan looks at PINN_FF_SPLIT.
   Switches sw = sw_in;
   const bool ff = is_ff(net);
   if (ff && (hbc.kind || ptime))
     return fail(-22, "pinn_plan_create: a net with the frozen sine first layer has no %s variant", hbc.kind ? "hard-wall (constrained)" : "pseudo-time");
-  const bool keep_split = !ff && (ptime ? sw.ptime_split != 0 : hbc.kind && sw.hbc_split != 0);
+  const bool keep_split = ff ? sw.ff_split != 0 : ptime ? sw.ptime_split != 0 : hbc.kind && sw.hbc_split != 0;
   if ((hbc.kind || ptime || ff) && !keep_split) { sw.sched_f = sw.sched_b = 0; sw.wsplit = 0; sw.fuse = 0; }
   p->net = net;
   p->hbc = hbc;
@@ -303,12 +309,14 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   const bool split_pair = sf == 2 && sb == 2 && net.prec_dw;
   if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
   if (hbc.kind || ptime) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained or pseudo-time variant)
+  if (ff && !split_pair) sf = sb = 0;                                      // (nor a frozen-sine one, and an FF plan mixes no layouts)
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
-  const bool s24w = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw && !ff;
+  const bool s24w_shape = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
   // K region must fit twice in the 512-element image rows); $PINN_WSPLIT=0 keeps the 8-wave kernels.
-  const bool wsplit = s24w && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
+  const bool wsplit = s24w_shape && L >= 2 && sw.wsplit != 0 && fwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX &&
                       bwd_lds(FAM_WSPLIT, net) <= PINN_LDS_MAX;
+  const bool s24w = s24w_shape && (!ff || wsplit);      // (the 8-wave FF kernels read and write SPILL_CLASSIC only)
   // The fused sweeps need the role-split pair on both sides, in one precision, and fit in LDS up to 7 hidden layers at hidden 256; deeper
   // nets keep the two launches.  $PINN_FUSE=0 keeps them too (same-build A/B).
   const bool fuse = sf == 2 && sb == 2 && split_pair && net.prec_fwd == net.prec_bwd && sw.fuse != 0 &&
@@ -328,8 +336,12 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
     fprintf(stderr, "[pinn] plan: pseudo-time sweeps: %s (PINN_PTIME_SPLIT=%d)\n",
             fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
             sw.ptime_split);
-  if (sw.verbose && ff)
+  if (sw.verbose && ff && !keep_split)
     fprintf(stderr, "[pinn] plan: frozen sine first layer: 8-wave kernels, layer 0 stored (PINN_SCHED, PINN_WSPLIT, PINN_FUSE and PINN_S0_SKIP32 are not consulted)\n");
+  if (sw.verbose && ff && keep_split)
+    fprintf(stderr, "[pinn] plan: frozen sine sweeps: %s (PINN_FF_SPLIT=%d)\n",
+            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
+            sw.ff_split);
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);
@@ -411,6 +423,7 @@ static BwdArgs bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, co
   a.spill = plan->spill;
   a.hbc = plan->hbc;
   a.ptime = plan->ptime; a.anchor = plan->anchor; a.sigma = plan->sigma; a.sigma_p = plan->sigma_p;
+  a.ff = plan->streams == 4 && is_ff(plan->net);
   return a;
 }
 static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y,

@@ -42,15 +42,17 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 // are in the 24-bit format (Spill::quad).  Template parameters, not run-time flags: the steady-state loop must stay one
 // basic block (see below).  The fp32 format with an unstored layer 0 has no reader here: no plan pairs SPILL_SKIP0 with
 // a bf16 dW kernel, and the launcher refuses it.
-// A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
-// the A operand is taken straight from it, no chain rule.  Chosen per workgroup like REC.
+// A0: layer l - 1 is layer 0 of a frozen sine first layer (DwArgs::ff), whose a-streams are the A operand as they are,
+// no chain rule: taken straight from the stored quad (SPILL_CLASSIC, the 8-wave plans), or with REC, in the compact
+// 24-bit layout of the role-split plans where layer 0 has no slot, recomputed from the point by layer0_sine of
+// layer0_z as the forward's E0 computes them.  Chosen per workgroup like REC.
 template <int HP, int NS, int TERMS, int PPL, bool REC, bool P24, bool A0 = false>
 __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
   constexpr int CPT = PPL / 8;                 // 32-column chunks per tile
   constexpr size_t ABLK = act_block(HP, 4 * PPL);
   using DI = DwImg<HP>;
   static_assert(P24 || !REC, "no fp32-format reader that recomputes layer 0");
-  static_assert(!A0 || (!REC && !P24 && NS == 4), "a stored sine layer: SPILL_CLASSIC, residual mode");
+  static_assert(!A0 || (NS == 4 && REC == P24), "a sine layer: stored in SPILL_CLASSIC or recomputed in SPILL_P24_COMPACT, residual mode");
   constexpr int T = HP / 32;
   constexpr int TM = DwCfgB<T>::TM, TN = DwCfgB<T>::TN;
   constexpr int WN = T / TN;
@@ -126,7 +128,15 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
       }
     }
     f32x4 av[4];
-    if (rec) {
+    if (rec && A0) {
+      const float px = R.px, py = R.py;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float f0, f1, f2, f3;
+        layer0_sine(layer0_z(wx4[e], wy4[e], b4[e], px, py), wx4[e], wy4[e], SinCosFast(), f0, f1, f2, f3);
+        av[0][e] = f0; av[1][e] = f1; av[2][e] = f2; av[3][e] = f3;
+      }
+    } else if (rec) {
       const float px = R.px, py = R.py;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -281,12 +291,13 @@ __device__ __forceinline__ void dw_bf16_body(const DwArgs& a) {
 }
 
 // P24: 24-bit format; REC0: layer 0 is not stored, so the layer-1 workgroups recompute it
-// FF: the plan's net has the frozen sine first layer, so the layer-1 workgroups run the A0 body
+// FF: the plan's net has the frozen sine first layer, so the layer-1 workgroups run the A0 body (stored layer 0, or
+// with P24 and REC0 the recomputed one)
 template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0, bool FF = false>
 __global__ __launch_bounds__(HP * 2) void dw_bf16_kernel(DwArgs a) {
   if constexpr (FF) {
-    if (blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, false, false, true>(a);
-    else dw_bf16_body<HP, NS, TERMS, PPL, false, false>(a);
+    if (blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, REC0, P24, true>(a);
+    else dw_bf16_body<HP, NS, TERMS, PPL, false, P24>(a);
   } else {
     if (REC0 && blockIdx.y == 0) dw_bf16_body<HP, NS, TERMS, PPL, REC0, P24>(a);
     else dw_bf16_body<HP, NS, TERMS, PPL, false, P24>(a);
@@ -317,7 +328,12 @@ static int launch_one(const DwArgs& a, hipStream_t s) {
   if (!spill_is(a.spill, act_block(HP, 4 * PPL), CAN_COMPACT ? IN_CLASSIC | IN_P24_COMPACT : IN_CLASSIC)) return -1000;
   const bool p24 = a.spill.quad == SPILL_QUAD_P24, rec0 = a.spill.skip0 != 0;
   if constexpr (NS == 4) {
-    if (a.ff) return p24 || rec0 ? -1000 : launch_fmt<HP, 4, TERMS, PPL, false, false, true>(a, s);
+    if (a.ff) {
+      if constexpr (CAN_COMPACT) {
+        if (p24 && rec0) return launch_fmt<HP, 4, TERMS, PPL, true, true, true>(a, s);
+      }
+      return p24 || rec0 ? -1000 : launch_fmt<HP, 4, TERMS, PPL, false, false, true>(a, s);
+    }
   }
   if constexpr (CAN_COMPACT) {
     if (p24 && rec0) return launch_fmt<HP, NS, TERMS, PPL, true, true>(a, s);

@@ -24,7 +24,8 @@ __device__ __forceinline__ u32x2 tr_read(const lds_u8* p) {
 // P24: S / Z-bar in the 24-bit three-plane spill format (Spill::quad; residual mode only) - a template parameter, the
 // steady-state loop must stay one basic block
 // A0: the stored quad of layer l - 1 holds the a-streams themselves (layer 0 of a frozen sine first layer, DwArgs::ff):
-// the A operand is taken straight from it.  A template parameter chosen per workgroup (dw_bf16_wide_kernel).
+// the A operand is taken straight from it, in the fp32 format (the 8-wave plans) or in the 24-bit one (the wide role-split
+// plans, whose forward stores the a-streams in layer 0's slot).  A template parameter chosen per workgroup (dw_bf16_wide_kernel).
 template <int NS, int TERMS, bool P24, bool A0>
 __device__ __forceinline__ void dw_bf16_wide_body(const DwArgs& a, int HP) {
   constexpr int TM = 4, TN = 2, WN = 4, PPL = 16, CPT = PPL / 8;
@@ -199,11 +200,11 @@ size_t dw_bf16_wide_lds_bytes() { return DI::BYTES; }
 template <int NS, int TERMS, bool P24 = false>
 static int launch_one(int HP, const DwArgs& a, hipStream_t s) {
   const bool ff = NS == 4 && a.ff;
-  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 && !ff ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
+  if (!spill_is(a.spill, act_block(HP, 64), NS == 4 ? IN_CLASSIC | IN_P24_WIDE : IN_CLASSIC)) return -1000;
   if (!P24 && NS == 4 && a.spill.quad == SPILL_QUAD_P24) return launch_one<NS, TERMS, NS == 4>(HP, a, s);
   const int nblk = (HP / 32 + 7) / 8;
-  if constexpr (NS == 4 && !P24) {
-    if (ff) return launch_or_configure(&dw_bf16_wide_kernel<4, TERMS, false, true>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
+  if constexpr (NS == 4) {
+    if (ff) return launch_or_configure(&dw_bf16_wide_kernel<4, TERMS, P24, true>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
   }
   return launch_or_configure(&dw_bf16_wide_kernel<NS, TERMS, P24>, dim3(a.groups, a.L - 1, nblk * nblk), dim3(512), DI::BYTES, s, a.configure, a, HP);
 }

@@ -40,10 +40,11 @@ struct SplitLds {
   static size_t bytes(int L) { return X_BYTES + (PART_F + OUTV_F + (size_t)L * HP + 6 * HP) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+// FF: the frozen sine first layer (split_phases.h): E0 forms the a-streams by layer0_sine; nothing else differs
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
   using G = SplitLds<HP>;
-  using SW = SplitWave<HP, TERMS>;
+  using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;      // GT: threads per group
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   float* const part = reinterpret_cast<float*>(ldsb + G::X_BYTES);
@@ -124,16 +125,20 @@ __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
 
 size_t fwd_split_lds_bytes(int HP, int L) { (void)HP; return SplitLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = SplitLds<HP>::bytes(a.L);
   if (a.S && !spill_is(a.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&fwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_split_kernel<HP, TERMS, HBC, PT, FF>, dim3(grid), dim3(2 * HP), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_fwd_split(int HP, int terms, const FwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
+    if (a.ptime || a.hbc.kind) return -1000;
+    return terms == 3 ? launch_one<256, 3, false, false, true>(a, grid, s) : launch_one<256, 1, false, false, true>(a, grid, s);
+  }
   if (a.ptime) {
     if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(a, grid, s) : launch_one<256, 1, true, true>(a, grid, s);
     return terms == 3 ? launch_one<256, 3, false, true>(a, grid, s) : launch_one<256, 1, false, true>(a, grid, s);

@@ -28,9 +28,11 @@
 #include "point_stage.h"
 #include "wsplit_phases.h"
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+// FF: the frozen sine first layer (wsplit_phases.h): E0 forms the a-streams by layer0_sine and stores them in layer 0's
+// slot; nothing else differs
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
-  using SW = WSplitWave<HP, TERMS>;
+  using SW = WSplitWave<HP, TERMS, FF>;
   constexpr int GT = 256, MQ = SW::MQ, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   float* const part = reinterpret_cast<float*>(ldsb + SW::XI::BYTES);
@@ -107,17 +109,21 @@ size_t fwd_wsplit_lds_bytes(int HP) {
   return wsplit_width(HP, (size_t)1 << 30, [](auto hp) { return WSplitWave<decltype(hp)::value, 3>::fwd_bytes(); });
 }
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = WSplitWave<HP, TERMS>::fwd_bytes();
   if (a.S && !spill_is(a.spill, act_block(HP, 64), IN_P24_WIDE)) return -1000;
-  return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(512), lds, s, a.configure, a);
+  return launch_or_configure(&fwd_wsplit_kernel<HP, TERMS, HBC, PT, FF>, dim3(grid), dim3(512), lds, s, a.configure, a);
 }
 
 // residual mode, saved activations in the 24-bit format, L >= 2 hidden layers (the caller checks)
 int launch_fwd_wsplit(int HP, int terms, const FwdArgs& a, int grid, hipStream_t s) {
   return wsplit_width(HP, -1000, [&](auto hp) {
     constexpr int H = decltype(hp)::value;
+    if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
+      if (a.ptime || a.hbc.kind) return -1000;
+      return terms == 3 ? launch_one<H, 3, false, false, true>(a, grid, s) : launch_one<H, 1, false, false, true>(a, grid, s);
+    }
     if (a.ptime) {
       if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true, true>(a, grid, s) : launch_one<H, 1, true, true>(a, grid, s);
       return terms == 3 ? launch_one<H, 3, false, true>(a, grid, s) : launch_one<H, 1, false, true>(a, grid, s);

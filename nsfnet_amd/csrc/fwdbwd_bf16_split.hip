@@ -31,6 +31,17 @@
 // (no LDS is left for them).  As the two launches do, XB builds the residuals q_k twice: for the loss sums from the
 // registers of the forward, and for the seeds from opaque copies of the values the reverse sweep would read back from
 // the planes.  The planes keep the steady residuals.
+//
+// FF (the frozen sine first layer): E0 forms the a-streams by layer0_sine, and the reverse half ends at
+// E'_1 as in bwd_bf16_split.hip (see there): no G_1, no E'_0.
+//
+//     per tile and group:  E0 M1 E1 ... M_{L-1}  XA XB  G_{L-1} E'_{L-2} ... G_2 E'_1        (L = 2:  E0 M1 XA XB)
+//
+// 4L - 4 phases per tile, two fewer, so the groups keep their opposite roles.  The last phase meets the other group's
+// image-reading G_2 (or, for L = 2, its XA, which touches no image) and is followed by the group's own E0 of the next
+// tile while the partner runs ITS last phase: E'_0's place, which is safe because E'_0 touches no image.  So the last
+// phase runs with park = false (split_phases.h): z-bar_1 goes to its spill block for dW and nowhere else.  Same bodies
+// and orders of summation as the FF two launches: bit for bit their results.
 #include "kernels.h"
 #include "point_stage.h"
 #include "split_phases.h"
@@ -43,10 +54,10 @@ struct FusedLds {
   static size_t bytes(int L) { return X_BYTES + (PART_F + 6 * HP + (size_t)sg_total(HP, L)) * sizeof(float); }
 };
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, BwdArgs a) {
   using G = FusedLds<HP>;
-  using SW = SplitWave<HP, TERMS>;
+  using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   float* const part = reinterpret_cast<float*>(ldsb + G::X_BYTES);
@@ -262,13 +273,26 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     }
     sw.template mphase<false, false>(L - 1, nullptr);
     sw.template fphase<2, true>(L - 1, tile, nullptr, a.x, a.y, a.n, partG, bias(L - 1), none);                 // XA
-    sw.template bphase<0, true>(L - 1, L, nullptr, Z_of(tile, L - 1), px, py, sgacc, sink, seed(tile, vtm_old), none);  // XB
-    for (int l = L - 1; l >= 2; --l) {
-      sw.template mphase<true, true>(l, S_of(tile, l - 1));
-      sw.template bphase<1, true>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, sink, none, none);
+    if constexpr (FF) {      // the reverse half that ends at E'_1 (see the head of the file)
+      const bool more = L > 2;      // (L = 2: XB is the last phase)
+      sw.template bphase<0, true>(L - 1, L, nullptr, Z_of(tile, L - 1), px, py, sgacc, sink, seed(tile, vtm_old), none, more);  // XB
+      if (more) {
+        for (int l = L - 1; l >= 3; --l) {
+          sw.template mphase<true, true>(l, S_of(tile, l - 1));
+          sw.template bphase<1, true>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, sink, none, none);
+        }
+        sw.template mphase<true, true>(2, S_of(tile, 1));
+        sw.template bphase<1, true>(1, L, S_of(tile, 1), Z_of(tile, 1), px, py, sgacc, sink, none, none, false);
+      }
+    } else {
+      sw.template bphase<0, true>(L - 1, L, nullptr, Z_of(tile, L - 1), px, py, sgacc, sink, seed(tile, vtm_old), none);  // XB
+      for (int l = L - 1; l >= 2; --l) {
+        sw.template mphase<true, true>(l, S_of(tile, l - 1));
+        sw.template bphase<1, true>(l - 1, L, S_of(tile, l - 1), Z_of(tile, l - 1), px, py, sgacc, sink, none, none);
+      }
+      sw.template mphase<true, false>(1, nullptr);
+      sw.template bphase<2, true>(0, L, nullptr, Z_of(tile, 0), px, py, sgacc, sink, none, none);
     }
-    sw.template mphase<true, false>(1, nullptr);
-    sw.template bphase<2, true>(0, L, nullptr, Z_of(tile, 0), px, py, sgacc, sink, none, none);
   }
   if (grp == 0) SW::idle();
   // ---------------- flush: loss partials (fwd_split order), then dbo and the skinny gradients (bwd_split order) ----------------
@@ -300,16 +324,20 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
 
 size_t fwdbwd_split_lds_bytes(int HP, int L) { (void)HP; return FusedLds<256>::bytes(L); }
 
-template <int HP, int TERMS, bool HBC = false, bool PT = false>
+template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   const size_t lds = FusedLds<HP>::bytes(a.L);
   if (!spill_is(a.spill, act_block(HP), IN_P24_COMPACT) || !spill_is(fa.spill, act_block(HP), IN_P24_COMPACT)) return -1000;
-  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS, HBC, PT>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
+  return launch_or_configure(&fwdbwd_split_kernel<HP, TERMS, HBC, PT, FF>, dim3(grid), dim3(2 * HP), lds, s, a.configure, fa, a);
 }
 
 // residual mode, MSE seeds, role-split plan (HP = 256, SPILL_P24_COMPACT)
 int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
   if (HP != 256) return -1000;
+  if (fa.ff || a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
+    if (!fa.ff || !a.ff || fa.ptime || fa.hbc.kind || a.L < 2) return -1000;
+    return terms == 3 ? launch_one<256, 3, false, false, true>(fa, a, grid, s) : launch_one<256, 1, false, false, true>(fa, a, grid, s);
+  }
   if (fa.ptime) {
     if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(fa, a, grid, s) : launch_one<256, 1, true, true>(fa, a, grid, s);
     return terms == 3 ? launch_one<256, 3, false, true>(fa, a, grid, s) : launch_one<256, 1, false, true>(fa, a, grid, s);

@@ -108,6 +108,8 @@ struct BwdArgs {
   int ptime;
   const float* anchor;   // [3][npad] anchors u*, v*, p*
   float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation
+  int ff;                // != 0 (residual mode): the net's first layer is the frozen sine layer.  The role-split and fused
+                         // families launch their FF instantiation, whose sweep ends at layer 1; the 8-wave families do not read it.
 };
 
 struct DwArgs {

@@ -16,12 +16,19 @@
 //   SPILL_P24_WIDE     p24   ablk      0      0      fwd_bf16_wide, fwd_bf16_wsplit; bwd_bf16_wide, bwd_bf16_wsplit (which
 //                                                    bwd_bf16_wide, bwd_bf16_wsplit  recomputes layer 0 all the same),
 //                                                    (3 of the block's 4 planes)     dw_bf16_wide
+//                                                    FF: fwd_bf16_wsplit alone       FF: dw_bf16_wide alone reads layer 0
 //   SPILL_P24_COMPACT  p24   3/4 ablk  1      1      fwd_bf16_split, bwd_bf16_split, bwd_bf16_split, fwdbwd_bf16_split,
 //                                                    fwdbwd_bf16_split               dw_bf16: all recompute layer 0
+//                                                    (FF: the same three)            FF: dw_bf16 alone recomputes layer 0
 //
-// A plan over a net with the frozen sine first layer (kernels.h FwdArgs::ff) is SPILL_CLASSIC in every precision, and what
-// its layer-0 block of S holds is that layer's a-streams (a, a_x, a_y, a_D) themselves: dW's layer-1 workgroups take
-// their A operand straight from it, and nothing recomputes a sine layer.
+// A plan over a net with the frozen sine first layer (kernels.h FwdArgs::ff; FF above) is by default SPILL_CLASSIC in every
+// precision, on the 8-wave kernels, and what its layer-0 block of S holds is that layer's a-streams (a, a_x, a_y, a_D)
+// themselves: dW's layer-1 workgroups take their A operand straight from it, and nothing recomputes a sine layer.
+// With $PINN_FF_SPLIT=1 a plan whose two sweeps are both role-split takes the layout of its families as any plan does:
+// SPILL_P24_COMPACT at hidden 256, where layer 0 has no slot and dW's layer-1 workgroups recompute the a-streams from
+// the point (spill_io.h layer0_sine of layer0_z, as the forward's first epilogue does), or SPILL_P24_WIDE at hidden
+// 288..448, where layer 0's slot holds the a-streams in the 24-bit format - the 8-wave convention carried over.  The
+// layer is frozen, so the reverse sweep of such a plan ends at layer 1 and reads nothing of layer 0 in either layout.
 // Z-bar of layer 0 is never stored in any layout (dW_0 is accumulated by the reverse sweep itself); with first == 0 its
 // slot exists and stays unused.
 #pragma once

@@ -8,12 +8,17 @@
 //
 // Every phase is force-inlined into a straight-line per-group program: no per-phase dispatch (with one, the register
 // allocator spilled the whole accumulator set around the phase loop).
+//
+// FF: the net's first layer is the frozen sine layer (spill_io.h layer0_sine).  The forward's E phase of
+// layer 0 forms the four a-streams by that one function instead of the tanh chain rule; nothing else of the forward
+// changes (layer 0 has no slot in the compact layout either way).  The layer is not trained, so the reverse sweep of an
+// FF kernel ends at E_1 - no G_1, no E_0 - and that last phase runs with park = false (bphase).
 #pragma once
 #include "kernels.h"
 #include "bf16_util.h"
 #include "reduce_util.h"
 
-template <int HP, int TERMS>
+template <int HP, int TERMS, bool FF = false>
 struct SplitWave {
   static_assert(HP == 256, "four waves x 64 features per group");
   using XI = XImg<HP, 32>;
@@ -143,7 +148,7 @@ struct SplitWave {
   }
 
   // ---------------- forward E phase: tanh chain rule of layer lE ----------------
-  // EK: 0 = layer 0 (pre-activations from the point (x, y) on the VALU; nothing spilled), 1 = hidden layer 1..L-2,
+  // EK: 0 = layer 0 (pre-activations from the point (x, y) on the VALU; nothing spilled; FF: layer0_sine), 1 = hidden layer 1..L-2,
   // 2 = last hidden layer (output layer folded into the per-wave partials partG, nothing parked).  S goes to the
   // block Sl, or, for EK 2 with KEEP, to skeep.  bias(fb, g, o, h): the bias quad of features o..o+3;
   // quarter(q): the kernel's work at the top of quarter q.
@@ -190,11 +195,17 @@ struct SplitWave {
           } else {
             z = acc[fb][0][r] + b4[e]; zx = acc[fb][1][r]; zy = acc[fb][2][r]; zd = acc[fb][3][r];
           }
-          const float t = fast_tanh(z);
-          const float d1 = 1.f - t * t;
-          const float d2 = -2.f * t * d1;
-          av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * (zx * zx + zy * zy) + d1 * zd;
-          sv[0][e] = t; sv[1][e] = zx; sv[2][e] = zy; sv[3][e] = zd;
+          if constexpr (FF && first) {      // the frozen sine layer: the a-streams by its one statement, nothing saved
+            float f0, f1, f2, f3;
+            layer0_sine(z, zx, zy, SinCosFast(), f0, f1, f2, f3);
+            av[0][e] = f0; av[1][e] = f1; av[2][e] = f2; av[3][e] = f3;
+          } else {
+            const float t = fast_tanh(z);
+            const float d1 = 1.f - t * t;
+            const float d2 = -2.f * t * d1;
+            av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * (zx * zx + zy * zy) + d1 * zd;
+            sv[0][e] = t; sv[1][e] = zx; sv[2][e] = zy; sv[3][e] = zd;
+          }
           __builtin_amdgcn_sched_barrier(0);      // the epilogue's elements / planes are scheduled one at a time
         }
         const unsigned so = (unsigned)(((o - 4 * h) >> 2) + h) * PPL + col;
@@ -247,9 +258,14 @@ struct SplitWave {
   // EK 0 with KEEP, from skeep.  Z-bar goes to the block Zl.  The column sums of the skinny gradients go into sgacc;
   // the lanes that own no slot add into sink[lane].  seed(col, h, oc): EK 0's output adjoints [output][stream];
   // quarter(q): the kernel's work at the end of quarter q.
+  // park = false (orthogonal to EK; the last phase of an FF reverse sweep, E_1 or for L = 2 the seed phase itself): no G
+  // phase follows, so z-bar is spilled to Zl as ever (dW reads it) but neither split into st nor dumped into the image,
+  // no weight k-step of a G phase is requested, and have_parked stays false.  The phase then touches no image, as EK 2
+  // does, and keeps its four barriers.  An argument, not a template parameter: uniform, a constant wherever the phase
+  // is inlined but in the seed phase of an FF kernel (L = 2 or not), which a second instantiation would duplicate.
   template <int EK, bool KEEP, class Seed, class Quarter>
   __device__ __forceinline__ void bphase(int lE, int L, const float* Sl, float* Zl, float pxE, float pyE, float* sgacc,
-                                         float* sink, Seed seed, Quarter quarter) {
+                                         float* sink, Seed seed, Quarter quarter, bool park = true) {
     constexpr bool first = EK == 0, last = EK == 2;
     const int lane = phase_lane(), col = lane & 31, h = lane >> 5;
     float oc[3][4];
@@ -264,13 +280,13 @@ struct SplitWave {
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      if (q > 0 && !last) dump((q - 1) >> 1, 2 * ((q - 1) & 1), col, h);
+      if (q > 0 && !last && park) dump((q - 1) >> 1, 2 * ((q - 1) & 1), col, h);
       const int fb = q >> 1;
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int g = 2 * (q & 1) + k, qq = 2 * q + k, o = quad_o(qq, h);
         if (!last && !(first && KEEP) && qq + SQ < 8) sload(Sl, qq + SQ, col, h);
-        if (!last && qq == 7) {      // first weight k-steps of G_lE
+        if (!last && park && qq == 7) {      // first weight k-steps of G_lE
 #pragma unroll
           for (int s = 0; s < WPRE; ++s) wload(prep_wtf(HP, lE), s, w_lane(col, h));
         }
@@ -342,7 +358,7 @@ struct SplitWave {
           u32x4 pk[3];
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
-            split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], st[k][p][0], st[k][p][1]);
+            if (park) split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], st[k][p][0], st[k][p][1]);
             pack24_plane(zq[p], p, pk);
             store24_planes(Zl, PLQ, so, p, pk);
             __builtin_amdgcn_sched_barrier(0);
@@ -353,6 +369,6 @@ struct SplitWave {
       quarter(q);
       __syncthreads();
     }
-    have_parked = !last;
+    have_parked = !last && park;
   }
 };

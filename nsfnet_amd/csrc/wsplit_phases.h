@@ -5,13 +5,17 @@
 // and its program; it hands the phases what differs as arguments (spill blocks, LDS rows) and as per-quarter callables.
 //
 // Every phase is force-inlined into a straight-line per-group program (split_phases.h).
+//
+// FF: the frozen sine first layer, as in split_phases.h.  The forward's E phase of layer 0 forms the a-streams by
+// layer0_sine and stores THEM in layer 0's slot of S, in the 24-bit format (the 8-wave FF convention: dw_bf16_wide.hip
+// takes the layer-1 A operand from that quad); the reverse sweep ends at E_1, run with park = false (bphase).
 #pragma once
 #include <type_traits>
 #include "kernels.h"
 #include "bf16_util.h"
 #include "reduce_util.h"
 
-template <int HP, int TERMS>
+template <int HP, int TERMS, bool FF = false>
 struct WSplitWave {
   using XI = XImg<HP, 16>;
   typedef __attribute__((address_space(1))) u32x4 gu32x4;
@@ -192,13 +196,20 @@ struct WSplitWave {
         } else {
           z = acc[bq][0][r] + b4[e]; zx = acc[bq][0][r + 8]; zy = acc[bq][1][r]; zd = acc[bq][1][r + 8];
         }
-        const float t = fast_tanh(z);
-        const float d1 = 1.f - t * t;
-        const float d2 = -2.f * t * d1;
-        // (zx zx + zy zy as one fmaf, in the pairing contraction chose before these bodies were shared: left to it, the
-        // last block's quads now pair the other way - see bphase)
-        av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * fmaf(zx, zx, zy * zy) + d1 * zd;
-        sv[0][e] = t; sv[1][e] = zx; sv[2][e] = zy; sv[3][e] = zd;
+        if constexpr (FF && first) {      // the frozen sine layer: the a-streams by its one statement, saved as they are
+          float f0, f1, f2, f3;
+          layer0_sine(z, zx, zy, SinCosFast(), f0, f1, f2, f3);
+          av[0][e] = f0; av[1][e] = f1; av[2][e] = f2; av[3][e] = f3;
+          sv[0][e] = f0; sv[1][e] = f1; sv[2][e] = f2; sv[3][e] = f3;
+        } else {
+          const float t = fast_tanh(z);
+          const float d1 = 1.f - t * t;
+          const float d2 = -2.f * t * d1;
+          // (zx zx + zy zy as one fmaf, in the pairing contraction chose before these bodies were shared: left to it, the
+          // last block's quads now pair the other way - see bphase)
+          av[0][e] = t; av[1][e] = d1 * zx; av[2][e] = d1 * zy; av[3][e] = d2 * fmaf(zx, zx, zy * zy) + d1 * zd;
+          sv[0][e] = t; sv[1][e] = zx; sv[2][e] = zy; sv[3][e] = zd;
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
     };
@@ -281,9 +292,14 @@ struct WSplitWave {
   // spill).  Saved activations come from the block Sl (requested SQ quads ahead; all but EK 0's by the G phase before),
   // z-bar goes to the block Zl.  The column sums of the skinny gradients go into sgacc; the lanes that own no slot add
   // into sink[lane].  quarter(q): the kernel's work at the end of quarter q.
+  // park = false (orthogonal to EK; the last phase of an FF reverse sweep, E_1 or for L = 2 the first phase itself): no
+  // G phase follows, so z-bar is spilled to Zl as ever (dW reads it) but is neither split nor written to the image -
+  // not parked, not dumped, not put into the group's copy of the last region - and no weight k-step is requested.  The
+  // phase then touches no image, as EK 2 does, and keeps its MQ barriers.  An argument, not a template parameter
+  // (split_phases.h).
   template <int EK, class Quarter>
   __device__ __forceinline__ void bphase(int lE, int L, const float* Sl, float* Zl, float pxE, float pyE, const float* oadj,
-                                         float* sgacc, float* sink, Quarter quarter) {
+                                         float* sgacc, float* sink, Quarter quarter, bool park = true) {
     constexpr bool first = EK == 0, last = EK == 2;
     const int lane = phase_lane(), col = lane & 31, h = lane >> 5, hi = col >> 4, pp = col & 15;
     float oc[3][4];
@@ -373,11 +389,11 @@ struct WSplitWave {
       u32x4 pk[3];
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        if (direct) {
+        if (park && direct) {
           u32x2 th, tl;
           split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], th, tl);
           img_put(bq, k, p, pp, hi, h, th, tl);
-        } else {
+        } else if (park) {
           split4(zq[p][0], zq[p][1], zq[p][2], zq[p][3], st[k][p][0], st[k][p][1]);
         }
         pack24_plane(zq[p], p, pk);
@@ -388,7 +404,7 @@ struct WSplitWave {
 #pragma unroll
     for (int q = 0; q < MQ; ++q) {
       const bool mainb = q < MQ - 1;                     // blocks 0 .. MQ - 2 ride in their own quarter (every wave owns them)
-      const bool prev = q > 0 && !last;                  // block q - 1 is parked and its region is free now
+      const bool prev = q > 0 && !last && park;          // block q - 1 is parked and its region is free now
       const bool extra = q < 2 && mc == MQ;              // the last block's quads ride in quarters 0 and 1 (uniform)
       const int i0 = q < 2 ? 3 * q : 6 + 2 * (q - 2);    // first item of this quarter
       if (mainb && !first) swaps(q);
@@ -398,7 +414,7 @@ struct WSplitWave {
         const int i = i0 + k;
         if (mainb && !last && i + SQ < NQD) sload(Sl, i + SQ, pp, hi, h);
         // first weight k-step of the G phase that follows (its first MFMA would otherwise wait out an L2 round trip)
-        if (!last && q == MQ - 1 && k == 1) wload(prep_wtf(HP, lE), 0, lane);
+        if (!last && park && q == MQ - 1 && k == 1) wload(prep_wtf(HP, lE), 0, lane);
         f32x4 zq[4];
         if (mainb) compute(i, zq);
         // block q - 1, parked in the previous quarter: its region is free now; quad k leaves its registers before the refill

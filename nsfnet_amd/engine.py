@@ -1822,8 +1822,12 @@ class PinnEngine:
         sigma's default 1.0 is a guess; no value has been compared in training.
 
         Layer 0 is not trained: its 3 * hidden entries lead every gradient vector as +0.0 (grads, the term vectors of
-        balancing and ConFIG, the L-BFGS gradient), so Adam, clipping and L-BFGS leave it where it is.  The plans run
-        the 8-wave kernel families.  Needs an even hidden width and at least 2 hidden layers; not available together
+        balancing and ConFIG, the L-BFGS gradient), so Adam, clipping and L-BFGS leave it where it is.  By default the
+        plans run the 8-wave kernel families and store layer 0.  With PINN_FF_SPLIT=1 in the environment when a residual
+        plan is created it keeps the role-split, fused and wide role-split sweeps the other switches choose, in their
+        frozen-sine variants, whose reverse sweep ends at layer 1; where either sweep would not be a role-split one the
+        whole plan is the default one (fourier_info()["kernels"] names what the collocation plan launches).  Needs an
+        even hidden width and at least 2 hidden layers; not available together
         with hard walls or pseudo-time.  Must be called before any point set is attached (ValueError otherwise).
         sigma = None without frequencies: off (layer 0 is tanh again and trainable; its weights stay as they are)."""
         if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val)):
@@ -1863,11 +1867,19 @@ class PinnEngine:
         self._ff = dict(sigma=sigma, seed=seed, frequencies=B.clone())
 
     def fourier_info(self):
-        """dict(kind="sine", sigma, seed, frequencies=B as an fp64 (hidden / 2, 2) tensor) of set_fourier_features (sigma
-        and seed None where B was given); None when the option is off."""
+        """dict(kind="sine", sigma, seed, frequencies=B as an fp64 (hidden / 2, 2) tensor, kernels, split) of
+        set_fourier_features (sigma and seed None where B was given); None when the option is off.  kernels: the three
+        names the collocation plan launches (None before one is attached); split: $PINN_FF_SPLIT as plan creation reads
+        it now (an integer, 0 when unset)."""
         if self._ff is None:
             return None
-        return dict(kind="sine", sigma=self._ff["sigma"], seed=self._ff["seed"], frequencies=self._ff["frequencies"].clone())
+        try:
+            split = int(os.environ.get("PINN_FF_SPLIT", "0"))
+        except ValueError:
+            split = 0
+        names = getattr(self.plan_f, "kernel_names", None)      # (a stand-in plan of the CPU tests has no kernels)
+        return dict(kind="sine", sigma=self._ff["sigma"], seed=self._ff["seed"], frequencies=self._ff["frequencies"].clone(),
+                    kernels=None if names is None else names(), split=split)
 
     # ---- hard wall conditions by an output transform (DESIGN.md section 7.10) ----
     def set_hard_boundary(self, enabled=True, lift_power=2, lid_sharpness=10.0, origin=(0.0, 0.0), inv_len=1.0):
