@@ -637,6 +637,79 @@ int64_t pinn_ptime_scratch_bytes(int64_t n);
 int pinn_ptime_advance(int64_t n, const float* fields, int64_t npad, const float* w, float* anchor, int64_t every,
                        int force, double* scratch, double* record, void* stream);
 
+/* ---- convergence monitor: a stage that has stopped making progress is noticed on the device ----
+ * Two launches, both meant for the captured step; the host reads the state at its log points only.
+ * pinn_monitor_vis_stats: over vis_t = [n] fp32 (non-negative entries, 16-byte aligned; the last quad is read by
+ *   element), in fp64 with a fixed order (no float atomics, bit-reproducible): the sum, rounded once to fp32, into
+ *   *sum_out - a free slot of the loss-sum block, so that the exchange that is made anyway turns it into the global sum -
+ *   and, for this rank alone, info (PINN_MON_INFO doubles) =
+ *     [0] max entry, NaN-propagating     [1] entries >= vis_t0 (compared in fp32)     [2] the fp64 sum     [3] n
+ *   scratch: pinn_monitor_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (the launch
+ *   leaves its ticket word 0 again).
+ * pinn_monitor_observe: one workgroup, after an optimiser update.  eq, bc, sup: the three loss-sum blocks (PINN_NLOSS
+ *   floats each; sup NULL: no supervised term) of the evaluation that produced the update, after the exchange - eq[4] is
+ *   the slot pinn_monitor_vis_stats wrote.  lam: the balancing weights (lambda_b, lambda_s) in device memory, or NULL:
+ *   the launch constants alpha_b, alpha_s.  state[0] goes up by one (t); unless t % every == 0 nothing else happens.
+ *   An observation, every operation fp64 from the fp32 sums, rounded once, in this order:
+ *     eq_k = eq[k] / n_eq (k = 0..3)       loss_e = (eq_0 + eq_1) + eq_2       ev:  loss_e = loss_e + eq4_weight eq_3
+ *     loss_b = (bc[0] + bc[1]) / n_b       loss_s = (sup[0] + sup[1]) / n_s  [ + sup[2] / n_p  where n_p > 0 ]   (n_s = 0: 0)
+ *     loss = ((w_b loss_b) + (alpha_e loss_e)) + (w_s loss_s)
+ *     vis_mean = eq[4] / n_eq (ev; else 0)       Re_eff = 1 / (1 / Re + vis_mean)
+ *   the row (PINN_MON_RECORD doubles), written at ring[(observations so far) % capacity]:
+ *     [0] t
+ *     [1] loss
+ *     [2] loss_e
+ *     [3] loss_b
+ *     [4] loss_s
+ *     [5..8] eq_0 .. eq_3
+ *     [9] vis_mean
+ *     [10] Re_eff
+ *     [11] the stop code after this observation
+ *   A non-finite loss is counted, sets PINN_MON_STOP_NONFINITE and stays out of the window.  Otherwise Q (quantity: 0
+ *   loss, 1 loss_e, 2 loss_b) and Re_eff join the window sums; at `window` observations the window means (sum / window)
+ *   are compared with the previous window's (the first complete window only sets them) and the window restarts:
+ *     plateau_on:  prev == 0 or (prev - mean) / |prev| < min_rel_improvement  ->  stale + 1, else stale = 0
+ *     re_eff_on:   |mean_re - prev_re| / prev_re < re_eff_tol                 ->  settled + 1, else settled = 0
+ *   At every observation with t >= min_updates: stale >= patience sets PINN_MON_STOP_PLATEAU, settled >= patience sets
+ *   PINN_MON_STOP_RE_EFF.  The bits are sticky; the call sets bits and writes nothing else.
+ *   state (PINN_MON_STATE doubles of device memory, zero at the start, 8-byte aligned):
+ *     [0] updates counted (t)
+ *     [1] observations (rows written)
+ *     [2] observations with a non-finite loss
+ *     [3] observations in the current window
+ *     [4] sum of Q over the current window
+ *     [5] sum of Re_eff over the current window
+ *     [6] complete windows
+ *     [7] mean of Q over the last complete window
+ *     [8] mean of Re_eff over the last complete window
+ *     [9] stale
+ *     [10] settled
+ *     [11] stop code (PINN_MON_STOP_* bits)
+ *     [12] t of the observation that set PLATEAU (0: not set)
+ *     [13] t of the observation that set RE_EFF
+ *     [14] t of the observation that set NONFINITE
+ *     [15] 0
+ *   Refused with -22 (pinn_last_error names the field): every < 1, window < 1, patience < 1, capacity < 1,
+ *   min_updates < 0, a quantity outside 0..2, a tolerance that is switched on and negative or not finite, re_eff_on
+ *   without ev; n_eq or n_b < 1, n_s or n_p < 0, Re not finite and > 0. */
+#define PINN_MON_RECORD 12
+#define PINN_MON_STATE 16
+#define PINN_MON_INFO 4
+enum { PINN_MON_STOP_PLATEAU = 1, PINN_MON_STOP_RE_EFF = 2, PINN_MON_STOP_NONFINITE = 4 };
+typedef struct {
+  int64_t every, window, patience, min_updates, capacity;
+  int32_t quantity;     /* 0 loss, 1 loss_e, 2 loss_b */
+  int32_t ev;           /* != 0: the ev flavour - eq4 enters loss_e, eq[4] holds the vis_t sum */
+  int32_t plateau_on, re_eff_on;
+  double min_rel_improvement, re_eff_tol;
+} pinn_monitor_config_t;
+int64_t pinn_monitor_scratch_bytes(void);
+int pinn_monitor_vis_stats(int64_t n, const float* vis_t, float vis_t0, float* sum_out, double* info, double* scratch,
+                           void* stream);
+int pinn_monitor_observe(const float* eq, const float* bc, const float* sup, const float* lam, double alpha_b,
+                         double alpha_s, double alpha_e, double eq4_weight, double n_eq, double n_b, double n_s, double n_p,
+                         double Re, const pinn_monitor_config_t* cfg, double* state, double* ring, void* stream);
+
 /* ---- training-state snapshots: many device buffers <-> one staging buffer, with digests ----
  * A snapshot is a list of segments (any number; a launch takes up to 64, more take several launches).  In the staging
  * buffer segment k starts at align256(end of the segment stored before it) and the padding behind a segment is zero,

@@ -99,6 +99,10 @@ SIGNATURES = {
     "pinn_ptime_scratch_bytes": (c_int64, [c_int64]),
     "pinn_ptime_advance": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                    c_void_p]),
+    "pinn_monitor_scratch_bytes": (c_int64, []),
+    "pinn_monitor_vis_stats": (c_int, [c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_monitor_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_double,
+                                     c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_state_scratch_bytes": (c_int64, []),
     "pinn_state_layout": (c_int64, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "pinn_state_digest_host": (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -120,6 +124,13 @@ class HardBcStruct(ctypes.Structure):
     """pinn_hard_bc_t"""
     _fields_ = [("kind", ctypes.c_int32), ("lift_power", ctypes.c_int32), ("x0", c_float), ("y0", c_float),
                 ("inv_len", c_float), ("lid_sharpness", c_float)]
+
+
+class MonitorConfigStruct(ctypes.Structure):
+    """pinn_monitor_config_t"""
+    _fields_ = [("every", c_int64), ("window", c_int64), ("patience", c_int64), ("min_updates", c_int64),
+                ("capacity", c_int64), ("quantity", ctypes.c_int32), ("ev", ctypes.c_int32), ("plateau_on", ctypes.c_int32),
+                ("re_eff_on", ctypes.c_int32), ("min_rel_improvement", c_double), ("re_eff_tol", c_double)]
 
 
 _lib = None

@@ -1229,6 +1229,65 @@ int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1,
   return rc ? hipfail(rc, "pinn_val_keep") : 0;
 }
 
+// ---- convergence monitor (monitor.hip) ----
+int64_t pinn_monitor_scratch_bytes(void) { return (int64_t)monitor_scratch_bytes(); }
+
+int pinn_monitor_vis_stats(int64_t n, const float* vis_t, float vis_t0, float* sum_out, double* info, double* scratch,
+                           void* stream) {
+  static_assert(PINN_MON_INFO == MON_INFO, "monitor info size mismatch");
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_monitor_vis_stats: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (!vis_t || !sum_out || !info || !scratch) return fail(-22, "pinn_monitor_vis_stats: null argument%s");
+  if (misaligned(vis_t, 16)) return fail(-22, "pinn_monitor_vis_stats: vis_t must be 16-byte aligned%s");
+  if (misaligned(sum_out, 4) || misaligned(info, 8) || misaligned(scratch, 8))
+    return fail(-22, "pinn_monitor_vis_stats: sum_out must be 4-byte aligned, info and scratch 8-byte%s");
+  MonVisArgs a;
+  a.n = (long)n; a.vis_t = vis_t; a.vis_t0 = vis_t0; a.sum_out = sum_out; a.info = info; a.scratch = scratch;
+  int rc = launch_monitor_vis_stats(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_monitor_vis_stats") : 0;
+}
+
+int pinn_monitor_observe(const float* eq, const float* bc, const float* sup, const float* lam, double alpha_b,
+                         double alpha_s, double alpha_e, double eq4_weight, double n_eq, double n_b, double n_s, double n_p,
+                         double Re, const pinn_monitor_config_t* cfg, double* state, double* ring, void* stream) {
+  static_assert(PINN_MON_RECORD == MON_RECORD && PINN_MON_STATE == MON_STATE, "monitor record / state size mismatch");
+  static_assert((int)PINN_MON_STOP_PLATEAU == MON_STOP_PLATEAU && (int)PINN_MON_STOP_RE_EFF == MON_STOP_RE_EFF &&
+                (int)PINN_MON_STOP_NONFINITE == MON_STOP_NONFINITE, "monitor stop bits mismatch");
+  if (!cfg) return fail(-22, "pinn_monitor_observe: null configuration%s");
+  // the configuration first: it needs no device
+  if (cfg->every < 1) return fail(-22, "pinn_monitor_observe: every must be >= 1 (got %s%ld)", "", (long)cfg->every);
+  if (cfg->window < 1) return fail(-22, "pinn_monitor_observe: window must be >= 1 (got %s%ld)", "", (long)cfg->window);
+  if (cfg->patience < 1) return fail(-22, "pinn_monitor_observe: patience must be >= 1 (got %s%ld)", "", (long)cfg->patience);
+  if (cfg->capacity < 1 || cfg->capacity > (int64_t)1 << 30)
+    return fail(-22, "pinn_monitor_observe: capacity must be 1..2^30 (got %s%ld)", "", (long)cfg->capacity);
+  if (cfg->min_updates < 0) return fail(-22, "pinn_monitor_observe: min_updates must be >= 0 (got %s%ld)", "", (long)cfg->min_updates);
+  if (cfg->quantity < 0 || cfg->quantity > 2) return fail(-22, "pinn_monitor_observe: quantity must be 0..2 (got %s%ld)", "", (long)cfg->quantity);
+  if (cfg->plateau_on && !(std::isfinite(cfg->min_rel_improvement) && cfg->min_rel_improvement >= 0.0))
+    return fail(-22, "pinn_monitor_observe: min_rel_improvement must be finite and >= 0%s");
+  if (cfg->re_eff_on && !(std::isfinite(cfg->re_eff_tol) && cfg->re_eff_tol >= 0.0))
+    return fail(-22, "pinn_monitor_observe: re_eff_tol must be finite and >= 0%s");
+  if (cfg->re_eff_on && !cfg->ev) return fail(-22, "pinn_monitor_observe: re_eff_on needs the ev flavour (there is no vis_t)%s");
+  if (!(n_eq >= 1.0 && std::isfinite(n_eq)) || !(n_b >= 1.0 && std::isfinite(n_b)))
+    return fail(-22, "pinn_monitor_observe: n_eq and n_b must be finite and >= 1%s");
+  if (!(n_s >= 0.0 && std::isfinite(n_s)) || !(n_p >= 0.0 && std::isfinite(n_p)))
+    return fail(-22, "pinn_monitor_observe: n_s and n_p must be finite and >= 0%s");
+  if (!(Re > 0.0 && std::isfinite(Re))) return fail(-22, "pinn_monitor_observe: Re must be finite and > 0%s");
+  if (!eq || !bc || !state || !ring) return fail(-22, "pinn_monitor_observe: null argument%s");
+  if (misaligned(eq, 4) || misaligned(bc, 4) || misaligned(sup, 4) || misaligned(lam, 4) || misaligned(state, 8) ||
+      misaligned(ring, 8))
+    return fail(-22, "pinn_monitor_observe: the sums and lam must be 4-byte aligned, state and ring 8-byte%s");
+  MonObserveArgs a;
+  a.eq = eq; a.bc = bc; a.sup = sup; a.lam = lam;
+  a.alpha_b = alpha_b; a.alpha_s = alpha_s; a.alpha_e = alpha_e; a.w4 = eq4_weight;
+  a.n_eq = n_eq; a.n_b = n_b; a.n_s = n_s; a.n_p = n_p; a.Re = Re;
+  a.every = (long)cfg->every; a.window = (long)cfg->window; a.patience = (long)cfg->patience;
+  a.min_updates = (long)cfg->min_updates; a.capacity = (long)cfg->capacity;
+  a.quantity = cfg->quantity; a.ev = cfg->ev != 0; a.plateau_on = cfg->plateau_on != 0; a.re_on = cfg->re_eff_on != 0;
+  a.min_rel = cfg->min_rel_improvement; a.re_tol = cfg->re_eff_tol;
+  a.state = state; a.ring = ring;
+  int rc = launch_monitor_observe(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_monitor_observe") : 0;
+}
+
 
 // ---- training-state snapshots (state.hip) ----
 int64_t pinn_state_scratch_bytes(void) { return (int64_t)state_scratch_bytes(); }

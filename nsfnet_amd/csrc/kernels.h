@@ -341,6 +341,30 @@ struct PtimeArgs {
 };
 size_t ptime_scratch_bytes(long n);
 int launch_ptime_advance(const PtimeArgs& a, hipStream_t s);
+// convergence monitor: the vis_t statistics of an evaluation and the per-update observation (monitor.hip)
+constexpr int MON_RECORD = 12, MON_STATE = 16, MON_INFO = 4;
+constexpr int MON_STOP_PLATEAU = 1, MON_STOP_RE_EFF = 2, MON_STOP_NONFINITE = 4;
+struct MonVisArgs {
+  long n;                                  // local entries of the plane
+  const float* vis_t;                      // [n], 16-byte aligned
+  float vis_t0;                            // the cap: entries >= vis_t0 are counted
+  float* sum_out;                          // one fp32 slot of the loss-sum block
+  double *info, *scratch;                  // [MON_INFO] per-rank words; scratch
+};
+struct MonObserveArgs {
+  const float *eq, *bc, *sup;              // the exchanged loss-sum blocks (PINN_NLOSS floats each) of the evaluation that
+                                           // produced the update: eq[0..3] sum w eq_k^2, eq[4] sum vis_t; bc[0..1]; sup[0..2] (NULL: none)
+  const float* lam;                        // [2] balancing weights (lambda_b, lambda_s) on the device, or NULL: alpha_b, alpha_s
+  double alpha_b, alpha_s, alpha_e, w4;
+  double n_eq, n_b, n_s, n_p, Re;          // the normalisers (n_s / n_p 0: that part is absent)
+  long every, window, patience, min_updates, capacity;
+  int quantity, ev, plateau_on, re_on;     // quantity: 0 loss, 1 loss_e, 2 loss_b; ev: eq4 and vis_t take part
+  double min_rel, re_tol;
+  double *state, *ring;                    // [MON_STATE]; [capacity][MON_RECORD]
+};
+size_t monitor_scratch_bytes();
+int launch_monitor_vis_stats(const MonVisArgs& a, hipStream_t s);
+int launch_monitor_observe(const MonObserveArgs& a, hipStream_t s);
 size_t val_scratch_bytes();
 int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s);

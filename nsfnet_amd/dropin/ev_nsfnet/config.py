@@ -176,6 +176,28 @@ class ValidationConfig:
     patience: int = 0
 
 
+EARLY_STOP_QUANTITIES = ("loss", "loss_e", "loss_b")
+EARLY_STOP_MODES = ("any", "all")
+
+
+@dataclass
+class EarlyStopConfig:
+    """The device convergence monitor that ends an Adam stage early (solver.set_early_stopping; DESIGN.md section 7.14);
+    the key's absence means off.  window: observed updates per window mean; min_rel_improvement: a window that improves
+    the mean of `quantity` by less than this fraction is stale (null: criterion off); re_eff_tol: a window whose mean
+    Re_eff moves by less than this fraction is settled (null, the default: criterion off); patience: windows in a row;
+    min_updates: no stop bit before this update of the stage; mode: any | all criteria; every: updates per observation.
+    The defaults are guesses: no value has been compared in training."""
+    window: int = 1000
+    min_rel_improvement: Optional[float] = 1e-3
+    patience: int = 3
+    re_eff_tol: Optional[float] = None
+    min_updates: int = 0
+    quantity: str = "loss"
+    mode: str = "any"
+    every: int = 1
+
+
 @dataclass
 class CheckpointConfig:
     """Training-state snapshots that resume bit for bit (solver.set_checkpointing), off by default: path of the file
@@ -216,6 +238,7 @@ class TrainingConfig:
     hard_boundary: HardBoundaryConfig = field(default_factory=HardBoundaryConfig)
     pseudo_time: PseudoTimeConfig = field(default_factory=PseudoTimeConfig)
     checkpoint: CheckpointConfig = field(default_factory=CheckpointConfig)
+    early_stop: Optional[EarlyStopConfig] = None
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -252,6 +275,17 @@ def _fill(obj, data):
         elif key == "fourier_features":          # absent, null or false: off
             if val is not None and val is not False:
                 setattr(obj, key, _fill(FourierFeaturesConfig(), val))
+        elif key == "early_stop":                # absent, null or false: off
+            if val is not None and val is not False:
+                es = EarlyStopConfig()
+                for k, v in (val.items() if isinstance(val, dict) else ()):
+                    if k in ("min_rel_improvement", "re_eff_tol"):
+                        setattr(es, k, None if v is None else float(v))
+                    elif k in ("quantity", "mode"):
+                        setattr(es, k, str(v))
+                    elif k in ("window", "patience", "min_updates", "every"):
+                        setattr(es, k, int(v))
+                setattr(obj, key, es)
         elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
             if val is not None and val is not False:
                 cur.enabled = True
@@ -323,6 +357,17 @@ class ConfigManager:
         if va.enabled and (va.every < 1 or va.patience < 0 or va.metric not in VALIDATION_METRICS):
             problems.append("training.validation: every >= 1, patience >= 0 and metric one of %s required"
                             % " | ".join(VALIDATION_METRICS))
+        es = c.training.early_stop
+        if es is not None:
+            tol_ok = lambda v: v is None or 0.0 <= v < float("inf")
+            if (es.window < 1 or es.patience < 1 or es.every < 1 or es.min_updates < 0 or not tol_ok(es.min_rel_improvement)
+                    or not tol_ok(es.re_eff_tol) or es.quantity not in EARLY_STOP_QUANTITIES
+                    or es.mode not in EARLY_STOP_MODES):
+                problems.append("training.early_stop: window, patience, every >= 1, min_updates >= 0, finite tolerances >= 0 "
+                                "(or null), quantity one of %s and mode one of %s required"
+                                % (" | ".join(EARLY_STOP_QUANTITIES), " | ".join(EARLY_STOP_MODES)))
+            if es.min_rel_improvement is None and es.re_eff_tol is None:
+                problems.append("training.early_stop: at least one of min_rel_improvement and re_eff_tol must be set")
         ck = c.training.checkpoint
         if ck.every < 0 or (ck.every > 0 and not ck.path):
             problems.append("training.checkpoint: every >= 0, and a path when every > 0, required")
@@ -395,6 +440,11 @@ class ConfigManager:
         if t.validation.enabled:
             print("validation : every=%d metric=%s keep_best=%s patience=%d"
                   % (t.validation.every, t.validation.metric, t.validation.keep_best, t.validation.patience))
+        if t.early_stop is not None:
+            es = t.early_stop
+            print("early stop : window=%d min_rel_improvement=%s patience=%d re_eff_tol=%s min_updates=%d quantity=%s "
+                  "mode=%s every=%d" % (es.window, es.min_rel_improvement, es.patience, es.re_eff_tol, es.min_updates,
+                                        es.quantity, es.mode, es.every))
         if t.checkpoint.enabled:
             print("checkpoint : path=%s every=%d" % (t.checkpoint.path, t.checkpoint.every))
         for st in t.training_stages:

@@ -171,6 +171,11 @@ def main():
             # last: a change of the factorization would drop the best.  Every rank validates the whole grid
             PINN.set_validation_data(*star, every=va.every, metric=va.metric, keep_best=va.keep_best,
                                      patience=va.patience)
+        es = cfg.training.early_stop
+        if es is not None:    # an Adam stage that has stopped improving ends at a log point; the loop below goes on
+            PINN.set_early_stopping(every=es.every, window=es.window, min_rel_improvement=es.min_rel_improvement,
+                                    patience=es.patience, re_eff_tol=es.re_eff_tol, min_updates=es.min_updates,
+                                    quantity=es.quantity, mode=es.mode)
         ck = cfg.training.checkpoint
         if ck.enabled:
             PINN.set_checkpointing(ck.path, ck.every)

@@ -694,6 +694,39 @@ def val_keep(segs, state):
                                          0 if s1 is None else s1.numel(), _ptr(state), _stream()), "pinn_val_keep")
 
 
+MON_RECORD = 12          # PINN_MON_RECORD
+MON_STATE = 16           # PINN_MON_STATE
+MON_INFO = 4             # PINN_MON_INFO: this rank's [max vis_t, entries >= vis_t0, fp64 sum, n]
+MON_ROW = ("t", "loss", "loss_e", "loss_b", "loss_s", "eq1", "eq2", "eq3", "eq4", "vis_mean", "Re_eff", "stop")
+MON_STATE_NAMES = ("updates", "observations", "nonfinite", "window_fill", "window_sum", "window_sum_re", "windows",
+                   "window_mean", "window_mean_re", "stale", "settled", "stop", "t_plateau", "t_re_eff", "t_nonfinite")
+MON_QUANTITIES = dict(loss=0, loss_e=1, loss_b=2)
+MON_STOP = dict(plateau=1, re_eff=2, nonfinite=4)       # PINN_MON_STOP_*
+MON_VIS_SLOT = 4         # the slot of the equation block of the loss sums that carries the vis_t sum (4..7 are free)
+
+
+def monitor_scratch(device):
+    """Zeroed device scratch of monitor_vis_stats."""
+    return torch.zeros(int(_lib.load().pinn_monitor_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def monitor_vis_stats(vis_t, n, vis_t0, sum_out, info, scratch):
+    """pinn_monitor_vis_stats: the fixed-order fp64 sum of vis_t [n], rounded to fp32, into sum_out[0]; this rank's max,
+    cap count, fp64 sum and n into info.  One launch."""
+    _lib.check(_lib.load().pinn_monitor_vis_stats(int(n), _ptr(vis_t), float(vis_t0), _ptr(sum_out), _ptr(info),
+                                                  _ptr(scratch), _stream()), "pinn_monitor_vis_stats")
+
+
+def monitor_observe(eq, bc, sup, lam, alpha_b, alpha_s, alpha_e, w4, n_eq, n_b, n_s, n_p, Re, cfg, state, ring):
+    """pinn_monitor_observe: count one optimiser update and, on the cadence, observe the loss sums eq / bc / sup (None:
+    no supervised term; lam None: the constants alpha_b, alpha_s) - a row into ring, state updated.  cfg: a
+    MonitorConfigStruct.  One launch."""
+    _lib.check(_lib.load().pinn_monitor_observe(_ptr(eq), _ptr(bc), _ptr(sup), _ptr(lam), float(alpha_b), float(alpha_s),
+                                                float(alpha_e), float(w4), float(n_eq), float(n_b), float(n_s), float(n_p),
+                                                float(Re), ctypes.byref(cfg), _ptr(state), _ptr(ring), _stream()),
+               "pinn_monitor_observe")
+
+
 OPTIM_RECORD = 6         # PINN_OPTIM_RECORD
 
 
@@ -973,6 +1006,30 @@ class _Validation:
         self.plan = self.pred = self.tgt = self.scratch = self.state = self.ring = self.snap = None
 
 
+class _Monitor:
+    """State of the convergence monitor (set_convergence_monitor): the launch constants (every, window, patience,
+    min_updates, quantity, the two tolerances - None: that criterion is off -, mode, capacity) and the device tensors
+    state [MON_STATE] fp64, ring [capacity, MON_RECORD] fp64, info [MON_INFO] fp64 (this rank's vis_t statistics) and
+    scratch (ev flavour)."""
+
+    def __init__(self, every, window, min_rel, patience, re_tol, min_updates, quantity, mode, capacity):
+        self.every, self.window, self.min_rel, self.patience, self.re_tol = every, window, min_rel, patience, re_tol
+        self.min_updates, self.quantity, self.mode, self.capacity = min_updates, quantity, mode, capacity
+        self.state = self.ring = self.info = self.scratch = None
+
+    def key(self):
+        return ("monitor", self.every, self.window, self.min_rel, self.patience, self.re_tol, self.min_updates,
+                self.quantity, self.capacity)
+
+    def c_struct(self, ev):
+        return _lib.MonitorConfigStruct(
+            every=self.every, window=self.window, patience=self.patience, min_updates=self.min_updates,
+            capacity=self.capacity, quantity=MON_QUANTITIES[self.quantity], ev=1 if ev else 0,
+            plateau_on=0 if self.min_rel is None else 1, re_eff_on=0 if self.re_tol is None else 1,
+            min_rel_improvement=0.0 if self.min_rel is None else self.min_rel,
+            re_eff_tol=0.0 if self.re_tol is None else self.re_tol)
+
+
 # What an evaluation is made for.  Each mode holds what the one before it holds, and more:
 EVAL_ADAM = 0           # an Adam step: a fresh batch, attention and balance updates, the conflict-free combination
 EVAL_FULL_BATCH = 1     # loss_and_grad(full_batch=True): the whole store, the attention weights held
@@ -1035,6 +1092,7 @@ class PinnEngine:
         self._val = None                    # device validation monitor (set_validation; None = off)
         self._pt = None                     # pseudo-time stepping (set_pseudo_time; None = off)
         self._ff = None                     # frozen Fourier-feature first layer (set_fourier_features; None = off)
+        self._mon = None                    # convergence monitor (set_convergence_monitor; None = off)
         self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
 
     # ---- what the evaluations are made for ----
@@ -1086,6 +1144,8 @@ class PinnEngine:
             raise ValueError("residual attention needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         if self._pt is not None and chunk_points and n > int(chunk_points):
             raise ValueError("pseudo-time stepping needs a resident store: chunk_points=%d with it on" % int(chunk_points))
+        if self._mon is not None and chunk_points and n > int(chunk_points):
+            raise ValueError("the convergence monitor needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         self._graphs.clear()      # captured steps hold the old plan's pointers
         self.lbfgs_reset()
         if chunk_points and n > int(chunk_points):
@@ -1517,7 +1577,7 @@ class PinnEngine:
         l2 = mode == "L2"
         for state, needs in ((self._bal, "loss balancing needs"), (self._cfg, "conflict-free gradients need"),
                              (self._batch, "mini-batching needs"), (self._rba, "residual attention needs"),
-                             (self._pt, "pseudo-time stepping needs")):
+                             (self._pt, "pseudo-time stepping needs"), (self._mon, "the convergence monitor needs")):
             if l2 and state is not None:
                 raise ValueError("%s the MSE loss (loss mode %r)" % (needs, mode))
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
@@ -1615,6 +1675,11 @@ class PinnEngine:
             batch_scatter(bt.idx, bt.B, self.plan_f.n, f.vis_t_minus, self.plan_f.vis_t_minus)
         if self._rba is not None and self._mode == EVAL_ADAM:      # the weights of the NEXT evaluation
             self._attention_update(f, bt)
+        mon = self._mon
+        if mon is not None and self.net_e is not None and self._mode != EVAL_LBFGS:
+            # after the loss-sum launch of the pass (which zeroes the slot) and before the exchange below, which makes
+            # the sum global in the message that is sent anyway: every rank then observes the same bits
+            monitor_vis_stats(f.vis_t, f.n, self.vis_t0, eq_sums[MON_VIS_SLOT:], mon.info, mon.scratch)
         if side is not None:
             main.wait_stream(side)
         last = passes[-1][1]
@@ -2142,10 +2207,13 @@ class PinnEngine:
         m = self._val
         return m is not None and (m.n + 1) % m.every == 0
 
-    def _updated(self, validate=None):
-        """An optimizer update is in place: count it, and validate when the cadence (or the caller) says so."""
+    def _updated(self, validate=None, observe=True):
+        """An optimizer update is in place: count it, let the convergence monitor observe it (observe False: an L-BFGS
+        call, whose sums are a trial point's), and validate when the cadence (or the caller) says so."""
         if self._pt is not None:
             ptime_advance(self.plan_f, self._pt.every, False, self._pt.scratch, self._pt.record)
+        if observe and self._mon is not None:
+            self._observe()
         m = self._val
         if m is None:
             return
@@ -2243,6 +2311,139 @@ class PinnEngine:
             net.update_params()
         self.lbfgs_reset()
 
+    # ---- convergence monitor: a stage that has stopped making progress ----
+    def set_convergence_monitor(self, every=1, window=1000, min_rel_improvement=1e-3, patience=3, re_eff_tol=None,
+                                min_updates=0, quantity="loss", mode="any", history=4096):
+        """Watch the loss terms (and, ev flavour, Re_eff = 1 / (1/Re + mean vis_t)) of every every-th Adam update on
+        the device.  One launch after the update (between the pseudo-time advance and the validation) forms loss,
+        loss_e, loss_b, loss_s, eq1..4, the global mean of vis_t and Re_eff in fp64 from the exchanged loss sums of the
+        evaluation that produced the update, writes them as a row [t, loss, loss_e, loss_b, loss_s, eq1..eq4, vis_mean,
+        Re_eff, stop code] into a ring of `history` rows and adds the monitored `quantity` ('loss' | 'loss_e' |
+        'loss_b') and Re_eff to the sums of the current window of `window` observations.  A complete window's means are
+        compared with the previous window's: (prev - mean) / |prev| < min_rel_improvement counts as stale, |mean_re -
+        prev_re| / prev_re < re_eff_tol as settled (anything else restarts that count; the first window only sets the
+        means); from update min_updates on, `patience` stale windows in a row set the sticky stop bit 'plateau',
+        `patience` settled ones the bit 're_eff'.  A non-finite loss sets 'nonfinite' at once and stays out of the
+        window.  A tolerance of None switches its criterion off.  The launch only sets bits: should_stop() - one host
+        read, meant for log points - combines the two criteria by mode ('any': either; 'all': every criterion that is
+        on), and 'nonfinite' always stops.  Window means, not moving averages: they ride over the loss jump where the ev
+        schedule re-creates Adam, and have an exact numpy statement (tests/monitor_model.py).
+
+        Ev flavour: one more launch per evaluation sums the vis_t plane of the plan that was evaluated (the batch plan
+        under mini-batching) into slot 4 of the equation block of the loss sums, before the exchange - so the mean is
+        global, and every rank takes the same decision from the same bits; this rank's own max and cap fraction are in
+        monitor_info().  An lbfgs_step does not observe.  The loss terms are those of loss_terms(): with batching the
+        batch's, with attention the weighted ones, with pseudo-time the minimised loss_e.  Everything is device memory
+        allocated here once and rewritten in place: one captured step serves a whole stage, and monitor_history() is a
+        full training curve without a synchronisation in between.  Refused: re_eff_tol on the plain flavour (no
+        vis_t), chunked collocation passes, the 'L2' loss mode.  The defaults are guesses: no value has been compared
+        in training.  every = 0: off (the step launches what it launches without the feature).  A call restarts the
+        state."""
+        every, window, patience, min_updates, history = (int(v) for v in (every, window, patience, min_updates, history))
+        if every < 0:
+            raise ValueError("convergence monitor: every must be >= 0")
+        self._graphs.clear()        # captured steps hold the other monitor's buffers and constants
+        if every == 0:
+            self._mon = None
+            return
+        if window < 1 or patience < 1 or history < 1 or min_updates < 0:
+            raise ValueError("convergence monitor: window, patience and history must be >= 1, min_updates >= 0 (got "
+                             "window=%d patience=%d history=%d min_updates=%d)" % (window, patience, history, min_updates))
+        tol = {}
+        for name, v in (("min_rel_improvement", min_rel_improvement), ("re_eff_tol", re_eff_tol)):
+            tol[name] = None if v is None else float(v)
+            if v is not None and not (math.isfinite(tol[name]) and tol[name] >= 0.0):
+                raise ValueError("convergence monitor: %s must be finite and >= 0, or None (got %r)" % (name, v))
+        if quantity not in MON_QUANTITIES:
+            raise ValueError("convergence monitor: quantity must be one of %s (got %r)" % (sorted(MON_QUANTITIES), quantity))
+        if mode not in ("any", "all"):
+            raise ValueError("convergence monitor: mode must be 'any' or 'all' (got %r)" % (mode,))
+        if tol["re_eff_tol"] is not None and self.net_e is None:
+            raise ValueError("convergence monitor: re_eff_tol needs the ev flavour (the plain flavour has no vis_t)")
+        if isinstance(self.plan_f, ChunkedResidual):
+            raise ValueError("the convergence monitor needs a resident store: the collocation set is chunked (chunk_points)")
+        m = _Monitor(every, window, tol["min_rel_improvement"], patience, tol["re_eff_tol"], min_updates, quantity, mode,
+                     history)
+        m.state = torch.zeros(MON_STATE, dtype=torch.float64, device=self.device)
+        m.ring = torch.zeros(history, MON_RECORD, dtype=torch.float64, device=self.device)
+        m.info = torch.zeros(MON_INFO, dtype=torch.float64, device=self.device)
+        m.scratch = monitor_scratch(self.device) if self.net_e is not None else None
+        self._mon = m
+
+    def reset_convergence_monitor(self):
+        """The state at its start and an empty ring (in place: captured steps stay valid)."""
+        m = self._mon_on()
+        m.state.zero_()
+        m.ring.zero_()
+        m.info.zero_()
+
+    def _mon_on(self):
+        if self._mon is None:
+            raise RuntimeError("the convergence monitor is off: call set_convergence_monitor() first")
+        return self._mon
+
+    def _observe(self):
+        """The observation of the update that is in place, from the sums of the evaluation that produced it."""
+        m, s = self._mon, self.sums
+        sup_on = self._sup_on()
+        n_eq = self._batch.B * self.world_size if self._eval_batch else self.n_f_global
+        monitor_observe(s[S_EQ:S_EQ + NLOSS], s[S_BC:S_BC + NLOSS], s[S_SUP:S_SUP + NLOSS] if sup_on else None,
+                        None if self._bal is None else self._bal.lam, self.alpha_b, self.alpha_s, self.alpha_e,
+                        self._w4(), n_eq, self.n_b_global, self.n_s_global if sup_on else 0,
+                        self._n_p_valid_global() if sup_on else 0, self.Re, m.c_struct(self.net_e is not None), m.state,
+                        m.ring)
+
+    def _stop_reasons(self, code, m):
+        """The names of the bits in `code`, and whether they end the stage under m.mode."""
+        reasons = [k for k, bit in MON_STOP.items() if code & bit]
+        on = [k for k, v in (("plateau", m.min_rel), ("re_eff", m.re_tol)) if v is not None]
+        hit = [k in reasons for k in on]
+        stop = "nonfinite" in reasons or (bool(on) and (any(hit) if m.mode == "any" else all(hit)))
+        return reasons, stop
+
+    def monitor_info(self):
+        """The monitor state (one host read), or None when the feature is off: updates, observations, nonfinite,
+        windows, window_mean / window_mean_re (of the last complete window), stale, settled, stop (the code), reasons
+        (the names of its bits), should_stop, t_plateau / t_re_eff / t_nonfinite (the update that set each bit; 0:
+        not set), last (the newest row as a dict; None before the first), and this rank's vis_t_max and cap_fraction
+        (entries >= vis_t0; None on the plain flavour or before the first evaluation), with the settings."""
+        m = self._mon
+        if m is None:
+            return None
+        k = torch.remainder(m.state[1:2] - 1.0, float(m.capacity)).long()       # the newest row (device index: no sync)
+        both = torch.cat([m.state, m.info, m.ring.index_select(0, k).reshape(-1)]).cpu().tolist()
+        st, info, row = both[:MON_STATE], both[MON_STATE:MON_STATE + MON_INFO], both[MON_STATE + MON_INFO:]
+        out = dict(zip(MON_STATE_NAMES, st))
+        for key in MON_STATE_NAMES:
+            if key not in ("window_sum", "window_sum_re", "window_mean", "window_mean_re"):
+                out[key] = int(out[key])
+        out["reasons"], out["should_stop"] = self._stop_reasons(out["stop"], m)
+        out["last"] = dict(zip(MON_ROW, row)) if out["observations"] > 0 else None
+        seen = self.net_e is not None and info[3] > 0
+        out["vis_t_max"] = info[0] if seen else None
+        out["cap_fraction"] = info[1] / info[3] if seen else None
+        out.update(every=m.every, window=m.window, min_rel_improvement=m.min_rel, patience=m.patience,
+                   re_eff_tol=m.re_tol, min_updates=m.min_updates, quantity=m.quantity, mode=m.mode, history=m.capacity)
+        return out
+
+    def monitor_history(self):
+        """fp64 numpy array [rows, MON_RECORD] of the observed rows in time order (the ring unwrapped: the newest
+        `history` of them); one host read."""
+        m = self._mon_on()
+        both = torch.cat([m.state, m.ring.reshape(-1)]).cpu().numpy()
+        k, ring = int(both[1]), both[MON_STATE:].reshape(m.capacity, MON_RECORD)
+        if k <= m.capacity:
+            return ring[:k].copy()
+        return np.concatenate([ring[k % m.capacity:], ring[:k % m.capacity]])
+
+    def should_stop(self):
+        """True when the stop bits end the stage under the configured mode (one host read; False with the monitor
+        off).  Every rank reads the same bits."""
+        m = self._mon
+        if m is None:
+            return False
+        return self._stop_reasons(int(m.state[11].item()), m)[1]
+
     # ---- L-BFGS (DESIGN.md section 7.2) ----
     def lbfgs_reset(self):
         """Forget the L-BFGS history: the next lbfgs_step starts like a fresh torch.optim.LBFGS."""
@@ -2281,7 +2482,7 @@ class PinnEngine:
         finally:
             self.e_trainable = e_trainable
         self.lbfgs_info = info
-        self._updated()     # one call = one update; the accepted point is in place
+        self._updated(observe=False)     # one call = one update; the accepted point is in place
         return loss
 
     def step(self, lr):
@@ -2331,6 +2532,7 @@ class PinnEngine:
         key += () if o is None else (o.spec.key(), o.max_norm)
         key += (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
         key += () if self._pt is None else (("ptime", self._pt.sigma, self._pt.sigma_p, self._pt.every),)
+        key += () if self._mon is None else (self._mon.key(),)
         v = self._val
         return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 
@@ -2343,7 +2545,7 @@ class PinnEngine:
         """[(name, tensor, stored)]: everything in device memory that a step reads and an earlier step wrote, in the
         file's fixed order - per net (net, net_e) trainable, m, v, adam_t; per collocation pass x, y, w (the static
         weights), vis_t_minus; plan_e x, y; opt epoch, rec; bal lam, rec; cfg coef, rec; batch counter, idx; rba lam, w,
-        rec; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
+        rec; monitor state, ring; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
         (stored False), the sets a resume must attach again unchanged: boundary, supervised, validation, resample pool."""
         segs = []
 
@@ -2365,7 +2567,8 @@ class PinnEngine:
             add("plan_e.y", self.plan_e.y)
         for name, obj, keys in (("opt", self._opt, ("epoch", "rec")), ("bal", self._bal, ("lam", "rec")),
                                 ("cfg", self._cfg, ("coef", "rec")), ("batch", self._batch, ("counter", "idx")),
-                                ("rba", self._rba, ("lam", "w", "rec")), ("val", self._val, ("state", "ring"))):
+                                ("rba", self._rba, ("lam", "w", "rec")), ("val", self._val, ("state", "ring")),
+                                ("monitor", self._mon, ("state", "ring"))):
             if obj is not None:
                 for key in keys:
                     add("%s.%s" % (name, key), getattr(obj, key))
@@ -2396,8 +2599,9 @@ class PinnEngine:
         shape = lambda net: None if net is None else [net.n_out, net.n_hidden, net.hidden]
         count = lambda plan, g: None if plan is None else [plan.n, int(g)]
         v, f = self._val, self.plan_f
+        mon = {} if self._mon is None else dict(monitor=dict(capacity=self._mon.capacity))      # (off: the file's bytes of before)
         return dict(
-            flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
+            mon, flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
             points_colloc=count(f, self.n_f_global), points_boundary=count(self.plan_b, self.n_b_global),
             points_supervised=[0 if self.plan_s is None else self.plan_s.n, int(self.n_s_global)],
             points_val=None if v is None else v.plan.n, points_pool=None if self._pool is None else self._pool.n,
@@ -2417,8 +2621,11 @@ class PinnEngine:
         """What a file records beside the structure; load_training_state reports the keys that differ."""
         o, a, b, bt, v, pt = self._opt, self._rba, self._bal, self._batch, self._val, self._pt
         kernels = getattr(self.plan_f, "kernel_names", None)
+        m = self._mon
+        mon = {} if m is None else dict(monitor=[m.every, m.window, m.min_rel, m.patience, m.re_tol, m.min_updates,
+                                                 m.quantity, m.mode])
         return dict(
-            precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
+            mon, precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
             kernels=None if kernels is None else list(kernels()), Re=self.Re, alpha_b=self.alpha_b, alpha_e=self.alpha_e,
             alpha_s=self.alpha_s, alpha_evm=self.alpha_evm, scale=self.scale, vis_t0=self.vis_t0, eq4_weight=self._w4(),
             pseudo_time=None if pt is None else [pt.sigma, pt.sigma_p, pt.every],

@@ -338,6 +338,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         if not hasattr(self, 'log_interval'):
             self.log_interval = 100
         scheduler = self._begin_adam_stage(scheduler, resume=start_epoch > 0)
+        self._early_stop_begin(resume=start_epoch > 0)
         if not start_epoch:
             self.freeze_evm_net(0)
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
@@ -361,7 +362,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop%d.pth' % (epoch_id), N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
-            if self._at_log(epoch_id, num_epoch, interval) and self._patience_out():
+            if self._at_log(epoch_id, num_epoch, interval) and (self._patience_out() or self._early_stop_out(epoch_id)):
                 break
         if num_epoch > start_epoch:
             self._publish_terms()
@@ -417,6 +418,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             print('  ' + self._confgrad_log())
         if self._validation:
             print('  ' + self.validation_log())
+        if self._early_stop:
+            print('  ' + self.early_stop_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]

@@ -69,6 +69,7 @@ class SolverBase:
     _validation = False
     _val_patience = 0           # set_validation_data(patience=k): a stage ends at a log point with stale >= k
     _pseudo_time = False
+    _early_stop = False         # set_early_stopping: solve_Adam leaves the stage at a log point once the monitor says so
 
     def set_resampling(self, every=0, k=1.0, c=1.0, seed=0):
         """every > 0: solve_Adam resamples before steps every, 2 every, ... of each train() call."""
@@ -288,6 +289,54 @@ class SolverBase:
         if not self._validation or self._val_patience <= 0:
             return False
         return self.engine.validation_info()["stale"] >= self._val_patience
+
+    def set_early_stopping(self, every=1, window=1000, min_rel_improvement=1e-3, patience=3, re_eff_tol=None,
+                           min_updates=0, quantity="loss", mode="any", history=4096):
+        """End an Adam stage that has stopped making progress (PinnEngine.set_convergence_monitor; DESIGN.md section
+        7.14): the device compares the means of `quantity` (and, with re_eff_tol, of Re_eff) over consecutive windows
+        of `window` observed updates and sets a stop bit after `patience` windows in a row that improved by less than
+        min_rel_improvement (changed by less than re_eff_tol); a non-finite loss stops at once.  solve_Adam reads the
+        bits where it logs - on every rank, which all hold the same bits - and leaves the stage there with one line
+        naming the reason and the update that set it; print_log adds the monitor line.  Every stage start resets the
+        monitor (a resumed stage, start_epoch > 0, keeps it); solve_LBFGS neither observes nor asks.  The defaults are
+        guesses: no value has been compared in training.  every = 0: off."""
+        self.engine.set_convergence_monitor(every=every, window=window, min_rel_improvement=min_rel_improvement,
+                                            patience=patience, re_eff_tol=re_eff_tol, min_updates=min_updates,
+                                            quantity=quantity, mode=mode, history=history)
+        self._early_stop = self.engine.monitor_info() is not None
+
+    def _early_stop_begin(self, resume=False):
+        """A stage start: the monitor starts over (not on a resumed stage, whose state load_training_state restored)."""
+        if self._early_stop and not resume:
+            self.engine.reset_convergence_monitor()
+
+    def early_stop_log(self):
+        """One line on the convergence monitor (one host read)."""
+        i = self.engine.monitor_info()
+        if i is None or i["last"] is None:
+            return "early stop: no observation yet"
+        return ("early stop (t=%d): %s window mean=%.4e Re_eff window mean=%.1f  windows=%d stale=%d settled=%d/%d "
+                "nonfinite=%d  reasons=%s" % (i["last"]["t"], i["quantity"], i["window_mean"], i["window_mean_re"],
+                                              i["windows"], i["stale"], i["settled"], i["patience"], i["nonfinite"],
+                                              ",".join(i["reasons"]) or "-"))
+
+    def monitor_history(self):
+        """The observed rows [t, loss, loss_e, loss_b, loss_s, eq1..eq4, vis_mean, Re_eff, stop] in time order (one host
+        read)."""
+        return self.engine.monitor_history()
+
+    def _early_stop_out(self, epoch_id=None):
+        """True when the convergence monitor ends the stage (one host read; solve_Adam asks at its log cadence only, on
+        every rank - the bits are identical).  Prints the reason and the update that set it."""
+        if not self._early_stop:
+            return False
+        i = self.engine.monitor_info()
+        if not i["should_stop"]:
+            return False
+        if getattr(self, "rank", 0) == 0:
+            print("early stop%s: %s" % ("" if epoch_id is None else " after epoch %d" % (epoch_id + 1), "; ".join(
+                "%s (set by update %d)" % (r, i["t_" + r]) for r in i["reasons"])))
+        return True
 
     def save_weight_factors(self, path):
         """Write the sidecar of the checkpoint at `path`: {net name: flat fp32 s} as path + '_rwf' (torch.save).  With
@@ -633,6 +682,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         checkpoint every 10000 (incl. step 0).  Adam moments persist across calls."""
         fused = getattr(loss_func, "__func__", None) is PysicsInformedNeuralNetwork.fwd_computing_loss_2d
         scheduler = self._begin_adam_stage(scheduler, resume=start_epoch > 0)
+        self._early_stop_begin(resume=start_epoch > 0)
         epoch_id, end_epoch = int(start_epoch), self._end_epoch(num_epoch, stop_epoch)
         print('--------')
         print(num_epoch)
@@ -655,7 +705,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
             if save_now:
                 self.save('model_cavity_loop_%d.pth' % epoch_id, N_HLayer=self.layers, N_neu=self.hidden_size,
                           N_f=self.N_f)
-            if log_now and self._patience_out():
+            if log_now and (self._patience_out() or self._early_stop_out(epoch_id)):
                 break
             epoch_id += 1
         self._publish_terms()
@@ -673,7 +723,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("\n" + self._pseudo_time_log(),) if self._pseudo_time else ()),
               *(("\n" + self._confgrad_log(),) if self._confgrad else ()),
               *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()),
-              *(("\n" + self.validation_log(),) if self._validation else ()))
+              *(("\n" + self.validation_log(),) if self._validation else ()),
+              *(("\n" + self.early_stop_log(),) if self._early_stop else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

@@ -26,6 +26,10 @@ pseudo-time anchors, a resampled collocation set.  The call must be given the sa
         [--validate-every 1000 --val-metric uv]   (error against the DNS field on the device every that many updates of
                                                   a stage, the stage's best weights kept: validation.jsonl,
                                                   net_best.pth / net_best_evm.pth; off by default)
+        [--early-stop 1000 1e-3 --re-eff-tol 1e-3]   (device convergence monitor: a stage ends at a log point after three
+                                                  windows of that many updates that improved the mean loss by less than
+                                                  that fraction - or, with --re-eff-tol, moved the mean Re_eff by less;
+                                                  the per-update curve goes to monitor.jsonl; off by default)
         [--state FILE --state-every 50000 --max-steps 400000]   (training-state snapshots: continue from FILE when it
                                                   exists, write it every that many updates, end the call after that many
                                                   updates, anywhere in a stage)
@@ -97,6 +101,12 @@ def main():
                     help="> 0: validate against the DNS field on the device every this many updates of a stage and keep "
                          "the stage's best weights (DESIGN.md 7.9)")
     ap.add_argument("--val-metric", choices=("uv", "u", "v", "p", "p0"), default="uv", help="what `best` means")
+    ap.add_argument("--early-stop", type=float, nargs=2, default=None, metavar=("WINDOW", "TOL"),
+                    help="end a stage early on a loss plateau: window means over WINDOW updates, stale below a relative "
+                         "improvement of TOL, three stale windows in a row (DESIGN.md 7.14)")
+    ap.add_argument("--re-eff-tol", type=float, default=None, metavar="TOL",
+                    help="also (or, without --early-stop, only) end a stage when the window mean of Re_eff moves by less "
+                         "than TOL for three windows in a row (windows of --early-stop's WINDOW, else 1000 updates)")
     ap.add_argument("--state", default=None, metavar="FILE",
                     help="training-state file (DESIGN.md 7.12): continue from it when it exists, and write it")
     ap.add_argument("--state-every", type=int, default=0, help="updates between two non-blocking snapshots (0: only where the call ends)")
@@ -155,6 +165,11 @@ def main():
             P.set_weight_factorization(factors=torch.load(side, map_location="cpu", weights_only=True))
         else:
             P.set_weight_factorization(mean=a.rwf_mean, std=a.rwf_std, seed=a.rwf_seed)
+    monitor = a.early_stop is not None or a.re_eff_tol is not None
+    if monitor:                                         # every stage start resets it; the ring keeps the stage's curve
+        P.set_early_stopping(window=1000 if a.early_stop is None else int(a.early_stop[0]),
+                             min_rel_improvement=None if a.early_stop is None else a.early_stop[1],
+                             re_eff_tol=a.re_eff_tol, history=1 << 16)
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     first, start, left = a.first, 0, a.max_steps if a.max_steps > 0 else None
@@ -192,7 +207,10 @@ def main():
             return
         if left is not None:
             left -= n - start
-        ran, start = n - start, 0
+        ran = n - start
+        if monitor:                                     # a stage that stopped early ran fewer (the monitor counts the stage's updates)
+            ran = max(1, min(ran, P.engine.monitor_info()["updates"] - start))
+        start = 0
         dt = time.time() - t0
         eu, ev = P.evaluate(*star)[:2]
         rec = dict(stage=k, alpha_evm=alpha, lr=lr, steps=n, seconds=round(dt, 1), ms_per_step=round(1e3 * dt / ran, 4),
@@ -223,6 +241,14 @@ def main():
             if best is not None:
                 torch.save(best, "net_best.pth")
                 torch.save(P.engine.best_state_dict_e(), "net_best_evm.pth")
+        if monitor:
+            info = P.engine.monitor_info()
+            rec.update(early_stop=dict(updates=info["updates"], reasons=info["reasons"], stopped=info["should_stop"],
+                                       window_mean=info["window_mean"], window_mean_re=info["window_mean_re"]))
+            with open("monitor.jsonl", "a") as fh:
+                for row in P.monitor_history().tolist():
+                    fh.write(json.dumps(dict(zip(("t", "loss", "loss_e", "loss_b", "loss_s", "eq1", "eq2", "eq3", "eq4",
+                                                  "vis_mean", "Re_eff", "stop"), row), stage=k)) + "\n")
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
