@@ -195,16 +195,14 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   return launch_or_configure(&bwd_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
-#define BWD_CASE(hp)                                                        \
-  case hp:                                                                  \
-    if (a.ptime && NS == 4) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
-    if (a.hbc.kind && NS == 4) return launch_one<hp, 4, true>(a, grid, s);  \
-    return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
-
 int launch_bwd(int HP, int NS, const BwdArgs& a, int grid, hipStream_t s) {
-  switch (HP) {
-    BWD_CASE(32) BWD_CASE(64) BWD_CASE(96) BWD_CASE(128)
-    BWD_CASE(160) BWD_CASE(192) BWD_CASE(224) BWD_CASE(256)
-    default: return -1000;
-  }
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(NS, 1, [&](auto ns, auto) {
+      constexpr int N = decltype(ns)::value;      // (value mode reads no flag; ff is not read: the plain kernel serves it)
+      return dispatch_variant<N == 4 ? VARIANTS_WAVE8_BWD : VARIANTS_WAVE8_BWD_VALUE>(N == 4 && a.hbc.kind, N == 4 && a.ptime, false, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, N, V::hbc, V::pt>(a, grid, s);
+      });
+    });
+  });
 }

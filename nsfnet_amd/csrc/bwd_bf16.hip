@@ -281,9 +281,8 @@ template <int HP, int COLS>
 static size_t lds_bytes_t(int L) { return XImg<HP, COLS / 4>::BYTES + ((size_t)4 * COLS + sg_total(HP, L)) * sizeof(float); }
 
 size_t bwd_bf16_lds_bytes(int HP, int L, int cols) {
-#define LB(hp) case hp: return cols == 64 ? lds_bytes_t<hp, 64>(L) : lds_bytes_t<hp, 128>(L);
-  switch (HP) { LB(32) LB(64) LB(96) LB(128) LB(160) LB(192) LB(224) default: return cols == 64 ? lds_bytes_t<256, 64>(L) : lds_bytes_t<256, 128>(L); }
-#undef LB
+  const auto bytes = [&](auto hp) { return cols == 64 ? lds_bytes_t<decltype(hp)::value, 64>(L) : lds_bytes_t<decltype(hp)::value, 128>(L); };
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224>(HP, bytes(std::integral_constant<int, 256>{}), bytes);
 }
 
 template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
@@ -295,31 +294,16 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
 
 template <int HP, int COLS>
 static int launch_hp(int NS, int terms, const BwdArgs& a, int grid, hipStream_t s) {
-  if (a.ptime && NS == 4)
-    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
-      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, COLS, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, COLS, false, true>(a, grid, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) {
+    constexpr int N = decltype(ns)::value;      // (value mode reads no flag; ff is not read: the plain kernel serves it)
+    return dispatch_variant<N == 4 ? VARIANTS_WAVE8_BWD : VARIANTS_WAVE8_BWD_VALUE>(N == 4 && a.hbc.kind, N == 4 && a.ptime, false, [&](auto v) {
+      using V = decltype(v);
+      return launch_one<HP, N, decltype(t)::value, COLS, V::hbc, V::pt>(a, grid, s);
     });
-  if (a.hbc.kind && NS == 4) return dispatch_ns_terms(4, terms, [&](auto, auto t) { return launch_one<HP, 4, decltype(t)::value, COLS, true>(a, grid, s); });
-  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, COLS>(a, grid, s); });
+  });
 }
 
 int launch_bwd_bf16(int HP, int NS, int terms, int cols, const BwdArgs& a, int grid, hipStream_t s) {
-  if (cols == 64) {
-    switch (HP) {
-      case 128: return launch_hp<128, 64>(NS, terms, a, grid, s);
-      case 256: return launch_hp<256, 64>(NS, terms, a, grid, s);
-      default: return -1000;
-    }
-  }
-  switch (HP) {
-    case 32: return launch_hp<32, 128>(NS, terms, a, grid, s);
-    case 64: return launch_hp<64, 128>(NS, terms, a, grid, s);
-    case 96: return launch_hp<96, 128>(NS, terms, a, grid, s);
-    case 128: return launch_hp<128, 128>(NS, terms, a, grid, s);
-    case 160: return launch_hp<160, 128>(NS, terms, a, grid, s);
-    case 192: return launch_hp<192, 128>(NS, terms, a, grid, s);
-    case 224: return launch_hp<224, 128>(NS, terms, a, grid, s);
-    case 256: return launch_hp<256, 128>(NS, terms, a, grid, s);
-    default: return -1000;
-  }
+  if (cols == 64) return dispatch_width<128, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) { return launch_hp<decltype(hp)::value, 64>(NS, terms, a, grid, s); });
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) { return launch_hp<decltype(hp)::value, 128>(NS, terms, a, grid, s); });
 }

@@ -334,6 +334,12 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
 
 // residual mode, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_bwd_pipe(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
-  if (HP != 256) return -1000;
-  return terms == 3 ? launch_one<256, 3>(a, grid, s) : launch_one<256, 1>(a, grid, s);
+  // (tanh only: a constrained, pseudo-time or frozen-sine plan is refused here, not run on the plain kernel)
+  return dispatch_width<256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return dispatch_variant<VARIANTS_PIPE>(a.hbc.kind, a.ptime, a.ff, [&](auto) {
+        return launch_one<decltype(hp)::value, decltype(t)::value>(a, grid, s);
+      });
+    });
+  });
 }

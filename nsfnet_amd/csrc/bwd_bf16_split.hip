@@ -150,15 +150,13 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
 
 // residual mode, L >= 2 hidden layers, HP = 256 (the caller checks)
 int launch_bwd_split(int HP, int terms, const BwdArgs& a, int grid, hipStream_t s) {
-  if (HP != 256) return -1000;
-  if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
-    if (a.ptime || a.hbc.kind || a.L < 2) return -1000;
-    return terms == 3 ? launch_one<256, 3, false, false, true>(a, grid, s) : launch_one<256, 1, false, false, true>(a, grid, s);
-  }
-  if (a.ptime) {
-    if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(a, grid, s) : launch_one<256, 1, true, true>(a, grid, s);
-    return terms == 3 ? launch_one<256, 3, false, true>(a, grid, s) : launch_one<256, 1, false, true>(a, grid, s);
-  }
-  if (a.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(a, grid, s) : launch_one<256, 1, true>(a, grid, s);
-  return terms == 3 ? launch_one<256, 3>(a, grid, s) : launch_one<256, 1>(a, grid, s);
+  if (a.ff && a.L < 2) return DISPATCH_UNSUPPORTED;      // (the FF sweep ends at layer 1)
+  return dispatch_width<256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return dispatch_variant<VARIANTS_SPLIT>(a.hbc.kind, a.ptime, a.ff, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, decltype(t)::value, V::hbc, V::pt, V::ff>(a, grid, s);
+      });
+    });
+  });
 }

@@ -227,16 +227,14 @@ static int launch_one(const BwdArgs& a, int grid, hipStream_t s) {
   return launch_or_configure(&bwd_wide_kernel<HP, NS, HBC, PT>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
-#define BWD_CASE(hp)                                                        \
-  case hp:                                                                  \
-    if (a.ptime && NS == 4) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
-    if (a.hbc.kind && NS == 4) return launch_one<hp, 4, true>(a, grid, s);  \
-    return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
-
 int launch_bwd_wide(int HP, int NS, const BwdArgs& a, int grid, hipStream_t s) {
-  switch (HP) {
-    BWD_CASE(128) BWD_CASE(256) BWD_CASE(288) BWD_CASE(320) BWD_CASE(352) BWD_CASE(384)
-    BWD_CASE(416) BWD_CASE(448) BWD_CASE(480) BWD_CASE(512)
-    default: return -1000;
-  }
+  return dispatch_width<128, 256, 288, 320, 352, 384, 416, 448, 480, 512>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(NS, 1, [&](auto ns, auto) {
+      constexpr int N = decltype(ns)::value;      // (value mode reads no flag; ff is not read: the plain kernel serves it)
+      return dispatch_variant<N == 4 ? VARIANTS_WAVE8_BWD : VARIANTS_WAVE8_BWD_VALUE>(N == 4 && a.hbc.kind, N == 4 && a.ptime, false, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, N, V::hbc, V::pt>(a, grid, s);
+      });
+    });
+  });
 }

@@ -109,6 +109,18 @@ static constexpr unsigned FAMILY_SPILLS[][3] = {
     {IN_P24_WIDE, IN_P24_WIDE, 0},
     {IN_P24_COMPACT, IN_P24_COMPACT, 0},
 };
+// The variants (launch_dispatch.h) each family's sweeps have in residual mode, by the names its launchers dispatch on.
+// resolve_plan keeps a sweep out of a family that lacks the plan's variant and checks every role again once the plan
+// is resolved; the launchers refuse what is outside their mask.  The dW kernels serve every variant.
+static constexpr unsigned FAMILY_VARIANTS[] = {
+    0,
+    VARIANTS_WAVE8, VARIANTS_WAVE8, VARIANTS_WAVE8, VARIANTS_WAVE8,      // fp32, fp32 wide, bf16, bf16 wide
+    VARIANTS_PIPE,
+    VARIANTS_SPLIT, VARIANTS_SPLIT, VARIANTS_SPLIT,                      // role-split, wide role-split, fused
+};
+static const char* variant_name(unsigned bit) {
+  return bit == VAR_FF ? "frozen-sine" : bit == VAR_HBC_PT ? "constrained pseudo-time" : bit == VAR_PT ? "pseudo-time" : bit == VAR_HBC ? "constrained" : "plain";
+}
 // the 8-wave family of one precision on this net: the only place precision and tile geometry are weighed
 static Family base_family(const pinn_net_s& n, int prec) {
   return prec ? (n.HP > 256 ? FAM_BF16_WIDE : FAM_BF16) : n.wide ? FAM_FP32_WIDE : FAM_FP32;
@@ -234,25 +246,18 @@ static int run_fused(const pinn_plan_s* plan, const FwdArgs& fa, const BwdArgs& 
 // (no HIP call) on the net, the point and stream counts, the compute-unit count and the switches.
 static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, int streams, int cus, const Switches& sw_in,
                         const HardBc& hbc = HardBc{}, bool ptime = false) {
-  // The 8-wave, role-split (hidden 256 and wide) and fused families have constrained point stages (point_stage.h); the
-  // pipelined schedule has none.  By default a constrained plan resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
-  // would.  With $PINN_HBC_SPLIT=1 it keeps what the other switches give it, except that a sweep which would run
-  // the pipelined kernels (PINN_SCHED=1, an incomplete role-split pair, an fp32 dW) runs the 8-wave kernel instead.
-  // Either way the spill format follows from the resolved families as for any other plan, and an unconstrained plan
-  // never looks at the switch.
-  // The pseudo-time term has a variant in the same families, with and without walls, and none in the pipelined
-  // schedule.  By default a pseudo-time plan, constrained or not, resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0
-  // would; $PINN_PTIME_SPLIT=1 is to it what $PINN_HBC_SPLIT=1 is to a constrained plan.  A pseudo-time plan never
-  // looks at PINN_HBC_SPLIT, and no other plan looks at PINN_PTIME_SPLIT.
-  // A net with the frozen sine first layer has no variant with walls or pseudo-time.  By default its plans resolve as
-  // PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever those switches say, and store layer 0 (SPILL_CLASSIC in every
-  // precision): what is stored there is the layer's a-streams, which no reader recomputes.  With $PINN_FF_SPLIT=1 a
-  // residual plan keeps the role-split sweeps the other switches give it, but only where BOTH sweeps land in the same
-  // role-split family - the complete hidden-256 pair with the bf16 dW (fused where that holds), or the wide pair.  If
-  // either sweep would run the pipelined schedule or an 8-wave kernel, the whole plan is the default one: no mixed
-  // layouts.  The layout follows from the families: the compact one recomputes layer 0 (layer0_sine), the wide one keeps
-  // the a-streams in layer 0's slot, in the 24-bit format.  Such a plan never looks at PINN_HBC_SPLIT or
-  // PINN_PTIME_SPLIT, and no other plan looks at PINN_FF_SPLIT.
+  // Which family has which variant of the point stage - hard walls, the pseudo-time term, both, the frozen sine first
+  // layer - is FAMILY_VARIANTS: every family but the pipelined schedule has all of them.  By default a plan of any
+  // variant but the plain one resolves as PINN_SCHED=0 PINN_WSPLIT=0 PINN_FUSE=0 would, whatever those switches say.
+  // One switch per variant opts out of that, each read by its own plans only: $PINN_PTIME_SPLIT=1 for a pseudo-time plan
+  // (constrained or not), $PINN_HBC_SPLIT=1 for any other constrained plan, $PINN_FF_SPLIT=1 for a residual plan over a
+  // sine net.  Such a plan keeps what the other switches give it, except that a sweep which would run the pipelined
+  // kernels (PINN_SCHED=1, an incomplete role-split pair, an fp32 dW) runs the 8-wave kernel instead.  The spill format
+  // follows from the resolved families as for any other plan.  A sine net has no variant with walls or pseudo-time, and
+  // its layer 0 holds the a-streams, which no reader recomputes: its 8-wave plans are SPILL_CLASSIC in every precision,
+  // and it keeps the role-split sweeps only where BOTH land in the same role-split family - the complete hidden-256 pair
+  // with the bf16 dW (fused where that holds; the compact layout recomputes layer 0, layer0_sine) or the wide pair (the
+  // a-streams stay in layer 0's slot, in the 24-bit format) - so no plan mixes layouts.
   Switches sw = sw_in;
   const bool ff = is_ff(net);
   if (ff && (hbc.kind || ptime))
@@ -308,8 +313,11 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   // one of them alone runs that sweep on schedule 1.
   const bool split_pair = sf == 2 && sb == 2 && net.prec_dw;
   if (!split_pair) { if (sf == 2) sf = 1; if (sb == 2) sb = 1; }
-  if (hbc.kind || ptime) { if (sf == 1) sf = 0; if (sb == 1) sb = 0; }     // (schedule 1 has no constrained or pseudo-time variant)
-  if (ff && !split_pair) sf = sb = 0;                                      // (nor a frozen-sine one, and an FF plan mixes no layouts)
+  // a sweep whose family lacks the plan's variant runs the 8-wave kernel (for a sine net that is both sweeps or neither:
+  // without the pair no sweep is on schedule 2 here, so no plan mixes layouts)
+  const unsigned variant = variant_bit(hbc.kind != 0, ptime, ff);
+  if (sf == 1 && !(FAMILY_VARIANTS[FAM_PIPE] & variant)) sf = 0;
+  if (sb == 1 && !(FAMILY_VARIANTS[FAM_PIPE] & variant)) sb = 0;
   // wide nets (hidden > 256), all three kernels in a bf16 mode, residual mode: the same 24-bit spill format
   const bool s24w_shape = HP > 256 && streams == 4 && net.prec_fwd && net.prec_bwd && net.prec_dw;
   // wide nets in the 24-bit format: the role-split sweeps at 64-column tiles where their LDS fits (hidden <= 448: the last
@@ -328,20 +336,12 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   if (sw.verbose && hbc.kind)
     fprintf(stderr, "[pinn] plan: hard wall conditions, lid-driven cavity at (%g, %g) x %g, lift power %d, lid sharpness %g\n",
             (double)hbc.x0, (double)hbc.y0, (double)hbc.inv_len, hbc.m, (double)hbc.r);
-  if (sw.verbose && hbc.kind)
-    fprintf(stderr, "[pinn] plan: constrained sweeps: %s (PINN_HBC_SPLIT=%d)\n",
-            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
-            sw.hbc_split);
-  if (sw.verbose && ptime)
-    fprintf(stderr, "[pinn] plan: pseudo-time sweeps: %s (PINN_PTIME_SPLIT=%d)\n",
-            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
-            sw.ptime_split);
+  const char* path = fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels";
+  if (sw.verbose && hbc.kind) fprintf(stderr, "[pinn] plan: constrained sweeps: %s (PINN_HBC_SPLIT=%d)\n", path, sw.hbc_split);
+  if (sw.verbose && ptime) fprintf(stderr, "[pinn] plan: pseudo-time sweeps: %s (PINN_PTIME_SPLIT=%d)\n", path, sw.ptime_split);
   if (sw.verbose && ff && !keep_split)
     fprintf(stderr, "[pinn] plan: frozen sine first layer: 8-wave kernels, layer 0 stored (PINN_SCHED, PINN_WSPLIT, PINN_FUSE and PINN_S0_SKIP32 are not consulted)\n");
-  if (sw.verbose && ff && keep_split)
-    fprintf(stderr, "[pinn] plan: frozen sine sweeps: %s (PINN_FF_SPLIT=%d)\n",
-            fuse ? "fused role-split kernel" : wsplit ? "wide role-split kernels" : sf == 2 ? "role-split kernels, two launches" : "8-wave kernels",
-            sw.ff_split);
+  if (sw.verbose && ff && keep_split) fprintf(stderr, "[pinn] plan: frozen sine sweeps: %s (PINN_FF_SPLIT=%d)\n", path, sw.ff_split);
   const Family fs = wsplit ? FAM_WSPLIT : sf == 2 ? FAM_SPLIT : sf == 1 ? FAM_PIPE : f8;
   const Family bs = wsplit ? FAM_WSPLIT : sb == 2 ? FAM_SPLIT : sb == 1 ? FAM_PIPE : b8;
   role(ROLE_FWD, f8, grid_f, lds_f, 0);
@@ -371,6 +371,12 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   const size_t ablk = act_block(HP, wide ? 64 : PINN_TILE_COLS);
   const bool skip32 = streams == 4 && L >= 2 && !net.prec_fwd && !net.prec_bwd && !net.prec_dw && sw.s0_skip32 != 0 && !ff;
   p->spill = spill_make(split_pair ? SPILL_P24_COMPACT : s24w ? SPILL_P24_WIDE : skip32 ? SPILL_SKIP0 : SPILL_CLASSIC, ablk);
+  for (int r = 0; r < ROLE_COUNT; ++r)
+    if (p->role[r].family && !(FAMILY_VARIANTS[p->role[r].family] & variant)) {
+      char what[96];
+      snprintf(what, sizeof(what), "%s has no %s", p->role[r].name, variant_name(variant));
+      return fail(-5, "pinn_plan_create: internal error: %s variant", what);
+    }
   for (int r = 0; r < ROLE_COUNT; ++r)
     if (ROLE_SPILL_COL[r] >= 0 && p->role[r].family && (r != ROLE_DW || p->groups) &&
         !spill_is(p->spill, ablk, FAMILY_SPILLS[p->role[r].family][ROLE_SPILL_COL[r]]))
@@ -656,10 +662,6 @@ int pinn_residual_forward(pinn_plan_t plan, void* ws, const float* prep,
   return run_loss_sums(r, a, loss_sums, (hipStream_t)stream, "pinn_residual_forward(loss sums)");
 }
 
-static int run_dw_and_stash(pinn_plan_t plan, void* ws, const float* prep, const float* x, const float* y, hipStream_t s) {
-  return run_dw(plan, dw_args(plan, ws, prep, x, y), s);
-}
-
 int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
                                   const float* x, const float* y, const float* e, const float* w,
                                   const float* vis_t, const float* fields, const float* coef_eq4,
@@ -673,7 +675,7 @@ int pinn_residual_backward_phases(pinn_plan_t plan, void* ws, const float* prep,
     rc = run_bwd(plan, a, (hipStream_t)stream);
     if (rc) return hipfail(rc, "pinn_residual_backward");
   }
-  if (phases & 2) rc = run_dw_and_stash(plan, ws, prep, x, y, (hipStream_t)stream);
+  if (phases & 2) rc = run_dw(plan, dw_args(plan, ws, prep, x, y), (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_residual_backward(dW)") : 0;
 }
 
@@ -710,7 +712,7 @@ int pinn_residual_forward_backward(pinn_plan_t plan, void* ws, const float* prep
   if (rc) return hipfail(rc, "pinn_residual_forward_backward");
   rc = run_loss_sums(plan->role[ROLE_FUSED], fa, loss_sums, s, "pinn_residual_forward_backward(loss sums)");
   if (rc) return rc;
-  rc = run_dw_and_stash(plan, ws, prep, x, y, s);
+  rc = run_dw(plan, dw_args(plan, ws, prep, x, y), s);
   return rc ? hipfail(rc, "pinn_residual_forward_backward(dW)") : 0;
 }
 
@@ -743,7 +745,7 @@ int pinn_value_backward(pinn_plan_t plan, void* ws, const float* prep,
   a.oadj = out_adj ? out_adj : WS(plan, off_oadj);
   int rc = run_bwd(plan, a, (hipStream_t)stream);
   if (rc) return hipfail(rc, "pinn_value_backward");
-  rc = run_dw_and_stash(plan, ws, prep, x, y, (hipStream_t)stream);
+  rc = run_dw(plan, dw_args(plan, ws, prep, x, y), (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_value_backward(dW)") : 0;
 }
 

@@ -162,16 +162,15 @@ static int launch_one(const DwArgs& a, hipStream_t s) {
   return launch_or_configure(&dw_kernel<HP, NS, FF>, dim3(a.groups, a.L - 1), dim3(HP * 2), lds, s, a.configure, a);
 }
 
-#define DW_CASE(hp)                                                         \
-  case hp:                                                                  \
-    if (NS == 4 && a.ff) return launch_one<hp, 4, true>(a, s);             \
-    return NS == 4 ? launch_one<hp, 4>(a, s) : launch_one<hp, 1>(a, s);
-
 int launch_dw(int HP, int NS, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
-  switch (HP) {
-    DW_CASE(32) DW_CASE(64) DW_CASE(96) DW_CASE(128)
-    DW_CASE(160) DW_CASE(192) DW_CASE(224) DW_CASE(256)
-    default: return -1000;
-  }
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(NS, 1, [&](auto ns, auto) {
+      constexpr int H = decltype(hp)::value, N = decltype(ns)::value;
+      if constexpr (N == 4) {
+        if (a.ff) return launch_one<H, 4, true>(a, s);
+      }
+      return launch_one<H, N>(a, s);
+    });
+  });
 }

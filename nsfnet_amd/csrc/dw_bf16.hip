@@ -308,11 +308,7 @@ template <int HP>
 static size_t lds_bytes_t() { return DwImg<HP>::BYTES; }
 
 size_t dw_bf16_lds_bytes(int HP) {
-  switch (HP) {
-    case 32: return lds_bytes_t<32>(); case 64: return lds_bytes_t<64>(); case 96: return lds_bytes_t<96>();
-    case 128: return lds_bytes_t<128>(); case 160: return lds_bytes_t<160>(); case 192: return lds_bytes_t<192>();
-    case 224: return lds_bytes_t<224>(); default: return lds_bytes_t<256>();
-  }
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224>(HP, lds_bytes_t<256>(), [](auto hp) { return lds_bytes_t<decltype(hp)::value>(); });
 }
 
 template <int HP, int NS, int TERMS, int PPL, bool P24, bool REC0, bool FF = false>
@@ -343,28 +339,11 @@ static int launch_one(const DwArgs& a, hipStream_t s) {
 
 template <int HP, int PPL>
 static int launch_hp(int NS, int terms, const DwArgs& a, hipStream_t s) {
-  if (terms == 3) return NS == 4 ? launch_one<HP, 4, 3, PPL>(a, s) : launch_one<HP, 1, 3, PPL>(a, s);
-  return NS == 4 ? launch_one<HP, 4, 1, PPL>(a, s) : launch_one<HP, 1, 1, PPL>(a, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, PPL>(a, s); });
 }
 
 int launch_dw_bf16(int HP, int NS, int terms, int cols, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
-  if (cols == 64) {
-    switch (HP) {
-      case 128: return launch_hp<128, 16>(NS, terms, a, s);
-      case 256: return launch_hp<256, 16>(NS, terms, a, s);
-      default: return -1000;
-    }
-  }
-  switch (HP) {
-    case 32: return launch_hp<32, 32>(NS, terms, a, s);
-    case 64: return launch_hp<64, 32>(NS, terms, a, s);
-    case 96: return launch_hp<96, 32>(NS, terms, a, s);
-    case 128: return launch_hp<128, 32>(NS, terms, a, s);
-    case 160: return launch_hp<160, 32>(NS, terms, a, s);
-    case 192: return launch_hp<192, 32>(NS, terms, a, s);
-    case 224: return launch_hp<224, 32>(NS, terms, a, s);
-    case 256: return launch_hp<256, 32>(NS, terms, a, s);
-    default: return -1000;
-  }
+  if (cols == 64) return dispatch_width<128, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) { return launch_hp<decltype(hp)::value, 16>(NS, terms, a, s); });
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) { return launch_hp<decltype(hp)::value, 32>(NS, terms, a, s); });
 }

@@ -212,6 +212,5 @@ static int launch_one(int HP, const DwArgs& a, hipStream_t s) {
 int launch_dw_bf16_wide(int HP, int NS, int terms, const DwArgs& a, hipStream_t s) {
   if (a.L <= 1 || a.groups <= 0) return 0;
   if (HP <= 256 || HP > 512 || HP % 32) return -1000;
-  if (terms == 3) return NS == 4 ? launch_one<4, 3>(HP, a, s) : launch_one<1, 3>(HP, a, s);
-  return NS == 4 ? launch_one<4, 1>(HP, a, s) : launch_one<1, 1>(HP, a, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<decltype(ns)::value, decltype(t)::value>(HP, a, s); });
 }

@@ -193,17 +193,14 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   return launch_or_configure(&fwd_kernel<HP, NS, HBC, PT, FF>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
-#define FWD_CASE(hp)                                                        \
-  case hp:                                                                  \
-    if (a.ff) return a.hbc.kind || (NS == 4 && a.ptime) ? -1000 : NS == 4 ? launch_one<hp, 4, false, false, true>(a, grid, s) : launch_one<hp, 1, false, false, true>(a, grid, s); \
-    if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
-    if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
-    return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
-
 int launch_fwd(int HP, int NS, const FwdArgs& a, int grid, hipStream_t s) {
-  switch (HP) {
-    FWD_CASE(32) FWD_CASE(64) FWD_CASE(96) FWD_CASE(128)
-    FWD_CASE(160) FWD_CASE(192) FWD_CASE(224) FWD_CASE(256)
-    default: return -1000;
-  }
+  return dispatch_width<32, 64, 96, 128, 160, 192, 224, 256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(NS, 1, [&](auto ns, auto) {
+      constexpr int N = decltype(ns)::value;      // (ptime shares its bytes with the value-mode coef[]: residual mode only)
+      return dispatch_variant<N == 4 ? VARIANTS_WAVE8 : VARIANTS_WAVE8_FWD_VALUE>(a.hbc.kind, N == 4 && a.ptime, a.ff, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, N, V::hbc, V::pt, V::ff>(a, grid, s);
+      });
+    });
+  });
 }

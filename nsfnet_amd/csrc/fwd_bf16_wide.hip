@@ -295,28 +295,15 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
 
 template <int HP>
 static int launch_hp(int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
-  if (a.ff) {
-    if (a.hbc.kind || (NS == 4 && a.ptime)) return -1000;
-    return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, false, false, true>(a, grid, s); });
-  }
-  if (NS == 4 && a.ptime)
-    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
-      return a.hbc.kind ? launch_one<HP, 4, decltype(t)::value, true, true>(a, grid, s) : launch_one<HP, 4, decltype(t)::value, false, true>(a, grid, s);
+  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) {
+    constexpr int N = decltype(ns)::value;      // (ptime shares its bytes with the value-mode coef[]: residual mode only)
+    return dispatch_variant<N == 4 ? VARIANTS_WAVE8 : VARIANTS_WAVE8_FWD_VALUE>(a.hbc.kind, N == 4 && a.ptime, a.ff, [&](auto v) {
+      using V = decltype(v);
+      return launch_one<HP, N, decltype(t)::value, V::hbc, V::pt, V::ff>(a, grid, s);
     });
-  if (a.hbc.kind) return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value, true>(a, grid, s); });
-  return dispatch_ns_terms(NS, terms, [&](auto ns, auto t) { return launch_one<HP, decltype(ns)::value, decltype(t)::value>(a, grid, s); });
+  });
 }
 
 int launch_fwd_bf16_wide(int HP, int NS, int terms, const FwdArgs& a, int grid, hipStream_t s) {
-  switch (HP) {
-    case 288: return launch_hp<288>(NS, terms, a, grid, s);
-    case 320: return launch_hp<320>(NS, terms, a, grid, s);
-    case 352: return launch_hp<352>(NS, terms, a, grid, s);
-    case 384: return launch_hp<384>(NS, terms, a, grid, s);
-    case 416: return launch_hp<416>(NS, terms, a, grid, s);
-    case 448: return launch_hp<448>(NS, terms, a, grid, s);
-    case 480: return launch_hp<480>(NS, terms, a, grid, s);
-    case 512: return launch_hp<512>(NS, terms, a, grid, s);
-    default: return -1000;
-  }
+  return dispatch_width<288, 320, 352, 384, 416, 448, 480, 512>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) { return launch_hp<decltype(hp)::value>(NS, terms, a, grid, s); });
 }

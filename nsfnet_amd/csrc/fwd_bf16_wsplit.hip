@@ -106,7 +106,7 @@ __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
 }
 
 size_t fwd_wsplit_lds_bytes(int HP) {
-  return wsplit_width(HP, (size_t)1 << 30, [](auto hp) { return WSplitWave<decltype(hp)::value, 3>::fwd_bytes(); });
+  return dispatch_width<WSPLIT_WIDTHS>(HP, (size_t)1 << 30, [](auto hp) { return WSplitWave<decltype(hp)::value, 3>::fwd_bytes(); });
 }
 
 template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
@@ -118,17 +118,12 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
 
 // residual mode, saved activations in the 24-bit format, L >= 2 hidden layers (the caller checks)
 int launch_fwd_wsplit(int HP, int terms, const FwdArgs& a, int grid, hipStream_t s) {
-  return wsplit_width(HP, -1000, [&](auto hp) {
-    constexpr int H = decltype(hp)::value;
-    if (a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
-      if (a.ptime || a.hbc.kind) return -1000;
-      return terms == 3 ? launch_one<H, 3, false, false, true>(a, grid, s) : launch_one<H, 1, false, false, true>(a, grid, s);
-    }
-    if (a.ptime) {
-      if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true, true>(a, grid, s) : launch_one<H, 1, true, true>(a, grid, s);
-      return terms == 3 ? launch_one<H, 3, false, true>(a, grid, s) : launch_one<H, 1, false, true>(a, grid, s);
-    }
-    if (a.hbc.kind) return terms == 3 ? launch_one<H, 3, true>(a, grid, s) : launch_one<H, 1, true>(a, grid, s);
-    return terms == 3 ? launch_one<H, 3>(a, grid, s) : launch_one<H, 1>(a, grid, s);
+  return dispatch_width<WSPLIT_WIDTHS>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return dispatch_variant<VARIANTS_SPLIT>(a.hbc.kind, a.ptime, a.ff, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, decltype(t)::value, V::hbc, V::pt, V::ff>(a, grid, s);
+      });
+    });
   });
 }

@@ -198,17 +198,14 @@ static int launch_one(const FwdArgs& a, int grid, hipStream_t s) {
   return launch_or_configure(&fwd_wide_kernel<HP, NS, HBC, PT, FF>, dim3(grid), dim3(HP * 2), lds, s, a.configure, a);
 }
 
-#define FWD_CASE(hp)                                                        \
-  case hp:                                                                  \
-    if (a.ff) return a.hbc.kind || (NS == 4 && a.ptime) ? -1000 : NS == 4 ? launch_one<hp, 4, false, false, true>(a, grid, s) : launch_one<hp, 1, false, false, true>(a, grid, s); \
-    if (NS == 4 && a.ptime) return a.hbc.kind ? launch_one<hp, 4, true, true>(a, grid, s) : launch_one<hp, 4, false, true>(a, grid, s); \
-    if (a.hbc.kind) return NS == 4 ? launch_one<hp, 4, true>(a, grid, s) : launch_one<hp, 1, true>(a, grid, s); \
-    return NS == 4 ? launch_one<hp, 4>(a, grid, s) : launch_one<hp, 1>(a, grid, s);
-
 int launch_fwd_wide(int HP, int NS, const FwdArgs& a, int grid, hipStream_t s) {
-  switch (HP) {
-    FWD_CASE(128) FWD_CASE(256) FWD_CASE(288) FWD_CASE(320) FWD_CASE(352) FWD_CASE(384)
-    FWD_CASE(416) FWD_CASE(448) FWD_CASE(480) FWD_CASE(512)
-    default: return -1000;
-  }
+  return dispatch_width<128, 256, 288, 320, 352, 384, 416, 448, 480, 512>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(NS, 1, [&](auto ns, auto) {
+      constexpr int N = decltype(ns)::value;      // (ptime shares its bytes with the value-mode coef[]: residual mode only)
+      return dispatch_variant<N == 4 ? VARIANTS_WAVE8 : VARIANTS_WAVE8_FWD_VALUE>(a.hbc.kind, N == 4 && a.ptime, a.ff, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, N, V::hbc, V::pt, V::ff>(a, grid, s);
+      });
+    });
+  });
 }

@@ -333,15 +333,13 @@ static int launch_one(const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t
 
 // residual mode, MSE seeds, role-split plan (HP = 256, SPILL_P24_COMPACT)
 int launch_fwdbwd_split(int HP, int terms, const FwdArgs& fa, const BwdArgs& a, int grid, hipStream_t s) {
-  if (HP != 256) return -1000;
-  if (fa.ff || a.ff) {      // (never with walls or pseudo-time: pinn_plan_create refuses the combination)
-    if (!fa.ff || !a.ff || fa.ptime || fa.hbc.kind || a.L < 2) return -1000;
-    return terms == 3 ? launch_one<256, 3, false, false, true>(fa, a, grid, s) : launch_one<256, 1, false, false, true>(fa, a, grid, s);
-  }
-  if (fa.ptime) {
-    if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true, true>(fa, a, grid, s) : launch_one<256, 1, true, true>(fa, a, grid, s);
-    return terms == 3 ? launch_one<256, 3, false, true>(fa, a, grid, s) : launch_one<256, 1, false, true>(fa, a, grid, s);
-  }
-  if (fa.hbc.kind) return terms == 3 ? launch_one<256, 3, true>(fa, a, grid, s) : launch_one<256, 1, true>(fa, a, grid, s);
-  return terms == 3 ? launch_one<256, 3>(fa, a, grid, s) : launch_one<256, 1>(fa, a, grid, s);
+  if (!fa.ff != !a.ff || (a.ff && a.L < 2)) return DISPATCH_UNSUPPORTED;      // (one net on both sides; the FF sweep ends at layer 1)
+  return dispatch_width<256>(HP, DISPATCH_UNSUPPORTED, [&](auto hp) {
+    return dispatch_ns_terms(4, terms, [&](auto, auto t) {
+      return dispatch_variant<VARIANTS_SPLIT>(fa.hbc.kind, fa.ptime, fa.ff, [&](auto v) {
+        using V = decltype(v);
+        return launch_one<decltype(hp)::value, decltype(t)::value, V::hbc, V::pt, V::ff>(fa, a, grid, s);
+      });
+    });
+  });
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "fixed_fold.h"
+#include "launch_dispatch.h"
 #include "layout.h"
 #include "spill.h"
 
@@ -28,14 +29,6 @@ static int launch_or_configure(void (*kernel)(Params...), dim3 grid, dim3 block,
     return -(int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PINN_LDS_MAX);
   hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
   return -(int)hipGetLastError();
-}
-// A sweep's run-time mode as template arguments: f(ns, terms) with NS = 4 (residual) / 1 (value) streams and TERMS = 3
-// (bf16x3) / 1 (bf16) products per term, each a std::integral_constant.
-template <class F>
-static int dispatch_ns_terms(int NS, int terms, F f) {
-  using std::integral_constant;
-  if (terms == 3) return NS == 4 ? f(integral_constant<int, 4>{}, integral_constant<int, 3>{}) : f(integral_constant<int, 1>{}, integral_constant<int, 3>{});
-  return NS == 4 ? f(integral_constant<int, 4>{}, integral_constant<int, 1>{}) : f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
 }
 #endif
 

@@ -438,14 +438,6 @@ struct WSplitWave {
   }
 };
 
-// The supported widths (those whose last K region fits twice in the image rows): f(std::integral_constant<int, HP>{})
-// for one of them, `other` for any other width (480, 512: the 8-wave kernels stay).
-template <class R, class F>
-static R wsplit_width(int HP, R other, F f) {
-  switch (HP) {
-    case 288: return f(std::integral_constant<int, 288>{}); case 320: return f(std::integral_constant<int, 320>{});
-    case 352: return f(std::integral_constant<int, 352>{}); case 384: return f(std::integral_constant<int, 384>{});
-    case 416: return f(std::integral_constant<int, 416>{}); case 448: return f(std::integral_constant<int, 448>{});
-    default: return other;
-  }
-}
+// The supported widths (those whose last K region fits twice in the image rows), as dispatch_width's list; 480 and
+// 512 keep the 8-wave kernels.
+#define WSPLIT_WIDTHS 288, 320, 352, 384, 416, 448
