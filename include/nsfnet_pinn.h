@@ -710,6 +710,40 @@ int pinn_monitor_observe(const float* eq, const float* bc, const float* sup, con
                          double alpha_s, double alpha_e, double eq4_weight, double n_eq, double n_b, double n_s, double n_p,
                          double Re, const pinn_monitor_config_t* cfg, double* state, double* ring, void* stream);
 
+/* ---- viscosity identification: the molecular viscosity nu = 1 / Re as a trainable scalar ----
+ * pinn_plan_set_viscosity: a residual (4-stream) plan may carry two device pointers.  nu_dev: one fp32; every residual
+ *   launch of the plan (forward, reverse sweep, fused) then uses *nu_dev wherever it would use 1 / Re - the Re argument of
+ *   those calls is still checked and otherwise unused.  lap: [2][padded points] fp32, 16-byte aligned; the forward leaves
+ *   the physical Laplacians Lap u, Lap v there (after coord_scale^2; on a constrained plan those of the constrained
+ *   fields), padded like the field planes.  lap may be NULL (a plan that is only evaluated); nu_dev = NULL with lap = NULL
+ *   turns both off, and the plan computes what it computed before the call, bit for bit.  A value-mode plan, lap
+ *   without nu_dev and misaligned pointers are refused with -22.  pinn_plan_viscosity returns the two pointers.
+ * pinn_visc_grad: one streaming launch over the planes an evaluation left.  Per point i < n, fp64 from the fp32
+ *   planes, one rounding per operation in this order:
+ *     a1 = eq1 + (w4 eq4) (u - 1/2)     a2 = eq2 + (w4 eq4) (v - 1/2)     t_i = w_i ((a1 Lap u) + (a2 Lap v))
+ *   (w NULL: w_i = 1; w4 = 0: a1 = eq1, a2 = eq2 and the eq4, u, v planes are not read).  S = sum t_i in a fixed order (no
+ *   float atomics, bit-reproducible), rounded once to fp32 into *sum_out - a free slot of the loss-sum block, so that
+ *   the exchange that is made anyway turns it into the global sum.  d loss / d nu = -(2 alpha_e / N) S.
+ *   fields, lap, w 16-byte aligned, npad % 4 == 0.  scratch: pinn_visc_scratch_bytes(n) bytes of device memory, 8-byte
+ *   aligned, ZERO before the first call (the launch leaves its ticket word 0 again).
+ * pinn_visc_update: one workgroup, after the nets' updates.  s = (double)*sum.  A non-finite s raises state[7] and
+ *   changes nothing else.  Otherwise, fp64, one rounding per operation in this order (torch.optim.Adam on theta = ln nu):
+ *     G = coef s                 g = (double)*nu_dev G
+ *     p1 = state[3] beta1        p2 = state[4] beta2
+ *     m = (beta1 m) + ((1 - beta1) g)            v = (beta2 v) + (((1 - beta2) g) g)
+ *     theta = theta - (lr / (1 - p1)) (m / ((sqrt(v) / sqrt(1 - p2)) + eps))
+ *     theta = min(max(theta, theta_min), theta_max)          *nu_dev = (float)exp(theta)
+ *   state (PINN_VISC_STATE doubles of device memory, 8-byte aligned; start: theta, 0, 0, 1, 1, 0, 0, 0):
+ *     [0] theta   [1] m   [2] v   [3] beta1^t   [4] beta2^t   [5] t (updates made)   [6] the last G   [7] skipped updates */
+#define PINN_VISC_STATE 8
+int pinn_plan_set_viscosity(pinn_plan_t plan, const float* nu_dev, float* lap);
+int pinn_plan_viscosity(pinn_plan_t plan, const float** nu_dev, float** lap);
+int64_t pinn_visc_scratch_bytes(int64_t n);
+int pinn_visc_grad(int64_t n, const float* fields, int64_t npad, const float* lap, const float* w, double w4,
+                   float* sum_out, double* scratch, void* stream);
+int pinn_visc_update(const float* sum, double coef, double lr, double beta1, double beta2, double eps, double theta_min,
+                     double theta_max, double* state, float* nu_dev, void* stream);
+
 /* ---- training-state snapshots: many device buffers <-> one staging buffer, with digests ----
  * A snapshot is a list of segments (any number; a launch takes up to 64, more take several launches).  In the staging
  * buffer segment k starts at align256(end of the segment stored before it) and the padding behind a segment is zero,

@@ -103,6 +103,12 @@ SIGNATURES = {
     "pinn_monitor_vis_stats": (c_int, [c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_monitor_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_double,
                                      c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_plan_set_viscosity": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pinn_plan_viscosity": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)]),
+    "pinn_visc_scratch_bytes": (c_int64, [c_int64]),
+    "pinn_visc_grad": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "pinn_visc_update": (c_int, [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_void_p,
+                                 c_void_p, c_void_p]),
     "pinn_state_scratch_bytes": (c_int64, []),
     "pinn_state_layout": (c_int64, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "pinn_state_digest_host": (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_uint64)]),

@@ -14,6 +14,7 @@
 
 template <int HP, int NS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2) void bwd_kernel(BwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   constexpr int NT = HP * 2;
   extern __shared__ float lds[];
   float* X = lds;                 // [HP][128]

@@ -12,6 +12,7 @@
 
 template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2, 2) void bwd_bf16_kernel(BwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
   constexpr int NT = HP * 2, KS = HP / 16;

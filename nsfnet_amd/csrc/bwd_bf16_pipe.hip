@@ -39,6 +39,7 @@ struct PipeBwdLds {
 
 template <int HP, int TERMS>
 __global__ __launch_bounds__(HP, 1) void bwd_pipe_kernel(BwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using G = PipeBwdLds<HP>;
   using XI = typename G::XI;
   constexpr int NW = HP / 64, NT = HP, KS = HP / 16, PPL = 32, COLS = 128;

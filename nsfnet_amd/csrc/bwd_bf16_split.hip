@@ -40,6 +40,7 @@ struct SplitBwdLds {
 
 template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void bwd_split_kernel(BwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using G = SplitBwdLds<HP>;
   using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;

@@ -33,6 +33,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void bwd_bf16_wide_kernel
   float dbo[3] = {0.f, 0.f, 0.f};
   __syncthreads();
 
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     // ---------------- output adjoints per column (point_stage.h) ----------------
     float px[NTL], py[NTL];

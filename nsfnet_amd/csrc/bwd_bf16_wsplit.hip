@@ -59,6 +59,7 @@ __global__ __launch_bounds__(512, 1) void bwd_wsplit_kernel(BwdArgs a) {
 
   // Straight-line program per group: per tile E_{L-1} G_{L-1} E_{L-2} ... G_1 E_0, group 1 one phase behind group 0.
   // Tile of pair i: 2 i + grp.  The next tile's output adjoints ride in the last quarter of E_0.
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   const int npairs = (a.ntiles + 1) / 2;
   float px = 0.f, py = 0.f, pxN = 0.f, pyN = 0.f;
   if ((int)blockIdx.x < npairs) seeds(2 * (int)blockIdx.x + grp, px, py);

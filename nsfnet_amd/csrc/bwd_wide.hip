@@ -9,6 +9,7 @@
 
 template <int HP, int NS, bool HBC = false, bool PT = false>
 __global__ __launch_bounds__(HP * 2) void bwd_wide_kernel(BwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   constexpr int NT = HP * 2, COLS = 64, PPL = 16, NQ = HP / 8;
   constexpr int PRE = 4, RING = 8;
   extern __shared__ float lds[];

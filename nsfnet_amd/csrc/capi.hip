@@ -147,6 +147,8 @@ struct pinn_plan_s {
   int ptime;             // a pseudo-time plan (pinn_plan_create_pseudo_time); resolve_plan says which families it runs
   const float* anchor;   // its anchors [3][npad] (pinn_plan_set_pseudo_time; NULL: unset, residual calls are refused)
   float sigma, sigma_p;  // its rates
+  const float* nu_dev;   // viscosity identification (pinn_plan_set_viscosity; residual plans): the fp32 read in place of 1 / Re, or NULL
+  float* lap;            // and the planes [2][npad] the forward leaves Lap u, Lap v in, or NULL
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -267,6 +269,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   p->net = net;
   p->hbc = hbc;
   p->ptime = ptime; p->anchor = nullptr; p->sigma = p->sigma_p = 0.f;
+  p->nu_dev = nullptr; p->lap = nullptr;
   p->n = n_points; p->streams = streams;
   const bool wide = net.wide != 0;
   const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
@@ -416,6 +419,7 @@ static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float*
   FwdArgs a = fwd_args(plan, ws, prep, x, y, save, coord_scale);
   a.fld = fields; a.e = e; a.w = w; a.vtm = vis_t_minus; a.vis_used = vis_t_out;
   a.inv_re = 1.0f / Re; a.vis_t0 = vis_t0; a.alpha_evm = alpha_evm;
+  a.nu_dev = plan->nu_dev; a.lap = plan->lap;
   a.stagger = stagger && plan->ntiles > 4 * plan->role[ROLE_FWD].grid ? plan->stagger : 0;
   return a;
 }
@@ -439,6 +443,7 @@ static BwdArgs residual_bwd_args(const pinn_plan_s* plan, void* ws, const float*
   a.fld = fields; a.e = e; a.w = w; a.vis_used = vis_t;
   for (int k = 0; k < 4; ++k) a.coef_eq[k] = coef_eq4[k];
   a.inv_re = 1.0f / Re; a.ebar = ebar_out;
+  a.nu_dev = plan->nu_dev;
   return a;
 }
 static DwArgs dw_args(const pinn_plan_s* plan, void* ws, const float* prep, const float* x, const float* y) {
@@ -597,6 +602,21 @@ int pinn_plan_pseudo_time(pinn_plan_t plan, float* sigma, float* sigma_p) {
   if (!plan || !sigma || !sigma_p) return fail(-22, "pinn_plan_pseudo_time: null argument%s");
   if (!plan->ptime) return fail(-22, "pinn_plan_pseudo_time: not a pseudo-time plan (pinn_plan_create_pseudo_time)%s");
   *sigma = plan->sigma; *sigma_p = plan->sigma_p;
+  return 0;
+}
+int pinn_plan_set_viscosity(pinn_plan_t plan, const float* nu_dev, float* lap) {
+  if (!plan) return fail(-22, "pinn_plan_set_viscosity: null plan%s");
+  if (plan->streams != 4) return fail(-22, "pinn_plan_set_viscosity: plan is not a residual (4-stream) plan%s");
+  if (!nu_dev && lap) return fail(-22, "pinn_plan_set_viscosity: lap comes with nu_dev%s");
+  if (reinterpret_cast<uintptr_t>(nu_dev) % 4 != 0) return fail(-22, "pinn_plan_set_viscosity: nu_dev must be 4-byte aligned%s");
+  if (reinterpret_cast<uintptr_t>(lap) % 16 != 0) return fail(-22, "pinn_plan_set_viscosity: lap must be 16-byte aligned%s");
+  plan->nu_dev = nu_dev; plan->lap = lap;
+  return 0;
+}
+int pinn_plan_viscosity(pinn_plan_t plan, const float** nu_dev, float** lap) {
+  if (!plan || !nu_dev || !lap) return fail(-22, "pinn_plan_viscosity: null argument%s");
+  if (plan->streams != 4) return fail(-22, "pinn_plan_viscosity: plan is not a residual (4-stream) plan%s");
+  *nu_dev = plan->nu_dev; *lap = plan->lap;
   return 0;
 }
 int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out) {
@@ -1229,6 +1249,45 @@ int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1,
   a.state = state;
   int rc = launch_val_keep(a, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_val_keep") : 0;
+}
+
+// ---- viscosity identification (visc.hip) ----
+int64_t pinn_visc_scratch_bytes(int64_t n) {
+  return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)visc_scratch_bytes((long)n);
+}
+
+int pinn_visc_grad(int64_t n, const float* fields, int64_t npad, const float* lap, const float* w, double w4,
+                   float* sum_out, double* scratch, void* stream) {
+  if (n < 1 || n > (int64_t)1 << 30) return fail(-22, "pinn_visc_grad: n must be 1..2^30 (got %s%ld)", "", (long)n);
+  if (!fields || !lap || !sum_out || !scratch) return fail(-22, "pinn_visc_grad: null argument%s");
+  if (npad < n || npad % 4 != 0) return fail(-22, "pinn_visc_grad: npad must be >= n and a multiple of 4%s");
+  if (!(w4 >= 0.0) || !std::isfinite(w4)) return fail(-22, "pinn_visc_grad: w4 must be finite and >= 0%s");
+  if (misaligned(fields, 16) || misaligned(lap, 16) || misaligned(w, 16))
+    return fail(-22, "pinn_visc_grad: fields, lap and w must be 16-byte aligned%s");
+  if (misaligned(sum_out, 4) || misaligned(scratch, 8))
+    return fail(-22, "pinn_visc_grad: sum_out must be 4-byte aligned, scratch 8-byte%s");
+  ViscGradArgs a;
+  a.n = (long)n; a.npad = (long)npad; a.fld = fields; a.lap = lap; a.w = w; a.w4 = w4; a.sum_out = sum_out; a.scratch = scratch;
+  int rc = launch_visc_grad(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_visc_grad") : 0;
+}
+
+int pinn_visc_update(const float* sum, double coef, double lr, double beta1, double beta2, double eps, double theta_min,
+                     double theta_max, double* state, float* nu_dev, void* stream) {
+  static_assert(PINN_VISC_STATE == VISC_STATE, "viscosity state size mismatch");
+  if (!sum || !state || !nu_dev) return fail(-22, "pinn_visc_update: null argument%s");
+  if (misaligned(sum, 4) || misaligned(nu_dev, 4) || misaligned(state, 8))
+    return fail(-22, "pinn_visc_update: sum and nu_dev must be 4-byte aligned, state 8-byte%s");
+  if (!std::isfinite(coef) || !std::isfinite(lr) || lr < 0.0) return fail(-22, "pinn_visc_update: coef must be finite, lr finite and >= 0%s");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0) || !std::isfinite(eps))
+    return fail(-22, "pinn_visc_update: betas must lie in [0, 1), eps must be finite and > 0%s");
+  if (!std::isfinite(theta_min) || !std::isfinite(theta_max) || !(theta_min <= theta_max))
+    return fail(-22, "pinn_visc_update: theta_min <= theta_max, both finite%s");
+  ViscUpdateArgs a;
+  a.sum = sum; a.coef = coef; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.theta_min = theta_min; a.theta_max = theta_max; a.state = state; a.nu_dev = nu_dev;
+  int rc = launch_visc_update(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_visc_update") : 0;
 }
 
 // ---- convergence monitor (monitor.hip) ----

@@ -20,6 +20,7 @@
 // of the tanh chain rule and saves the a-streams; layers >= 1 run the code below unchanged.
 template <int HP, int NS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(HP * 2) void fwd_kernel(FwdArgs a) {
+  if (NS == 4) resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   constexpr int NW = HP / 32;
   constexpr int NT = HP * 2;
   extern __shared__ float lds[];

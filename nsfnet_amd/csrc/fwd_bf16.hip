@@ -23,6 +23,7 @@
 // FF: the frozen sine first layer (fwd.hip, spill_io.h layer0_sine), on the hardware sine / cosine (SinCosFast)
 template <int HP, int NS, int TERMS, int COLS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(HP * 2, (COLS == 64 && HP == 256) ? 4 : 2) void fwd_bf16_kernel(FwdArgs a) {
+  if (NS == 4) resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   constexpr int PPL = COLS / 4, NTL = COLS / 32;
   using XI = XImg<HP, PPL>;
   constexpr int NW = HP / 32, NT = HP * 2, KS = HP / 16;

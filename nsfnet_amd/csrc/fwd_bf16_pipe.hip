@@ -58,6 +58,7 @@ struct PipeLds {
 
 template <int HP, int TERMS>
 __global__ __launch_bounds__(HP, 1) void fwd_pipe_kernel(FwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using G = PipeLds<HP>;
   using XI = typename G::XI;
   constexpr int NW = HP / 64, NT = HP, KS = HP / 16, PPL = 32, COLS = 128;

@@ -43,6 +43,7 @@ struct SplitLds {
 // FF: the frozen sine first layer (split_phases.h): E0 forms the a-streams by layer0_sine; nothing else differs
 template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwd_split_kernel(FwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using G = SplitLds<HP>;
   using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;      // GT: threads per group

@@ -41,6 +41,7 @@ __global__ __launch_bounds__(((HP / 32 + 1) / 2) * 64) void fwd_bf16_wide_kernel
   for (int i = tid; i < (a.L - 1) * HP; i += NT) biasL[HP + i] = a.prep[prep_b(HP, 1 + i / HP) + (i % HP)];
   __syncthreads();
 
+  if (NS == 4) resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     f32x16 acc[MT][NTL];
     {

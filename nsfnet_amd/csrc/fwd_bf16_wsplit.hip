@@ -32,6 +32,7 @@
 // slot; nothing else differs
 template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(512, 1) void fwd_wsplit_kernel(FwdArgs a) {
+  resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using SW = WSplitWave<HP, TERMS, FF>;
   constexpr int GT = 256, MQ = SW::MQ, PPL = SW::PPL, COLS = SW::COLS;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];

@@ -30,6 +30,7 @@ __global__ __launch_bounds__(HP * 2) void fwd_wide_kernel(FwdArgs a) {
   const int npad = a.ntiles * (NS == 4 ? PPL : COLS);
   float lsum[4] = {0.f, 0.f, 0.f, 0.f};
 
+  if (NS == 4) resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     f32x16 acc[2];
     {

@@ -56,6 +56,7 @@ struct FusedLds {
 
 template <int HP, int TERMS, bool HBC = false, bool PT = false, bool FF = false>
 __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, BwdArgs a) {
+  resolve_viscosity(fa); resolve_viscosity(a);     // viscosity identification: *nu_dev in place of the launch constant (kernels.h)
   using G = FusedLds<HP>;
   using SW = SplitWave<HP, TERMS, FF>;
   constexpr int GT = HP, PPL = SW::PPL, COLS = SW::COLS;
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(2 * HP, 1) void fwdbwd_split_kernel(FwdArgs fa, Bwd
     float nu = fa.inv_re + vt;
     float eq1 = (u * ux + v * uy) + pxx - nu * ud;
     float eq2 = (u * vx + v * vy) + pyy - nu * vd;
+    if (owner && fa.lap) { fa.lap[pt] = ud; fa.lap[(size_t)npad + pt] = vd; }      // viscosity identification (point_stage.h)
     float eq3 = ux + vy;
     float eq4 = fa.e ? (eq1 * (u - 0.5f) + eq2 * (v - 0.5f)) - ev : 0.f;
     if (owner) {

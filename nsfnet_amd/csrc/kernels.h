@@ -20,6 +20,20 @@ __device__ __forceinline__ gf32x4* pin_base(const void* q) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
   return (gf32x4*)(((unsigned long long)hi << 32) | lo);
 }
+// Viscosity identification (visc.hip): once per residual kernel, before anything reads a.inv_re - that is before the
+// tile loop AND before a prologue that already runs a point stage (the role-split reverse sweeps build their first
+// tile's output adjoints ahead of the loop).  It is the kernel's first statement, except in the four wide kernels whose
+// register allocation that place disturbed: fwd_wide, fwd_bf16_wide and bwd_bf16_wide call it right
+// before their tile loop, bwd_bf16_wsplit right before its prologue's seeds.  Where the plan carries a trainable
+// viscosity (FwdArgs / BwdArgs::nu_dev), the kernel's own copy of the argument block gets *nu_dev as its inv_re, so the
+// per-point stages (point_stage.h, fwdbwd_bf16_split.hip) form nu = a.inv_re + vis_t as they always did and the tile
+// loops carry no new state.  Only another launch ever writes *nu_dev, so it is read through the constant address
+// space: one scalar load per workgroup, no vector register.
+template <class Args>
+__device__ __forceinline__ void resolve_viscosity(Args& a) {
+  typedef const __attribute__((address_space(4))) float cfloat;
+  if (a.nu_dev) a.inv_re = *(cfloat*)(unsigned long long)a.nu_dev;
+}
 // The host tail of every sweep and dW launcher.  configure != 0 (pinn_plan_create's configure pass): launch nothing,
 // raise the kernel's dynamic-LDS limit on the current device.  Otherwise launch.  Returns 0 or -(the HIP error).
 template <typename... Params, typename... Args>
@@ -69,6 +83,9 @@ struct FwdArgs {
       const float* anchor;   // [3][npad] anchors u*, v*, p*
       float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation
       int ptime;             // != 0: launch the pseudo-time variant
+      // Viscosity identification (residual mode, every family; point_stage.h, visc.hip), behind ptime in the same bytes:
+      const float* nu_dev;   // one fp32 in device memory read in place of inv_re (the trainable 1 / Re), or null
+      float* lap;            // [2][npad] planes Lap u, Lap v (physical, of the constrained fields on a constrained plan), or null
     };
   };
   float* partials;       // [grid][PINN_NLOSS]
@@ -103,6 +120,7 @@ struct BwdArgs {
   float sigma, sigma_p;  // 1 / dtau of the momentum equations, of the continuity equation
   int ff;                // != 0 (residual mode): the net's first layer is the frozen sine layer.  The role-split and fused
                          // families launch their FF instantiation, whose sweep ends at layer 1; the 8-wave families do not read it.
+  const float* nu_dev;   // see FwdArgs (residual mode; last, so that no other member moves)
 };
 
 struct DwArgs {
@@ -358,6 +376,26 @@ struct MonObserveArgs {
 size_t monitor_scratch_bytes();
 int launch_monitor_vis_stats(const MonVisArgs& a, hipStream_t s);
 int launch_monitor_observe(const MonObserveArgs& a, hipStream_t s);
+// viscosity identification: d loss / d nu of an evaluation and the update of theta = ln nu (visc.hip)
+constexpr int VISC_STATE = 8;
+struct ViscGradArgs {
+  long n, npad;                            // points; plane stride of fld and of lap
+  const float* fld;                        // [FLD_COUNT][npad] field planes of the evaluation
+  const float* lap;                        // [2][npad] Lap u, Lap v of the same evaluation
+  const float* w;                          // [n] weights (NULL: 1)
+  double w4;                               // the weight of eq4 (0: the plane is not read)
+  float* sum_out;                          // one fp32 slot of the loss-sum block
+  double* scratch;
+};
+struct ViscUpdateArgs {
+  const float* sum;                        // the (exchanged) slot ViscGradArgs::sum_out named
+  double coef, lr, beta1, beta2, eps, theta_min, theta_max;
+  double* state;                           // [VISC_STATE]
+  float* nu_dev;                           // the fp32 the sweeps read
+};
+size_t visc_scratch_bytes(long n);
+int launch_visc_grad(const ViscGradArgs& a, hipStream_t s);
+int launch_visc_update(const ViscUpdateArgs& a, hipStream_t s);
 size_t val_scratch_bytes();
 int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s);

@@ -73,9 +73,12 @@ __device__ __forceinline__ void residual_point_stage(const FwdArgs& a, const flo
     a.vtm[pt] = a.alpha_evm * fabsf(ev);
   }
   if (a.vis_used && m) a.vis_used[pt] = vt;
-  float nu = a.inv_re + vt;
+  float nu = a.inv_re + vt;               // (viscosity identification: the kernel put *nu_dev there, resolve_viscosity)
   float eq1 = (u * ux + v * uy) + pxx - nu * ud;
   float eq2 = (u * vx + v * vy) + pyy - nu * vd;
+  if (a.lap) {                            // viscosity identification (visc.hip): d eq1 / d nu = -Lap u, d eq2 / d nu = -Lap v,
+    a.lap[pt] = ud; a.lap[(size_t)npad + pt] = vd;      // the physical Laplacians, padded like fld
+  }
   float eq3 = ux + vy;
   float eq4 = a.e ? (eq1 * (u - 0.5f) + eq2 * (v - 0.5f)) - ev : 0.f;
   float* f = a.fld + pt;

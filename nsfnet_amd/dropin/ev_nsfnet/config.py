@@ -199,6 +199,17 @@ class EarlyStopConfig:
 
 
 @dataclass
+class IdentifyViscosityConfig:
+    """The Reynolds number learned from the supervised data (solver.set_viscosity_identification; DESIGN.md section
+    7.15); the key's absence means off.  re0: the starting estimate (null: physics.Re); lr: the rate of the scalar's own
+    Adam on ln nu; re_min, re_max: the bounds of the estimate."""
+    re0: Optional[float] = None
+    lr: float = 1e-2
+    re_min: float = 1e-2
+    re_max: float = 1e6
+
+
+@dataclass
 class CheckpointConfig:
     """Training-state snapshots that resume bit for bit (solver.set_checkpointing), off by default: path of the file
     (one per rank) and the optimizer updates between two non-blocking snapshots."""
@@ -239,6 +250,7 @@ class TrainingConfig:
     pseudo_time: PseudoTimeConfig = field(default_factory=PseudoTimeConfig)
     checkpoint: CheckpointConfig = field(default_factory=CheckpointConfig)
     early_stop: Optional[EarlyStopConfig] = None
+    identify_viscosity: Optional[IdentifyViscosityConfig] = None
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -286,6 +298,13 @@ def _fill(obj, data):
                     elif k in ("window", "patience", "min_updates", "every"):
                         setattr(es, k, int(v))
                 setattr(obj, key, es)
+        elif key == "identify_viscosity":        # absent, null or false: off
+            if val is not None and val is not False:
+                iv = IdentifyViscosityConfig()
+                for k, v in (val.items() if isinstance(val, dict) else ()):
+                    if k in ("re0", "lr", "re_min", "re_max"):
+                        setattr(iv, k, None if v is None and k == "re0" else float(v))
+                setattr(obj, key, iv)
         elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
             if val is not None and val is not False:
                 cur.enabled = True
@@ -368,6 +387,14 @@ class ConfigManager:
                                 % (" | ".join(EARLY_STOP_QUANTITIES), " | ".join(EARLY_STOP_MODES)))
             if es.min_rel_improvement is None and es.re_eff_tol is None:
                 problems.append("training.early_stop: at least one of min_rel_improvement and re_eff_tol must be set")
+        iv = c.training.identify_viscosity
+        if iv is not None:
+            if not (0.0 < iv.re_min <= iv.re_max < float("inf") and 0.0 <= iv.lr < float("inf")
+                    and (iv.re0 is None or iv.re_min <= iv.re0 <= iv.re_max)):
+                problems.append("training.identify_viscosity: 0 < re_min <= re0 <= re_max < inf and a finite lr >= 0 required")
+            if es is not None or pt.enabled or c.training.conflict_free_gradients.enabled:
+                problems.append("training.identify_viscosity does not go together with training.early_stop, "
+                                "training.pseudo_time or training.conflict_free_gradients")
         ck = c.training.checkpoint
         if ck.every < 0 or (ck.every > 0 and not ck.path):
             problems.append("training.checkpoint: every >= 0, and a path when every > 0, required")
@@ -445,6 +472,9 @@ class ConfigManager:
             print("early stop : window=%d min_rel_improvement=%s patience=%d re_eff_tol=%s min_updates=%d quantity=%s "
                   "mode=%s every=%d" % (es.window, es.min_rel_improvement, es.patience, es.re_eff_tol, es.min_updates,
                                         es.quantity, es.mode, es.every))
+        if t.identify_viscosity is not None:
+            iv = t.identify_viscosity
+            print("identify Re: re0=%s lr=%g bounds=[%g, %g]" % (iv.re0, iv.lr, iv.re_min, iv.re_max))
         if t.checkpoint.enabled:
             print("checkpoint : path=%s every=%d" % (t.checkpoint.path, t.checkpoint.every))
         for st in t.training_stages:

@@ -176,6 +176,9 @@ def main():
             PINN.set_early_stopping(every=es.every, window=es.window, min_rel_improvement=es.min_rel_improvement,
                                     patience=es.patience, re_eff_tol=es.re_eff_tol, min_updates=es.min_updates,
                                     quantity=es.quantity, mode=es.mode)
+        iv = cfg.training.identify_viscosity
+        if iv is not None:    # the Reynolds number becomes a trainable scalar, pinned down by the supervised data
+            PINN.set_viscosity_identification(re0=iv.re0, lr=iv.lr, re_bounds=(iv.re_min, iv.re_max))
         ck = cfg.training.checkpoint
         if ck.enabled:
             PINN.set_checkpointing(ck.path, ck.every)

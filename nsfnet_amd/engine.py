@@ -371,6 +371,15 @@ class ResidualPlan(PointPlan):
         _lib.check(self.lib.pinn_plan_set_pseudo_time(self.handle, _ptr(self.anchor), float(sigma), float(sigma_p)),
                    "pinn_plan_set_pseudo_time")
 
+    def set_viscosity(self, nu, with_lap=True):
+        """Viscosity identification: every residual launch of the plan reads the fp32 device scalar `nu` in place of
+        1 / Re, and (with_lap) its forward leaves Lap u, Lap v in self.lap [2, npad].  nu None: off."""
+        self.nu = nu
+        self.lap = None
+        if nu is not None and with_lap:
+            self.lap = torch.zeros(2, self.npad, dtype=torch.float32, device=self.net.device)
+        _lib.check(self.lib.pinn_plan_set_viscosity(self.handle, _ptr(nu), _ptr(self.lap)), "pinn_plan_set_viscosity")
+
     def pseudo_time(self):
         """(sigma, sigma_p) the plan carries."""
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -727,6 +736,34 @@ def monitor_observe(eq, bc, sup, lam, alpha_b, alpha_s, alpha_e, w4, n_eq, n_b, 
                "pinn_monitor_observe")
 
 
+VISC_STATE = 8           # PINN_VISC_STATE: [theta, m, v, beta1^t, beta2^t, t, last G, skipped]
+VISC_STATE_NAMES = ("theta", "m", "v", "beta1_t", "beta2_t", "updates", "grad", "skipped")
+VISC_SLOT = 5            # the slot of the equation block of the loss sums that carries S of d loss / d nu = -(2 alpha_e / N) S
+
+
+def visc_scratch(n, device):
+    """Zeroed device scratch of visc_grad for n points (the launch leaves its ticket word 0 again)."""
+    nbytes = int(_lib.load().pinn_visc_scratch_bytes(int(n)))
+    if nbytes < 0:
+        raise ValueError("bad point count %d" % n)
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def visc_grad(plan, w4, sum_out, scratch):
+    """pinn_visc_grad over the planes (fields, lap) the last evaluation of the ResidualPlan `plan` left: the fixed-order
+    fp64 sum S of the per-point terms of d loss / d nu, rounded to fp32, into sum_out[0].  One launch."""
+    _lib.check(_lib.load().pinn_visc_grad(plan.n, _ptr(plan.fields), plan.npad, _ptr(plan.lap), _ptr(plan.w), float(w4),
+                                          _ptr(sum_out), _ptr(scratch), _stream()), "pinn_visc_grad")
+
+
+def visc_update(sum_in, coef, lr, betas, eps, theta_bounds, state, nu):
+    """pinn_visc_update: Adam on theta = ln nu from the (exchanged) sum sum_in[0], G = coef * sum; state and the fp32 nu
+    the sweeps read are rewritten in place.  One launch."""
+    _lib.check(_lib.load().pinn_visc_update(_ptr(sum_in), float(coef), float(lr), float(betas[0]), float(betas[1]),
+                                            float(eps), float(theta_bounds[0]), float(theta_bounds[1]), _ptr(state),
+                                            _ptr(nu), _stream()), "pinn_visc_update")
+
+
 OPTIM_RECORD = 6         # PINN_OPTIM_RECORD
 
 
@@ -1030,6 +1067,29 @@ class _Monitor:
             re_eff_tol=0.0 if self.re_tol is None else self.re_tol)
 
 
+class _Viscosity:
+    """Identification of the molecular viscosity (PinnEngine.set_viscosity_identification): the constants, the device
+    state of the scalar's Adam [VISC_STATE], the fp32 nu every residual plan reads, the scratch of the gradient launch;
+    fresh: the last evaluation was made for Adam (its slot holds a gradient the next adam_step may use); n_eq: its
+    normalisation."""
+
+    def __init__(self, re0, lr, betas, eps, re_bounds):
+        self.re0, self.lr, self.betas, self.eps, self.re_bounds = re0, lr, betas, eps, re_bounds
+        self.theta_bounds = (math.log(1.0 / re_bounds[1]), math.log(1.0 / re_bounds[0]))
+        self.state = self.nu = self.scratch = None
+        self.fresh, self.n_eq = False, 0
+
+    def key(self):
+        return ("visc", self.lr, self.betas, self.eps, self.re_bounds)
+
+    def start(self):
+        """The state of an optimiser that has made no update, at re0 (in place).  nu is the fp32 quotient 1 / Re the
+        launches would have used as a constant, theta its logarithm: exp(theta) rounds back to it."""
+        nu = np.float32(1.0) / np.float32(self.re0)
+        self.nu.fill_(float(nu))
+        self.state.copy_(torch.tensor([math.log(float(nu)), 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float64))
+
+
 # What an evaluation is made for.  Each mode holds what the one before it holds, and more:
 EVAL_ADAM = 0           # an Adam step: a fresh batch, attention and balance updates, the conflict-free combination
 EVAL_FULL_BATCH = 1     # loss_and_grad(full_batch=True): the whole store, the attention weights held
@@ -1094,6 +1154,7 @@ class PinnEngine:
         self._ff = None                     # frozen Fourier-feature first layer (set_fourier_features; None = off)
         self._mon = None                    # convergence monitor (set_convergence_monitor; None = off)
         self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
+        self._visc = None                   # viscosity identification (set_viscosity_identification; None = off)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -1146,6 +1207,8 @@ class PinnEngine:
             raise ValueError("pseudo-time stepping needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         if self._mon is not None and chunk_points and n > int(chunk_points):
             raise ValueError("the convergence monitor needs a resident store: chunk_points=%d with it on" % int(chunk_points))
+        if self._visc is not None and chunk_points and n > int(chunk_points):
+            raise ValueError("viscosity identification needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         self._graphs.clear()      # captured steps hold the old plan's pointers
         self.lbfgs_reset()
         if chunk_points and n > int(chunk_points):
@@ -1153,6 +1216,8 @@ class PinnEngine:
         else:
             self.plan_f = ResidualPlan(self.net, x, y, weights, **({} if self._pt is None else dict(pseudo_time=True)))
         self.n_f_global = int(n_global if n_global is not None else self.plan_f.n)
+        if self._visc is not None:
+            self._attach_viscosity(self.plan_f)
         if self.net_e is not None:
             self.plan_e = ValuePlan(self.net_e, x, y)
             self.init_vis_t()
@@ -1310,6 +1375,8 @@ class PinnEngine:
         """The batch plan(s) of bt.B points for the current store; the buffers are filled by every draw."""
         z = lambda: np.zeros(bt.B, dtype=np.float32)       # one array per buffer: a host tensor may alias its source
         bt.f = ResidualPlan(self.net, z(), z(), None if self.plan_f.w is None else z())
+        if self._visc is not None:
+            self._attach_viscosity(bt.f)
         bt.e = None
         if self.net_e is not None:
             bt.f.vis_t_minus = torch.zeros(bt.B, dtype=torch.float32, device=self.device)
@@ -1400,6 +1467,8 @@ class PinnEngine:
         if self.plan_f is not None and (weights is None) != (self._static_w() is None):
             raise ValueError("pool weights must be given exactly when the collocation set has weights")
         pool = ResidualPlan(self.net, x, y, with_backward=False)
+        if self._visc is not None:
+            self._attach_viscosity(pool, with_lap=False)
         w = None
         if weights is not None:
             w = torch.as_tensor(np.asarray(weights, dtype=np.float32).reshape(-1)).to(self.device).contiguous()
@@ -1545,6 +1614,10 @@ class PinnEngine:
         if enabled and self._bal is not None:
             raise ValueError("conflict-free gradients and loss balancing both decide how the term gradients are "
                              "combined: switch set_loss_balancing off first")
+        if enabled and self._visc is not None:
+            raise ValueError("conflict-free gradients are not available with viscosity identification "
+                             "(set_viscosity_identification): the combined direction is not the gradient of the loss "
+                             "whose d / d nu the scalar follows")
         self._graphs.clear()        # captured steps hold the launches and buffers of the other mode
         if not enabled:
             self._cfg = None
@@ -1577,7 +1650,8 @@ class PinnEngine:
         l2 = mode == "L2"
         for state, needs in ((self._bal, "loss balancing needs"), (self._cfg, "conflict-free gradients need"),
                              (self._batch, "mini-batching needs"), (self._rba, "residual attention needs"),
-                             (self._pt, "pseudo-time stepping needs"), (self._mon, "the convergence monitor needs")):
+                             (self._pt, "pseudo-time stepping needs"), (self._mon, "the convergence monitor needs"),
+                             (self._visc, "viscosity identification needs")):
             if l2 and state is not None:
                 raise ValueError("%s the MSE loss (loss mode %r)" % (needs, mode))
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
@@ -1673,6 +1747,14 @@ class PinnEngine:
                     grad_reduce_terms(self.net, [[p], [], []], [self.grads, None, None], acc_mask=1 if k > 0 else 0)
         if bt is not None and f.vis_t_minus is not None:      # the forward left alpha_evm |e| of the batch points there
             batch_scatter(bt.idx, bt.B, self.plan_f.n, f.vis_t_minus, self.plan_f.vis_t_minus)
+        vs = self._visc
+        if vs is not None:
+            # after the loss-sum launch of the pass, before the attention update below rewrites the weights the sweep
+            # read, and before the exchange, which makes the sum global in the message that is sent anyway.  An evaluation that
+            # is not made for Adam (L-BFGS, full_batch) leaves the slot at the 0 the loss-sum launch wrote, and holds nu
+            vs.fresh, vs.n_eq = self._mode == EVAL_ADAM, n_f
+            if vs.fresh:
+                visc_grad(f, self._w4(), eq_sums[VISC_SLOT:], vs.scratch)
         if self._rba is not None and self._mode == EVAL_ADAM:      # the weights of the NEXT evaluation
             self._attention_update(f, bt)
         mon = self._mon
@@ -1778,6 +1860,10 @@ class PinnEngine:
             if with_e:
                 self.net_e.adam_step_sched(ge, lr, o, advance=False)
             self.net.adam_step_sched(g, lr, o, advance=True)        # last: it moves the epoch on
+        vs = self._visc
+        if vs is not None and vs.fresh:     # the scalar's own Adam, from the exchanged slot of the evaluation just used
+            visc_update(self.sums[S_EQ + VISC_SLOT:], -2.0 * self.alpha_e / vs.n_eq, vs.lr, vs.betas, vs.eps,
+                        vs.theta_bounds, vs.state, vs.nu)
         if self._bal is not None:
             self._bal.n += 1
         self._updated(validate)
@@ -2041,6 +2127,9 @@ class PinnEngine:
         if self._batch is not None:
             raise ValueError("pseudo-time stepping is not available with mini-batching: the anchors live with the "
                              "evaluated plan (store-level anchors and a gather are a follow-up)")
+        if self._visc is not None:
+            raise ValueError("pseudo-time stepping is not available with viscosity identification "
+                             "(set_viscosity_identification): switch it off first")
         self._pt = _PseudoTime(float(dtau), ev, None if pressure_dtau is None else float(pressure_dtau))
 
     def _attach_pseudo_time(self):
@@ -2342,6 +2431,9 @@ class PinnEngine:
         every, window, patience, min_updates, history = (int(v) for v in (every, window, patience, min_updates, history))
         if every < 0:
             raise ValueError("convergence monitor: every must be >= 0")
+        if every > 0 and self._visc is not None:
+            raise ValueError("the convergence monitor is not available with viscosity identification "
+                             "(set_viscosity_identification): its Re_eff is built on the configured Re")
         self._graphs.clear()        # captured steps hold the other monitor's buffers and constants
         if every == 0:
             self._mon = None
@@ -2444,6 +2536,93 @@ class PinnEngine:
             return False
         return self._stop_reasons(int(m.state[11].item()), m)[1]
 
+    # ---- identification of the viscosity from data ----
+    def set_viscosity_identification(self, re0=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, re_bounds=(1e-2, 1e6),
+                                     enabled=True):
+        """Make the molecular viscosity nu = 1 / Re a trainable scalar (the inverse problem of Raissi, Perdikaris &
+        Karniadakis 2019: with measurements attached by set_supervised, the flow's Reynolds number is identified along
+        with the field).  nu lives in device memory as one fp32 that every residual launch of the engine's plans reads
+        in place of 1 / Re - the collocation plan, the batch plan, the resampling pool - and the evaluated plan's
+        forward also leaves Lap u, Lap v.  Every evaluation made for Adam is followed by one streaming launch that forms
+        S = sum_i w_i ((eq1 + w4 eq4 (u - 1/2)) Lap u + (eq2 + w4 eq4 (v - 1/2)) Lap v) in fp64 with a fixed order and
+        puts it into slot 5 of the equation block of the loss sums, before the exchange: with several ranks the sum is
+        global in the message that is sent anyway, and every rank updates from the same bits.  adam_step then runs, after
+        the nets' updates, one launch of torch-Adam in fp64 on theta = ln nu with d loss / d theta = nu (-(2 alpha_e / N) S)
+        (N: the global collocation count, or batch_points x world size under mini-batching), its own rate `lr`, betas and
+        eps, theta clamped to ln(1 / re_bounds[1]) .. ln(1 / re_bounds[0]).  Both launches are part of the captured step.
+        The nets' schedule and clipping do not see the scalar.
+
+        re0: the starting estimate (None: the engine's Re).  The engine's Re itself stays what it was configured: with
+        the ev flavour vis_t0 = vis_t0_factor / Re keeps its configured value.  nu is held fixed during lbfgs_step and
+        by loss_and_grad(full_batch=True).  viscosity_info() reads the estimate.
+
+        Refused with ValueError, each way round: pseudo-time stepping, conflict-free gradients, the convergence monitor
+        (whose Re_eff is built on the configured Re), chunked collocation passes and the loss mode 'L2'.  lr None or
+        enabled False: off - the plans carry no pointer and the step launches what it launches without the feature.
+        A call restarts the scalar's optimiser at re0."""
+        self._graphs.clear()        # captured steps hold the other mode's launches and pointers
+        if not enabled or lr is None:
+            if self._visc is not None:
+                self._visc = None
+                for plan, _ in self._visc_plans():
+                    plan.set_viscosity(None)
+            return
+        re0 = self.Re if re0 is None else float(re0)
+        lr, eps, betas = float(lr), float(eps), (float(betas[0]), float(betas[1]))
+        re_bounds = (float(re_bounds[0]), float(re_bounds[1]))
+        if not (math.isfinite(lr) and lr >= 0.0 and math.isfinite(eps) and eps > 0.0):
+            raise ValueError("viscosity identification: lr must be finite and >= 0, eps finite and > 0 (got lr=%r eps=%r)"
+                             % (lr, eps))
+        if not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError("viscosity identification: betas must lie in [0, 1) (got %r)" % (betas,))
+        if not (0.0 < re_bounds[0] <= re_bounds[1] and math.isfinite(re_bounds[1])):
+            raise ValueError("viscosity identification: re_bounds must be 0 < re_min <= re_max < inf (got %r)" % (re_bounds,))
+        if not (math.isfinite(re0) and re_bounds[0] <= re0 <= re_bounds[1]):
+            raise ValueError("viscosity identification: re0 must lie inside re_bounds (got re0=%r, bounds %r)"
+                             % (re0, re_bounds))
+        for state, what in ((self._pt, "pseudo-time stepping (set_pseudo_time)"),
+                            (self._cfg, "conflict-free gradients (set_conflict_free_gradients)"),
+                            (self._mon, "the convergence monitor (set_convergence_monitor), whose Re_eff is built on "
+                                        "the configured Re")):
+            if state is not None:
+                raise ValueError("viscosity identification is not available with %s: switch it off first" % what)
+        if isinstance(self.plan_f, ChunkedResidual):
+            raise ValueError("viscosity identification needs a resident store: the collocation set is chunked (chunk_points)")
+        vs = _Viscosity(re0, lr, betas, eps, re_bounds)
+        vs.state = torch.zeros(VISC_STATE, dtype=torch.float64, device=self.device)
+        vs.nu = torch.zeros(1, dtype=torch.float32, device=self.device)
+        vs.start()
+        self._visc = vs
+        for plan, with_lap in self._visc_plans():
+            self._attach_viscosity(plan, with_lap)
+
+    def _visc_plans(self):
+        """[(residual plan, it is evaluated for a gradient)] of every residual plan the engine owns."""
+        bt = self._batch
+        return [(p, lap) for p, lap in ((self.plan_f, True), (None if bt is None else bt.f, True), (self._pool, False))
+                if p is not None]
+
+    def _attach_viscosity(self, plan, with_lap=True):
+        vs = self._visc
+        plan.set_viscosity(vs.nu, with_lap)
+        if with_lap:
+            s = visc_scratch(plan.n, self.device)
+            if vs.scratch is None or s.numel() > vs.scratch.numel():
+                vs.scratch = s
+
+    def viscosity_info(self):
+        """dict(Re, nu, theta, grad (the last d loss / d nu), updates, skipped (updates left out for a non-finite sum),
+        m, v, and the settings re0, lr, betas, eps, re_bounds) - one host read; None when the feature is off."""
+        vs = self._visc
+        if vs is None:
+            return None
+        both = torch.cat([vs.state, vs.nu.double()]).cpu().tolist()
+        out = dict(zip(VISC_STATE_NAMES, both[:VISC_STATE]))
+        nu = both[VISC_STATE]
+        out.update(nu=nu, Re=1.0 / nu if nu > 0.0 else float("inf"), updates=int(out["updates"]), skipped=int(out["skipped"]),
+                   re0=vs.re0, lr=vs.lr, betas=vs.betas, eps=vs.eps, re_bounds=vs.re_bounds)
+        return out
+
     # ---- L-BFGS (DESIGN.md section 7.2) ----
     def lbfgs_reset(self):
         """Forget the L-BFGS history: the next lbfgs_step starts like a fresh torch.optim.LBFGS."""
@@ -2533,6 +2712,7 @@ class PinnEngine:
         key += (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
         key += () if self._pt is None else (("ptime", self._pt.sigma, self._pt.sigma_p, self._pt.every),)
         key += () if self._mon is None else (self._mon.key(),)
+        key += () if self._visc is None else (self._visc.key(),)
         v = self._val
         return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 
@@ -2545,7 +2725,7 @@ class PinnEngine:
         """[(name, tensor, stored)]: everything in device memory that a step reads and an earlier step wrote, in the
         file's fixed order - per net (net, net_e) trainable, m, v, adam_t; per collocation pass x, y, w (the static
         weights), vis_t_minus; plan_e x, y; opt epoch, rec; bal lam, rec; cfg coef, rec; batch counter, idx; rba lam, w,
-        rec; monitor state, ring; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
+        rec; monitor state, ring; visc state, nu; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
         (stored False), the sets a resume must attach again unchanged: boundary, supervised, validation, resample pool."""
         segs = []
 
@@ -2568,7 +2748,7 @@ class PinnEngine:
         for name, obj, keys in (("opt", self._opt, ("epoch", "rec")), ("bal", self._bal, ("lam", "rec")),
                                 ("cfg", self._cfg, ("coef", "rec")), ("batch", self._batch, ("counter", "idx")),
                                 ("rba", self._rba, ("lam", "w", "rec")), ("val", self._val, ("state", "ring")),
-                                ("monitor", self._mon, ("state", "ring"))):
+                                ("monitor", self._mon, ("state", "ring")), ("visc", self._visc, ("state", "nu"))):
             if obj is not None:
                 for key in keys:
                     add("%s.%s" % (name, key), getattr(obj, key))
@@ -2600,6 +2780,8 @@ class PinnEngine:
         count = lambda plan, g: None if plan is None else [plan.n, int(g)]
         v, f = self._val, self.plan_f
         mon = {} if self._mon is None else dict(monitor=dict(capacity=self._mon.capacity))      # (off: the file's bytes of before)
+        if self._visc is not None:
+            mon["viscosity"] = True
         return dict(
             mon, flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
             points_colloc=count(f, self.n_f_global), points_boundary=count(self.plan_b, self.n_b_global),
@@ -2624,6 +2806,9 @@ class PinnEngine:
         m = self._mon
         mon = {} if m is None else dict(monitor=[m.every, m.window, m.min_rel, m.patience, m.re_tol, m.min_updates,
                                                  m.quantity, m.mode])
+        vs = self._visc
+        if vs is not None:
+            mon["viscosity"] = [vs.re0, vs.lr, list(vs.betas), vs.eps, list(vs.re_bounds)]
         return dict(
             mon, precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
             kernels=None if kernels is None else list(kernels()), Re=self.Re, alpha_b=self.alpha_b, alpha_e=self.alpha_e,

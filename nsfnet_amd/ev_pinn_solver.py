@@ -420,6 +420,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             print('  ' + self.validation_log())
         if self._early_stop:
             print('  ' + self.early_stop_log())
+        if self._identify:
+            print('  ' + self.viscosity_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]
@@ -487,15 +489,19 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self.save_weight_factors(save_results_to + filename)
         self.save_hard_boundary(save_results_to + filename)
         self.save_fourier_features(save_results_to + filename)
+        self.save_viscosity(save_results_to + filename)
         self._save_best(save_results_to + filename)
 
     def neural_net_equations(self, x, y):
         """eq1..eq4 at arbitrary points, forward only, with vis_t = vis_t0 as the reference does
-        when no lagged state exists (:330-331)."""
+        when no lagged state exists (:330-331).  With viscosity identification on the molecular viscosity is the
+        identified one, the one training minimises the residuals at; vis_t0 keeps the configured Re."""
         xs, ys = _col(x), _col(y)
         pe = _eng.ValuePlan(self.engine.net_e, xs, ys, with_backward=False)
         pe.forward(save=False)
         plan = _eng.ResidualPlan(self.engine.net, xs, ys, with_backward=False)
+        if self.engine._visc is not None:
+            plan.set_viscosity(self.engine._visc.nu, with_lap=False)
         plan.vis_t_minus = torch.full((plan.n,), float("inf"), dtype=torch.float32, device=self.device)
         plan.forward(self.Re, e=pe.pred[0], vis_t0=self.vis_t0, alpha_evm=self.alpha_evm, scale=self.coord_scale,
                      save=False)

@@ -338,6 +338,47 @@ class SolverBase:
                 "%s (set by update %d)" % (r, i["t_" + r]) for r in i["reasons"])))
         return True
 
+    # ---- identification of the viscosity from data ----
+    _identify = False           # set_viscosity_identification: print_log adds Re_est, save() writes the _visc sidecar
+
+    def set_viscosity_identification(self, re0=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, re_bounds=(1e-2, 1e6),
+                                     enabled=True):
+        """Learn the Reynolds number along with the field (PinnEngine.set_viscosity_identification): nu = 1 / Re becomes
+        a device scalar with its own Adam (rate `lr`) on ln nu, started at re0 (None: this solver's Re) and clamped to
+        re_bounds.  It needs data that pin the flow down - supervised samples (the ev class's set_supervision_data) or
+        boundary data that do - since the residual alone is minimised by any Re with a matching field.  self.Re keeps
+        the configured value (checkpoint folders, vis_t0); print_log adds Re_est, save() writes the sidecar
+        <checkpoint>_visc (the settings, the optimiser state and nu) and load() takes it up.  Held fixed during
+        solve_LBFGS.  lr None or enabled False: off."""
+        self.engine.set_viscosity_identification(re0=re0, lr=lr, betas=betas, eps=eps, re_bounds=re_bounds, enabled=enabled)
+        self._identify = self.engine.viscosity_info() is not None
+
+    def viscosity_log(self):
+        """One line on the identified viscosity (one host read)."""
+        i = self.engine.viscosity_info()
+        return "Re_est=%.4f (nu=%.6e, d loss / d nu=%.3e, updates=%d, skipped=%d)" % (
+            i["Re"], i["nu"], i["grad"], i["updates"], i["skipped"])
+
+    def save_viscosity(self, path):
+        """Write the sidecar of the checkpoint at `path`: dict(re0, lr, betas, eps, re_bounds, state, nu) as path +
+        '_visc' (torch.save).  With the identification off nothing is written."""
+        vs = self.engine._visc
+        if vs is not None:
+            torch.save(dict(re0=vs.re0, lr=vs.lr, betas=tuple(vs.betas), eps=vs.eps, re_bounds=tuple(vs.re_bounds),
+                            state=vs.state.cpu().tolist(), nu=float(vs.nu.cpu()[0])), path + '_visc')
+
+    def _load_viscosity(self, path):
+        """Take up the sidecar <path>_visc, if there is one: the identification is switched on with the saved settings
+        and continues from the saved optimiser state and nu."""
+        if not os.path.exists(path + '_visc'):
+            return
+        s = torch.load(path + '_visc', map_location="cpu", weights_only=True)
+        self.set_viscosity_identification(re0=float(s["re0"]), lr=float(s["lr"]), betas=tuple(float(b) for b in s["betas"]),
+                                          eps=float(s["eps"]), re_bounds=tuple(float(b) for b in s["re_bounds"]))
+        vs = self.engine._visc
+        vs.state.copy_(torch.tensor([float(v) for v in s["state"]], dtype=torch.float64))
+        vs.nu.fill_(float(s["nu"]))
+
     def save_weight_factors(self, path):
         """Write the sidecar of the checkpoint at `path`: {net name: flat fp32 s} as path + '_rwf' (torch.save).  With
         the factorization off nothing is written."""
@@ -444,6 +485,7 @@ class SolverBase:
                 self.engine._ff.update(sigma=ff.get("sigma"), seed=ff.get("seed"))
         if self._pseudo_time and self.engine.plan_f is not None:       # anchors are not checkpointed
             self.engine.reset_pseudo_time()
+        self._load_viscosity(path)
 
     def _begin_adam_stage(self, scheduler, resume=False):
         """Resolve solve_Adam's scheduler= argument.  resume (train(start_epoch > 0)): the schedule object is installed
@@ -610,8 +652,11 @@ class PysicsInformedNeuralNetwork(SolverBase):
         return u.reshape(-1, 1), v.reshape(-1, 1), p.reshape(-1, 1)
 
     def neural_net_equations(self, x, y):
-        """eq1, eq2, eq3 at arbitrary points (solver :132-163), forward only."""
+        """eq1, eq2, eq3 at arbitrary points (solver :132-163), forward only.  With viscosity identification on they are
+        formed at the identified viscosity, the one training minimises them at, not at self.Re."""
         plan = _eng.ResidualPlan(self.engine.net, _col(x), _col(y), with_backward=False)
+        if self.engine._visc is not None:
+            plan.set_viscosity(self.engine._visc.nu, with_lap=False)
         plan.forward(self.Re, save=False)
         return tuple(plan.field(k).reshape(-1, 1).clone() for k in ("eq1", "eq2", "eq3"))
 
@@ -724,7 +769,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("\n" + self._confgrad_log(),) if self._confgrad else ()),
               *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()),
               *(("\n" + self.validation_log(),) if self._validation else ()),
-              *(("\n" + self.early_stop_log(),) if self._early_stop else ()))
+              *(("\n" + self.early_stop_log(),) if self._early_stop else ()),
+              *(("\n" + self.viscosity_log(),) if self._identify else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):
@@ -774,6 +820,7 @@ class PysicsInformedNeuralNetwork(SolverBase):
         self.save_weight_factors(save_results_to + filename)
         self.save_hard_boundary(save_results_to + filename)
         self.save_fourier_features(save_results_to + filename)
+        self.save_viscosity(save_results_to + filename)
         self._save_best(save_results_to + filename)
         save_matlab_to = directory + '/loss/'
         os.makedirs(save_matlab_to, exist_ok=True)

@@ -30,6 +30,10 @@ pseudo-time anchors, a resampled collocation set.  The call must be given the sa
                                                   windows of that many updates that improved the mean loss by less than
                                                   that fraction - or, with --re-eff-tol, moved the mean Re_eff by less;
                                                   the per-update curve goes to monitor.jsonl; off by default)
+        [--identify-re 1000 1e-2]                 (the Reynolds number as a trainable scalar started at that value, its own
+                                                  Adam rate on ln nu; every stage writes net.pth_visc (settings, state, nu) and
+                                                  the estimate into stages.jsonl, a --resume slice continues from the sidecar
+                                                  with its settings; off by default)
         [--state FILE --state-every 50000 --max-steps 400000]   (training-state snapshots: continue from FILE when it
                                                   exists, write it every that many updates, end the call after that many
                                                   updates, anywhere in a stage)
@@ -107,6 +111,9 @@ def main():
     ap.add_argument("--re-eff-tol", type=float, default=None, metavar="TOL",
                     help="also (or, without --early-stop, only) end a stage when the window mean of Re_eff moves by less "
                          "than TOL for three windows in a row (windows of --early-stop's WINDOW, else 1000 updates)")
+    ap.add_argument("--identify-re", type=float, nargs="+", default=None, metavar=("RE0", "LR"),
+                    help="learn the Reynolds number from the data (DESIGN.md 7.15): start at RE0, Adam rate LR on ln nu "
+                         "(default 1e-2); not with --early-stop, --re-eff-tol, --pseudo-time or --confgrad")
     ap.add_argument("--state", default=None, metavar="FILE",
                     help="training-state file (DESIGN.md 7.12): continue from it when it exists, and write it")
     ap.add_argument("--state-every", type=int, default=0, help="updates between two non-blocking snapshots (0: only where the call ends)")
@@ -170,6 +177,12 @@ def main():
         P.set_early_stopping(window=1000 if a.early_stop is None else int(a.early_stop[0]),
                              min_rel_improvement=None if a.early_stop is None else a.early_stop[1],
                              re_eff_tol=a.re_eff_tol, history=1 << 16)
+    if a.identify_re is not None:
+        if len(a.identify_re) > 2:
+            ap.error("--identify-re takes RE0 and, optionally, LR")
+        P.set_viscosity_identification(re0=a.identify_re[0], lr=a.identify_re[1] if len(a.identify_re) > 1 else 1e-2)
+        if res is not None:                             # carry the estimate and its optimiser state across slices
+            P._load_viscosity(os.path.join(res, "net.pth"))
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     first, start, left = a.first, 0, a.max_steps if a.max_steps > 0 else None
@@ -249,6 +262,9 @@ def main():
                 for row in P.monitor_history().tolist():
                     fh.write(json.dumps(dict(zip(("t", "loss", "loss_e", "loss_b", "loss_s", "eq1", "eq2", "eq3", "eq4",
                                                   "vis_mean", "Re_eff", "stop"), row), stage=k)) + "\n")
+        if a.identify_re is not None:
+            info = P.engine.viscosity_info()
+            rec.update(viscosity={k_: info[k_] for k_ in ("Re", "nu", "grad", "updates", "skipped")})
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
@@ -256,6 +272,7 @@ def main():
         torch.save(P.net_1.state_dict(), "net_evm.pth")
         P.save_weight_factors("net.pth")                 # net.pth_rwf with --rwf, nothing without
         P.save_hard_boundary("net.pth")                  # net.pth_hardbc with --hard-bc, nothing without
+        P.save_viscosity("net.pth")                      # net.pth_visc with --identify-re, nothing without
         if left is not None and left <= 0:               # the call's budget ended with the stage
             return
 
