@@ -905,7 +905,25 @@ class _EngineSpace:
         self.e.flat.copy_(h)
 
 
-class _TermCombiner:
+class _Option:
+    """What a training option adds to the parts of PinnEngine that cut across the options; the defaults add nothing.
+    PinnEngine._options() lists the options that are on: the refusals, the graph key and the header and segments of a
+    training state are loops over it."""
+    resident = mse = None       # "<subject> needs": the option refuses a chunked collocation set / the loss mode 'L2'
+    stored = ()                 # (segment prefix, attribute, ...): the device tensors a training state stores
+    off = ({}, {}, {})          # header() while the option is off ({}: the keys are absent, as in older files)
+
+    def graph_key(self):        # the launch constants a captured step depends on (beyond those in _graph_key's head)
+        return ()
+
+    def header(self):           # the entries of a training state's (fingerprint, settings, host mirrors)
+        return {}, {}, {}
+
+    def restore_host(self, host):       # the host mirrors back from a training state's
+        pass
+
+
+class _TermCombiner(_Option):
     """What the rules that combine the per-term gradients share: buf = [grads | grads_e | sums | g_b | g_s], the
     engine's exchange buffer (content kept; engine.flat becomes the view of it) with the term vectors gb / gs behind
     it, so several ranks all-reduce the used prefix in one message.  A rule tells _loss_and_grad what the final
@@ -929,6 +947,8 @@ class _Balance(_TermCombiner):
     last n whose balance update has run) and the device tensors: lam [2] fp32, rec [BALANCE_RECORD] fp64 (the
     state and the statistics of the last balance step), parts (block partials), buf / gb / gs (term vectors)."""
     unit_seeds = True       # the weights are applied by the combine (device memory, not a launch argument)
+    mse, stored = "loss balancing needs", ("bal", "lam", "rec")
+    off = (dict(balancing=False), dict(balancing=None), dict(bal=None))
 
     def __init__(self, engine, every, beta):
         super().__init__(engine)
@@ -939,6 +959,12 @@ class _Balance(_TermCombiner):
         rec[9], rec[10] = engine.alpha_b, engine.alpha_s
         self.rec = torch.tensor(rec, dtype=torch.float64).to(engine.device)
         self.parts = balance_partials(engine.P, engine.device)
+
+    def header(self):
+        return dict(balancing=True), dict(balancing=[self.every, self.beta]), dict(bal=[self.n, self.done])
+
+    def restore_host(self, host):
+        self.n, self.done = (int(v) for v in host["bal"])
 
     def assembly(self, e, update):      # one rank: the local vectors are the global ones, their partials come along
         return dict(partials=self.parts if update and e.world_size == 1 else None)
@@ -960,12 +986,20 @@ class _ConflictFree(_TermCombiner):
     """Device tensors of the conflict-free gradient combination (set_conflict_free_gradients): buf / gb / gs (the
     exchange buffer with the term vectors alpha_b g_b / alpha_s g_s behind it), parts (Gram block partials), coef [3]
     fp32 and rec [CONFGRAD_RECORD] fp64 (the statistics of the last step and the counters)."""
+    mse, stored = "conflict-free gradients need", ("cfg", "coef", "rec")
+    off = (dict(confgrad=False), {}, {})
 
     def __init__(self, engine):
         super().__init__(engine)
         self.coef = torch.ones(3, dtype=torch.float32, device=engine.device)
         self.rec = torch.zeros(CONFGRAD_RECORD, dtype=torch.float64, device=engine.device)
         self.parts = confgrad_partials(engine.P, engine.device)
+
+    def graph_key(self):
+        return ("confgrad",)
+
+    def header(self):
+        return dict(confgrad=True), {}, {}
 
     def assembly(self, e, update):      # one rank: the local vectors are the global ones, their Gram partials too
         return dict(gram=self.parts if e.world_size == 1 else None)
@@ -979,31 +1013,46 @@ class _ConflictFree(_TermCombiner):
         confgrad_combine(e.grads, e.grads, self.gb, gs, self.coef)
 
 
-class _Batching:
+class _Batching(_Option):
     """State of the stochastic mini-batching (set_batching): the batch plan f of B points (and, ev flavour, the
     entropy net's plan e on the same x / y buffers), the device index vector idx [B] int64 and the device draw
     counter [t, scratch]."""
+    resident = mse = "mini-batching needs"
+    stored, off = ("batch", "counter", "idx"), (dict(batch_points=0), dict(batch_seed=None), {})
 
     def __init__(self, B, seed, rank):
         self.B, self.seed, self.rank = B, seed, rank
         self.f = self.e = self.idx = self.counter = None
 
+    def header(self):
+        return dict(batch_points=self.B), dict(batch_seed=self.seed), {}
 
-class _Attention:
+
+class _Attention(_Option):
     """State of the residual-based attention (set_residual_attention): the device tensors lam [N] (multipliers),
     s [N] or None (the static weights given to set_collocation), w [N] (the effective weights s lam^2, which is what
     plan_f.w points to while the feature is on), scratch (statistics) and rec [RBA_RECORD] fp64 (the last update);
     n_eval = local points of the last evaluation that updated."""
+    resident = mse = "residual attention needs"
+    stored, off = ("rba", "lam", "w", "rec"), (dict(attention=False), dict(attention=None), dict(rba_n_eval=None))
 
     def __init__(self, eta, gamma, init):
         self.eta, self.gamma, self.init = eta, gamma, init
         self.lam = self.s = self.w = self.scratch = self.rec = None
         self.n_eval = 0
 
+    def header(self):
+        return dict(attention=True), dict(attention=[self.eta, self.gamma, self.init]), dict(rba_n_eval=self.n_eval)
 
-class _PseudoTime:
+    def restore_host(self, host):
+        self.n_eval = int(host["rba_n_eval"])
+
+
+class _PseudoTime(_Option):
     """State of the pseudo-time stepping (PinnEngine.set_pseudo_time): the launch constants here, anchors on the
-    collocation plan, scratch and record in device memory."""
+    collocation plan, scratch and record in device memory (_state_segments adds anchors and record itself)."""
+    resident = mse = "pseudo-time stepping needs"
+    off = (dict(pseudo_time=False), dict(pseudo_time=None), {})
 
     def __init__(self, dtau, every, pressure_dtau):
         self.dtau, self.pressure_dtau, self.every = dtau, pressure_dtau, every
@@ -1011,12 +1060,19 @@ class _PseudoTime:
         self.sigma_p = 0.0 if pressure_dtau is None else 1.0 / pressure_dtau
         self.scratch = self.record = None
 
+    def graph_key(self):
+        return (("ptime", self.sigma, self.sigma_p, self.every),)
 
-class _Optim:
+    def header(self):
+        return dict(pseudo_time=True), dict(pseudo_time=[self.sigma, self.sigma_p, self.every]), {}
+
+
+class _Optim(_Option):
     """State of the device learning-rate schedule and gradient clipping (set_lr_schedule / set_grad_clipping): the
     schedule (an LrSchedule; constant while only clipping is on) with its C struct, max_norm (0 = no clipping) and the
     device tensors epoch [1] int64 (the schedule position e), rec [OPTIM_RECORD] fp64 (the last update) and scratch
     (the squared norm and its partials)."""
+    stored, off = ("opt", "epoch", "rec"), (dict(schedule_or_clipping=False), dict(schedule=None, max_norm=None), {})
 
     def __init__(self, device):
         self.user_spec, self.max_norm = None, 0.0
@@ -1030,33 +1086,52 @@ class _Optim:
         self.spec = spec if spec is not None else _schedule.LrSchedule()
         self.cstruct = self.spec.c_struct()
 
+    def header(self):
+        return dict(schedule_or_clipping=True), dict(schedule=repr(self.spec.key()), max_norm=self.max_norm), {}
 
-class _Validation:
+
+class _Validation(_Option):
     """State of the device validation monitor (set_validation): the forward-only value plan over the validation
     points, whose pred is a view of the prediction planes; tgt (target planes), scratch, state [VAL_STATE] fp64, ring
     [capacity, VAL_RECORD] fp64 and snap (one snapshot vector per net, of its trainable vector's size).  n counts the
-    optimizer updates since set_validation on the host (the device counts the cadence records itself)."""
+    optimizer updates since set_validation on the host (the device counts the cadence records itself).
+    (_state_segments adds the snapshots and the digested points and targets itself.)"""
+    stored = ("val", "state", "ring")
+    off = (dict(points_val=None, validation=None), dict(validation_every=None), dict(val_n=None))
 
     def __init__(self, every, metric, keep_best, capacity, with_p):
         self.every, self.metric, self.keep_best, self.capacity, self.with_p = every, metric, keep_best, capacity, with_p
         self.n = 0
         self.plan = self.pred = self.tgt = self.scratch = self.state = self.ring = self.snap = None
 
+    def header(self):
+        val = dict(capacity=self.capacity, metric=self.metric, with_p=self.with_p, keep_best=self.keep_best)
+        return dict(points_val=self.plan.n, validation=val), dict(validation_every=self.every), dict(val_n=self.n)
 
-class _Monitor:
+    def restore_host(self, host):
+        self.n = int(host["val_n"])
+
+
+class _Monitor(_Option):
     """State of the convergence monitor (set_convergence_monitor): the launch constants (every, window, patience,
     min_updates, quantity, the two tolerances - None: that criterion is off -, mode, capacity) and the device tensors
     state [MON_STATE] fp64, ring [capacity, MON_RECORD] fp64, info [MON_INFO] fp64 (this rank's vis_t statistics) and
     scratch (ev flavour)."""
+    resident = mse = "the convergence monitor needs"
+    stored = ("monitor", "state", "ring")
 
     def __init__(self, every, window, min_rel, patience, re_tol, min_updates, quantity, mode, capacity):
         self.every, self.window, self.min_rel, self.patience, self.re_tol = every, window, min_rel, patience, re_tol
         self.min_updates, self.quantity, self.mode, self.capacity = min_updates, quantity, mode, capacity
         self.state = self.ring = self.info = self.scratch = None
 
-    def key(self):
-        return ("monitor", self.every, self.window, self.min_rel, self.patience, self.re_tol, self.min_updates,
-                self.quantity, self.capacity)
+    def graph_key(self):
+        return (("monitor", self.every, self.window, self.min_rel, self.patience, self.re_tol, self.min_updates,
+                 self.quantity, self.capacity),)
+
+    def header(self):
+        rec = [self.every, self.window, self.min_rel, self.patience, self.re_tol, self.min_updates, self.quantity, self.mode]
+        return dict(monitor=dict(capacity=self.capacity)), dict(monitor=rec), {}
 
     def c_struct(self, ev):
         return _lib.MonitorConfigStruct(
@@ -1067,11 +1142,13 @@ class _Monitor:
             re_eff_tol=0.0 if self.re_tol is None else self.re_tol)
 
 
-class _Viscosity:
+class _Viscosity(_Option):
     """Identification of the molecular viscosity (PinnEngine.set_viscosity_identification): the constants, the device
     state of the scalar's Adam [VISC_STATE], the fp32 nu every residual plan reads, the scratch of the gradient launch;
     fresh: the last evaluation was made for Adam (its slot holds a gradient the next adam_step may use); n_eq: its
     normalisation."""
+    resident = mse = "viscosity identification needs"
+    stored = ("visc", "state", "nu")
 
     def __init__(self, re0, lr, betas, eps, re_bounds):
         self.re0, self.lr, self.betas, self.eps, self.re_bounds = re0, lr, betas, eps, re_bounds
@@ -1079,8 +1156,12 @@ class _Viscosity:
         self.state = self.nu = self.scratch = None
         self.fresh, self.n_eq = False, 0
 
-    def key(self):
-        return ("visc", self.lr, self.betas, self.eps, self.re_bounds)
+    def graph_key(self):
+        return (("visc", self.lr, self.betas, self.eps, self.re_bounds),)
+
+    def header(self):
+        rec = [self.re0, self.lr, list(self.betas), self.eps, list(self.re_bounds)]
+        return dict(viscosity=True), dict(viscosity=rec), {}
 
     def start(self):
         """The state of an optimiser that has made no update, at re0 (in place).  nu is the fp32 quotient 1 / Re the
@@ -1088,6 +1169,18 @@ class _Viscosity:
         nu = np.float32(1.0) / np.float32(self.re0)
         self.nu.fill_(float(nu))
         self.state.copy_(torch.tensor([math.log(float(nu)), 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float64))
+
+
+# The engine attribute of every option (None while it is off) and its class, in the one order every loop over the
+# options runs in: that of the options' segments in a training-state file and of their entries in the graph key.
+_OPTIONS = (("_opt", _Optim), ("_bal", _Balance), ("_cfg", _ConflictFree), ("_batch", _Batching), ("_rba", _Attention),
+            ("_val", _Validation), ("_pt", _PseudoTime), ("_mon", _Monitor), ("_visc", _Viscosity))
+
+
+def _refuse_chunked(option, chunked):
+    """The refusal of a chunked collocation set by an option (its class or its state) that needs a resident one."""
+    if chunked and option.resident is not None:
+        raise ValueError("%s a resident store: the collocation set is chunked (chunk_points)" % option.resident)
 
 
 # What an evaluation is made for.  Each mode holds what the one before it holds, and more:
@@ -1176,6 +1269,20 @@ class PinnEngine:
     def _w4(self):      # the weight of eq4 (the plain flavour has none)
         return self.eq4_weight if self.net_e is not None else 0.0
 
+    def _options(self):
+        """The training options that are on, in the order of _OPTIONS (for configuration, graph-key and checkpoint time:
+        the step's path tests the attributes it needs directly)."""
+        return [o for o in (getattr(self, attr) for attr, _ in _OPTIONS) if o is not None]
+
+    def _option_header(self, part):
+        """What the options add to part 0 / 1 / 2 (fingerprint / settings / host mirrors) of a training state's header:
+        an option's header() where it is on, its class's `off` where it is not."""
+        out = {}
+        for attr, cls in _OPTIONS:
+            o = getattr(self, attr)
+            out.update((cls.off if o is None else o.header())[part])
+        return out
+
     # ---- views into the exchange buffer ----
     @property
     def grads(self):
@@ -1197,21 +1304,14 @@ class PinnEngine:
             chunk_points = int(os.environ["NSFNET_CHUNK_POINTS"])
         n = int(np.asarray(x).size)
         bt = self._batch
-        if bt is not None and chunk_points and n > int(chunk_points):
-            raise ValueError("mini-batching needs a resident store: chunk_points=%d with batching on" % int(chunk_points))
+        chunked = bool(chunk_points) and n > int(chunk_points)
+        for option in self._options():
+            _refuse_chunked(option, chunked)
         if bt is not None and bt.B > n:
             raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points" % (bt.B, n))
-        if self._rba is not None and chunk_points and n > int(chunk_points):
-            raise ValueError("residual attention needs a resident store: chunk_points=%d with it on" % int(chunk_points))
-        if self._pt is not None and chunk_points and n > int(chunk_points):
-            raise ValueError("pseudo-time stepping needs a resident store: chunk_points=%d with it on" % int(chunk_points))
-        if self._mon is not None and chunk_points and n > int(chunk_points):
-            raise ValueError("the convergence monitor needs a resident store: chunk_points=%d with it on" % int(chunk_points))
-        if self._visc is not None and chunk_points and n > int(chunk_points):
-            raise ValueError("viscosity identification needs a resident store: chunk_points=%d with it on" % int(chunk_points))
         self._graphs.clear()      # captured steps hold the old plan's pointers
         self.lbfgs_reset()
-        if chunk_points and n > int(chunk_points):
+        if chunked:
             self.plan_f = ChunkedResidual(self.net, x, y, weights, chunk_points)
         else:
             self.plan_f = ResidualPlan(self.net, x, y, weights, **({} if self._pt is None else dict(pseudo_time=True)))
@@ -1260,9 +1360,7 @@ class PinnEngine:
         if eta > 0.0:
             if self.plan_f is None:
                 raise RuntimeError("set_residual_attention() needs set_collocation() first")
-            if isinstance(self.plan_f, ChunkedResidual):
-                raise ValueError("residual attention needs a resident store: the collocation set is chunked "
-                                 "(chunk_points)")
+            _refuse_chunked(_Attention, isinstance(self.plan_f, ChunkedResidual))
         self._graphs.clear()        # captured steps hold the other weight buffer and gamma / eta
         old = self._rba
         if old is not None:
@@ -1355,8 +1453,7 @@ class PinnEngine:
         if B > 0:
             if self.plan_f is None:
                 raise RuntimeError("set_batching() needs set_collocation() first")
-            if isinstance(self.plan_f, ChunkedResidual):
-                raise ValueError("mini-batching needs a resident store: the collocation set is chunked (chunk_points)")
+            _refuse_chunked(_Batching, isinstance(self.plan_f, ChunkedResidual))
             if B > self.plan_f.n:
                 raise ValueError("mini-batching: batch_points=%d exceeds the %d local collocation points"
                                  % (B, self.plan_f.n))
@@ -1648,12 +1745,9 @@ class PinnEngine:
         if mode not in ("MSE", "L2"):
             raise ValueError("loss mode must be 'MSE' or 'L2' (got %r)" % (mode,))
         l2 = mode == "L2"
-        for state, needs in ((self._bal, "loss balancing needs"), (self._cfg, "conflict-free gradients need"),
-                             (self._batch, "mini-batching needs"), (self._rba, "residual attention needs"),
-                             (self._pt, "pseudo-time stepping needs"), (self._mon, "the convergence monitor needs"),
-                             (self._visc, "viscosity identification needs")):
-            if l2 and state is not None:
-                raise ValueError("%s the MSE loss (loss mode %r)" % (needs, mode))
+        for option in self._options() if l2 else ():
+            if option.mse is not None:
+                raise ValueError("%s the MSE loss (loss mode %r)" % (option.mse, mode))
         if l2 and (self.net_e is not None or self.world_size > 1 or self._sup_on() or len(_passes(self.plan_f)) > 1):
             raise NotImplementedError("loss mode 'L2' exists for the plain NSFnet flavour on one GPU (NSFnet/pinn_solver.py:202-217)")
         with self._evaluating(EVAL_FULL_BATCH) if full_batch else _SAME_MODE:
@@ -2452,8 +2546,7 @@ class PinnEngine:
             raise ValueError("convergence monitor: mode must be 'any' or 'all' (got %r)" % (mode,))
         if tol["re_eff_tol"] is not None and self.net_e is None:
             raise ValueError("convergence monitor: re_eff_tol needs the ev flavour (the plain flavour has no vis_t)")
-        if isinstance(self.plan_f, ChunkedResidual):
-            raise ValueError("the convergence monitor needs a resident store: the collocation set is chunked (chunk_points)")
+        _refuse_chunked(_Monitor, isinstance(self.plan_f, ChunkedResidual))
         m = _Monitor(every, window, tol["min_rel_improvement"], patience, tol["re_eff_tol"], min_updates, quantity, mode,
                      history)
         m.state = torch.zeros(MON_STATE, dtype=torch.float64, device=self.device)
@@ -2586,8 +2679,7 @@ class PinnEngine:
                                         "the configured Re")):
             if state is not None:
                 raise ValueError("viscosity identification is not available with %s: switch it off first" % what)
-        if isinstance(self.plan_f, ChunkedResidual):
-            raise ValueError("viscosity identification needs a resident store: the collocation set is chunked (chunk_points)")
+        _refuse_chunked(_Viscosity, isinstance(self.plan_f, ChunkedResidual))
         vs = _Viscosity(re0, lr, betas, eps, re_bounds)
         vs.state = torch.zeros(VISC_STATE, dtype=torch.float64, device=self.device)
         vs.nu = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -2702,17 +2794,17 @@ class PinnEngine:
 
     def _graph_key(self, lr, update, validate=False):
         """What a captured step depends on besides device memory: the launch constants of the engine and of every
-        option that is on (lr is the base rate lr0 under a schedule: the rate of each update is device state)."""
+        option that is on (lr is the base rate lr0 under a schedule: the rate of each update is device state).  The
+        head holds balancing, batching, attention, the schedule and the factorization (which lives on the nets)."""
         bt, a, o = self._batch, self._rba, self._opt
         key = (float(lr), self.e_trainable, self.alpha_evm, self.alpha_b, self.alpha_e, self.alpha_s, self.scale,
                self.n_f_global, self.n_b_global, self.n_s_global, self.Re, self.vis_t0, self.eq4_weight,
                self._bal is not None, update, 0 if bt is None else bt.B,
                (False, 0.0, 0.0) if a is None else (True, a.gamma, a.eta))
         key += () if o is None else (o.spec.key(), o.max_norm)
-        key += (() if self._rwf is None else ("rwf",)) + (() if self._cfg is None else ("confgrad",))
-        key += () if self._pt is None else (("ptime", self._pt.sigma, self._pt.sigma_p, self._pt.every),)
-        key += () if self._mon is None else (self._mon.key(),)
-        key += () if self._visc is None else (self._visc.key(),)
+        key += () if self._rwf is None else ("rwf",)
+        for option in self._options():
+            key += option.graph_key()
         v = self._val
         return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 
@@ -2724,9 +2816,11 @@ class PinnEngine:
     def _state_segments(self, lbfgs=None):
         """[(name, tensor, stored)]: everything in device memory that a step reads and an earlier step wrote, in the
         file's fixed order - per net (net, net_e) trainable, m, v, adam_t; per collocation pass x, y, w (the static
-        weights), vis_t_minus; plan_e x, y; opt epoch, rec; bal lam, rec; cfg coef, rec; batch counter, idx; rba lam, w,
-        rec; monitor state, ring; visc state, nu; ptime anchor, record; val state, ring, snap per net; lbfgs ws, d, x0 - and then, digested but not stored
-        (stored False), the sets a resume must attach again unchanged: boundary, supervised, validation, resample pool."""
+        weights), vis_t_minus; plan_e x, y; what every option that is on names as `stored`, in the order of _OPTIONS
+        (opt epoch, rec; bal lam, rec; cfg coef, rec; batch counter, idx; rba lam, w, rec; val state, ring; monitor
+        state, ring; visc state, nu); ptime anchor, record; val snap per net; lbfgs ws, d, x0 - and then, digested but
+        not stored (stored False), the sets a resume must attach again unchanged: boundary, supervised, validation,
+        resample pool."""
         segs = []
 
         def add(name, t, stored=True):
@@ -2745,13 +2839,11 @@ class PinnEngine:
         if self.plan_e is not None:
             add("plan_e.x", self.plan_e.x)
             add("plan_e.y", self.plan_e.y)
-        for name, obj, keys in (("opt", self._opt, ("epoch", "rec")), ("bal", self._bal, ("lam", "rec")),
-                                ("cfg", self._cfg, ("coef", "rec")), ("batch", self._batch, ("counter", "idx")),
-                                ("rba", self._rba, ("lam", "w", "rec")), ("val", self._val, ("state", "ring")),
-                                ("monitor", self._mon, ("state", "ring")), ("visc", self._visc, ("state", "nu"))):
-            if obj is not None:
-                for key in keys:
-                    add("%s.%s" % (name, key), getattr(obj, key))
+        for option in self._options():
+            for key in option.stored[1:]:
+                add("%s.%s" % (option.stored[0], key), getattr(option, key))
+        # the file's order has two special cases: the pseudo-time anchors (they live on the plan) and record come
+        # behind every option's `stored` tensors, and the validation snapshots behind those
         if self._pt is not None and self.plan_f is not None:
             add("ptime.anchor", self.plan_f.anchor)
             add("ptime.record", self._pt.record)
@@ -2778,55 +2870,32 @@ class PinnEngine:
         """The structure a file must share with the engine that loads it."""
         shape = lambda net: None if net is None else [net.n_out, net.n_hidden, net.hidden]
         count = lambda plan, g: None if plan is None else [plan.n, int(g)]
-        v, f = self._val, self.plan_f
-        mon = {} if self._mon is None else dict(monitor=dict(capacity=self._mon.capacity))      # (off: the file's bytes of before)
-        if self._visc is not None:
-            mon["viscosity"] = True
+        f = self.plan_f
         return dict(
-            mon, flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
+            self._option_header(0), flavour=self.flavour, net=shape(self.net), net_e=shape(self.net_e),
             points_colloc=count(f, self.n_f_global), points_boundary=count(self.plan_b, self.n_b_global),
             points_supervised=[0 if self.plan_s is None else self.plan_s.n, int(self.n_s_global)],
-            points_val=None if v is None else v.plan.n, points_pool=None if self._pool is None else self._pool.n,
+            points_pool=None if self._pool is None else self._pool.n,
             points_colloc_passes=None if f is None else [[int(a), int(b)] for (a, b), _ in _passes(f)],
             colloc_weights=f is not None and self._static_w() is not None,
-            schedule_or_clipping=self._opt is not None, balancing=self._bal is not None, confgrad=self._cfg is not None,
-            batch_points=0 if self._batch is None else self._batch.B, attention=self._rba is not None,
-            validation=None if v is None else dict(capacity=v.capacity, metric=v.metric, with_p=v.with_p,
-                                                   keep_best=v.keep_best),
             lbfgs_history=None if self._lbfgs is None else self._lbfgs.history_size, rwf=self._rwf is not None,
             hard_bc=None if self.hard_boundary_info() is None else
             {k: list(x) if isinstance(x, tuple) else x for k, x in self.hard_boundary_info().items()},
-            pseudo_time=self._pt is not None, world_size=self.world_size, rank=self._rank(),
-            first_layer="sine" if self.net.first_layer else None)
+            world_size=self.world_size, rank=self._rank(), first_layer="sine" if self.net.first_layer else None)
 
     def _state_info(self):
         """What a file records beside the structure; load_training_state reports the keys that differ."""
-        o, a, b, bt, v, pt = self._opt, self._rba, self._bal, self._batch, self._val, self._pt
         kernels = getattr(self.plan_f, "kernel_names", None)
-        m = self._mon
-        mon = {} if m is None else dict(monitor=[m.every, m.window, m.min_rel, m.patience, m.re_tol, m.min_updates,
-                                                 m.quantity, m.mode])
-        vs = self._visc
-        if vs is not None:
-            mon["viscosity"] = [vs.re0, vs.lr, list(vs.betas), vs.eps, list(vs.re_bounds)]
         return dict(
-            mon, precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
+            self._option_header(1), precision=[list(getattr(net, "precision", ())) for _, net in self._nets()],
             kernels=None if kernels is None else list(kernels()), Re=self.Re, alpha_b=self.alpha_b, alpha_e=self.alpha_e,
-            alpha_s=self.alpha_s, alpha_evm=self.alpha_evm, scale=self.scale, vis_t0=self.vis_t0, eq4_weight=self._w4(),
-            pseudo_time=None if pt is None else [pt.sigma, pt.sigma_p, pt.every],
-            attention=None if a is None else [a.eta, a.gamma, a.init],
-            balancing=None if b is None else [b.every, b.beta], batch_seed=None if bt is None else bt.seed,
-            validation_every=None if v is None else v.every,
-            schedule=None if o is None else repr(o.spec.key()), max_norm=None if o is None else o.max_norm)
+            alpha_s=self.alpha_s, alpha_evm=self.alpha_evm, scale=self.scale, vis_t0=self.vis_t0, eq4_weight=self._w4())
 
     def _state_host(self):
         """The host mirrors of the device state."""
         ls = self._lbfgs_state
-        return dict(adam_t=[net.adam_t for _, net in self._nets()], e_trainable=bool(self.e_trainable),
-                    resample_calls=self._resample_calls,
-                    bal=None if self._bal is None else [self._bal.n, self._bal.done],
-                    rba_n_eval=None if self._rba is None else self._rba.n_eval,
-                    val_n=None if self._val is None else self._val.n,
+        return dict(self._option_header(2), adam_t=[net.adam_t for _, net in self._nets()],
+                    e_trainable=bool(self.e_trainable), resample_calls=self._resample_calls,
                     lbfgs=None if self._lbfgs is None else [ls.n_iter, ls.func_evals, ls.t, ls.prev_loss])
 
     def _state_path(self, path):
@@ -2990,12 +3059,8 @@ class PinnEngine:
         for (_, net), t in zip(self._nets(), host["adam_t"]):
             net.adam_t = int(t)
         self.e_trainable, self._resample_calls = bool(host["e_trainable"]), int(host["resample_calls"])
-        if self._bal is not None:
-            self._bal.n, self._bal.done = (int(v) for v in host["bal"])
-        if self._rba is not None:
-            self._rba.n_eval = int(host["rba_n_eval"])
-        if self._val is not None:
-            self._val.n = int(host["val_n"])
+        for option in self._options():
+            option.restore_host(host)
         self.lbfgs_reset()
         if host["lbfgs"] is not None:
             ls = self._lbfgs_state

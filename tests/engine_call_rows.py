@@ -1,8 +1,9 @@
 """The rows of tests/golden/engine_call_logs.json (TEST INFRASTRUCTURE): one PinnEngine per row on the oracle-backed
 fakes, driven through step / loss_and_grad + adam_step / lbfgs_step, with every device entry point it reaches logged
-together with its launch arguments (names, counts and floats: no computed result).  scripts/record_engine_calls.py
-writes the fixture from these rows and tests/test_engine_call_logs.py rebuilds them.  Nothing here is reachable from the
-product path."""
+together with its launch arguments (names, counts and floats: no computed result), and of
+tests/golden/engine_state_headers.json: what a training-state file of the driven engine would say of itself.
+scripts/record_engine_calls.py writes the fixtures from these rows and tests/test_engine_call_logs.py rebuilds them.
+Nothing here is reachable from the product path."""
 import hashlib
 import json
 
@@ -11,15 +12,16 @@ import pytest
 import torch
 
 import confgrad_fakes
-import fakes
-import rwf_fakes
+import ptime_model
+import visc_fakes
 from nsfnet_amd import engine as eng
 from nsfnet_amd.schedule import LrSchedule
 
 L, H, RE, N, NB, LR = 2, 8, 400.0, 300, 40, 2.0 ** -10
 SPIED = ("grad_reduce", "grad_reduce_terms", "balance_stats", "balance_update", "balance_combine", "confgrad_gram",
          "confgrad_coef", "confgrad_combine", "batch_draw", "batch_scatter", "rba_stats", "rba_apply", "rba_fill",
-         "grad_sqnorm")
+         "grad_sqnorm", "ptime_advance", "val_stats", "val_keep", "monitor_vis_stats", "monitor_observe", "visc_grad",
+         "visc_update")
 CONFGRAD = ("grad_reduce_terms", "confgrad_partials", "confgrad_gram", "confgrad_coef", "confgrad_combine")
 
 _BAL = dict(balance=dict(every=2, beta=0.1))
@@ -33,6 +35,11 @@ ROWS = [dict(name="%s-%s" % (flavour, name), flavour=flavour, opts=opts)
 for _name, _opts in OPTIONS[:3]:
     ROWS.append(dict(name="chunked-" + _name, flavour="nsfnet", opts=_opts, chunk=128))
     ROWS.append(dict(name="supervised-" + _name, flavour="nsfnet", opts=_opts, sup=True))
+_VAL, _MON = dict(validation=dict(n=16, every=2)), dict(monitor=dict(every=1, window=2))
+LATER = [("ptime", dict(ptime=dict(dtau=0.5, every=2, pressure_dtau=2.0))), ("validation", _VAL), ("monitor", _MON),
+         ("visc", dict(visc={})), ("attention_sched_clip_validation_monitor", dict(OPTIONS[4][1], **OPTIONS[5][1], **_VAL, **_MON))]
+ROWS += [dict(name="%s-%s" % (flavour, name), flavour=flavour, opts=opts)
+         for name, opts in LATER for flavour in ("nsfnet", "ev")]
 
 
 def _brief(a):
@@ -59,29 +66,56 @@ def _spy(log, name, fn):
     return wrapper
 
 
-def _spy_plan(log, base):
+def _spy_plan(log, base, name):
     class Spy(base):
         def forward(self, *a, **k):
-            log.append(_entry(base.__name__ + ".forward", (self.n,) + a, k))
+            log.append(_entry(name + ".forward", (self.n,) + a, k))
             return super().forward(*a, **k)
 
         def backward(self, *a, **k):
-            log.append(_entry(base.__name__ + ".backward", (self.n,) + a, k))
+            log.append(_entry(name + ".backward", (self.n,) + a, k))
             return super().backward(*a, **k)
-    Spy.__name__ = base.__name__
+    Spy.__name__ = name
     return Spy
 
 
+class PtimeResidualPlan(visc_fakes.ViscResidualPlan):
+    """The residual plan of the fakes stack with the anchors and the rates of the pseudo-time stepping.  Its sums and
+    gradient stay the steady term's: the rows pin which launches the engine makes, not what they compute."""
+    anchor = None
+
+    def __init__(self, net, x, y, weights=None, with_backward=True, ws=None, pseudo_time=False):
+        super().__init__(net, x, y, weights, with_backward, ws)
+        self.is_pseudo_time = pseudo_time
+
+    def set_pseudo_time(self, sigma, sigma_p):
+        assert self.is_pseudo_time
+        if self.anchor is None:
+            self.anchor = torch.zeros(3, self.npad)
+        self.rates = (float(sigma), float(sigma_p))
+
+
+def _ptime_advance(plan, every, force, scratch, record):
+    anchor, rec = ptime_model.advance(plan.fields.numpy(), plan.n, plan.anchor.numpy(), every, force,
+                                      None if plan.w is None else plan.w.numpy(), record.numpy())
+    plan.anchor.copy_(torch.tensor(anchor))
+    record.copy_(torch.tensor(rec))
+
+
 def install(mp):
-    """The rwf_fakes stack with the conflict-free-gradient entry points of confgrad_fakes on top (both log into one
-    list), logging plans, and a spy with the launch arguments around every entry point of SPIED.  Returns the log."""
-    rwf_fakes.install(mp)
-    log = rwf_fakes.CALLS
+    """The whole fakes stack (visc_fakes: monitor, training state and validation on the factorization, the optimiser
+    options and the rest) with the conflict-free-gradient entry points of confgrad_fakes and a pseudo-time plan and
+    advance on top (all log into one list), logging plans, and a spy with the launch arguments around every entry point
+    of SPIED.  Returns the log."""
+    visc_fakes.install(mp)
+    log = visc_fakes.CALLS
     mp.setattr(confgrad_fakes, "CALLS", log)
     for name in CONFGRAD:
         mp.setattr(eng, name, getattr(confgrad_fakes, "fake_" + name))
-    mp.setattr(eng, "ResidualPlan", _spy_plan(log, fakes.FakeResidualPlan))
-    mp.setattr(eng, "ValuePlan", _spy_plan(log, fakes.FakeValuePlan))
+    mp.setattr(eng, "ptime_scratch", lambda n, device: torch.zeros(8, dtype=torch.float64))
+    mp.setattr(eng, "ptime_advance", _ptime_advance)
+    mp.setattr(eng, "ResidualPlan", _spy_plan(log, PtimeResidualPlan, "FakeResidualPlan"))
+    mp.setattr(eng, "ValuePlan", _spy_plan(log, eng.ValuePlan, "FakeValuePlan"))
     for name in SPIED:
         mp.setattr(eng, name, _spy(log, name, getattr(eng, name)))
     return log
@@ -101,6 +135,8 @@ def engine(row):
         e.e_trainable = True
     x, y = rng.rand(N).astype(np.float32), rng.rand(N).astype(np.float32)
     xb, yb, ub, vb = (a.reshape(-1)[::51][:NB] for a in ar.cavity_boundary())
+    if "ptime" in o:
+        e.set_pseudo_time(**o["ptime"])
     e.set_collocation(x, y, chunk_points=row.get("chunk"))
     e.set_boundary(xb, yb, ub, vb)
     if row.get("sup"):
@@ -120,6 +156,13 @@ def engine(row):
         e.set_grad_clipping(o["clip"])
     if "rwf" in o:
         e.set_weight_factorization(seed=o["rwf"])
+    if "validation" in o:       # (the later rows draw after everything the earlier ones drew)
+        xv, yv = (rng.rand(o["validation"]["n"]).astype(np.float32) for _ in range(2))
+        e.set_validation(xv, yv, np.sin(xv), np.cos(yv), every=o["validation"]["every"])
+    if "monitor" in o:
+        e.set_convergence_monitor(**o["monitor"])
+    if "visc" in o:
+        e.set_viscosity_identification(**o["visc"])
     return e
 
 
@@ -180,15 +223,27 @@ def state_hashes(e):
                 flat=_sha(e.flat), records=[_sha(t) for t in recs])
 
 
+def state_header(e):
+    """What save_training_state would put into the file's header: the fingerprint, the settings, the host mirrors
+    (without the two floats of the L-BFGS state) and per segment [name, dtype, shape, bytes, stored].  No digests: they
+    hash floating-point results of the host's BLAS.  The offsets follow from the bytes (state_file.layout)."""
+    host = e._state_host()
+    if host["lbfgs"] is not None:
+        host["lbfgs"] = host["lbfgs"][:2]
+    segs = [[name, str(t.dtype).replace("torch.", ""), list(t.shape), t.numel() * t.element_size(), stored]
+            for name, t, stored in e._state_segments()]
+    return dict(fingerprint=e._state_fingerprint(), info=e._state_info(), host=host, segments=segs)
+
+
 def run(row, hashes=False):
-    """(call log, graph keys[, state hashes]) of one row, as JSON gives them back."""
+    """(call log, graph keys, state header[, state hashes]) of one row, as JSON gives them back."""
     with pytest.MonkeyPatch.context() as mp:
         log = install(mp)
         e = engine(row)
         del log[:]
         drive(e)
-        out = [list(log)]
+        out = [list(log), None, state_header(e)]
         h = state_hashes(e) if hashes else None
-        out.append(graph_keys(mp, e))
+        out[1] = graph_keys(mp, e)
     out = json.loads(json.dumps(out))
-    return (out[0], out[1], h) if hashes else (out[0], out[1])
+    return tuple(out) + ((h,) if hashes else ())
