@@ -24,7 +24,18 @@ SHAPE_E = (1, 2, 6)
 
 
 # ------------------------------------------------------------------ the formula and the rows' inputs
-@pytest.mark.parametrize("name", ["2x8-fp32", "4x50-fp32-ev", "4x50-bf16x3-hardbc"])
+def _one_per_reference(names):
+    """The first row of every fp64 reference (vm.ref_key): rows that differ by precision or switch share it."""
+    seen, out = set(), []
+    for name in names:
+        if vm.ref_key(name) not in seen:
+            seen.add(vm.ref_key(name))
+            out.append(name)
+    return out
+
+
+# (the first three: the rows this test was written on; then one row of every other reference of the second set)
+@pytest.mark.parametrize("name", _one_per_reference(["2x8-fp32", "4x50-fp32-ev", "4x50-bf16x3-hardbc"] + list(vm.ROWS)))
 def test_the_formula_is_the_central_difference_of_the_oracle_loss(name):
     c = vm.row_case(name)
     nu = float(np.float32(1.0) / np.float32(c["Re"]))
@@ -34,6 +45,8 @@ def test_the_formula_is_the_central_difference_of_the_oracle_loss(name):
     r = vm.row_reference(c, **ev)
     h = 1e-4 * nu
     kw = dict(w=c["w"], scale=c["scale"], **ev)
+    if c.get("ff"):
+        kw["ff"] = True
     if c.get("hard_bc"):
         import hardbc_model as hm
         kw["bc"] = hm.HardBc()
@@ -54,7 +67,7 @@ _REF = {}
 
 
 def _ref(name, shifted=False):
-    key = (vm.ROWS[name]["L"], vm.ROWS[name]["H"], vm.ROWS[name]["seed"], name if vm.ROWS[name]["L"] != 6 else "", shifted)
+    key = vm.ref_key(name) + (shifted,)
     if key not in _REF:
         c = vm.row_case(name)
         _REF[key] = vm.row_reference(c, re0=vm.row_re0(c, shifted))
@@ -87,6 +100,136 @@ def test_the_ev_row_sees_eq4_and_the_weighted_row_its_weights_and_scale():
     s2 = c["scale"] * c["scale"]
     no_sc2 = float(np.sum(vm.terms(r["eqs"], r["u"], r["v"], (r["lap"][0] / s2, r["lap"][1] / s2), c["w"], 0.1)))
     assert abs(r["S"] - no_sc2) > 10.0 * bar, (r["S"], no_sc2)
+
+
+def test_the_bf16x3_ev_row_sees_eq4_its_weights_and_scale():
+    name = "4x50-bf16x3-ev"
+    c, r = vm.row_case(name), _ref(name)
+    bar = S_BAR[c["prec"]] * abs(r["S"])
+    s2 = c["scale"] * c["scale"]
+    for what, lap, w, w4 in (("eq4", r["lap"], c["w"], 0.0), ("weights", r["lap"], None, 0.1),
+                             ("scale", (r["lap"][0] / s2, r["lap"][1] / s2), c["w"], 0.1)):
+        other = float(np.sum(vm.terms(r["eqs"], r["u"], r["v"], lap, w, w4)))
+        assert abs(r["S"] - other) > 10.0 * bar, (what, r["S"], other)
+
+
+# the bars of tests/test_viscosity_gpu.py per quantity: planes (lap, eq), S, sums, loss, gradient per block
+ROW_BARS = {"fp32": dict(plane=2e-5, S=3e-5, sums=1e-5, loss=1e-5, grad=1e-4),
+            "bf16x3": dict(plane=5e-4, S=6e-4, sums=2e-4, loss=1e-4, grad=1e-4)}
+
+
+class _Cast(torch.nn.Module):
+    """A model that rounds its input to `dtype`, computes in it and returns fp64 (tests/test_fourier_gpu.py model_step)."""
+
+    def __init__(self, m, dtype):
+        super().__init__()
+        self.m, self.dtype = m, dtype
+
+    def parameters(self, recurse=True):
+        return self.m.parameters(recurse)
+
+    def forward(self, X):
+        return self.m(X.to(self.dtype)).double()
+
+
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("name", _one_per_reference([n for n in vm.ROWS if vm.ROWS[n].get("ff")]))
+def test_sine_rows_keep_the_fp32_error_of_the_reference_within_a_quarter_of_each_bar(name, shifted):
+    """The check of tests/test_fourier_gpu.py's docstring on the rows with the sine first layer: a straight fp32 torch
+    evaluation of the row's model against the fp64 one - the fp32 rounding of the sine's argument, the reference's own
+    error - stays within a quarter of every bar the GPU test applies to the row, at both estimates."""
+    import fourier_model as fo
+    import hardbc_model as hm
+    from oracle import autograd_ref as ar
+    from oracle import fwdmode_ref as fr
+    c = vm.row_case(name)
+    nu = float(np.float32(1.0) / np.float32(vm.row_re0(c, shifted)))
+    xb, yb, ub, vb = (a.reshape(-1)[::16].astype(np.float32) for a in ar.cavity_boundary())
+    run = {}
+    for dtype in (torch.float64, torch.float32):
+        model = fo.sine_net(c["flat"], c["L"], c["H"], dtype=dtype)
+        r = hm.constrained_step(_Cast(model, dtype), c["x"], c["y"], 1.0 / nu, xb, yb, ub, vb, alpha_b=10.0, alpha_e=1.0)
+        f = r["fields"]
+        r["S"] = float(np.sum(vm.terms(r["eqs"], f["u"], f["v"], (f["u_d"], f["v_d"]))))
+        r["grad"] = fo.freeze(r["grad"], c["H"])
+        run[dtype] = r
+    a, b = run[torch.float32], run[torch.float64]
+    rel_max = lambda p, q: float(np.abs(p - q).max() / np.abs(q).max())
+    blocks = lambda g: [q for wb in fr.unflatten(np.asarray(g, np.float64), 2, 3, c["L"], c["H"]) for q in wb]
+    errs = dict(plane=max([rel_max(a["fields"][k], b["fields"][k]) for k in ("u_d", "v_d")] +
+                          [rel_max(p, q) for p, q in zip(a["eqs"], b["eqs"])]),
+                S=abs(a["S"] - b["S"]) / abs(b["S"]),
+                sums=rel_max(np.asarray(a["sums_eq"]), np.asarray(b["sums_eq"])),
+                loss=abs(a["loss"] - b["loss"]) / b["loss"],
+                grad=max(float(np.linalg.norm(p - q) / max(np.linalg.norm(q), 1e-300))
+                         for p, q in zip(blocks(a["grad"]), blocks(b["grad"]))))
+    print("[viscosity] %s nu=%g fp32 torch against fp64: %s" % (name, nu, " ".join("%s %.2e" % kv for kv in errs.items())))
+    for k, bar in ROW_BARS[c["prec"]].items():
+        assert errs[k] <= 0.25 * bar, (k, errs[k], bar)
+    # (the autograd statement and the forward-mode one the GPU test uses are the same model)
+    ref = _ref(name, shifted)
+    assert rel_max(b["fields"]["u_d"], ref["lap"][0]) < 1e-9 and abs(b["S"] - ref["S"]) < 1e-9 * abs(ref["S"])
+
+
+def test_the_two_estimates_of_the_lap_check_are_exact_and_a_factor_two_apart():
+    a, b = (np.float32(1.0) / np.float32(r) for r in vm.TWO_RE0)
+    assert a == 2.0 * b and float(a) * vm.TWO_RE0[0] == 1.0 and float(b) * vm.TWO_RE0[1] == 1.0
+    assert np.frexp(a)[0] == 0.5 and np.frexp(b)[0] == 0.5                  # powers of two: nu Lap u is exact in fp32
+    assert all(1e-2 <= r <= 1e6 for r in vm.TWO_RE0)                         # inside the default re_bounds
+    assert all(n in vm.BIT_ROWS or not vm.ROWS[n].get("ev") for n in vm.LAP_ROWS)
+    kinds = [dict(vm.BIT_ROWS, **vm.ROWS)[n] for n in vm.LAP_ROWS]
+    assert any(k.get("hard_bc") for k in kinds) and any(k.get("ff") for k in kinds)
+
+
+def test_the_pool_test_s_control_tells_the_two_viscosities_apart():
+    """tests/test_viscosity_gpu.py judges the pool plan's eq1 plane against the model at 1 / re0: at 1 / Re the model is
+    more than ten bars away, so a pool forward that kept the launch constant would miss."""
+    c = vm.row_case("2x8-fp32", n=vm.N_OPT)
+    xp, yp = vm.pool_points()
+    at = lambda re: vm.evaluate(c["flat"], c["L"], c["H"], xp, yp, float(np.float32(1.0) / np.float32(re)))["eqs"][0]
+    e0, e1 = at(c["Re"]), at(c["re0"])
+    assert np.abs(e1 - e0).max() > 10.0 * ROW_BARS["fp32"]["plane"] * np.abs(e1).max()
+    assert vm.B_OPT % 16 != 0 and vm.B_OPT < vm.N_OPT
+    r = vm.evaluate(c["flat"], c["L"], c["H"], c["x"], c["y"], float(np.float32(1.0) / np.float32(c["re0"])))
+    assert r["kappa"] <= 3.0, r["kappa"]
+
+
+# ------------------------------------------------------------------ the rows' plans, from the ABI without a device
+@pytest.mark.parametrize("name", list(vm.ROWS) + list(vm.BIT_ROWS))
+def test_every_row_s_plan_names_its_kernels_and_says_its_path(monkeypatch, capfd, name):
+    """resolve_plan is host arithmetic: the kernels a row's switches, width, precision and variant lead to, and the
+    $PINN_VERBOSE line of its path, need no GPU (the GPU test asserts both again on the plan it runs)."""
+    import ctypes
+    from nsfnet_amd import _lib, engine as eng
+    import hardbc_model as hm
+    r = dict(vm.BIT_ROWS, **vm.ROWS)[name]
+    for k in list(os.environ):
+        if k.startswith("PINN_") or k.startswith("NSFNET_"):
+            monkeypatch.delenv(k, raising=False)
+    for k, v in r.get("env", ()):
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("PINN_VERBOSE", "1")
+    lib = _lib.load()
+    net, plan = ctypes.c_void_p(), ctypes.c_void_p()
+    assert lib.pinn_net_create(3, r["L"], r["H"], ctypes.byref(net)) == 0
+    try:
+        assert lib.pinn_net_set_precision(net, *[eng.PRECISIONS[r["prec"]]] * 3) == 0
+        if r.get("ff"):
+            assert lib.pinn_net_set_first_layer(net, 1) == 0
+        capfd.readouterr()
+        if r.get("hard_bc"):
+            bc = hm.HardBc().struct()
+            assert lib.pinn_plan_create_constrained(net, vm.N_ROW, 4, ctypes.byref(bc), ctypes.byref(plan)) == 0
+        else:
+            assert lib.pinn_plan_create(net, vm.N_ROW, 4, ctypes.byref(plan)) == 0
+        err = capfd.readouterr().err
+        names = tuple((lib.pinn_plan_kernel(plan, k) or b"").decode() for k in (0, 1, 2))
+        lib.pinn_plan_destroy(plan)
+    finally:
+        lib.pinn_net_destroy(net)
+    assert names == r["names"], names
+    for s in r.get("say", ()):
+        assert any(s in line for line in err.splitlines() if line.startswith("[pinn] plan:")), (s, err)
 
 
 # ------------------------------------------------------------------ the update
