@@ -744,6 +744,46 @@ int pinn_visc_grad(int64_t n, const float* fields, int64_t npad, const float* la
 int pinn_visc_update(const float* sum, double coef, double lr, double beta1, double beta2, double eps, double theta_min,
                      double theta_max, double* state, float* nu_dev, void* stream);
 
+/* ---- Reynolds-number continuation: a device-held ramp of the viscosity nu = 1 / Re (and of the cap vis_t0) ----
+ * pinn_plan_set_viscosity_cap: beside nu_dev a residual plan may carry cap_dev, one fp32 of device memory; the forward
+ *   launches (the fused one included) then use *cap_dev wherever they would use the vis_t0 argument, which is still
+ *   checked and otherwise unused.  Refused with -22: a value-mode plan, a cap on a plan without nu_dev, a misaligned
+ *   pointer.  pinn_plan_set_viscosity drops the cap (set nu_dev first, the cap second); NULL takes it off.
+ *   pinn_plan_viscosity_cap returns the pointer.
+ * The schedule: with t updates made so far,
+ *     s = min(max((t - hold) / updates, 0), 1)        stairs = K > 0 and s < 1:  s = floor(s K) / K
+ *   s <= 0 selects nu_start, cap_start and s >= 1 nu_end, cap_end: the fp32 values given, never computed, so that a
+ *   finished ramp leaves the bits the launches would take as constants.  In between, fp64, one rounding per operation
+ *   in the order written, with n0 = (double)nu_start, n1 = (double)nu_end:
+ *     PINN_RAMP_GEOMETRIC   nu64 = exp(log(n0) + s (log(n1) - log(n0)))
+ *     PINN_RAMP_LINEAR_RE   nu64 = 1 / ((1 / n0) + s ((1 / n1) - (1 / n0)))
+ *     PINN_RAMP_LINEAR_NU   nu64 = n0 + s (n1 - n0)
+ *   nu64 is clamped to the interval of n0 and n1, cap64 = cap_factor nu64 to that of cap_start and cap_end; nu =
+ *   (float)nu64, cap = (float)cap64, Re_t = 1 / nu64 (at the ends: re_start, re_end).  Monotone in t.
+ * pinn_visc_schedule_value: host only, the same function the kernel runs; record6 (may be NULL) receives the record
+ *   below for position t; returns nu_t (NaN and pinn_last_error for a bad schedule or t < 0).
+ * pinn_visc_schedule_step: one workgroup, after the nets' updates.  t = *pos + 1 is stored to *pos (int64: positions
+ *   beyond 2^31 work), *nu_dev and (not NULL) *cap_dev are rewritten for t, and record (PINN_RAMP_RECORD doubles, 8-byte
+ *   aligned) becomes [0] t  [1] s  [2] Re_t  [3] nu_t  [4] cap_t (0 without cap_factor)  [5] done (s >= 1).
+ *   No atomics, bit-reproducible.  Refused with -22: updates <= 0, hold < 0, stairs < 0, an unknown shape, re_start /
+ *   re_end / the fp32 ends not finite and > 0, cap_factor not finite or < 0, NULL or misaligned pointers. */
+#define PINN_RAMP_RECORD 6
+enum { PINN_RAMP_GEOMETRIC = 0, PINN_RAMP_LINEAR_RE = 1, PINN_RAMP_LINEAR_NU = 2 };
+typedef struct {
+  int32_t shape;                /* PINN_RAMP_* */
+  int32_t stairs;               /* K: the ramp in K equal stairs; 0: smooth */
+  int64_t hold, updates;        /* updates at the start value before the ramp; its length */
+  double re_start, re_end;      /* the Reynolds numbers of the ends (the record's Re_t there) */
+  double cap_factor;            /* vis_t0_factor: cap = cap_factor nu inside the ramp; 0: no cap */
+  float nu_start, nu_end;       /* the fp32 written at s <= 0, at s >= 1 */
+  float cap_start, cap_end;
+} pinn_visc_schedule_t;
+int pinn_plan_set_viscosity_cap(pinn_plan_t plan, const float* cap_dev);
+int pinn_plan_viscosity_cap(pinn_plan_t plan, const float** cap_dev);
+double pinn_visc_schedule_value(const pinn_visc_schedule_t* schedule, int64_t t, double* record6);
+int pinn_visc_schedule_step(const pinn_visc_schedule_t* schedule, int64_t* pos, float* nu_dev, float* cap_dev,
+                            double* record, void* stream);
+
 /* ---- training-state snapshots: many device buffers <-> one staging buffer, with digests ----
  * A snapshot is a list of segments (any number; a launch takes up to 64, more take several launches).  In the staging
  * buffer segment k starts at align256(end of the segment stored before it) and the padding behind a segment is zero,

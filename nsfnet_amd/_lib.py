@@ -109,6 +109,10 @@ SIGNATURES = {
     "pinn_visc_grad": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "pinn_visc_update": (c_int, [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_void_p,
                                  c_void_p, c_void_p]),
+    "pinn_plan_set_viscosity_cap": (c_int, [c_void_p, c_void_p]),
+    "pinn_plan_viscosity_cap": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "pinn_visc_schedule_value": (c_double, [c_void_p, c_int64, c_void_p]),
+    "pinn_visc_schedule_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_state_scratch_bytes": (c_int64, []),
     "pinn_state_layout": (c_int64, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "pinn_state_digest_host": (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -130,6 +134,13 @@ class HardBcStruct(ctypes.Structure):
     """pinn_hard_bc_t"""
     _fields_ = [("kind", ctypes.c_int32), ("lift_power", ctypes.c_int32), ("x0", c_float), ("y0", c_float),
                 ("inv_len", c_float), ("lid_sharpness", c_float)]
+
+
+class ViscScheduleStruct(ctypes.Structure):
+    """pinn_visc_schedule_t"""
+    _fields_ = [("shape", ctypes.c_int32), ("stairs", ctypes.c_int32), ("hold", c_int64), ("updates", c_int64),
+                ("re_start", c_double), ("re_end", c_double), ("cap_factor", c_double), ("nu_start", c_float),
+                ("nu_end", c_float), ("cap_start", c_float), ("cap_end", c_float)]
 
 
 class MonitorConfigStruct(ctypes.Structure):

@@ -14,8 +14,8 @@ OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libnsfnet_pinn.so")
 SOURCES = ["fwd.hip", "bwd.hip", "dw.hip", "fwd_bf16.hip", "bwd_bf16.hip", "dw_bf16.hip", "fwd_wide.hip", "bwd_wide.hip", "dw_wide.hip",
-           "fwd_bf16_wide.hip", "bwd_bf16_wide.hip", "dw_bf16_wide.hip", "fwd_bf16_pipe.hip", "bwd_bf16_pipe.hip", "fwd_bf16_split.hip", "bwd_bf16_split.hip", "fwdbwd_bf16_split.hip", "fwd_bf16_wsplit.hip", "bwd_bf16_wsplit.hip", "misc.hip", "resample.hip", "lbfgs.hip", "balance.hip", "confgrad.hip", "batch.hip", "rba.hip", "optim.hip", "rwf.hip", "validate.hip", "ptime.hip", "monitor.hip", "visc.hip", "state.hip", "capi.hip"]
-HEADERS = ["kernels.h", "launch_dispatch.h", "layout.h", "spill.h", "spill_io.h", "bf16_util.h", "reduce_util.h", "point_stage.h", "split_phases.h", "wsplit_phases.h", "wave8_bodies.h", "optim.h", "rwf.h", "fixed_fold.h", "residual_planes.h", os.path.join("..", "..", "include", "nsfnet_pinn.h")]
+           "fwd_bf16_wide.hip", "bwd_bf16_wide.hip", "dw_bf16_wide.hip", "fwd_bf16_pipe.hip", "bwd_bf16_pipe.hip", "fwd_bf16_split.hip", "bwd_bf16_split.hip", "fwdbwd_bf16_split.hip", "fwd_bf16_wsplit.hip", "bwd_bf16_wsplit.hip", "misc.hip", "resample.hip", "lbfgs.hip", "balance.hip", "confgrad.hip", "batch.hip", "rba.hip", "optim.hip", "rwf.hip", "validate.hip", "ptime.hip", "monitor.hip", "visc.hip", "visc_sched.hip", "state.hip", "capi.hip"]
+HEADERS = ["kernels.h", "launch_dispatch.h", "layout.h", "spill.h", "spill_io.h", "bf16_util.h", "reduce_util.h", "point_stage.h", "split_phases.h", "wsplit_phases.h", "wave8_bodies.h", "optim.h", "visc_sched.h", "rwf.h", "fixed_fold.h", "residual_planes.h", os.path.join("..", "..", "include", "nsfnet_pinn.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  The pipelined kernels place their epilogue VALU in MFMA shadows: packed-f32 VALU (v_pk_*_f32, what
 # the SLP vectoriser makes of adjacent scalar f32 ops) costs more beside MFMAs than the two scalar ops it replaces

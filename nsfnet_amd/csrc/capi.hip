@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "optim.h"
 #include "rwf.h"
+#include "visc_sched.h"
 
 static_assert((int)PINN_FLD_COUNT == (int)FLD_COUNT, "field plane enum mismatch");
 
@@ -149,6 +150,7 @@ struct pinn_plan_s {
   float sigma, sigma_p;  // its rates
   const float* nu_dev;   // viscosity identification (pinn_plan_set_viscosity; residual plans): the fp32 read in place of 1 / Re, or NULL
   float* lap;            // and the planes [2][npad] the forward leaves Lap u, Lap v in, or NULL
+  const float* cap_dev;  // Reynolds-number continuation (pinn_plan_set_viscosity_cap): the fp32 read in place of vis_t0, or NULL
   // workspace offsets in bytes
   size_t off_partials, off_oadj, off_sg, off_slabs, off_S, off_Zb, bytes_fwd, bytes_all;
 };
@@ -269,7 +271,7 @@ static int resolve_plan(pinn_plan_s* p, const pinn_net_s& net, long n_points, in
   p->net = net;
   p->hbc = hbc;
   p->ptime = ptime; p->anchor = nullptr; p->sigma = p->sigma_p = 0.f;
-  p->nu_dev = nullptr; p->lap = nullptr;
+  p->nu_dev = nullptr; p->lap = nullptr; p->cap_dev = nullptr;
   p->n = n_points; p->streams = streams;
   const bool wide = net.wide != 0;
   const int per_tile = wide ? (streams == 4 ? 16 : 64) : (streams == 4 ? 32 : 128);
@@ -419,7 +421,7 @@ static FwdArgs residual_fwd_args(const pinn_plan_s* plan, void* ws, const float*
   FwdArgs a = fwd_args(plan, ws, prep, x, y, save, coord_scale);
   a.fld = fields; a.e = e; a.w = w; a.vtm = vis_t_minus; a.vis_used = vis_t_out;
   a.inv_re = 1.0f / Re; a.vis_t0 = vis_t0; a.alpha_evm = alpha_evm;
-  a.nu_dev = plan->nu_dev; a.lap = plan->lap;
+  a.nu_dev = plan->nu_dev; a.lap = plan->lap; a.cap_dev = plan->cap_dev;
   a.stagger = stagger && plan->ntiles > 4 * plan->role[ROLE_FWD].grid ? plan->stagger : 0;
   return a;
 }
@@ -610,13 +612,27 @@ int pinn_plan_set_viscosity(pinn_plan_t plan, const float* nu_dev, float* lap) {
   if (!nu_dev && lap) return fail(-22, "pinn_plan_set_viscosity: lap comes with nu_dev%s");
   if (reinterpret_cast<uintptr_t>(nu_dev) % 4 != 0) return fail(-22, "pinn_plan_set_viscosity: nu_dev must be 4-byte aligned%s");
   if (reinterpret_cast<uintptr_t>(lap) % 16 != 0) return fail(-22, "pinn_plan_set_viscosity: lap must be 16-byte aligned%s");
-  plan->nu_dev = nu_dev; plan->lap = lap;
+  plan->nu_dev = nu_dev; plan->lap = lap; plan->cap_dev = nullptr;
   return 0;
 }
 int pinn_plan_viscosity(pinn_plan_t plan, const float** nu_dev, float** lap) {
   if (!plan || !nu_dev || !lap) return fail(-22, "pinn_plan_viscosity: null argument%s");
   if (plan->streams != 4) return fail(-22, "pinn_plan_viscosity: plan is not a residual (4-stream) plan%s");
   *nu_dev = plan->nu_dev; *lap = plan->lap;
+  return 0;
+}
+int pinn_plan_set_viscosity_cap(pinn_plan_t plan, const float* cap_dev) {
+  if (!plan) return fail(-22, "pinn_plan_set_viscosity_cap: null plan%s");
+  if (plan->streams != 4) return fail(-22, "pinn_plan_set_viscosity_cap: plan is not a residual (4-stream) plan%s");
+  if (cap_dev && !plan->nu_dev) return fail(-22, "pinn_plan_set_viscosity_cap: cap_dev comes with nu_dev (pinn_plan_set_viscosity first)%s");
+  if (reinterpret_cast<uintptr_t>(cap_dev) % 4 != 0) return fail(-22, "pinn_plan_set_viscosity_cap: cap_dev must be 4-byte aligned%s");
+  plan->cap_dev = cap_dev;
+  return 0;
+}
+int pinn_plan_viscosity_cap(pinn_plan_t plan, const float** cap_dev) {
+  if (!plan || !cap_dev) return fail(-22, "pinn_plan_viscosity_cap: null argument%s");
+  if (plan->streams != 4) return fail(-22, "pinn_plan_viscosity_cap: plan is not a residual (4-stream) plan%s");
+  *cap_dev = plan->cap_dev;
   return 0;
 }
 int pinn_plan_hard_bc(pinn_plan_t plan, pinn_hard_bc_t* out) {
@@ -1288,6 +1304,45 @@ int pinn_visc_update(const float* sum, double coef, double lr, double beta1, dou
   a.theta_min = theta_min; a.theta_max = theta_max; a.state = state; a.nu_dev = nu_dev;
   int rc = launch_visc_update(a, (hipStream_t)stream);
   return rc ? hipfail(rc, "pinn_visc_update") : 0;
+}
+
+// ---- Reynolds-number continuation (visc_sched.hip) ----
+static int check_visc_schedule(const char* what, const pinn_visc_schedule_t* s) {
+  if (!s) return fail(-22, "%s: null schedule", what);
+  if (s->shape < PINN_RAMP_GEOMETRIC || s->shape > PINN_RAMP_LINEAR_NU) return fail(-22, "%s: unknown shape %ld", what, (long)s->shape);
+  if (s->updates <= 0) return fail(-22, "%s: updates must be > 0 (got %ld)", what, (long)s->updates);
+  if (s->hold < 0) return fail(-22, "%s: hold must be >= 0 (got %ld)", what, (long)s->hold);
+  if (s->stairs < 0) return fail(-22, "%s: stairs must be >= 0 (got %ld)", what, (long)s->stairs);
+  if (!std::isfinite(s->re_start) || !(s->re_start > 0.0)) return fail(-22, "%s: re_start must be finite and > 0", what);
+  if (!std::isfinite(s->re_end) || !(s->re_end > 0.0)) return fail(-22, "%s: re_end must be finite and > 0", what);
+  if (!std::isfinite(s->nu_start) || !(s->nu_start > 0.f) || !std::isfinite(s->nu_end) || !(s->nu_end > 0.f))
+    return fail(-22, "%s: nu_start and nu_end must be finite and > 0", what);
+  if (!std::isfinite(s->cap_factor) || s->cap_factor < 0.0) return fail(-22, "%s: cap_factor must be finite and >= 0", what);
+  if (s->cap_factor > 0.0 && (!std::isfinite(s->cap_start) || !(s->cap_start > 0.f) || !std::isfinite(s->cap_end) || !(s->cap_end > 0.f)))
+    return fail(-22, "%s: cap_start and cap_end must be finite and > 0 with a cap_factor", what);
+  return 0;
+}
+
+double pinn_visc_schedule_value(const pinn_visc_schedule_t* schedule, int64_t t, double* record6) {
+  static_assert(PINN_RAMP_RECORD == 6, "continuation record size mismatch");
+  if (check_visc_schedule("pinn_visc_schedule_value", schedule)) return NAN;
+  if (t < 0) { fail(-22, "pinn_visc_schedule_value: t must be >= 0%s"); return NAN; }
+  const ViscRampValue r = visc_schedule_value(*schedule, (long long)t);
+  if (record6) visc_schedule_record(r, (long long)t, record6);
+  return (double)r.nu;
+}
+
+int pinn_visc_schedule_step(const pinn_visc_schedule_t* schedule, int64_t* pos, float* nu_dev, float* cap_dev,
+                            double* record, void* stream) {
+  if (int rc = check_visc_schedule("pinn_visc_schedule_step", schedule)) return rc;
+  if (!pos || !nu_dev || !record) return fail(-22, "pinn_visc_schedule_step: null argument%s");
+  if (misaligned(pos, 8) || misaligned(record, 8) || misaligned(nu_dev, 4) || misaligned(cap_dev, 4))
+    return fail(-22, "pinn_visc_schedule_step: pos and record must be 8-byte aligned, nu_dev and cap_dev 4-byte%s");
+  if (cap_dev && !(schedule->cap_factor > 0.0)) return fail(-22, "pinn_visc_schedule_step: cap_dev needs a cap_factor > 0%s");
+  ViscSchedArgs a;
+  a.sched = *schedule; a.pos = reinterpret_cast<long long*>(pos); a.nu_dev = nu_dev; a.cap_dev = cap_dev; a.record = record;
+  int rc = launch_visc_sched(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_visc_schedule_step") : 0;
 }
 
 // ---- convergence monitor (monitor.hip) ----

@@ -86,6 +86,7 @@ struct FwdArgs {
       // Viscosity identification (residual mode, every family; point_stage.h, visc.hip), behind ptime in the same bytes:
       const float* nu_dev;   // one fp32 in device memory read in place of inv_re (the trainable 1 / Re), or null
       float* lap;            // [2][npad] planes Lap u, Lap v (physical, of the constrained fields on a constrained plan), or null
+      const float* cap_dev;  // Reynolds-number continuation: one fp32 read in place of vis_t0 (only beside nu_dev), or null
     };
   };
   float* partials;       // [grid][PINN_NLOSS]
@@ -96,6 +97,20 @@ struct FwdArgs {
   int ff;                // != 0: the net's first layer is the frozen sine layer (spill_io.h layer0_sine); the 8-wave families
                          // launch their FF instantiation, which saves layer 0's a-streams.  Never with hbc.kind or ptime.
 };
+
+#ifdef __HIPCC__
+// Reynolds-number continuation (visc_sched.hip): resolve_viscosity of a forward argument block also takes the cap of
+// the entropy viscosity, vis_t0, from device memory where the plan carries one (cap_dev, only ever beside nu_dev).
+// Being an overload it runs at the place the call already has in every forward kernel and in the fused one: one more
+// scalar load per workgroup.  The reverse sweeps read the stored vis_used plane and need nothing.
+__device__ __forceinline__ void resolve_viscosity(FwdArgs& a) {
+  typedef const __attribute__((address_space(4))) float cfloat;
+  if (a.nu_dev) {
+    a.inv_re = *(cfloat*)(unsigned long long)a.nu_dev;
+    if (a.cap_dev) a.vis_t0 = *(cfloat*)(unsigned long long)a.cap_dev;
+  }
+}
+#endif
 
 struct BwdArgs {
   const float* x; const float* y;

@@ -209,6 +209,21 @@ class IdentifyViscosityConfig:
     re_max: float = 1e6
 
 
+RE_CONTINUATION_SHAPES = ("geometric", "linear_re", "linear_nu")
+
+
+@dataclass
+class ReContinuationConfig:
+    """Continuation in the Reynolds number (solver.set_reynolds_continuation); the key's absence
+    means off.  The viscosity is ramped from 1 / re_start to 1 / physics.Re over `updates` Adam updates after `hold`
+    updates at the start; shape: geometric | linear_re | linear_nu; stairs = K > 0: in K equal stairs."""
+    re_start: float = 0.0
+    updates: int = 0
+    hold: int = 0
+    shape: str = "geometric"
+    stairs: int = 0
+
+
 @dataclass
 class CheckpointConfig:
     """Training-state snapshots that resume bit for bit (solver.set_checkpointing), off by default: path of the file
@@ -251,6 +266,7 @@ class TrainingConfig:
     checkpoint: CheckpointConfig = field(default_factory=CheckpointConfig)
     early_stop: Optional[EarlyStopConfig] = None
     identify_viscosity: Optional[IdentifyViscosityConfig] = None
+    re_continuation: Optional[ReContinuationConfig] = None
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -305,6 +321,17 @@ def _fill(obj, data):
                     if k in ("re0", "lr", "re_min", "re_max"):
                         setattr(iv, k, None if v is None and k == "re0" else float(v))
                 setattr(obj, key, iv)
+        elif key == "re_continuation":           # absent, null or false: off
+            if val is not None and val is not False:
+                rc = ReContinuationConfig()
+                for k, v in (val.items() if isinstance(val, dict) else ()):
+                    if k == "re_start":
+                        rc.re_start = float(v)
+                    elif k == "shape":
+                        rc.shape = str(v)
+                    elif k in ("updates", "hold", "stairs"):
+                        setattr(rc, k, int(v))
+                setattr(obj, key, rc)
         elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
             if val is not None and val is not False:
                 cur.enabled = True
@@ -395,6 +422,15 @@ class ConfigManager:
             if es is not None or pt.enabled or c.training.conflict_free_gradients.enabled:
                 problems.append("training.identify_viscosity does not go together with training.early_stop, "
                                 "training.pseudo_time or training.conflict_free_gradients")
+        rc = c.training.re_continuation
+        if rc is not None:
+            if not (0.0 < rc.re_start < float("inf") and rc.updates >= 1 and rc.hold >= 0 and rc.stairs >= 0
+                    and rc.shape in RE_CONTINUATION_SHAPES):
+                problems.append("training.re_continuation: finite re_start > 0, updates >= 1, hold >= 0, stairs >= 0 and "
+                                "shape one of %s required" % " | ".join(RE_CONTINUATION_SHAPES))
+            if es is not None or iv is not None:
+                problems.append("training.re_continuation does not go together with training.early_stop or "
+                                "training.identify_viscosity")
         ck = c.training.checkpoint
         if ck.every < 0 or (ck.every > 0 and not ck.path):
             problems.append("training.checkpoint: every >= 0, and a path when every > 0, required")
@@ -475,6 +511,10 @@ class ConfigManager:
         if t.identify_viscosity is not None:
             iv = t.identify_viscosity
             print("identify Re: re0=%s lr=%g bounds=[%g, %g]" % (iv.re0, iv.lr, iv.re_min, iv.re_max))
+        if t.re_continuation is not None:
+            rc = t.re_continuation
+            print("Re ramp    : re_start=%g updates=%d hold=%d shape=%s stairs=%d"
+                  % (rc.re_start, rc.updates, rc.hold, rc.shape, rc.stairs))
         if t.checkpoint.enabled:
             print("checkpoint : path=%s every=%d" % (t.checkpoint.path, t.checkpoint.every))
         for st in t.training_stages:

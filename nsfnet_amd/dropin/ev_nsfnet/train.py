@@ -179,6 +179,9 @@ def main():
         iv = cfg.training.identify_viscosity
         if iv is not None:    # the Reynolds number becomes a trainable scalar, pinned down by the supervised data
             PINN.set_viscosity_identification(re0=iv.re0, lr=iv.lr, re_bounds=(iv.re_min, iv.re_max))
+        rc = cfg.training.re_continuation
+        if rc is not None:    # the viscosity is ramped down to 1 / physics.Re while the stages train
+            PINN.set_reynolds_continuation(rc.re_start, rc.updates, hold=rc.hold, shape=rc.shape, stairs=rc.stairs)
         ck = cfg.training.checkpoint
         if ck.enabled:
             PINN.set_checkpointing(ck.path, ck.every)

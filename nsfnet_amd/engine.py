@@ -379,6 +379,13 @@ class ResidualPlan(PointPlan):
         if nu is not None and with_lap:
             self.lap = torch.zeros(2, self.npad, dtype=torch.float32, device=self.net.device)
         _lib.check(self.lib.pinn_plan_set_viscosity(self.handle, _ptr(nu), _ptr(self.lap)), "pinn_plan_set_viscosity")
+        self.cap = None
+
+    def set_viscosity_cap(self, cap):
+        """Reynolds-number continuation: the plan's forward launches read the fp32 device scalar `cap` in place of
+        vis_t0.  Only on a plan that carries nu (set_viscosity first, which drops the cap).  None: off."""
+        _lib.check(self.lib.pinn_plan_set_viscosity_cap(self.handle, _ptr(cap)), "pinn_plan_set_viscosity_cap")
+        self.cap = cap
 
     def pseudo_time(self):
         """(sigma, sigma_p) the plan carries."""
@@ -762,6 +769,28 @@ def visc_update(sum_in, coef, lr, betas, eps, theta_bounds, state, nu):
     _lib.check(_lib.load().pinn_visc_update(_ptr(sum_in), float(coef), float(lr), float(betas[0]), float(betas[1]),
                                             float(eps), float(theta_bounds[0]), float(theta_bounds[1]), _ptr(state),
                                             _ptr(nu), _stream()), "pinn_visc_update")
+
+
+RAMP_RECORD = 6          # PINN_RAMP_RECORD
+RAMP_RECORD_NAMES = ("t", "s", "Re_t", "nu_t", "cap_t", "done")
+RAMP_SHAPES = dict(geometric=0, linear_re=1, linear_nu=2)       # PINN_RAMP_*
+
+
+def visc_schedule_value(cstruct, t):
+    """pinn_visc_schedule_value: the record [t, s, Re_t, nu_t, cap_t, done] of position t on the host, by the same
+    function the step launch runs (nu_t and cap_t are the fp32 values as doubles)."""
+    rec = (ctypes.c_double * RAMP_RECORD)()
+    nu = _lib.load().pinn_visc_schedule_value(ctypes.byref(cstruct), int(t), rec)
+    if nu != nu:
+        _lib.check(-22, "pinn_visc_schedule_value")
+    return list(rec)
+
+
+def visc_schedule_step(cstruct, pos, nu, cap, rec):
+    """pinn_visc_schedule_step: the position pos [1] int64 moves on by one update; the fp32 nu, the fp32 cap (or None)
+    and the record are rewritten in place for it.  One launch."""
+    _lib.check(_lib.load().pinn_visc_schedule_step(ctypes.byref(cstruct), _ptr(pos), _ptr(nu), _ptr(cap), _ptr(rec),
+                                                   _stream()), "pinn_visc_schedule_step")
 
 
 OPTIM_RECORD = 6         # PINN_OPTIM_RECORD
@@ -1171,10 +1200,58 @@ class _Viscosity(_Option):
         self.state.copy_(torch.tensor([math.log(float(nu)), 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float64))
 
 
+class _Continuation(_Option):
+    """Reynolds-number continuation (PinnEngine.set_reynolds_continuation): the ramp's constants with their C struct
+    and the device tensors pos [1] int64 (Adam updates made), nu [1] fp32 and, ev flavour with follow_vis_t0, cap [1]
+    fp32 - what every residual plan reads in place of 1 / Re and vis_t0 - and rec [RAMP_RECORD] fp64 (the last step)."""
+    resident = mse = "Reynolds-number continuation needs"
+    stored = ("recont", "pos", "nu", "cap", "rec")
+
+    def __init__(self, engine, re_start, updates, hold, shape, stairs, follow):
+        self.re_start, self.updates, self.hold, self.shape, self.stairs = re_start, updates, hold, shape, stairs
+        self.follow = follow
+        with_cap = follow and engine.net_e is not None
+        f32 = np.float32
+        factor = engine.vis_t0_factor       # (a vis_t0 assigned since: the factor it amounts to)
+        if engine.vis_t0 != factor / engine.Re:
+            factor = engine.vis_t0 * engine.Re
+        # the ends as the launches form them from their constants: 1.0f / (float)Re, (float)vis_t0
+        self.cstruct = _lib.ViscScheduleStruct(
+            shape=RAMP_SHAPES[shape], stairs=stairs, hold=hold, updates=updates, re_start=re_start, re_end=engine.Re,
+            cap_factor=factor if with_cap else 0.0,
+            nu_start=f32(1.0) / f32(re_start), nu_end=f32(1.0) / f32(engine.Re),
+            cap_start=f32(factor / re_start) if with_cap else 0.0,
+            cap_end=f32(engine.vis_t0) if with_cap else 0.0)
+        dev = engine.device
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.nu = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.cap = torch.zeros(1, dtype=torch.float32, device=dev) if with_cap else None
+        self.rec = torch.zeros(RAMP_RECORD, dtype=torch.float64, device=dev)
+
+    def graph_key(self):
+        return (("recont", self.re_start, self.updates, self.hold, self.shape, self.stairs, self.follow),)
+
+    def header(self):
+        rec = [self.re_start, self.updates, self.hold, self.shape, self.stairs, self.follow]
+        return dict(re_continuation=True), dict(re_continuation=rec), {}
+
+    def place(self, t):
+        """The state of position t (in place: captured steps stay valid), by the formula the step launch runs,
+        evaluated on the host: inside a geometric ramp the host's exp / log may leave nu and the cap one fp32 ulp from
+        what stepping to t leaves; the linear shapes and the ends are the same bits."""
+        rec = visc_schedule_value(self.cstruct, t)
+        self.pos.fill_(int(t))
+        self.nu.fill_(rec[3])           # (the fp32 value as a double: exact)
+        if self.cap is not None:
+            self.cap.fill_(rec[4])
+        self.rec.copy_(torch.tensor(rec, dtype=torch.float64))
+
+
 # The engine attribute of every option (None while it is off) and its class, in the one order every loop over the
 # options runs in: that of the options' segments in a training-state file and of their entries in the graph key.
 _OPTIONS = (("_opt", _Optim), ("_bal", _Balance), ("_cfg", _ConflictFree), ("_batch", _Batching), ("_rba", _Attention),
-            ("_val", _Validation), ("_pt", _PseudoTime), ("_mon", _Monitor), ("_visc", _Viscosity))
+            ("_val", _Validation), ("_pt", _PseudoTime), ("_mon", _Monitor), ("_visc", _Viscosity),
+            ("_rc", _Continuation))
 
 
 def _refuse_chunked(option, chunked):
@@ -1213,6 +1290,7 @@ class PinnEngine:
         self.alpha_evm = float(alpha_evm)
         self.scale = float(coord_scale)
         self.vis_t0 = vis_t0_factor / self.Re
+        self.vis_t0_factor = float(vis_t0_factor)
         self.net = net if net is not None else DeviceNet(3, n_hidden, hidden, self.device, precision)
         if flavour == "ev":
             self.net_e = net_e if net_e is not None else DeviceNet(1, n_hidden_e, hidden_e, self.device, precision)
@@ -1248,6 +1326,7 @@ class PinnEngine:
         self._mon = None                    # convergence monitor (set_convergence_monitor; None = off)
         self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
         self._visc = None                   # viscosity identification (set_viscosity_identification; None = off)
+        self._rc = None                     # Reynolds-number continuation (set_reynolds_continuation; None = off)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -1318,6 +1397,8 @@ class PinnEngine:
         self.n_f_global = int(n_global if n_global is not None else self.plan_f.n)
         if self._visc is not None:
             self._attach_viscosity(self.plan_f)
+        if self._rc is not None:
+            self._attach_continuation(self.plan_f)
         if self.net_e is not None:
             self.plan_e = ValuePlan(self.net_e, x, y)
             self.init_vis_t()
@@ -1474,6 +1555,8 @@ class PinnEngine:
         bt.f = ResidualPlan(self.net, z(), z(), None if self.plan_f.w is None else z())
         if self._visc is not None:
             self._attach_viscosity(bt.f)
+        if self._rc is not None:
+            self._attach_continuation(bt.f)
         bt.e = None
         if self.net_e is not None:
             bt.f.vis_t_minus = torch.zeros(bt.B, dtype=torch.float32, device=self.device)
@@ -1566,6 +1649,8 @@ class PinnEngine:
         pool = ResidualPlan(self.net, x, y, with_backward=False)
         if self._visc is not None:
             self._attach_viscosity(pool, with_lap=False)
+        if self._rc is not None:
+            self._attach_continuation(pool)
         w = None
         if weights is not None:
             w = torch.as_tensor(np.asarray(weights, dtype=np.float32).reshape(-1)).to(self.device).contiguous()
@@ -1958,6 +2043,9 @@ class PinnEngine:
         if vs is not None and vs.fresh:     # the scalar's own Adam, from the exchanged slot of the evaluation just used
             visc_update(self.sums[S_EQ + VISC_SLOT:], -2.0 * self.alpha_e / vs.n_eq, vs.lr, vs.betas, vs.eps,
                         vs.theta_bounds, vs.state, vs.nu)
+        rc = self._rc
+        if rc is not None:      # the ramp moves on by one update: nu (and the cap) of the NEXT evaluation
+            visc_schedule_step(rc.cstruct, rc.pos, rc.nu, rc.cap, rc.rec)
         if self._bal is not None:
             self._bal.n += 1
         self._updated(validate)
@@ -2528,6 +2616,9 @@ class PinnEngine:
         if every > 0 and self._visc is not None:
             raise ValueError("the convergence monitor is not available with viscosity identification "
                              "(set_viscosity_identification): its Re_eff is built on the configured Re")
+        if every > 0 and self._rc is not None:
+            raise ValueError("the convergence monitor is not available with Reynolds-number continuation "
+                             "(set_reynolds_continuation): its Re_eff and plateau rule assume a fixed problem")
         self._graphs.clear()        # captured steps hold the other monitor's buffers and constants
         if every == 0:
             self._mon = None
@@ -2660,6 +2751,9 @@ class PinnEngine:
                 for plan, _ in self._visc_plans():
                     plan.set_viscosity(None)
             return
+        if self._rc is not None:
+            raise ValueError("viscosity identification is not available with Reynolds-number continuation "
+                             "(set_reynolds_continuation): both own nu - switch it off first")
         re0 = self.Re if re0 is None else float(re0)
         lr, eps, betas = float(lr), float(eps), (float(betas[0]), float(betas[1]))
         re_bounds = (float(re_bounds[0]), float(re_bounds[1]))
@@ -2713,6 +2807,96 @@ class PinnEngine:
         nu = both[VISC_STATE]
         out.update(nu=nu, Re=1.0 / nu if nu > 0.0 else float("inf"), updates=int(out["updates"]), skipped=int(out["skipped"]),
                    re0=vs.re0, lr=vs.lr, betas=vs.betas, eps=vs.eps, re_bounds=vs.re_bounds)
+        return out
+
+    # ---- continuation in the Reynolds number ----
+    def set_reynolds_continuation(self, re_start, updates, hold=0, shape="geometric", stairs=0, follow_vis_t0=True,
+                                  enabled=True):
+        """Ramp the molecular viscosity nu = 1 / Re from 1 / re_start to that of the engine's configured Re while
+        training, so that a steady high-Re solve follows the solution branch from a viscous, easy problem instead of
+        searching for it.  nu lives in device memory as one fp32 that every residual launch of the engine's plans reads
+        in place of 1 / Re - the collocation plan, the batch plan, the resampling pool - and, ev flavour with
+        follow_vis_t0, so does the cap vis_t0 = vis_t0_factor / Re of the artificial viscosity: the ramp then is a
+        continuation of one problem.  A position counter in device memory counts Adam updates; adam_step runs, after
+        the nets' updates, one one-workgroup launch that moves it on and rewrites nu, the cap and a record for
+        continuation_info().  The launch is part of the captured step: one hipGraph serves the whole ramp.
+
+        With t updates made, s = clamp((t - hold) / updates, 0, 1); stairs = K > 0 lowers s to floor(s K) / K (s = 1
+        stays).  shape 'geometric' (ln nu linear in s; the default: Re spans a decade), 'linear_re' (Re linear in s) or
+        'linear_nu'; fp64, rounded once to fp32.  At s = 0 and s = 1 the launch writes the fp32 values the residual
+        launches would form from Re = re_start and from the configured Re (and vis_t0) as constants: a finished ramp
+        computes what a plain engine at Re computes, bit for bit.
+
+        nu is held during lbfgs_step and by evaluations alone (loss_and_grad without adam_step); the position is not
+        an optimiser's state and survives reset_adam.  Refused with ValueError, each way round: viscosity
+        identification (both own nu), the convergence monitor (its Re_eff and plateau rule assume a fixed problem),
+        chunked collocation passes and the loss mode 'L2'.  enabled False: off - the plans carry no pointer and the
+        step launches what it launches without the feature.  A call restarts the ramp at position 0.
+
+        The ends are fixed by the call: the engine's Re and vis_t0 as they stand then (cap = vis_t0 Re / Re_t, which is
+        vis_t0_factor unless vis_t0 was assigned since construction).  While the ramp is on the residual launches read
+        the scalars, so an engine.Re or engine.vis_t0 assigned afterwards does not reach them: call again."""
+        self._graphs.clear()        # captured steps hold the other mode's launches and pointers
+        if not enabled:
+            if self._rc is not None:
+                self._rc = None
+                for plan, _ in self._visc_plans():
+                    plan.set_viscosity(None)
+            return
+        re_start = float(re_start)
+        if not (math.isfinite(re_start) and re_start > 0.0):
+            raise ValueError("Reynolds-number continuation: re_start must be finite and > 0 (got %r)" % (re_start,))
+        if int(updates) != updates or int(hold) != hold or int(stairs) != stairs:
+            raise ValueError("Reynolds-number continuation: updates, hold and stairs must be integers (got %r, %r, %r)"
+                             % (updates, hold, stairs))
+        updates, hold, stairs = int(updates), int(hold), int(stairs)
+        if updates <= 0 or hold < 0 or stairs < 0:
+            raise ValueError("Reynolds-number continuation: updates must be > 0, hold and stairs >= 0 (got updates=%d "
+                             "hold=%d stairs=%d)" % (updates, hold, stairs))
+        if shape not in RAMP_SHAPES:
+            raise ValueError("Reynolds-number continuation: shape must be one of %s (got %r)" % (sorted(RAMP_SHAPES), shape))
+        for state, what in ((self._visc, "viscosity identification (set_viscosity_identification): both own nu"),
+                            (self._mon, "the convergence monitor (set_convergence_monitor), whose Re_eff and plateau "
+                                        "rule assume a fixed problem")):
+            if state is not None:
+                raise ValueError("Reynolds-number continuation is not available with %s - switch it off first" % what)
+        _refuse_chunked(_Continuation, isinstance(self.plan_f, ChunkedResidual))
+        rc = _Continuation(self, re_start, updates, hold, shape, stairs, bool(follow_vis_t0))
+        rc.place(0)
+        self._rc = rc
+        for plan, _ in self._visc_plans():
+            self._attach_continuation(plan)
+
+    def _attach_continuation(self, plan):
+        """The scalars onto a residual plan: no Laplacian planes (nothing differentiates by nu)."""
+        plan.set_viscosity(self._rc.nu, with_lap=False)
+        if self._rc.cap is not None:
+            plan.set_viscosity_cap(self._rc.cap)
+
+    def _rc_on(self):
+        if self._rc is None:
+            raise RuntimeError("Reynolds-number continuation is off: call set_reynolds_continuation() first")
+        return self._rc
+
+    def reset_reynolds_continuation(self, t=0):
+        """Put the ramp at position t (Adam updates made): nu, the cap and the record become those of t, in place -
+        captured steps stay valid.  The values come from the host's evaluation of the schedule: for 'geometric' a placed
+        position inside the ramp may differ from a stepped one in the last bit of the fp32 (the next step rewrites them
+        from the position alone)."""
+        if int(t) != t or int(t) < 0:
+            raise ValueError("Reynolds-number continuation: the position must be an integer >= 0 (got %r)" % (t,))
+        self._rc_on().place(int(t))
+
+    def continuation_info(self):
+        """dict(t, s, Re_t, nu_t, cap_t (None without a cap), done, and the settings re_start, re_end, updates, hold,
+        shape, stairs, follow_vis_t0) of the ramp - one host read; None when the feature is off."""
+        rc = self._rc
+        if rc is None:
+            return None
+        out = dict(zip(RAMP_RECORD_NAMES, rc.rec.cpu().tolist()))
+        out.update(t=int(out["t"]), done=bool(out["done"]), cap_t=out["cap_t"] if rc.cap is not None else None,
+                   re_start=rc.re_start, re_end=self.Re, updates=rc.updates, hold=rc.hold, shape=rc.shape,
+                   stairs=rc.stairs, follow_vis_t0=rc.follow)
         return out
 
     # ---- L-BFGS (DESIGN.md section 7.2) ----

@@ -422,6 +422,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             print('  ' + self.early_stop_log())
         if self._identify:
             print('  ' + self.viscosity_log())
+        if self._recont:
+            print('  ' + self.continuation_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]

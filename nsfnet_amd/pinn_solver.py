@@ -359,6 +359,27 @@ class SolverBase:
         return "Re_est=%.4f (nu=%.6e, d loss / d nu=%.3e, updates=%d, skipped=%d)" % (
             i["Re"], i["nu"], i["grad"], i["updates"], i["skipped"])
 
+    # ---- continuation in the Reynolds number ----
+    _recont = False             # set_reynolds_continuation: print_log adds Re_t
+
+    def set_reynolds_continuation(self, re_start, updates, hold=0, shape="geometric", stairs=0, follow_vis_t0=True,
+                                  enabled=True):
+        """Ramp the viscosity from 1 / re_start down (or up) to that of this solver's Re over `updates` Adam updates,
+        after `hold` updates at the start (PinnEngine.set_reynolds_continuation): the net follows the solution branch
+        from a viscous, easy flow.  The position counts Adam updates on the device; it is not reset at a stage start
+        and survives a re-created Adam, as the lr schedule position does.  Held during solve_LBFGS.  print_log adds
+        Re_t; the training-state file carries the ramp, a finished ramp needs nothing.  enabled False: off."""
+        self.engine.set_reynolds_continuation(re_start, updates, hold=hold, shape=shape, stairs=stairs,
+                                              follow_vis_t0=follow_vis_t0, enabled=enabled)
+        self._recont = self.engine.continuation_info() is not None
+
+    def continuation_log(self):
+        """One line on the ramp (one host read)."""
+        i = self.engine.continuation_info()
+        return "Re_t=%.4f (nu=%.6e%s, s=%.4f, updates=%d%s)" % (
+            i["Re_t"], i["nu_t"], "" if i["cap_t"] is None else ", vis_t0=%.6e" % i["cap_t"], i["s"], i["t"],
+            ", done" if i["done"] else "")
+
     def save_viscosity(self, path):
         """Write the sidecar of the checkpoint at `path`: dict(re0, lr, betas, eps, re_bounds, state, nu) as path +
         '_visc' (torch.save).  With the identification off nothing is written."""
@@ -770,7 +791,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("\n" + self._optimizer_log(),) if self.engine._opt is not None else ()),
               *(("\n" + self.validation_log(),) if self._validation else ()),
               *(("\n" + self.early_stop_log(),) if self._early_stop else ()),
-              *(("\n" + self.viscosity_log(),) if self._identify else ()))
+              *(("\n" + self.viscosity_log(),) if self._identify else ()),
+              *(("\n" + self.continuation_log(),) if self._recont else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

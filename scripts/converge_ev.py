@@ -34,6 +34,10 @@ pseudo-time anchors, a resampled collocation set.  The call must be given the sa
                                                   Adam rate on ln nu; every stage writes net.pth_visc (settings, state, nu) and
                                                   the estimate into stages.jsonl, a --resume slice continues from the sidecar
                                                   with its settings; off by default)
+        [--re-continuation 400 500000]            (continuation in the Reynolds number: the viscosity is ramped geometrically
+                                                  from 1 / 400 to 1 / --re over that many Adam updates, counted across the
+                                                  stages; the position travels in --state: with --resume and no --state it
+                                                  is refused; off by default)
         [--state FILE --state-every 50000 --max-steps 400000]   (training-state snapshots: continue from FILE when it
                                                   exists, write it every that many updates, end the call after that many
                                                   updates, anywhere in a stage)
@@ -114,6 +118,9 @@ def main():
     ap.add_argument("--identify-re", type=float, nargs="+", default=None, metavar=("RE0", "LR"),
                     help="learn the Reynolds number from the data (DESIGN.md 7.15): start at RE0, Adam rate LR on ln nu "
                          "(default 1e-2); not with --early-stop, --re-eff-tol, --pseudo-time or --confgrad")
+    ap.add_argument("--re-continuation", type=float, nargs=2, default=None, metavar=("RE_START", "UPDATES"),
+                    help="ramp the viscosity from 1 / RE_START to 1 / --re over UPDATES Adam updates (DESIGN.md 7.16); not "
+                         "with --identify-re, --early-stop or --re-eff-tol")
     ap.add_argument("--state", default=None, metavar="FILE",
                     help="training-state file (DESIGN.md 7.12): continue from it when it exists, and write it")
     ap.add_argument("--state-every", type=int, default=0, help="updates between two non-blocking snapshots (0: only where the call ends)")
@@ -183,6 +190,11 @@ def main():
         P.set_viscosity_identification(re0=a.identify_re[0], lr=a.identify_re[1] if len(a.identify_re) > 1 else 1e-2)
         if res is not None:                             # carry the estimate and its optimiser state across slices
             P._load_viscosity(os.path.join(res, "net.pth"))
+    if a.re_continuation is not None:                   # the position counts on across the stages
+        if res is not None and state is None:
+            ap.error("--re-continuation with --resume needs --state: the ramp's position travels in the training-state "
+                     "file only, and a resumed slice without it would restart the trained net at RE_START")
+        P.set_reynolds_continuation(a.re_continuation[0], int(a.re_continuation[1]))
     P.save = lambda *args, **kw: None                   # no per-10 000-step checkpoints: one per stage below
     star = loader.loading_evaluate_data(dns)
     first, start, left = a.first, 0, a.max_steps if a.max_steps > 0 else None
@@ -265,6 +277,9 @@ def main():
         if a.identify_re is not None:
             info = P.engine.viscosity_info()
             rec.update(viscosity={k_: info[k_] for k_ in ("Re", "nu", "grad", "updates", "skipped")})
+        if a.re_continuation is not None:
+            info = P.engine.continuation_info()
+            rec.update(re_continuation={k_: info[k_] for k_ in ("t", "s", "Re_t", "nu_t", "cap_t", "done")})
         with open("stages.jsonl", "a") as fh:
             fh.write(json.dumps(rec) + "\n")
         print("STAGE", json.dumps(rec), flush=True)
