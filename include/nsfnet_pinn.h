@@ -535,6 +535,54 @@ int pinn_val_stats(int64_t n, const float* const* pred3, const float* const* tgt
 int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1, float* dst1, int64_t n1,
                   const double* state, void* stream);
 
+/* ---- flow diagnostics: stream function, vorticity and vortices on the device -----------
+ * Which steady solution a net is converging to, as device state: the cavity benchmark quantities of the field planes
+ * a residual forward (pinn_residual_forward) left on a tensor grid of nx x ny nodes.  Node (i, j) is point j nx + i (x
+ * fastest); xs [nx], ys [ny] are fp64 device arrays, strictly increasing (the plan's fp32 coordinates widened); the grid
+ * need not be uniform.  fields: [PINN_FLD_COUNT][npad] floats, 16-byte aligned, npad a multiple of 4 and >= nx ny
+ * (nothing past point nx ny reaches a result).  Everything is fp64 from the fp32 planes, one rounding per operation
+ * written, no contraction, no float atomics; the three sums have a fixed order (block partials of a grid-stride loop of
+ * min(ceil(n / 1024), 512) workgroups of 256 threads x 4 points, folded by the last workgroup: thread t takes partials
+ * t, t + 256, ... in order, then a pairwise tree); an extremum does not depend on the order: on a tie the lowest
+ * point wins.  3 <= nx, ny and nx ny <= 2^30, what a plan accepts.
+ *
+ * pinn_flow_stream_function (one launch, one thread per column, sequential in j: the trapezoid rule):
+ *   psi(i, 0) = 0,  psi(i, j) = psi(i, j - 1) + (0.5 (u(i, j) + u(i, j - 1))) (ys[j] - ys[j - 1])
+ * psi: nx ny doubles, 16-byte aligned.
+ *
+ * pinn_flow_stats (two launches) reads the planes and psi.  With w = v_x - u_y, div = u_x + v_y per node, the midlines
+ * xm = (xs[0] + xs[nx - 1]) 0.5, ym likewise, and the quadrants BL (x < xm, y < ym), BR (x >= xm, y < ym), TL (x < xm,
+ * y >= ym), TR, from which the lid row j = ny - 1 is left out, it writes one row of PINN_FLOW_RECORD doubles:
+ *   [0] t  [1] x_c  [2] y_c  [3] psi_min  [4] w at that node          the primary vortex: argmin psi over all nodes
+ *   [5 + 4q .. 8 + 4q] x, y, psi_max, area  for q = BL, BR, TL, TR     argmax psi of the quadrant; area = the quadrant's
+ *                                                                     nodes with psi > eps |psi_min|, divided by nx ny
+ *   [21] counter_area = ((area_BL + area_BR) + area_TL) + area_TR     [22] mass_defect = max |psi| on the lid row
+ *   [23] ke = sum (u u + v v) / (nx ny)   [24] enstrophy = sum w w / (nx ny)   [25] div_rms = sqrt(sum div div / (nx ny))
+ *   [26] div_max = max |div|   [27] nonfinite = the nodes where psi, w or div is not finite   [28..31] +0
+ * A centre (x, y) is the node's, refined per axis by the parabola through its two neighbours on that axis:
+ *   d = 0.5 (a - c) / ((a - 2 b) + c) clipped to +-0.5 (0 when the denominator is 0 or the node lies on the grid's edge of
+ *   that axis);  x = xs[i] + |d| (xs[i2] - xs[i]),  i2 = i + 1 for d > 0, else i - 1, kept inside the grid.
+ * nonfinite > 0: entries [1..26] are quiet NaNs - a poisoned field shows no vortex.  A quadrant without a node below the
+ * lid row (possible on a coarse non-uniform grid) has NaN for x, y, psi_max and area 0.
+ * state: PINN_FLOW_STATE doubles of device memory, zero at the start:
+ *   [0] n_records  [1] cadence records so far  [2] records with nonfinite > 0  [3..7] 0.
+ * ring: capacity rows; a call writes row n_records % capacity.  t = -1 (the cadence case): the row's t is
+ * (state[1] + 1) * every, read from the state, so one captured launch records the right position on every replay;
+ * otherwise t (finite, >= 0) is recorded as given and state[1] stays.  eps is finite and >= 0; the threshold
+ * eps |psi_min| is formed on the device from the first launch's result.
+ * scratch: pinn_flow_scratch_bytes() bytes of device memory, 8-byte aligned, ZERO before the first call (every launch
+ * leaves its workgroup ticket, the double [0], at 0); as doubles [1..16] hold psi_min, its point, (psi_max, point) per
+ * quadrant, the three sums, div_max, mass_defect, nonfinite of the last call, [17..20] the quadrant counts; then block
+ * partials.  One scratch serves one stream at a time. */
+#define PINN_FLOW_RECORD 32
+#define PINN_FLOW_STATE 8
+int64_t pinn_flow_scratch_bytes(void);
+int pinn_flow_stream_function(int64_t nx, int64_t ny, const float* fields, int64_t npad, const double* ys, double* psi,
+                              void* stream);
+int pinn_flow_stats(int64_t nx, int64_t ny, const float* fields, int64_t npad, const double* xs, const double* ys,
+                    const double* psi, double eps, double t, int64_t every, double* scratch, double* state, double* ring,
+                    int64_t capacity, void* stream);
+
 /* ---- hard boundary conditions: the cavity's wall values by an output transform ---------
  * The no-slip walls and the lid of the lid-driven unit cavity hold by construction instead of by a penalty term: a
  * constrained plan evaluates

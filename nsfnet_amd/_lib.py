@@ -82,6 +82,10 @@ SIGNATURES = {
     "pinn_val_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                c_void_p]),
     "pinn_val_keep": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pinn_flow_scratch_bytes": (c_int64, []),
+    "pinn_flow_stream_function": (c_int, [c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "pinn_flow_stats": (c_int, [c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pinn_plan_create_constrained": (c_int, [c_void_p, c_int64, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
     "pinn_plan_hard_bc": (c_int, [c_void_p, c_void_p]),
     "pinn_lr_schedule_value": (c_double, [c_void_p, c_double, c_int64]),

@@ -14,7 +14,7 @@ OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libnsfnet_pinn.so")
 SOURCES = ["fwd.hip", "bwd.hip", "dw.hip", "fwd_bf16.hip", "bwd_bf16.hip", "dw_bf16.hip", "fwd_wide.hip", "bwd_wide.hip", "dw_wide.hip",
-           "fwd_bf16_wide.hip", "bwd_bf16_wide.hip", "dw_bf16_wide.hip", "fwd_bf16_pipe.hip", "bwd_bf16_pipe.hip", "fwd_bf16_split.hip", "bwd_bf16_split.hip", "fwdbwd_bf16_split.hip", "fwd_bf16_wsplit.hip", "bwd_bf16_wsplit.hip", "misc.hip", "resample.hip", "lbfgs.hip", "balance.hip", "confgrad.hip", "batch.hip", "rba.hip", "optim.hip", "rwf.hip", "validate.hip", "ptime.hip", "monitor.hip", "visc.hip", "visc_sched.hip", "state.hip", "capi.hip"]
+           "fwd_bf16_wide.hip", "bwd_bf16_wide.hip", "dw_bf16_wide.hip", "fwd_bf16_pipe.hip", "bwd_bf16_pipe.hip", "fwd_bf16_split.hip", "bwd_bf16_split.hip", "fwdbwd_bf16_split.hip", "fwd_bf16_wsplit.hip", "bwd_bf16_wsplit.hip", "misc.hip", "resample.hip", "lbfgs.hip", "balance.hip", "confgrad.hip", "batch.hip", "rba.hip", "optim.hip", "rwf.hip", "validate.hip", "flowdiag.hip", "ptime.hip", "monitor.hip", "visc.hip", "visc_sched.hip", "state.hip", "capi.hip"]
 HEADERS = ["kernels.h", "launch_dispatch.h", "layout.h", "spill.h", "spill_io.h", "bf16_util.h", "reduce_util.h", "point_stage.h", "split_phases.h", "wsplit_phases.h", "wave8_bodies.h", "optim.h", "visc_sched.h", "rwf.h", "fixed_fold.h", "residual_planes.h", os.path.join("..", "..", "include", "nsfnet_pinn.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  The pipelined kernels place their epilogue VALU in MFMA shadows: packed-f32 VALU (v_pk_*_f32, what
@@ -23,7 +23,10 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # -pragma-unroll-threshold: a slot body (64 steps x (6 MFMAs + an epilogue slice)) must unroll completely - register
 # arrays are indexed by the step - and is larger than the default cap on `#pragma unroll`.
 _PIPE = ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"]
-EXTRA_FLAGS = {"fwd_bf16_pipe.hip": _PIPE, "bwd_bf16_pipe.hip": _PIPE, "fwd_bf16_split.hip": _PIPE, "bwd_bf16_split.hip": _PIPE, "fwdbwd_bf16_split.hip": _PIPE,
+# flowdiag.hip promises one rounding per operation written, bit for bit against a numpy statement: without this the
+# compiler fuses acc + a b into one fma, whatever intrinsic spells the product and the sum.
+_EXACT = ["-ffp-contract=off"]
+EXTRA_FLAGS = {"flowdiag.hip": _EXACT, "fwd_bf16_pipe.hip": _PIPE, "bwd_bf16_pipe.hip": _PIPE, "fwd_bf16_split.hip": _PIPE, "bwd_bf16_split.hip": _PIPE, "fwdbwd_bf16_split.hip": _PIPE,
                "fwd_bf16_wsplit.hip": _PIPE, "bwd_bf16_wsplit.hip": _PIPE}
 
 

@@ -1267,6 +1267,50 @@ int pinn_val_keep(const float* src0, float* dst0, int64_t n0, const float* src1,
   return rc ? hipfail(rc, "pinn_val_keep") : 0;
 }
 
+// ---- flow diagnostics (flowdiag.hip) ----
+int64_t pinn_flow_scratch_bytes(void) { return (int64_t)flow_scratch_bytes(); }
+
+static int flow_grid(const char* what, int64_t nx, int64_t ny, const float* fields, int64_t npad) {
+  if (nx < 3 || nx > (int64_t)1 << 30) return fail(-22, "%s: nx must be 3..2^30 (got %ld)", what, (long)nx);
+  if (ny < 3 || ny > (int64_t)1 << 30) return fail(-22, "%s: ny must be 3..2^30 (got %ld)", what, (long)ny);
+  if (nx * ny > (int64_t)1 << 30) return fail(-22, "%s: nx * ny must be at most 2^30 (got %ld)", what, (long)(nx * ny));
+  if (npad < nx * ny || npad % 4 != 0) return fail(-22, "%s: npad must be a multiple of 4 and >= nx * ny (got %ld)", what, (long)npad);
+  if (!fields || misaligned(fields, 16)) return fail(-22, "%s: fields must be given and 16-byte aligned", what);
+  return 0;
+}
+
+int pinn_flow_stream_function(int64_t nx, int64_t ny, const float* fields, int64_t npad, const double* ys, double* psi,
+                              void* stream) {
+  if (int rc = flow_grid("pinn_flow_stream_function", nx, ny, fields, npad)) return rc;
+  if (!ys || !psi) return fail(-22, "pinn_flow_stream_function: null argument%s");
+  if (misaligned(ys, 8) || misaligned(psi, 16)) return fail(-22, "pinn_flow_stream_function: ys must be 8-byte aligned, psi 16-byte%s");
+  FlowPsiArgs a;
+  a.nx = (long)nx; a.ny = (long)ny; a.npad = (long)npad; a.fld = fields; a.ys = ys; a.psi = psi;
+  int rc = launch_flow_psi(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_flow_stream_function") : 0;
+}
+
+int pinn_flow_stats(int64_t nx, int64_t ny, const float* fields, int64_t npad, const double* xs, const double* ys,
+                    const double* psi, double eps, double t, int64_t every, double* scratch, double* state, double* ring,
+                    int64_t capacity, void* stream) {
+  static_assert(PINN_FLOW_RECORD == FLOW_RECORD && PINN_FLOW_STATE == FLOW_STATE, "flow record / state size mismatch");
+  if (int rc = flow_grid("pinn_flow_stats", nx, ny, fields, npad)) return rc;
+  if (capacity < 1 || capacity > (int64_t)1 << 30) return fail(-22, "pinn_flow_stats: capacity must be 1..2^30 (got %s%ld)", "", (long)capacity);
+  if (every < 1) return fail(-22, "pinn_flow_stats: every must be >= 1 (got %s%ld)", "", (long)every);
+  if (!(eps >= 0.0 && std::isfinite(eps))) return fail(-22, "pinn_flow_stats: eps must be finite and >= 0%s");
+  if (!(t == -1.0 || (t >= 0.0 && std::isfinite(t)))) return fail(-22, "pinn_flow_stats: t must be -1 (the cadence) or finite and >= 0%s");
+  if (!xs || !ys || !psi || !scratch || !state || !ring) return fail(-22, "pinn_flow_stats: null argument%s");
+  if (misaligned(xs, 8) || misaligned(ys, 8) || misaligned(scratch, 8) || misaligned(state, 8) || misaligned(ring, 8))
+    return fail(-22, "pinn_flow_stats: xs, ys, scratch, state and ring must be 8-byte aligned%s");
+  if (misaligned(psi, 16)) return fail(-22, "pinn_flow_stats: psi must be 16-byte aligned%s");
+  FlowStatsArgs a;
+  a.nx = (long)nx; a.ny = (long)ny; a.npad = (long)npad; a.capacity = (long)capacity; a.fld = fields;
+  a.xs = xs; a.ys = ys; a.psi = psi; a.eps = eps; a.t = t; a.every = (double)every;
+  a.scratch = scratch; a.state = state; a.ring = ring;
+  int rc = launch_flow_stats(a, (hipStream_t)stream);
+  return rc ? hipfail(rc, "pinn_flow_stats") : 0;
+}
+
 // ---- viscosity identification (visc.hip) ----
 int64_t pinn_visc_scratch_bytes(int64_t n) {
   return n < 1 || n > (int64_t)1 << 30 ? -1 : (int64_t)visc_scratch_bytes((long)n);

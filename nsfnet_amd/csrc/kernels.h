@@ -414,6 +414,24 @@ int launch_visc_update(const ViscUpdateArgs& a, hipStream_t s);
 size_t val_scratch_bytes();
 int launch_val_stats(const ValStatsArgs& a, hipStream_t s);
 int launch_val_keep(const ValKeepArgs& a, hipStream_t s);
+// flow diagnostics: stream function, vorticity and vortices of a tensor grid's field planes (flowdiag.hip)
+constexpr int FLOW_RECORD = 32, FLOW_STATE = 8;
+struct FlowPsiArgs {
+  long nx, ny, npad;                       // nodes (node (i, j) = point j nx + i); plane stride of fld
+  const float* fld;                        // [FLD_COUNT][npad] field planes of a residual forward on the grid
+  const double* ys;                        // [ny]
+  double* psi;                             // [ny nx]
+};
+struct FlowStatsArgs {
+  long nx, ny, npad, capacity;             // nodes; plane stride of fld; rows of the history ring
+  const float* fld;
+  const double *xs, *ys, *psi;             // [nx], [ny], [ny nx] (16-byte aligned)
+  double eps, t, every;                    // t < 0: t = (cadence records + 1) * every, from the state
+  double *scratch, *state, *ring;
+};
+size_t flow_scratch_bytes();
+int launch_flow_psi(const FlowPsiArgs& a, hipStream_t s);
+int launch_flow_stats(const FlowStatsArgs& a, hipStream_t s);
 // training-state snapshots: gather / scatter of many buffers with per-segment digests (state.hip)
 constexpr int STATE_MAX_SEG = 64;
 struct StateSeg {

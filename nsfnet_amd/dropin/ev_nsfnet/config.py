@@ -225,6 +225,17 @@ class ReContinuationConfig:
 
 
 @dataclass
+class FlowDiagnosticsConfig:
+    """Flow diagnostics on the device (solver.set_flow_diagnostics); the key's absence means off.
+    After every `every` optimizer updates the primary vortex, the counter-rotating area (nodes with psi > eps |psi_min|)
+    and the mass defect of the net's field on an nx x ny grid of the cavity are recorded."""
+    nx: int = 257
+    ny: int = 257
+    every: int = 1000
+    eps: float = 1e-3
+
+
+@dataclass
 class CheckpointConfig:
     """Training-state snapshots that resume bit for bit (solver.set_checkpointing), off by default: path of the file
     (one per rank) and the optimizer updates between two non-blocking snapshots."""
@@ -267,6 +278,7 @@ class TrainingConfig:
     early_stop: Optional[EarlyStopConfig] = None
     identify_viscosity: Optional[IdentifyViscosityConfig] = None
     re_continuation: Optional[ReContinuationConfig] = None
+    flow_diagnostics: Optional[FlowDiagnosticsConfig] = None
     training_stages: List[TrainingStage] = field(default_factory=_default_stages)
 
 
@@ -332,6 +344,15 @@ def _fill(obj, data):
                     elif k in ("updates", "hold", "stairs"):
                         setattr(rc, k, int(v))
                 setattr(obj, key, rc)
+        elif key == "flow_diagnostics":          # absent, null or false: off
+            if val is not None and val is not False:
+                fd = FlowDiagnosticsConfig()
+                for k, v in (val.items() if isinstance(val, dict) else ()):
+                    if k in ("nx", "ny", "every"):
+                        setattr(fd, k, int(v))
+                    elif k == "eps":
+                        fd.eps = float(v)
+                setattr(obj, key, fd)
         elif key == "weight_factorization":      # the key's presence switches it on (`enabled: false` still wins)
             if val is not None and val is not False:
                 cur.enabled = True
@@ -422,6 +443,9 @@ class ConfigManager:
             if es is not None or pt.enabled or c.training.conflict_free_gradients.enabled:
                 problems.append("training.identify_viscosity does not go together with training.early_stop, "
                                 "training.pseudo_time or training.conflict_free_gradients")
+        fd = c.training.flow_diagnostics
+        if fd is not None and not (fd.nx >= 3 and fd.ny >= 3 and fd.every >= 1 and 0.0 <= fd.eps < float("inf")):
+            problems.append("training.flow_diagnostics: nx, ny >= 3, every >= 1 and a finite eps >= 0 required")
         rc = c.training.re_continuation
         if rc is not None:
             if not (0.0 < rc.re_start < float("inf") and rc.updates >= 1 and rc.hold >= 0 and rc.stairs >= 0

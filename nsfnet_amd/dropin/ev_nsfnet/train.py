@@ -182,6 +182,9 @@ def main():
         rc = cfg.training.re_continuation
         if rc is not None:    # the viscosity is ramped down to 1 / physics.Re while the stages train
             PINN.set_reynolds_continuation(rc.re_start, rc.updates, hold=rc.hold, shape=rc.shape, stairs=rc.stairs)
+        fd = cfg.training.flow_diagnostics
+        if fd is not None:    # which steady flow the net describes, recorded on the device; print_log adds the line
+            PINN.set_flow_diagnostics(nx=fd.nx, ny=fd.ny, every=fd.every, eps=fd.eps)
         ck = cfg.training.checkpoint
         if ck.enabled:
             PINN.set_checkpointing(ck.path, ck.every)

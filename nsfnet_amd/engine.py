@@ -710,6 +710,33 @@ def val_keep(segs, state):
                                          0 if s1 is None else s1.numel(), _ptr(state), _stream()), "pinn_val_keep")
 
 
+FLOW_RECORD = 32         # PINN_FLOW_RECORD
+FLOW_STATE = 8           # PINN_FLOW_STATE: [n_records, cadence records, records with non-finite nodes, 0 ...]
+FLOW_ROW = ("t", "x_c", "y_c", "psi_min", "omega_c") + tuple(
+    "%s_%s" % (k, q) for q in ("bl", "br", "tl", "tr") for k in ("x", "y", "psi_max", "area")) + (
+    "counter_area", "mass_defect", "ke", "enstrophy", "div_rms", "div_max", "nonfinite")
+
+
+def flow_scratch(device):
+    """Zeroed device scratch of flow_stats."""
+    return torch.zeros(int(_lib.load().pinn_flow_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def flow_stream_function(fields, nx, ny, ys, psi):
+    """pinn_flow_stream_function: psi [ny nx] fp64 from the u plane of the field planes `fields` [FLD_COUNT, npad] of a
+    residual forward on the nx x ny tensor grid (x fastest), by the trapezoid rule along y.  One launch."""
+    _lib.check(_lib.load().pinn_flow_stream_function(int(nx), int(ny), _ptr(fields), fields.shape[1], _ptr(ys), _ptr(psi),
+                                                     _stream()), "pinn_flow_stream_function")
+
+
+def flow_stats(fields, nx, ny, xs, ys, psi, eps, t, every, scratch, state, ring):
+    """pinn_flow_stats: one diagnostic record of the field planes and their psi - a row into ring, state updated;
+    t = -1: the cadence position from the state.  Two launches."""
+    _lib.check(_lib.load().pinn_flow_stats(int(nx), int(ny), _ptr(fields), fields.shape[1], _ptr(xs), _ptr(ys), _ptr(psi),
+                                           float(eps), float(t), int(every), _ptr(scratch), _ptr(state), _ptr(ring),
+                                           ring.shape[0], _stream()), "pinn_flow_stats")
+
+
 MON_RECORD = 12          # PINN_MON_RECORD
 MON_STATE = 16           # PINN_MON_STATE
 MON_INFO = 4             # PINN_MON_INFO: this rank's [max vis_t, entries >= vis_t0, fp64 sum, n]
@@ -1247,11 +1274,34 @@ class _Continuation(_Option):
         self.rec.copy_(torch.tensor(rec, dtype=torch.float64))
 
 
+class _FlowDiag(_Option):
+    """State of the flow diagnostics (set_flow_diagnostics): the forward-only residual plan over the nx x ny tensor
+    grid, whose field planes the kernels read; xs [nx], ys [ny] fp64 (the plan's fp32 coordinates widened), psi
+    [ny nx] fp64, scratch, state [FLOW_STATE] fp64 and ring [capacity, FLOW_RECORD] fp64.  n counts the optimizer
+    updates since set_flow_diagnostics on the host (the device counts the cadence records itself)."""
+    stored = ("flow", "state", "ring")
+
+    def __init__(self, nx, ny, every, eps, capacity):
+        self.nx, self.ny, self.every, self.eps, self.capacity = nx, ny, every, eps, capacity
+        self.n = 0
+        self.plan = self.xs = self.ys = self.psi = self.scratch = self.state = self.ring = None
+
+    def graph_key(self):
+        return (("flow", self.nx, self.ny, self.every, self.eps, self.capacity),)
+
+    def header(self):
+        return (dict(flow=dict(nx=self.nx, ny=self.ny, capacity=self.capacity)), dict(flow=[self.every, self.eps]),
+                dict(flow_n=self.n))
+
+    def restore_host(self, host):
+        self.n = int(host["flow_n"])
+
+
 # The engine attribute of every option (None while it is off) and its class, in the one order every loop over the
 # options runs in: that of the options' segments in a training-state file and of their entries in the graph key.
 _OPTIONS = (("_opt", _Optim), ("_bal", _Balance), ("_cfg", _ConflictFree), ("_batch", _Batching), ("_rba", _Attention),
             ("_val", _Validation), ("_pt", _PseudoTime), ("_mon", _Monitor), ("_visc", _Viscosity),
-            ("_rc", _Continuation))
+            ("_rc", _Continuation), ("_flow", _FlowDiag))
 
 
 def _refuse_chunked(option, chunked):
@@ -1327,6 +1377,7 @@ class PinnEngine:
         self._snap = None                   # training-state snapshots (save_training_state; buffers made at first use)
         self._visc = None                   # viscosity identification (set_viscosity_identification; None = off)
         self._rc = None                     # Reynolds-number continuation (set_reynolds_continuation; None = off)
+        self._flow = None                   # flow diagnostics (set_flow_diagnostics; None = off)
 
     # ---- what the evaluations are made for ----
     @contextlib.contextmanager
@@ -2017,11 +2068,11 @@ class PinnEngine:
         out["loss"] = self.alpha_b * loss_b + self.alpha_e * loss_e + self.alpha_s * loss_s
         return out
 
-    def adam_step(self, lr, validate=None):
+    def adam_step(self, lr, validate=None, diagnose=None):
         """Adam on the gradient of the last evaluation.  With a device schedule or clipping on, lr is the schedule's
         base rate lr0; every trainable net uses the lr_e and the clipping coefficient of the same epoch.  With
         set_validation on, the update that is due by its cadence is followed by a validation (validate: step()'s
-        decision for a captured sequence; None = by the count)."""
+        decision for a captured sequence; None = by the count); set_flow_diagnostics and `diagnose` likewise."""
         o = self._opt
         with_e = self.net_e is not None and self.e_trainable
         g, ge = self.grads, self.grads_e
@@ -2048,7 +2099,7 @@ class PinnEngine:
             visc_schedule_step(rc.cstruct, rc.pos, rc.nu, rc.cap, rc.rec)
         if self._bal is not None:
             self._bal.n += 1
-        self._updated(validate)
+        self._updated(validate, diagnose=diagnose)
 
     def _count_updates(self, d):
         """Move the host mirrors of the update count (what adam_step advances) by d = +1 / -1."""
@@ -2059,6 +2110,8 @@ class PinnEngine:
             self._bal.n += d
         if self._val is not None:
             self._val.n += d
+        if self._flow is not None:
+            self._flow.n += d
 
     # ---- random weight factorization of the dense layers ----
     def _nets(self):
@@ -2163,7 +2216,7 @@ class PinnEngine:
         even hidden width and at least 2 hidden layers; not available together
         with hard walls or pseudo-time.  Must be called before any point set is attached (ValueError otherwise).
         sigma = None without frequencies: off (layer 0 is tanh again and trainable; its weights stay as they are)."""
-        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val)):
+        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val, self._flow)):
             raise ValueError("fourier features: call set_fourier_features before any point set is attached")
         net = self.net
         if sigma is None and frequencies is None:
@@ -2232,7 +2285,7 @@ class PinnEngine:
         sweeps have no constrained variant yet.
 
         Must be called before any point set is attached (ValueError otherwise).  enabled=False: off."""
-        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val)):
+        if any(p is not None for p in (self.plan_f, self.plan_b, self.plan_s, self._pool, self._val, self._flow)):
             raise ValueError("hard boundary: call set_hard_boundary before any point set is attached")
         if not enabled:
             self.net.hard_bc = None
@@ -2478,20 +2531,26 @@ class PinnEngine:
         m = self._val
         return m is not None and (m.n + 1) % m.every == 0
 
-    def _updated(self, validate=None, observe=True):
+    def _updated(self, validate=None, observe=True, diagnose=None):
         """An optimizer update is in place: count it, let the convergence monitor observe it (observe False: an L-BFGS
-        call, whose sums are a trial point's), and validate when the cadence (or the caller) says so."""
+        call, whose sums are a trial point's), and validate and diagnose the flow when the cadences (or the caller)
+        say so."""
         if self._pt is not None:
             ptime_advance(self.plan_f, self._pt.every, False, self._pt.scratch, self._pt.record)
         if observe and self._mon is not None:
             self._observe()
         m = self._val
-        if m is None:
-            return
-        due = self._validation_due() if validate is None else validate
-        m.n += 1
-        if due:
-            self._validate(-1.0)
+        if m is not None:
+            due = self._validation_due() if validate is None else validate
+            m.n += 1
+            if due:
+                self._validate(-1.0)
+        d = self._flow
+        if d is not None:
+            due = self._flow_due() if diagnose is None else diagnose
+            d.n += 1
+            if due:
+                self._diagnose(-1.0)
 
     def _validate(self, t):
         m = self._val
@@ -2581,6 +2640,162 @@ class PinnEngine:
             net.trainable.copy_(snap)
             net.update_params()
         self.lbfgs_reset()
+
+    # ---- flow diagnostics: stream function, vorticity and vortices on the device ----
+    def set_flow_diagnostics(self, nx=257, ny=257, every=1000, eps=1e-3, history=4096, xs=None, ys=None, domain=None):
+        """Record which flow the net describes, on the device.  After the every-th optimizer update since this call,
+        and every every-th after that (counted like set_validation's cadence: Adam updates, and each lbfgs_step call as
+        one), four launches follow the update on the main stream, behind the pseudo-time advance, the monitor
+        observation and the validation: a forward-only residual forward of the main net on the nx x ny tensor grid,
+        whose field planes hold u, v and their exact first derivatives; the stream function psi = int u dy by the
+        trapezoid rule from the bottom wall; and two launches that reduce psi and the planes in fixed-order fp64 to one
+        row of a history ring of `history` rows (FLOW_ROW):
+          t, x_c, y_c, psi_min, omega_c           the primary vortex: argmin psi, its centre refined inside the cell
+          x, y, psi_max, area per quadrant        bl, br, tl, tr of the grid's midlines, the lid row left out: the
+                                                  strongest counter-rotating node and the fraction of all nodes that
+                                                  lie in the quadrant with psi > eps |psi_min|
+          counter_area                            the four areas added: 0.06 for the DNS flow at Re 2000, 0.46 for
+                                                  the other steady branch plain NSFnet can land on
+          mass_defect, ke, enstrophy, div_rms, div_max, nonfinite
+        with omega = v_x - u_y and div = u_x + v_y.  A field with a non-finite node records NaN for everything but t
+        and nonfinite.  Everything is device memory: the captured diagnosing step serves the whole stage and nothing
+        synchronises; the training is not changed by it.  Several ranks: every rank computes the same record.
+
+        xs, ys: the grid's coordinates (strictly increasing, at least 3 each; they are held in fp32 like every
+        point set) instead of nx / ny equidistant ones over domain = (x0, x1, y0, y1).  All three are in the net's
+        input coordinates, as every point set is.  The domain defaults to where the cavity lies in them: the box of
+        the hard walls when they are on, else the unit square at coordinate scale 1 and [-1, 1]^2 at scale 2 (the
+        map 2 x - 1 of the ev data loader); any other scale without hard walls is refused.  The record is physical:
+        the field planes hold physical derivatives (the sweeps multiply by the scale), so psi is integrated over, and
+        every centre is given in, x = (xi - o) / scale with o the cavity's lower-left corner in input coordinates
+        (the hard walls' origin, else (0, 0) or (-1, -1)); at scale 1 without hard walls that is xi itself.  The scale
+        is the one in force at this call; a diagnostic after it has changed raises.  Area is a node fraction: an area
+        only on a uniform grid.  The quadrant maxima are not connected regions: one that spans quadrants shows in several rows.
+        Like every point set the grid must be attached after set_hard_boundary / set_fourier_features.
+
+        every = 0: off (the step launches what it launches without the feature).  A call restarts the record."""
+        every, history = int(every), int(history)
+        if every < 0:
+            raise ValueError("flow diagnostics: every must be >= 0")
+        self._graphs.clear()        # captured steps hold the other grid's buffers and constants
+        if every == 0:
+            self._flow = None
+            return
+        eps = float(eps)
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError("flow diagnostics: eps must be finite and >= 0")
+        if history < 1:
+            raise ValueError("flow diagnostics: history must be >= 1")
+        bc, scale = self.hard_boundary_info(), float(self.scale)
+        if bc is not None:
+            origin, side = bc["origin"], 1.0 / bc["inv_len"]
+        elif scale in (1.0, 2.0):
+            origin, side = ((0.0, 0.0), 1.0) if scale == 1.0 else ((-1.0, -1.0), 2.0)
+        else:
+            raise ValueError("flow diagnostics: coordinate scale %g is neither the plain cavity's nor the [-1, 1] map's, "
+                             "and no hard walls say where the cavity lies" % scale)
+        if domain is None:
+            domain = (origin[0], origin[0] + side, origin[1], origin[1] + side)
+        x0, x1, y0, y1 = (float(c) for c in domain)
+        axes = []
+        for name, given, count, lo, hi in (("xs", xs, nx, x0, x1), ("ys", ys, ny, y0, y1)):
+            if given is None:
+                count = int(count)
+                if count < 3:
+                    raise ValueError("flow diagnostics: n%s must be >= 3 (got %d)" % (name[0], count))
+                if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+                    raise ValueError("flow diagnostics: domain must be finite with x0 < x1 and y0 < y1")
+                given = np.linspace(lo, hi, count)
+            c = np.asarray(given, dtype=np.float64).reshape(-1).astype(np.float32)
+            if c.size < 3:
+                raise ValueError("flow diagnostics: %s must have at least 3 entries (got %d)" % (name, c.size))
+            if not (np.all(np.isfinite(c)) and np.all(np.diff(c) > 0)):
+                raise ValueError("flow diagnostics: %s must be finite and strictly increasing in fp32" % name)
+            axes.append(c)
+        cx, cy = axes
+        nx, ny = cx.size, cy.size
+        if nx * ny > 1 << 30:
+            raise ValueError("flow diagnostics: nx * ny must be at most 2^30 (got %d)" % (nx * ny))
+        d = _FlowDiag(nx, ny, every, eps, history)
+        d.plan = ResidualPlan(self.net, np.tile(cx, ny), np.repeat(cy, nx), with_backward=False)
+        d.scale = scale
+        # physical coordinates, fp64 from the fp32 ones the plan holds (at scale 1 and origin 0: those, widened)
+        d.xs = torch.as_tensor((cx.astype(np.float64) - origin[0]) / scale).to(self.device)
+        d.ys = torch.as_tensor((cy.astype(np.float64) - origin[1]) / scale).to(self.device)
+        d.psi = torch.zeros(nx * ny, dtype=torch.float64, device=self.device)
+        d.scratch = flow_scratch(self.device)
+        d.state = torch.zeros(FLOW_STATE, dtype=torch.float64, device=self.device)
+        d.ring = torch.zeros(history, FLOW_RECORD, dtype=torch.float64, device=self.device)
+        self._flow = d
+
+    def _flow_due(self):
+        """True when the next optimizer update is one the cadence diagnoses after."""
+        d = self._flow
+        return d is not None and (d.n + 1) % d.every == 0
+
+    def _flow_forward(self):
+        d = self._flow
+        if self.scale != d.scale:
+            raise RuntimeError("flow diagnostics: the coordinate scale changed from %g to %g since set_flow_diagnostics; "
+                               "call it again" % (d.scale, self.scale))
+        d.plan.forward(self.Re, scale=self.scale, save=False)
+        flow_stream_function(d.plan.fields, d.nx, d.ny, d.ys, d.psi)
+
+    def _diagnose(self, t):
+        d = self._flow
+        self._flow_forward()
+        flow_stats(d.plan.fields, d.nx, d.ny, d.xs, d.ys, d.psi, d.eps, t, d.every, d.scratch, d.state, d.ring)
+
+    def _flow_on(self):
+        if self._flow is None:
+            raise RuntimeError("flow diagnostics are off: call set_flow_diagnostics() first")
+        return self._flow
+
+    def flow_diagnostics(self, t=None):
+        """One record now, of the current parameters, with the explicit position t (default: the updates counted since
+        set_flow_diagnostics).  Returns the row as a dict (one host read)."""
+        d = self._flow_on()
+        t = float(d.n if t is None else t)
+        if not (math.isfinite(t) and t >= 0.0):
+            raise ValueError("flow_diagnostics: t must be finite and >= 0")
+        self._diagnose(t)
+        return self.flow_info()["last"]
+
+    def flow_info(self):
+        """The state (one host read), or None when the feature is off: records, nonfinite (records of a field with
+        non-finite nodes), last (the newest row as a dict; None before the first), every, eps, nx, ny."""
+        d = self._flow
+        if d is None:
+            return None
+        st = d.state.cpu().tolist()
+        k = int(st[0])
+        last = None
+        if k > 0:
+            last = dict(zip(FLOW_ROW, d.ring[(k - 1) % d.capacity].cpu().tolist()))
+        return dict(records=k, nonfinite=int(st[2]), last=last, every=d.every, eps=d.eps, nx=d.nx, ny=d.ny)
+
+    def flow_history(self):
+        """fp64 numpy array [rows, FLOW_RECORD] of the recorded rows in time order (the ring unwrapped: the newest
+        `history` of them; columns FLOW_ROW, then +0); one host read."""
+        d = self._flow_on()
+        both = torch.cat([d.state, d.ring.reshape(-1)]).cpu().numpy()
+        k, ring = int(both[0]), both[FLOW_STATE:].reshape(d.capacity, FLOW_RECORD)
+        if k <= d.capacity:
+            return ring[:k].copy()
+        return np.concatenate([ring[k % d.capacity:], ring[:k % d.capacity]])
+
+    def flow_fields(self, refresh=True):
+        """The streamline / vorticity data on the grid, as device tensors shaped [ny, nx]: psi (fp64) and u, v, p,
+        omega, div (fp32), with the physical xs [nx] and ys [ny] (fp64).  refresh: evaluate the current parameters first (a forward
+        and the stream function, no record); otherwise the planes are those of the last diagnostic.  psi, u, v and p
+        are views that the next diagnostic rewrites."""
+        d = self._flow_on()
+        if refresh:
+            self._flow_forward()
+        n, shape = d.nx * d.ny, (d.ny, d.nx)
+        f = lambda name: d.plan.fields[FLD[name], :n].view(shape)
+        return dict(psi=d.psi.view(shape), u=f("u"), v=f("v"), p=f("p"), omega=f("v_x") - f("u_y"),
+                    div=f("u_x") + f("v_y"), xs=d.xs, ys=d.ys)
 
     # ---- convergence monitor: a stage that has stopped making progress (DESIGN.md section 7.14) ----
     def set_convergence_monitor(self, every=1, window=1000, min_rel_improvement=1e-3, patience=3, re_eff_tol=None,
@@ -2952,13 +3167,14 @@ class PinnEngine:
         # with balancing on, a balance step and a plain step are separate graphs (the weights are device state)
         update = self._balance_due()
         validate = self._validation_due()       # a validating step and a plain one are separate graphs, too
-        key = self._graph_key(lr, update, validate)
+        diagnose = self._flow_due()             # and so are a diagnosing step and one that does both
+        key = self._graph_key(lr, update, validate, diagnose)
         g = self._graphs.get(key)
         if g is None:
             # first use of this configuration: run it eagerly once (lazy host-side setup such as the
             # supervised-target census happens here), then capture
             self._loss_and_grad(update)
-            self.adam_step(lr, validate)
+            self.adam_step(lr, validate, diagnose)
             if len(self._graphs) >= 8:
                 self._graphs.clear()
             side = torch.cuda.Stream(device=self.device)
@@ -2967,7 +3183,7 @@ class PinnEngine:
             with torch.cuda.stream(side):
                 with torch.cuda.graph(graph, stream=side):
                     self._loss_and_grad(update)
-                    self.adam_step(lr, validate)
+                    self.adam_step(lr, validate, diagnose)
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._count_updates(-1)      # the capture itself does not execute
             self._graphs[key] = graph
@@ -2976,7 +3192,7 @@ class PinnEngine:
         self._eval_batch = self._batching_on()
         self._count_updates(1)
 
-    def _graph_key(self, lr, update, validate=False):
+    def _graph_key(self, lr, update, validate=False, diagnose=False):
         """What a captured step depends on besides device memory: the launch constants of the engine and of every
         option that is on (lr is the base rate lr0 under a schedule: the rate of each update is device state).  The
         head holds balancing, batching, attention, the schedule and the factorization (which lives on the nets)."""
@@ -2990,6 +3206,7 @@ class PinnEngine:
         for option in self._options():
             key += option.graph_key()
         v = self._val
+        key += ("diagnose",) if diagnose else ()        # (the grid, the cadence and eps: the option's graph_key)
         return key + (("validate", v.every, v.metric, v.keep_best, v.plan.n, v.with_p) if validate else ())
 
     def _graphs_enabled(self):
@@ -3048,6 +3265,9 @@ class PinnEngine:
         if self._val is not None:
             add("val.tgt", self._val.tgt, False)
         add("pool.w", self._pool_w, False)
+        if self._flow is not None:
+            add("flow.xs", self._flow.xs, False)
+            add("flow.ys", self._flow.ys, False)
         return segs
 
     def _state_fingerprint(self):

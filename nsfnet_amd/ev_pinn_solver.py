@@ -424,6 +424,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
             print('  ' + self.viscosity_log())
         if self._recont:
             print('  ' + self.continuation_log())
+        if self._flow_diag:
+            print('  ' + self.flow_log())
         if self._balancing:
             lam = self.engine.loss_weights().cpu().tolist()
             print('  loss weights: lambda_b=%.4e' % lam[0]

@@ -380,6 +380,32 @@ class SolverBase:
             i["Re_t"], i["nu_t"], "" if i["cap_t"] is None else ", vis_t0=%.6e" % i["cap_t"], i["s"], i["t"],
             ", done" if i["done"] else "")
 
+    # ---- flow diagnostics on the device ----
+    _flow_diag = False          # set_flow_diagnostics: print_log adds the vortex line
+
+    def set_flow_diagnostics(self, nx=257, ny=257, every=1000, eps=1e-3, history=4096, xs=None, ys=None, domain=None):
+        """Record the primary vortex, the counter-rotating area of every quadrant, the mass defect and the kinetic
+        energy, enstrophy and divergence of the net's field on an nx x ny tensor grid after every `every` optimizer
+        updates, on the device (PinnEngine.set_flow_diagnostics): the numbers that tell the steady solutions apart
+        without a reference field.  Nothing synchronises: flow_log() and flow_history() read when asked; print_log adds
+        the vortex line.  every = 0: off."""
+        self.engine.set_flow_diagnostics(nx=nx, ny=ny, every=every, eps=eps, history=history, xs=xs, ys=ys, domain=domain)
+        self._flow_diag = self.engine.flow_info() is not None
+
+    def flow_log(self):
+        """One line on the flow diagnostics (one host read)."""
+        i = self.engine.flow_info()
+        if i is None or i["last"] is None:
+            return "vortex: no record yet"
+        r = i["last"]
+        return "vortex (%.4f, %.4f) psi_min %.4f counter-area %.3f mass %.1e%s" % (
+            r["x_c"], r["y_c"], r["psi_min"], r["counter_area"], r["mass_defect"],
+            " nonfinite=%d" % r["nonfinite"] if r["nonfinite"] else "")
+
+    def flow_history(self):
+        """The recorded rows (engine.FLOW_ROW) in time order (one host read)."""
+        return self.engine.flow_history()
+
     def save_viscosity(self, path):
         """Write the sidecar of the checkpoint at `path`: dict(re0, lr, betas, eps, re_bounds, state, nu) as path +
         '_visc' (torch.save).  With the identification off nothing is written."""
@@ -792,7 +818,8 @@ class PysicsInformedNeuralNetwork(SolverBase):
               *(("\n" + self.validation_log(),) if self._validation else ()),
               *(("\n" + self.early_stop_log(),) if self._early_stop else ()),
               *(("\n" + self.viscosity_log(),) if self._identify else ()),
-              *(("\n" + self.continuation_log(),) if self._recont else ()))
+              *(("\n" + self.continuation_log(),) if self._recont else ()),
+              *(("\n" + self.flow_log(),) if self._flow_diag else ()))
 
     # ---------------------------------------------------------------- evaluation / io
     def _errors(self, x, y, u, v):

@@ -121,6 +121,10 @@ def main():
     ap.add_argument("--re-continuation", type=float, nargs=2, default=None, metavar=("RE_START", "UPDATES"),
                     help="ramp the viscosity from 1 / RE_START to 1 / --re over UPDATES Adam updates (DESIGN.md 7.16); not "
                          "with --identify-re, --early-stop or --re-eff-tol")
+    ap.add_argument("--flow-diag", type=int, nargs="+", default=None, metavar=("EVERY", "NX"),
+                    help="EVERY [NX NY]: record the primary vortex, the counter-rotating area and the mass defect of the "
+                         "net's field on an NX x NY grid (default 257 x 257) on the device every EVERY updates; the rows go "
+                         "to flow.jsonl (DESIGN.md 7.17)")
     ap.add_argument("--state", default=None, metavar="FILE",
                     help="training-state file (DESIGN.md 7.12): continue from it when it exists, and write it")
     ap.add_argument("--state-every", type=int, default=0, help="updates between two non-blocking snapshots (0: only where the call ends)")
@@ -184,6 +188,11 @@ def main():
         P.set_early_stopping(window=1000 if a.early_stop is None else int(a.early_stop[0]),
                              min_rel_improvement=None if a.early_stop is None else a.early_stop[1],
                              re_eff_tol=a.re_eff_tol, history=1 << 16)
+    if a.flow_diag is not None:
+        if len(a.flow_diag) not in (1, 3):
+            ap.error("--flow-diag takes EVERY or EVERY NX NY")
+        nx, ny = a.flow_diag[1:] if len(a.flow_diag) == 3 else (257, 257)
+        P.set_flow_diagnostics(nx=nx, ny=ny, every=a.flow_diag[0], history=1 << 16)
     if a.identify_re is not None:
         if len(a.identify_re) > 2:
             ap.error("--identify-re takes RE0 and, optionally, LR")
@@ -203,6 +212,7 @@ def main():
     resumed = state is not None and os.path.exists(P.engine._state_path(state))
     if resumed:       # the stage the file was cut in, entered at its next epoch
         first = int(es._eng._state_file.read_header(P.engine._state_path(state))["extra"]["current_stage"].split()[-1])
+    flow_seen = 0                                       # flow records already in flow.jsonl
     for k in range(first, a.last + 1):
         alpha, epochs, lr = STAGES[k - 1]
         n = max(1, int(epochs * a.epochs_scale))
@@ -213,6 +223,8 @@ def main():
                                   history=max(1, n // a.validate_every))
         if resumed:   # every option is attached as in the call that wrote the file
             start, resumed = int(P.load_training_state(state)["next_epoch"]), False
+            if a.flow_diag is not None:                 # the restored ring's rows were written by the call that made them
+                flow_seen = P.engine.flow_info()["records"]
             if start >= n:
                 start = 0
                 continue
@@ -274,6 +286,16 @@ def main():
                 for row in P.monitor_history().tolist():
                     fh.write(json.dumps(dict(zip(("t", "loss", "loss_e", "loss_b", "loss_s", "eq1", "eq2", "eq3", "eq4",
                                                   "vis_mean", "Re_eff", "stop"), row), stage=k)) + "\n")
+        if a.flow_diag is not None:
+            info = P.engine.flow_info()
+            rec.update(flow=info["last"])
+            new = info["records"] - flow_seen           # the ring runs on across the stages: this stage's rows
+            if new > 0:
+                from nsfnet_amd.engine import FLOW_ROW
+                with open("flow.jsonl", "a") as fh:
+                    for row in P.flow_history()[-new:].tolist():
+                        fh.write(json.dumps(dict(zip(FLOW_ROW, row), stage=k)) + "\n")
+            flow_seen = info["records"]
         if a.identify_re is not None:
             info = P.engine.viscosity_info()
             rec.update(viscosity={k_: info[k_] for k_ in ("Re", "nu", "grad", "updates", "skipped")})

@@ -14,6 +14,9 @@ psi is integrated from the bottom wall with the trapezoid rule, psi(x, y) = int_
     python scripts/flow_topology.py --dns tests/golden/dns/cavity_Re2000_256.mat
     python scripts/flow_topology.py --dns ... --ev-net net.pth [--layers 6 --hidden 80]     (GPU: HIP predict)
     python scripts/flow_topology.py --dns ... --nsfnet-net net.pth --layers 4 --hidden 120
+    python scripts/flow_topology.py --dns ... --ev-net net.pth --device-fields     (u, v and psi from the engine's flow
+                                                                                   diagnostics instead of predict + host
+                                                                                   integration)
 """
 import argparse
 import json
@@ -63,8 +66,9 @@ def _where(x, y):
     return v + "-" + h
 
 
-def topology(X, Y, U, V, eps=1e-3, min_area=2e-4):
-    psi = stream_function(X, Y, U)
+def topology(X, Y, U, V, eps=1e-3, min_area=2e-4, psi=None):
+    """psi: the stream function where it is already known (device_fields), with the layout of U."""
+    psi = stream_function(X, Y, U) if psi is None else psi
     i, j = np.unravel_index(np.argmin(psi), psi.shape)
     cx, cy = _refine(psi, i, j, X, Y)
     psi_min = float(psi[i, j])
@@ -105,6 +109,18 @@ def predict_field(kind, net_path, X, Y, layers, hidden, evm_path=None, Re=2000.0
     return u.cpu().numpy().reshape(X.shape).astype(np.float64), v.cpu().numpy().reshape(X.shape).astype(np.float64)
 
 
+def device_fields(net_path, X, Y, layers, hidden, Re=2000.0):
+    """(u, v, psi) of a trained net on the DNS grid (y along axis 0) from PinnEngine.flow_fields(): the residual
+    forward's planes and the device's stream function (needs the GPU)."""
+    import torch
+    from nsfnet_amd import engine as eng
+    E = eng.PinnEngine(torch.device("cuda:0"), layers, hidden, Re)
+    E.net.load_state_dict(torch.load(net_path, map_location="cpu", weights_only=True))
+    E.set_flow_diagnostics(xs=X[0], ys=Y[:, 0], every=1)
+    f = E.flow_fields()
+    return tuple(f[k].cpu().numpy().astype(np.float64) for k in ("u", "v", "psi"))
+
+
 def describe(name, t):
     p = t["primary"]
     s = "%-28s primary vortex (%.4f, %.4f) psi_min %.5f | KE %.4f | mass defect %.1e | eddies: " % (
@@ -122,14 +138,20 @@ def main():
     ap.add_argument("--hidden", type=int, default=None)
     ap.add_argument("--re", type=float, default=2000.0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--device-fields", action="store_true",
+                    help="take u, v and psi of the nets from the engine's flow diagnostics (PinnEngine.flow_fields)")
     a = ap.parse_args()
     X, Y, U, V = load_dns(a.dns)
     out = {"dns": topology(X, Y, U, V)}
     print(describe("DNS " + os.path.basename(a.dns), out["dns"]))
     for kind, path, dl, dh in (("ev-NSFnet", a.ev_net, 6, 80), ("NSFnet", a.nsfnet_net, 4, 120)):
         if path:
-            u, v = predict_field(kind, path, X, Y, a.layers or dl, a.hidden or dh, Re=a.re)
-            t = topology(X, Y, u, v)
+            if a.device_fields:
+                u, v, psi = device_fields(path, X, Y, a.layers or dl, a.hidden or dh, Re=a.re)
+                t = topology(X, Y, u, v, psi=psi)
+            else:
+                u, v = predict_field(kind, path, X, Y, a.layers or dl, a.hidden or dh, Re=a.re)
+                t = topology(X, Y, u, v)
             t["err_u"] = float(np.linalg.norm(u - U) / np.linalg.norm(U))
             t["err_v"] = float(np.linalg.norm(v - V) / np.linalg.norm(V))
             out[kind] = t
